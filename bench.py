@@ -12,6 +12,12 @@ hit-colour surfaces and history halos over RCCL every frame.  N = 2, 4, 8 cut th
 
 Prints ONE JSON line on rank 0.  `value` = full-resolution pixels of the whole frame processed
 per second (all ranks), with every input resident in HBM when the timed region starts.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`ms_per_step`: wall clock of the
+timed steps over their number).  --full adds what takes runs or events of its own: the per-pass calibration,
+the roofline, per-step event times, the N > 1 exchange diagnostics, the timed loops with the empty-tile
+skips off and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as .npy files;
+the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -160,6 +166,24 @@ def cpu_baseline(frame, setup, threads=None):
     }
 
 
+DUMP_SAMPLE = 1 << 20  # texels kept of a larger image: at most 14 channels in all (--shading) x 4 bytes x 2^20 = 59 MB
+
+
+def dump_outputs(frame, names, out_dir):
+    """--dump-outputs: the images the last step computed, read after end_frame() has turned them into the next frame's
+    histories (taa_hist = the TAA output, ...), decoded to float32 and written as out_dir/<name>.npy.  An image of more
+    than DUMP_SAMPLE texels is reduced to the texels at DUMP_SAMPLE fixed positions (seeded, in raster order): an array
+    [DUMP_SAMPLE, channels]; a smaller one is written whole, [h, w, channels]."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, image in names.items():
+        img = frame.download(image).decode(0)
+        h, w, c = img.shape
+        if h * w > DUMP_SAMPLE:
+            at = np.sort(np.random.default_rng(20261016).choice(h * w, DUMP_SAMPLE, replace=False))
+            img = img.reshape(h * w, c)[at]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(img, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,6 +209,13 @@ def main():
                     help="synthetic scene: 'flat' = one roughness per object (the frozen scene the metric is quoted on); 'textured' = "
                          "roughness perturbed per texel (VKR_SYNTH_TEXTURED_ROUGHNESS): the blur's sigma varies inside every wavefront")
     ap.add_argument("--shading", action="store_true", help="add the deferred-shading composite (SURVEY 8(f) #1) between GTAO and TAA")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-pass calibration run, the roofline (an event pair around the dominant pass in "
+                         "the timed steps, the stream-read microbenchmark, the committed PMC digests), the per-step event times, the "
+                         "exchange diagnostics of N > 1, the timed loops with the skips off and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, rank 0's window); "
+                         f"images of more than {DUMP_SAMPLE} texels as a fixed, seeded sample of that many texels")
     args = ap.parse_args()
     if args.config is None:
         args.config = "c2" if args.gpus == 1 else "c4"
@@ -360,51 +391,52 @@ def main():
             tiled.flush()
             barrier()
 
-    # Per-pass times come from a short calibration run with an event pair around every pass; the timed region then
+    # --full: per-pass times come from a short calibration run with an event pair around every pass; the timed region then
     # keeps only the pair around the dominant pass (the roofline's live measurement): an event record costs ~3.5 us
-    # of queue time, and nine pairs per frame would slow the 1 ms frame that is being measured by 7 %.
+    # of queue time, and nine pairs per frame would slow the 1 ms frame that is being measured by 7 %.  A plain run times
+    # the steps alone.
     CAL_STEPS = 10
-    frame.enable_task_timing(True)
-    timed_waits = tiled.native and frame.tiled_handle is not None and comm is not None
-    if timed_waits:  # how long the compute stream stands still for each exchange (diagnostics of the multi-GPU wire)
-        frame.tiled_time_waits(True)
-    for _ in range(CAL_STEPS):
-        tiled.step()
-    tiled.flush()
-    barrier()
-    exchange_wait_ms = None
-    if timed_waits:
-        mine = {k: v / CAL_STEPS for k, v in frame.tiled_wait_times().items()}
-        frame.tiled_time_waits(False)
-        every = [None] * world
-        if world > 1:
+    exchange_wait_ms = exchange_bytes_per_rank = None
+    if args.full:
+        frame.enable_task_timing(True)
+        timed_waits = tiled.native and frame.tiled_handle is not None and comm is not None
+        if timed_waits:  # how long the compute stream stands still for each exchange (diagnostics of the multi-GPU wire)
+            frame.tiled_time_waits(True)
+        for _ in range(CAL_STEPS):
+            tiled.step()
+        tiled.flush()
+        barrier()
+        if timed_waits:
+            mine = {k: v / CAL_STEPS for k, v in frame.tiled_wait_times().items()}
+            frame.tiled_time_waits(False)
+            every = [None] * world
+            if world > 1:
+                dist.all_gather_object(every, mine)
+            else:
+                every = [mine]
+            exchange_wait_ms = {k: [round(e[k], 4) for e in every] for k in mine}  # per rank
+        # bytes every rank RECEIVES per frame over the wire: the other ranks' shares of the gathered surfaces + its halo rows
+        if tiled.native and frame.tiled_handle is not None and world > 1:
+            by_gather = frame.albedo_by_gather
+            mine = {"hiz": sum(p[2] for p in frame.tiled_gather_parts(0)), "albedo": sum(p[2] for p in frame.tiled_gather_parts(1)) if by_gather else 0,
+                    "halo": sum(p[3] for s_ in range(3) for p in frame.tiled_halo_peers(s_)), "hit": 0 if by_gather else frame.tiled_hit_bytes()}
+            every = [None] * world
             dist.all_gather_object(every, mine)
-        else:
-            every = [mine]
-        exchange_wait_ms = {k: [round(e[k], 4) for e in every] for k in mine}  # per rank
-    # bytes every rank RECEIVES per frame over the wire: the other ranks' shares of the gathered surfaces + its halo rows
-    exchange_bytes_per_rank = None
-    if tiled.native and frame.tiled_handle is not None and world > 1:
-        by_gather = frame.albedo_by_gather
-        mine = {"hiz": sum(p[2] for p in frame.tiled_gather_parts(0)), "albedo": sum(p[2] for p in frame.tiled_gather_parts(1)) if by_gather else 0,
-                "halo": sum(p[3] for s_ in range(3) for p in frame.tiled_halo_peers(s_)), "hit": 0 if by_gather else frame.tiled_hit_bytes()}
-        every = [None] * world
-        dist.all_gather_object(every, mine)
-        # hit colours: by request / reply (4-byte requests in + 16-byte replies in, last frame's segments) or the all-gathered albedo
-        exchange_bytes_per_rank = [{"hiz_gather_in": sum(e["hiz"] for e in every) - every[r]["hiz"],
-                                    "hit_colours_in": (sum(e["albedo"] for e in every) - every[r]["albedo"]) if by_gather else every[r]["hit"],
-                                    "hit_colours": "all-gather of the albedo" if by_gather else "request / reply",
-                                    "halo_in": every[r]["halo"]} for r in range(world)]
-        for e in exchange_bytes_per_rank:
-            e["total_in"] = e["hiz_gather_in"] + e["hit_colours_in"] + e["halo_in"]
-    calibration = frame.collect_task_times()
-    per_pass_ms = {k: v[0] / CAL_STEPS for k, v in calibration.items()}          # all executions of the task in one step
-    launches_per_step = {k: v[1] / CAL_STEPS for k, v in calibration.items()}    # executions of the task per step (c5: 8 x SSR)
-    dominant = max(per_pass_ms, key=per_pass_ms.get)
-    frame.enable_task_timing(True, only=dominant)
-    # one event per step boundary on the frame's stream (= torch's current stream): the median step time of SURVEY 8(d)
+            # hit colours: by request / reply (4-byte requests in + 16-byte replies in, last frame's segments) or the all-gathered albedo
+            exchange_bytes_per_rank = [{"hiz_gather_in": sum(e["hiz"] for e in every) - every[r]["hiz"],
+                                        "hit_colours_in": (sum(e["albedo"] for e in every) - every[r]["albedo"]) if by_gather else every[r]["hit"],
+                                        "hit_colours": "all-gather of the albedo" if by_gather else "request / reply",
+                                        "halo_in": every[r]["halo"]} for r in range(world)]
+            for e in exchange_bytes_per_rank:
+                e["total_in"] = e["hiz_gather_in"] + e["hit_colours_in"] + e["halo_in"]
+        calibration = frame.collect_task_times()
+        per_pass_ms = {k: v[0] / CAL_STEPS for k, v in calibration.items()}          # all executions of the task in one step
+        launches_per_step = {k: v[1] / CAL_STEPS for k, v in calibration.items()}    # executions of the task per step (c5: 8 x SSR)
+        dominant = max(per_pass_ms, key=per_pass_ms.get)
+        frame.enable_task_timing(True, only=dominant)
+    # --full: one event per step boundary on the frame's stream (= torch's current stream): the median step time of SURVEY 8(d)
     stream = torch.cuda.current_stream(device)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.steps >= 10 else []
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full and args.steps >= 10 else []
     # The W untimed warm-up steps, immediately ahead of the timed region: everything above (balancing, the calibration run and
     # the host-side reading of its events) leaves the device idle for a moment, and the first frames after an idle gap run at a
     # lower clock (measured: a 20-step loop right after such a gap 0.682 ms per frame, the same loop in steady state 0.650).
@@ -421,14 +453,23 @@ def main():
     tiled.flush()  # the halo refreshes of the last frame are still in flight: they belong to the timed work
     barrier()
     elapsed = time.perf_counter() - t0
-    task_times = frame.collect_task_times()
-    frame.enable_task_timing(False)
+    if args.full:
+        task_times = frame.collect_task_times()
+        frame.enable_task_timing(False)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)] if marks else []
 
+    if args.dump_outputs and rank == 0:
+        # what a caller of the frame reads once the step has ended: the TAA output, the accumulated AO and the blurred
+        # reflections (c1: the GTAO main pass alone), plus the shaded colour with --shading
+        outputs = {"gtao_raw": "raw"} if args.config == "c1" else {"taa_output": "taa_hist", "ao": "acc_hist", "reflections": "blurred_hist"}
+        if args.shading:
+            outputs["shaded"] = "color_out"
+        dump_outputs(frame, outputs, args.dump_outputs)
+
     # The headline depends on the frame's content: tiles of the blur / filter without a reflection / hit skip their taps
-    # (bit-identical output).  A second, short timed loop with the skips switched off gives the content-independent number.
+    # (bit-identical output).  --full: a second, short timed loop with the skips switched off gives the content-independent number.
     noskip_ms = generic_ms = None
-    if world == 1 and args.config in ("c2", "c3", "c4", "c5") and not args.no_noskip:
+    if args.full and world == 1 and args.config in ("c2", "c3", "c4", "c5") and not args.no_noskip:
         lib = abi.product()
         before = lib.vkr_get_switches()
         NOSKIP_STEPS = max(10, min(args.steps, 20))
@@ -459,37 +500,6 @@ def main():
     if rank == 0:
         px = W * H
         tile_px = tiled.window[2] * tiled.window[3]  # pixels this rank's kernels actually process (tile + halo)
-        # One execution of a task processes the whole window once (the two launches of the Hi-Z chain are ONE
-        # DownsampleDepth task; the eight SSSR_blur executions of c5 each move the full bytes).
-        avg_launch_ms = task_times[dominant][0] / task_times[dominant][1]  # live, over the timed region
-        algo_bytes_launch = BYTES_PER_PX[dominant] * tile_px
-        achieved = algo_bytes_launch / (avg_launch_ms * 1e-3) / 1e9
-        measured_read = measured_read_bandwidth(device)
-
-        def from_profiles(fname):
-            path = os.path.join(ROOT, "profiles", fname)
-            if not os.path.exists(path):
-                return None, None
-            with open(path) as f:
-                d = json.load(f).get(args.config)  # one digest per BASELINE config
-            if not d:
-                return None, None
-            note = ""
-            if d.get("_library_sha16"):  # was the digest taken with the kernel library this run has loaded?
-                import hashlib
-
-                with open(abi.PRODUCT_LIB, "rb") as lf:
-                    mine = hashlib.sha256(lf.read()).hexdigest()[:16]
-                note = "; SAME kernel library as this run" if mine == d["_library_sha16"] else f"; digest of ANOTHER build of the kernel library ({d['_library_sha16']}, this run {mine})"
-            return d.get(dominant), f"profiles/{fname}[{args.config}]" + (f" ({d['_source']}{note})" if "_source" in d else "")
-
-        # HBM bytes / VALU-busy of the dominant kernel are NOT measured in this run: they are the committed rocprofv3
-        # --pmc digests of the same command (tools/profile_run.sh + tools/profile_digest.py --config), kept per BASELINE
-        # config and only valid for that config's own frame, the frozen scene and one GPU.
-        own_frame = world == 1 and args.material == "flat" and not args.shading and not args.raster and (W, H) == {
-            "c1": (1920, 1080), "c2": (TILE_W, TILE_H), "c3": (7680, 4320), "c4": (C4_W, C4_H), "c5": (TILE_W, TILE_H)}[args.config]
-        traffic, traffic_src = from_profiles("traffic.json") if own_frame else (None, None)
-        valu_busy, valu_src = from_profiles("valu_busy.json") if own_frame else (None, None)
         workload = {"c1": f"{W}x{H} synthetic G-buffer: GTAO main pass only (non-MIS)",
                     "c5": f"{W}x{H} synthetic G-buffer: Hi-Z downsample + 8 x SSR (trace, filter, blur) + TAA"}.get(
             args.config, f"{W}x{H} synthetic G-buffer: Hi-Z downsample + SSR (trace, filter, blur) + GTAO (main, filter, accumulate)"
@@ -525,6 +535,40 @@ def main():
                 "gbuffer": "rasterised procedural mesh scene (GbufferPass timed)" if args.raster else "analytic generator (not timed)",
                 "material": args.material + (" (one roughness per object)" if args.material == "flat" else " (roughness per texel, VKR_SYNTH_TEXTURED_ROUGHNESS)"),
             },
+        }
+    if rank == 0 and args.full:
+        # One execution of a task processes the whole window once (the two launches of the Hi-Z chain are ONE
+        # DownsampleDepth task; the eight SSSR_blur executions of c5 each move the full bytes).
+        avg_launch_ms = task_times[dominant][0] / task_times[dominant][1]  # live, over the timed region
+        algo_bytes_launch = BYTES_PER_PX[dominant] * tile_px
+        achieved = algo_bytes_launch / (avg_launch_ms * 1e-3) / 1e9
+        measured_read = measured_read_bandwidth(device)
+
+        def from_profiles(fname):
+            path = os.path.join(ROOT, "profiles", fname)
+            if not os.path.exists(path):
+                return None, None
+            with open(path) as f:
+                d = json.load(f).get(args.config)  # one digest per BASELINE config
+            if not d:
+                return None, None
+            note = ""
+            if d.get("_library_sha16"):  # was the digest taken with the kernel library this run has loaded?
+                import hashlib
+
+                with open(abi.PRODUCT_LIB, "rb") as lf:
+                    mine = hashlib.sha256(lf.read()).hexdigest()[:16]
+                note = "; SAME kernel library as this run" if mine == d["_library_sha16"] else f"; digest of ANOTHER build of the kernel library ({d['_library_sha16']}, this run {mine})"
+            return d.get(dominant), f"profiles/{fname}[{args.config}]" + (f" ({d['_source']}{note})" if "_source" in d else "")
+
+        # HBM bytes / VALU-busy of the dominant kernel are NOT measured in this run: they are the committed rocprofv3
+        # --pmc digests of the same command (tools/profile_run.sh + tools/profile_digest.py --config), kept per BASELINE
+        # config and only valid for that config's own frame, the frozen scene and one GPU.
+        own_frame = world == 1 and args.material == "flat" and not args.shading and not args.raster and (W, H) == {
+            "c1": (1920, 1080), "c2": (TILE_W, TILE_H), "c3": (7680, 4320), "c4": (C4_W, C4_H), "c5": (TILE_W, TILE_H)}[args.config]
+        traffic, traffic_src = from_profiles("traffic.json") if own_frame else (None, None)
+        valu_busy, valu_src = from_profiles("valu_busy.json") if own_frame else (None, None)
+        out.update({
             "roofline": {
                 "bound": "hbm",
                 "kernel": dominant,
@@ -562,7 +606,7 @@ def main():
                               # pipelined_step; the benchmark's G-buffer is static, so the next frame's is resident); every step runs every pass once
                               "frames_in_flight": 2 if frame.tiled_pipelined() else 1} if (tiled.native and frame.tiled_handle is not None) else None,
             "measured_read_gbps": measured_read,
-        }
+        })
         if noskip_ms is not None:
             out["ms_per_step_noskip"] = noskip_ms
             out["value_noskip"] = px / (noskip_ms * 1e-3) / 1e6
@@ -590,6 +634,7 @@ def main():
             out["value_median"] = px / (med * 1e-3) / 1e6  # rank 0's stream only: meaningful at N = 1
         if world == 1 and not args.no_cpu_baseline and args.config == "c2" and not args.shading and not args.rehearse_tiled:
             out["cpu_baseline"] = cpu_baseline(frame, setup)
+    if rank == 0:
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if world > 1:

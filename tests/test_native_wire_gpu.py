@@ -241,7 +241,7 @@ def test_bench_native_branch_between_real_processes(world, balance, tmp_path):
     env = dict(os.environ, VKR_BENCH_REHEARSE_ON_ONE_GPU="1", VKR_RCCL_LIBRARY=_stub(), VKR_STUB_RCCL_LOG=str(log), VKR_STUB_RCCL_TIMEOUT_S="120",
                VKR_BALANCE_ANY_FRAME="1" if balance else "0", VKR_BALANCE_REBUILD="1" if balance else "0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     H = 384 * world
-    rc, out, err = _launch(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2", "--frame", f"512x{H}"], env, timeout=600)
+    rc, out, err = _launch(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2", "--frame", f"512x{H}", "--full"], env, timeout=600)
     assert rc == 0, out[-2000:] + err[-3000:]
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1, f"exactly one line on stdout, got {len(lines)}: {lines[:3]}"

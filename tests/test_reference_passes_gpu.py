@@ -1,9 +1,9 @@
 """Drop-in check, executed: the REFERENCE'S OWN pass sources driving the HIP kernels.
 
-`make -C vk-renderer_amd/host refpasses` (run by __graft_entry__.build() wherever /root/reference is mounted) compiles
+`make -C oracle -f ref.mk` (run by __graft_entry__.build() wherever the reference's sources are present) compiles
 src/{downsample_pass,gtao,advanced_ssr,taa,defered_shading}.cpp of the reference, unchanged and where they lie, against the host mirror and
 links them — instead of host/passes.cpp's own implementations of those five classes — with the mirror's rendergraph, gpu:: layer
-and headless frame loop into host/build/refpasses/libvkr_host_refpasses.so.  Here one process loads that library, runs two
+and headless frame loop into oracle/_ref/libvkr_host_refpasses.so.  Here one process loads that library, runs two
 frames (reference code records every task: ten DownsampleDepth draws per frame, rand()-jittered GTAO angle pinned through
 --wrap=rand, the raw Halton table ...) and compares every output with the oracle, exactly like the host-mirror parity test.
 The built library travels to the GPU box; the reference sources do not have to.  Not an oracle: the arithmetic is the HIP
@@ -17,7 +17,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFLIB = os.path.join(ROOT, "vk-renderer_amd", "host", "build", "refpasses", "libvkr_host_refpasses.so")
+REFLIB = os.path.join(ROOT, "oracle", "_ref", "libvkr_host_refpasses.so")
 
 WORKER = textwrap.dedent("""
     import os, sys
@@ -80,7 +80,7 @@ WORKER = textwrap.dedent("""
 """) % (ROOT, ROOT)
 
 
-@pytest.mark.skipif(not os.path.exists(REFLIB), reason="host/build/refpasses/libvkr_host_refpasses.so not built (needs the reference mounted at build time)")
+@pytest.mark.skipif(not os.path.exists(REFLIB), reason="oracle/_ref/libvkr_host_refpasses.so not built (needs the reference's sources at build time)")
 @pytest.mark.parametrize("size", [(640, 360), (1920, 1080)])
 def test_reference_pass_sources_drive_the_hip_kernels(size, tmp_path, oracle_lib):
     script = tmp_path / "dropin.py"

@@ -58,7 +58,7 @@ def test_bench_rebuilds_the_frame_on_balanced_strips():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29548", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0", VKR_BALANCE_REBUILD="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse-tiled", "--frame", "1024x576", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(line) == 1, out.stdout
