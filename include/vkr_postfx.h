@@ -446,6 +446,55 @@ int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, const vkr_img
                       const vkr_img* material, const vkr_img* velocity,
                       const vkr_synth_params* params, void* stream);
 
+/* ---- ray-traced AO (gtao.cpp:150-196 + gtao/rt_main.frag) over the project's own acceleration structure ---------------------
+ * MI355X has no ray-tracing hardware: the scene's triangles, transformed to world space on the host, go into one bounding-
+ * volume hierarchy (binned SAH, built on the host: deterministic, the same triangles always give the same bytes), traversed in
+ * software.  Every ray is an ANY-hit query of the segment origin + t * dir, t in [tmin, tmax], against all triangles: opaque,
+ * no facing culling, nothing but "was anything hit" is reported.  The frozen fp32 triangle test (DESIGN_NUMERICS.md, the one
+ * device helper both entries below use): Moller-Trumbore in a fixed operation order, det == 0 a miss, inclusive edges
+ * (u >= 0, v >= 0, u + v <= 1), tmin <= t <= tmax, and the computed point origin + t * dir inside the triangle's bounding box
+ * widened by (max |coordinate| + 1) * 2^-12 — which makes every box test of the traversal provably conservative, so the
+ * result does not depend on the hierarchy.                                                                                  */
+typedef struct vkr_accel_node {  /* 32 bytes; count == 0: interior node whose children are nodes first and first + 1    */
+  float    lo[3];                /* count > 0: leaf of the triangle records [first, first + count)                        */
+  uint32_t first;
+  float    hi[3];
+  uint32_t count;
+} vkr_accel_node;
+typedef struct vkr_accel_tri {   /* 64 bytes: v0, its edges e1 = v1 - v0, e2 = v2 - v0 (fp32), the widened box, and the     */
+  float    v0[3];                /* index of the triangle in the caller's input                                            */
+  uint32_t index;
+  float    e1[3], e2[3];
+  float    lo[3], hi[3];
+} vkr_accel_tri;
+typedef struct vkr_accel vkr_accel;
+/* Pure host function, no GPU: the hierarchy of tri_count world-space triangles (tri_vertices: tri_count x 3 vertices x xyz,
+ * host memory) into caller-provided host arrays: at most max(1, 2 * tri_count - 1) nodes (node_capacity), exactly tri_count
+ * triangle records.  *node_count receives the number of nodes written (0 for an empty scene).                                 */
+int vkr_accel_layout(const float* tri_vertices, uint32_t tri_count, vkr_accel_node* nodes, uint32_t node_capacity,
+                     vkr_accel_tri* tris, uint32_t* node_count);
+/* layout + upload (synchronous, allocates device memory): the handle the ray-query kernels take                               */
+int vkr_accel_create(const float* tri_vertices, uint32_t tri_count, vkr_accel** out);
+int vkr_accel_destroy(vkr_accel* accel);
+int vkr_accel_info(const vkr_accel* accel, uint32_t* node_count, uint32_t* tri_count);
+/* any-hit of n arbitrary rays (origins, dirs: device, n x xyz floats): out_hit[i] = 1 when the frozen test reports a hit for
+ * some triangle, else 0.  A wave of 64 rays traverses the hierarchy together (node order on a stack in LDS).                   */
+int vkr_accel_query(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                    uint32_t* out_hit, void* stream);
+/* GTAORTParams, gtao.hpp:20-26 / rt_main.frag:11-17 */
+typedef struct vkr_gtao_rt_params {
+  vkr_mat4 camera_to_world;
+  float fovy, aspect, znear, zfar;
+} vkr_gtao_rt_params;
+typedef struct vkr_gtao_rt_push { float rotation; } vkr_gtao_rt_push;  /* rt_main.frag:29-31 */
+/* program "gtao_rt_main": gtao.cpp:150-196 + gtao/rt_main.frag — full-screen triangle into `raw` (RGBA16F, half resolution).
+ * Bindings 0 GTAORTParams, 1 depth (view mip depth_lod), 2 normal (full resolution), 3 the acceleration structure, 4 the 64
+ * random directions (device, 64 x vec4, gtao.cpp:415-443); push: rotation.  Per pixel: (2 * sum / 64, 1, 0, 0) of the
+ * 64 visibility-weighted cosines of rays 0.2 long; sky (depth >= 1): (0, 1, 0, 0).  The 16 (cos, sin) pairs of
+ * 2 PI (rotation + k / 16) are evaluated on the host.  One wave per pixel, one lane per direction.                        */
+int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel,
+                     const float* directions, const vkr_img* out_raw, const vkr_gtao_rt_push* push, void* stream);
+
 /* Multi-GPU exchange helper (the reference is single-GPU, so there is no program this
  * replaces): copies `count` pitch-linear byte rectangles on `stream`, VKR_MAX_RECTS per launch.  Used to pack
  * a tile's surfaces for the all-gather, to scatter the gathered tiles into the whole-frame images and to

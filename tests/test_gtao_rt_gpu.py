@@ -1,0 +1,189 @@
+"""Program gtao_rt_main (gtao.cpp:150-196, gtao/rt_main.frag) on the GPU: known answers, parity with the numpy restatement of
+steps 1-6 (tests/gtao_rt_reference.py) on the rasterised procedural scene, and the frame stage STAGE_GTAO_RT (main.cpp's
+use_rt_ao branch) with its error cases.
+
+Parity: the restatement takes the G-buffer downloaded from the GPU and the frame's own camera_to_world and follows the
+kernel's fp32 operation order (fused multiply-adds of the numeric contract emulated exactly, the frozen triangle test,
+the wave's butterfly sum), so the images must agree under tests/parity.py's rule with no exception."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from vk_renderer_amd import abi, host
+from vk_renderer_amd import scene as scn
+from vk_renderer_amd.camera import FrameSetup
+from vk_renderer_amd.images import ImageBuf
+
+import gtao_rt_reference as ref
+from parity import mismatches, report
+
+F32 = np.float32
+
+
+def _directions_device():
+    import torch
+
+    dirs = np.zeros((64, 4), F32)
+    assert host.lib().vkrh_gtao_directions(dirs.ctypes.data, 64) == 0
+    return dirs, torch.from_numpy(dirs).to("cuda")
+
+
+def _launch(params, depth_desc, normal_desc, accel, dirs_dev, out, rotation):
+    import torch
+
+    lib = abi.product()
+    push = abi.GtaoRtPush(rotation)
+    rc = lib.vkr_gtao_rt_main(C.byref(params), C.byref(depth_desc), C.byref(normal_desc), accel.handle, dirs_dev.data_ptr(),
+                              C.byref(out.desc()), C.byref(push), torch.cuda.current_stream().cuda_stream)
+    abi.check(rc, lib)
+    torch.cuda.synchronize()
+    return out.raw(0, out.to_host())
+
+
+def _raster_frame(W, H, sc):
+    import torch
+
+    setup = FrameSetup(W, H)
+    frame = host.HostFrame(setup, device="cuda")
+    frame.load_scene(sc)
+    frame.run(host.STAGE_RASTER | host.STAGE_DOWNSAMPLE)
+    torch.cuda.synchronize()
+    return setup, frame
+
+
+def _cam(params):
+    return np.array(params.camera_to_world.m, F32).reshape(4, 4).T
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", [(256, 144), (640, 360)])
+def test_parity_with_numpy_restatement(W, H):
+    sc = scn.procedural_scene(detail=16)
+    setup, frame = _raster_frame(W, H, sc)
+    try:
+        params = frame.gtao_rt_params()
+        dirs, dirs_dev = _directions_device()
+        tris = abi.scene_triangles(sc)
+        accel = abi.Accel(tris)
+        out = ImageBuf(abi.FMT_RGBA16_SFLOAT, W // 2, H // 2, device="cuda")
+        rotation = 0.3
+        got = _launch(params, frame.image("depth", 1, 1), frame.image("normal"), accel, dirs_dev, out, rotation)
+        depth_bits = frame.download("depth").raw(1)[..., 0]
+        normal_codes = frame.download("normal").raw(0)
+        ar = ref.Arith(int(abi.product().vkr_numeric_contract()))
+        want = ref.gtao_rt(ar, depth_bits, normal_codes, (_cam(params), params.fovy, params.aspect, params.znear, params.zfar),
+                           rotation, dirs, tris, W // 2, H // 2)
+        n, _ = report(f"gtao_rt {W}x{H}", abi.FMT_RGBA16_SFLOAT, got.astype(F32), want.astype(F32))
+        assert n == 0
+        occ = want[..., 0].astype(F32)
+        live = want[..., 1] == 1
+        assert (occ[live] > 0).any() and (occ[live] < occ[live].max()).any(), "the scene occludes some rays and not others"
+        accel.close()
+    finally:
+        frame.close()
+
+
+@pytest.mark.gpu
+def test_known_answers_far_geometry_and_sky():
+    """No triangle within reach: every non-sky pixel is 2/64 * sum max(dir_i.z, 0); sky pixels are (0, 1, 0, 0)."""
+    W, H = 256, 144
+    sc = scn.procedural_scene(detail=8)
+    setup, frame = _raster_frame(W, H, sc)
+    try:
+        params = frame.gtao_rt_params()
+        dirs, dirs_dev = _directions_device()
+        depth_bits = frame.download("depth").raw(1)[..., 0]
+        normal_codes = frame.download("normal").raw(0)
+        ar = ref.Arith(int(abi.product().vkr_numeric_contract()))
+        sky = ref.pixel_setup(ar, depth_bits, normal_codes, _cam(params), params.fovy, params.aspect, params.znear, params.zfar,
+                              0.0, W // 2, H // 2)[0]
+        expected = 2.0 / 64.0 * float(np.maximum(dirs[:, 2].astype(np.float64), 0.0).sum())
+        for tris in (np.array([[[1000, 1000, 1000], [1001, 1000, 1000], [1000, 1001, 1000]]], F32), np.zeros((0, 3, 3), F32)):
+            accel = abi.Accel(tris)
+            out = ImageBuf(abi.FMT_RGBA16_SFLOAT, W // 2, H // 2, device="cuda")
+            got = _launch(params, frame.image("depth", 1, 1), frame.image("normal"), accel, dirs_dev, out, 0.0).astype(F32)
+            accel.close()
+            live = ~sky
+            assert live.sum() > 0
+            ref_img = np.full(got[live].shape, [expected, 1, 0, 0], F32)
+            assert int(mismatches(abi.FMT_RGBA16_SFLOAT, got[live], ref_img).sum()) == 0
+            if sky.any():
+                assert np.array_equal(got[sky], np.tile(np.array([0, 1, 0, 0], F32), (int(sky.sum()), 1)))
+    finally:
+        frame.close()
+
+
+@pytest.mark.gpu
+def test_known_answer_closed_slot_is_black():
+    """A pixel inside a closed box of half-size 0.05 around its surface point: every 0.2-long ray hits a wall or the
+    ceiling (or the floor), so the pixel is exactly 0."""
+    import torch
+
+    w, h = 16, 16
+    depth = ImageBuf(abi.FMT_D24_UNORM_S8, 2 * w, 2 * h, 2)
+    depth.set_raw(np.full((2 * h, 2 * w, 1), 0x800000, np.uint32), 0)
+    depth.set_raw(np.full((h, w, 1), 0x800000, np.uint32), 1)
+    normal = ImageBuf(abi.FMT_RG16_UNORM, 2 * w, 2 * h)
+    normal.set_raw(np.full((2 * h, 2 * w, 2), 32768, np.uint16), 0)
+    ddev = ImageBuf(abi.FMT_D24_UNORM_S8, 2 * w, 2 * h, 2, device="cuda")
+    ddev.upload(depth.to_host())
+    ndev = ImageBuf(abi.FMT_RG16_UNORM, 2 * w, 2 * h, device="cuda")
+    ndev.upload(normal.to_host())
+    params = abi.GtaoRtParams(abi.Mat4.from_np(np.eye(4)), 1.0471976, 1.0, 0.05, 80.0)
+    ar = ref.Arith(int(abi.product().vkr_numeric_contract()))
+    world = ref.pixel_setup(ar, depth.raw(1)[..., 0], normal.raw(0), np.eye(4, dtype=F32), params.fovy, params.aspect,
+                            params.znear, params.zfar, 0.0, w, h)[1]
+    c = world[h // 2, w // 2].astype(F32)
+    s = F32(0.05)
+    corners = np.array([[x, y, z] for x in (-s, s) for y in (-s, s) for z in (-s, s)], F32) + c
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tris = np.array([[corners[a], corners[b], corners[cc]] for q in quads for a, b, cc in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))], F32)
+    accel = abi.Accel(tris)
+    dirs, dirs_dev = _directions_device()
+    out = ImageBuf(abi.FMT_RGBA16_SFLOAT, w, h, device="cuda")
+    got = _launch(params, ddev.desc(1, 1), ndev.desc(), accel, dirs_dev, out, 0.0).astype(F32)
+    accel.close()
+    assert got[h // 2, w // 2, 0] == 0.0 and got[h // 2, w // 2, 1] == 1.0
+    assert got[0, 0, 0] > 0.5  # a pixel far from the box sees the open hemisphere
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_frame_stage():
+    import torch
+
+    W, H = 256, 144
+    sc = scn.procedural_scene(detail=16)
+    setup, frame = _raster_frame(W, H, sc)
+    try:
+        frame.run(host.STAGE_GTAO_RT)
+        torch.cuda.synchronize()
+        assert frame.last_tasks() == ["GTAO_rt_main", "GTAO_filter", "GTAO_accumulate"]
+        raw = frame.download("raw").raw(0).astype(F32)
+        # the same inputs through the C-ABI directly (the frame pins the rotation to its angle jitter: 0)
+        params = frame.gtao_rt_params()
+        dirs, dirs_dev = _directions_device()
+        accel = abi.Accel.from_scene(sc)
+        out = ImageBuf(abi.FMT_RGBA16_SFLOAT, W // 2, H // 2, device="cuda")
+        direct = _launch(params, frame.image("depth", 1, 1), frame.image("normal"), accel, dirs_dev, out, 0.0).astype(F32)
+        accel.close()
+        assert np.array_equal(raw.view(np.uint32), direct.view(np.uint32))
+        acc = frame.download("acc_ao").decode(0)
+        assert np.isfinite(acc).all()
+        with pytest.raises(RuntimeError, match="together with VKRH_STAGE_GTAO"):
+            frame.run(host.STAGE_GTAO_RT | host.STAGE_GTAO)
+    finally:
+        frame.close()
+    bare = host.HostFrame(FrameSetup(W, H), device="cuda")
+    try:
+        with pytest.raises(RuntimeError, match="without a loaded scene"):
+            bare.run(host.STAGE_GTAO_RT)
+    finally:
+        bare.close()
+    tiled = host.HostFrame(FrameSetup(W, H), device="cuda", tiled=True)
+    try:
+        with pytest.raises(RuntimeError, match="tiled frame"):
+            tiled.run(host.STAGE_GTAO_RT)
+    finally:
+        tiled.close()

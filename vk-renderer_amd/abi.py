@@ -200,6 +200,24 @@ class HitSources(C.Structure):  # vkr_hit_sources
                 ("normal_width", C.c_uint32), ("normal_height", C.c_uint32), ("normal_row0", C.c_uint32), ("normal_row1", C.c_uint32)]
 
 
+# ---- ray-traced AO: the acceleration structure (vkr_accel_*) and program gtao_rt_main ----
+class AccelNode(C.Structure):  # vkr_accel_node
+    _fields_ = [("lo", C.c_float * 3), ("first", C.c_uint32), ("hi", C.c_float * 3), ("count", C.c_uint32)]
+
+
+class AccelTri(C.Structure):  # vkr_accel_tri
+    _fields_ = [("v0", C.c_float * 3), ("index", C.c_uint32), ("e1", C.c_float * 3), ("e2", C.c_float * 3),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+class GtaoRtParams(C.Structure):  # vkr_gtao_rt_params == GTAORTParams
+    _fields_ = [("camera_to_world", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
+
+
+class GtaoRtPush(C.Structure):  # vkr_gtao_rt_push
+    _fields_ = [("rotation", C.c_float)]
+
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -315,6 +333,15 @@ def product():
         lib.vkr_last_error.restype = C.c_char_p
         lib.vkr_format_bytes.argtypes = [C.c_uint32]
         lib.vkr_format_bytes.restype = C.c_uint32
+        # ray-traced AO (no twin in the oracle: its checker is the numpy restatement of tests/test_gtao_rt_gpu.py)
+        lib.vkr_accel_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)]
+        lib.vkr_accel_create.argtypes = [C.c_void_p, C.c_uint32, P(C.c_void_p)]
+        lib.vkr_accel_destroy.argtypes = [C.c_void_p]
+        lib.vkr_accel_info.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]
+        lib.vkr_accel_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.vkr_gtao_rt_main.argtypes = [P(GtaoRtParams), _IMG, _IMG, C.c_void_p, C.c_void_p, _IMG, P(GtaoRtPush), C.c_void_p]
+        for name in ("accel_layout", "accel_create", "accel_destroy", "accel_info", "accel_query", "gtao_rt_main"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
         _product = lib
     return _product
 
@@ -397,3 +424,77 @@ class Comm:
         if self.handle:
             check(product().vkr_comm_destroy(C.c_void_p(self.handle)), product())
             self.handle = None
+
+
+# ---- the scene's acceleration structure, for tests and tools -------------------------------------------------------------
+def scene_triangles(sc):
+    """World-space triangles of a scene.Scene as (n, 3, 3) float32, in the order the host mirror's
+    scene::SceneAccelerationStructure puts them into its structure (draw by draw, the draw's index range, vertex_offset added
+    to every index), each vertex transformed in fp32 as ((m00 x + m01 y) + m02 z) + m03 per row (scene/scene_as.hpp)."""
+    import numpy as np
+
+    out = []
+    for d in sc.draws:
+        m = np.asarray(sc.transforms[d["transform"]][0], dtype=np.float32)
+        n = d["index_count"] // 3 * 3
+        idx = sc.indices[d["index_offset"]:d["index_offset"] + n].astype(np.int64) + d["vertex_offset"]
+        p = sc.vertices[idx, :3].astype(np.float32)
+        w = np.empty_like(p)
+        for r in range(3):
+            w[:, r] = ((m[r, 0] * p[:, 0] + m[r, 1] * p[:, 1]) + m[r, 2] * p[:, 2]) + m[r, 3]
+        out.append(w.reshape(-1, 3, 3))
+    return np.concatenate(out) if out else np.zeros((0, 3, 3), np.float32)
+
+
+def accel_layout(triangles):
+    """vkr_accel_layout on the host (no GPU): -> (nodes, tris) as numpy structured copies of the records"""
+    import numpy as np
+
+    tri = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    n = len(tri)
+    cap = max(1, 2 * n - 1)
+    nodes = (AccelNode * cap)()
+    recs = (AccelTri * max(1, n))()
+    count = C.c_uint32(0)
+    lib = product()
+    check(lib.vkr_accel_layout(tri.ctypes.data if n else None, n, nodes, cap, recs, C.byref(count)), lib)
+    node_arr = np.frombuffer(bytes(nodes), dtype=np.uint8).reshape(cap, C.sizeof(AccelNode))[:count.value].copy()
+    tri_arr = np.frombuffer(bytes(recs), dtype=np.uint8).reshape(max(1, n), C.sizeof(AccelTri))[:n].copy()
+    return node_arr, tri_arr
+
+
+class Accel:
+    """vkr_accel_create / _destroy around world-space triangles ((n, 3, 3) float32, e.g. scene_triangles(sc))."""
+
+    def __init__(self, triangles):
+        import numpy as np
+
+        tri = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+        self.lib = product()
+        self.handle = C.c_void_p()
+        check(self.lib.vkr_accel_create(tri.ctypes.data if len(tri) else None, len(tri), C.byref(self.handle)), self.lib)
+
+    @classmethod
+    def from_scene(cls, sc):
+        return cls(scene_triangles(sc))
+
+    def info(self):
+        nodes, tris = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.vkr_accel_info(self.handle, C.byref(nodes), C.byref(tris)), self.lib)
+        return nodes.value, tris.value
+
+    def query(self, origins, dirs, tmin, tmax, out, stream=None):
+        """origins, dirs: device tensors (n, 3) float32; out: device tensor (n,) int32 / uint32"""
+        n = int(origins.shape[0])
+        check(self.lib.vkr_accel_query(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
+
+    def close(self):
+        if self.handle:
+            self.lib.vkr_accel_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -15,6 +15,7 @@ STAGE_SHADING, STAGE_BRDF_LUT, STAGE_GTAO_MAIN_ONLY = 256, 512, 1024
 STAGE_GTAO_GRAPHICS, STAGE_GTAO_DEINTERLEAVED, STAGE_SCREEN_TRACE = 2048, 4096, 8192
 STAGE_SSR_CLASSIFIED, STAGE_SSR_TRACE, STAGE_SSR_RESOLVE = 16384, 32768, 65536
 STAGE_RASTER = 131072
+STAGE_GTAO_RT = 1 << 21  # ray-traced AO (main.cpp:379-388 use_rt_ao): needs load_scene(); not with STAGE_GTAO, not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -115,6 +116,14 @@ def lib():
         l.vkrh_tiled_wait_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         l.vkrh_balance_rows.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         l.vkrh_balance_rows.restype = C.c_int
+        # ray-traced AO entries: typed where the loaded library exports them.  VKR_HOST_LIB may name a build of the mirror made
+        # by another recipe (tests/test_reference_passes_gpu.py loads oracle/_ref/libvkr_host_refpasses.so) that predates them;
+        # frames that never ask for them must still load it.  Calling one that is missing raises AttributeError.
+        for name, args in (("vkrh_gtao_rt_params", [C.c_void_p, C.POINTER(abi.GtaoRtParams)]),
+                           ("vkrh_gtao_directions", [C.c_void_p, C.c_uint32]),
+                           ("vkrh_selftest_ray_query", [C.c_char_p, C.c_uint32])):
+            if hasattr(l, name):
+                getattr(l, name).argtypes = args
         _lib = l
     return _lib
 
@@ -260,6 +269,12 @@ class HostFrame:
                 tex[i].levels[m] = a.ctypes.data
         self._check(lib().vkrh_load_scene(self.h, C.c_void_p(verts.ctypes.data), len(verts), C.c_void_p(idx.ctypes.data), len(idx),
                                           draws, len(sc.draws), tex, len(sc.textures)))
+
+    def gtao_rt_params(self):
+        """abi.GtaoRtParams that STAGE_GTAO_RT uses for the current camera (camera_to_world = inverse(view))"""
+        p = abi.GtaoRtParams()
+        self._check(lib().vkrh_gtao_rt_params(self.h, C.byref(p)))
+        return p
 
     def set_gathered_mips(self, n):
         """tiled frames: how many whole-frame Hi-Z mips (image mips 1..n) arrive by all-gather; STAGE_HIZ_TAIL rebuilds the rest"""

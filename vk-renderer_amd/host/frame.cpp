@@ -21,6 +21,7 @@
 #include "downsample_pass.hpp"
 #include "gtao.hpp"
 #include "image_readback.hpp"
+#include "scene/scene_as.hpp"
 #include "scene_renderer.hpp"
 #include "screen_trace.hpp"
 #include "synthetic_gbuffer.hpp"
@@ -55,6 +56,7 @@ struct PostFxFrame {
   ReadBackSystem readback;
   std::unique_ptr<scene::CompiledScene> loaded_scene;
   std::unique_ptr<SceneRenderer> scene_renderer;
+  std::unique_ptr<scene::SceneAccelerationStructure> scene_as;  // main.cpp:257-258, built by vkrh_load_scene
 
   DrawTAAParams draw_params{};
   glm::mat4 projection, view, prev_view;
@@ -62,9 +64,9 @@ struct PostFxFrame {
   std::string task_names, task_lanes;
 
   explicit PostFxFrame(const vkrh_config& c)
-      : cfg{c}, graph{c.stream}, init{graph, c}, transfer_init{graph},
+      : cfg{c}, graph{c.stream, gpu::DeviceConfig{true}}, init{graph, c}, transfer_init{graph},  // main.cpp:73: a ray-query device
         gbuffer{graph, c.width, c.height},
-        gtao{graph, c.width, c.height, false, true},  // main.cpp:265: (graph, W, H, USE_RAY_QUERY = 0, half_res = 1)
+        gtao{graph, c.width, c.height, true, true},  // main.cpp:265 with USE_RAY_QUERY = 1: (graph, W, H, true, half_res = 1)
         ssr{graph, c.width, c.height},
         taa_pass{graph, c.width, c.height},
         shading_pass{graph, nullptr},
@@ -91,8 +93,21 @@ struct PostFxFrame {
     has_camera = true;
   }
 
+  // main.cpp:369-371
+  GTAORTParams gtao_rt_params() const {
+    const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
+    return GTAORTParams{glm::inverse(view), fazz.x, fazz.y, fazz.z, fazz.w};
+  }
+
   void run(uint32_t mask) {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
+    if (mask & VKRH_STAGE_GTAO_RT) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT on a tiled frame (ray-traced AO runs on one GPU)"};
+      if (mask & VKRH_STAGE_GTAO)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT together with VKRH_STAGE_GTAO (both write GTAO's raw, filtered and accumulated images)"};
+      if (!scene_as || !scene_as->tlas)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
+    }
     const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
     if (mask & VKRH_STAGE_BRDF_LUT) ssr.preintegrate_brdf(graph);
@@ -135,6 +150,11 @@ struct PostFxFrame {
       gtao.add_main_pass(graph, gtao_params, gbuffer.depth, gbuffer.normal, gbuffer.material, ssr.get_preintegrated_pdf());
     if (mask & VKRH_STAGE_GTAO) {                                                           // main.cpp:384-388
       gtao.add_main_pass(graph, gtao_params, gbuffer.depth, gbuffer.normal, gbuffer.material, ssr.get_preintegrated_pdf());
+      gtao.add_filter_pass(graph, gtao_params, gbuffer.depth);
+      gtao.add_accumulate_pass(graph, draw_params, gbuffer);
+    }
+    if (mask & VKRH_STAGE_GTAO_RT) {                                                        // main.cpp:379-388 (use_rt_ao)
+      gtao.add_main_rt_pass(graph, gtao_rt_params(), scene_as->tlas, gbuffer.depth, gbuffer.normal);
       gtao.add_filter_pass(graph, gtao_params, gbuffer.depth);
       gtao.add_accumulate_pass(graph, draw_params, gbuffer);
     }
@@ -940,11 +960,31 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
       for (uint32_t m = 0; m < textures[i].mip_levels; m++) tex[i].levels[m] = textures[i].levels[m];
     }
     f->scene_renderer.reset();
+    f->scene_as.reset();
     f->loaded_scene.reset(new scene::CompiledScene(scene::make_scene((const scene::Vertex*)vertices, vertex_count, indices, index_count,
                                                                      flat.data(), draw_count, tex.data(), texture_count)));
     f->scene_renderer.reset(new SceneRenderer(*f->loaded_scene));
     f->scene_renderer->init_pipeline(f->graph, f->gbuffer);  // main.cpp:256-259
     f->scene_renderer->update_scene();
+    gpu::TransferCmdPool transfer_pool{f->graph.get_stream()};  // main.cpp:257-258
+    f->scene_as.reset(new scene::SceneAccelerationStructure);
+    f->scene_as->build(transfer_pool, *f->loaded_scene);
+  });
+}
+int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    if (!f || !out) throw std::runtime_error{"NULL argument"};
+    if (!f->has_camera) throw std::runtime_error{"vkrh_gtao_rt_params: camera not set"};
+    const GTAORTParams p = f->gtao_rt_params();
+    std::memcpy(out, &p, sizeof(*out));
+  });
+}
+int vkrh_gtao_directions(float* out, uint32_t count) {
+  return guarded([&] {
+    if (!out && count) throw std::runtime_error{"NULL argument"};
+    const auto dirs = gtao_random_directions(count);
+    std::memcpy(out, dirs.data(), sizeof(glm::vec4) * dirs.size());
   });
 }
 int vkrh_pin_screen_trace(void* frame, float angle_jitter, float random_offset, uint32_t frame_count) {
@@ -1142,6 +1182,46 @@ int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
     gpu::UniformBufferPool pool;
     struct Big { char b[6000]; };
     pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>();
+  });
+  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
+  return 0;
+}
+
+int vkrh_selftest_ray_query(char* buf, uint32_t buf_size) {
+  std::string out;
+  auto expect = [&](const char* name, std::function<void()> f) {
+    try { f(); out += std::string{name} + ": no error\n"; }
+    catch (const std::exception& e) { out += std::string{name} + ": " + e.what() + "\n"; }
+  };
+  const GTAORTParams params{glm::mat4{1.f}, 1.0f, 1.0f, 0.05f, 80.f};
+  auto images = [](rendergraph::RenderGraph& g, rendergraph::ImageResourceId& depth, rendergraph::ImageResourceId& normal) {
+    const auto u = VK_IMAGE_USAGE_SAMPLED_BIT;
+    depth = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 64, 64, 1, 7, 1}, VK_IMAGE_TILING_OPTIMAL, u);
+    normal = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 64, 64}, VK_IMAGE_TILING_OPTIMAL, u);
+  };
+  expect("default_graph", [] { rendergraph::RenderGraph g; GTAO gtao{g, 64, 64, true}; });
+  expect("ray_query_graph", [] { rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}}; GTAO gtao{g, 64, 64, true}; });
+  expect("device_config", [] {
+    rendergraph::RenderGraph a, b{nullptr, gpu::DeviceConfig{true}};
+    if (a.get_device_config().use_ray_query || !b.get_device_config().use_ray_query) throw std::runtime_error{"device config not kept per graph"};
+  });
+  expect("null_tlas", [&] {
+    rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}};
+    GTAO gtao{g, 64, 64, true};
+    rendergraph::ImageResourceId depth, normal;
+    images(g, depth, normal);
+    gtao.add_main_rt_pass(g, params, nullptr, depth, normal);
+  });
+  expect("rt_pass_without_ray_query", [&] {
+    rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}};
+    GTAO gtao{g, 64, 64, false};
+    rendergraph::ImageResourceId depth, normal;
+    images(g, depth, normal);
+    gtao.add_main_rt_pass(g, params, (VkAccelerationStructureKHR)&gtao, depth, normal);
+  });
+  expect("null_accel_binding", [] {
+    gpu::CmdContext cmd;
+    gpu::write_set(cmd.allocate_set(), gpu::AccelerationStructBinding{3, nullptr});
   });
   if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
   return 0;

@@ -51,6 +51,10 @@ enum {
   VKRH_STAGE_SSR_TRACE_HEAD     = 1u << 18,
   VKRH_STAGE_SSR_TRACE_RESUME   = 1u << 19,
   VKRH_STAGE_DOWNSAMPLE_NEXT    = 1u << 20,  /* the downsample of the NEXT frame into the G-buffer's second set (pipelined tiled frame) */
+  /* main.cpp:379-388, the use_rt_ao branch: gtao.add_main_rt_pass against the loaded scene's acceleration structure (built by
+   * vkrh_load_scene), add_filter_pass, add_accumulate_pass.  One GPU only (not on a tiled frame), not together with
+   * VKRH_STAGE_GTAO (both write GTAO's images), and only after vkrh_load_scene.                                           */
+  VKRH_STAGE_GTAO_RT            = 1u << 21,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -81,6 +85,12 @@ typedef struct vkrh_scene_texture {
 } vkrh_scene_texture;
 int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
                     const vkrh_scene_draw* draws, uint32_t draw_count, const vkrh_scene_texture* textures, uint32_t texture_count);
+/* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
+int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
+/* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */
+int vkrh_gtao_directions(float* out, uint32_t count);
+/* the ray-query cases of the host mirror's error paths (no kernel is launched; writes "case: message" lines into buf) */
+int vkrh_selftest_ray_query(char* buf, uint32_t buf_size);
 /* pin ScreenSpaceTrace's per-frame randoms (screen_trace.cpp:49-53) */
 int vkrh_pin_screen_trace(void* frame, float angle_jitter, float random_offset, uint32_t frame_count);
 /* 1 when the program table of the host layer knows `name` (a name of src/shaders/config.json or one of this path's own) */

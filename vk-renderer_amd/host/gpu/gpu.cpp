@@ -191,8 +191,11 @@ static const ImageViewObject& view_of(VkImageView v) {
   if (!v) throw std::runtime_error{"write_set: null image view"};
   return *(const ImageViewObject*)v;
 }
-void write_binding(VkDescriptorSet, const AccelerationStructBinding&) {
-  throw std::runtime_error{"Acceleration structures are not supported on the post-process path (ray-query AO is out of scope)"};
+void write_binding(VkDescriptorSet set, const AccelerationStructBinding& b) {
+  auto& s = slot_of(set, b.binding);
+  if (!b.tlas) throw std::runtime_error{"write_set: null acceleration structure"};
+  s = SetSlot{};
+  s.kind = SetSlot::AccelStruct; s.tlas = b.tlas;
 }
 void write_binding(VkDescriptorSet set, const TextureBinding& b) {
   auto& s = slot_of(set, b.binding);
@@ -321,8 +324,22 @@ void register_hot_path_programs() {
     });
     // Programs the reference's constructors name but this path does not implement (out of scope):
     // known to the table, so that constructing the pass works as it does in the reference; launching one throws.
-    for (const char* name : {"tile_regression", "gtao_rt_main"})
+    for (const char* name : {"tile_regression"})
       create_program(name, [name](LaunchState&) -> int { throw std::runtime_error{std::string{name} + ": program is not implemented on the post-process path"}; });
+    // gtao/rt_main.frag: set {0 GTAORTParams, 1 depth, 2 normal, 3 acceleration structure, 4 RandomVectors}; colour attachment raw
+    create_program("gtao_rt_main", [=](LaunchState& st) {
+      const char* P = "gtao_rt_main";
+      if (st.attachments.size() != 1) throw std::runtime_error{"gtao_rt_main: expects one colour attachment"};
+      vkr_img depth = tex(st, 1, T, P), normal = tex(st, 2, T, P);
+      const SetSlot& as = st.set->slots[3];
+      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"gtao_rt_main: acceleration structure (binding 3) is not bound"};
+      const SetSlot& dirs = st.set->slots[4];
+      if (dirs.kind != SetSlot::Ubo || !dirs.buffer || dirs.buffer->get_size() < 64 * 16)
+        throw std::runtime_error{"gtao_rt_main: random directions (binding 4, 64 x vec4) are not bound"};
+      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      return vkr_gtao_rt_main(ubo<vkr_gtao_rt_params>(st, 0, P), &depth, &normal, (const vkr_accel*)as.tlas,
+                              (const float*)dirs.buffer->device_ptr(st.stream), &out, push<vkr_gtao_rt_push>(st, P), st.stream);
+    });
     create_program("pdf_preintegrate", [=](LaunchState& st) {
       vkr_img out = tex(st, 0, S, "pdf_preintegrate");
       return vkr_pdf_preintegrate(&out, st.stream);

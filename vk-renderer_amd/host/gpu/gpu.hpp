@@ -25,6 +25,21 @@
 
 namespace gpu {
 
+// gpu/driver.hpp:30-34: what the device offers.  Only ray query matters here: a graph whose device has it accepts the
+// ray-query AO pass (GTAO(..., use_ray_query = true)); MI355X traverses the scene's structure in software (csrc/accel.hip),
+// so any device can be configured with it.  A property of the graph (rendergraph::RenderGraph(stream, config)), not of
+// the process.
+struct DeviceConfig {
+  bool use_ray_query = false;
+};
+
+// gpu/transfer.hpp: the reference builds its acceleration structures through a transfer command pool; here the structure is
+// laid out on the host and uploaded synchronously, so the pool only names the stream (unused by the build).
+struct TransferCmdPool {
+  explicit TransferCmdPool(void* hip_stream = nullptr) : stream{hip_stream} {}
+  void* stream;
+};
+
 // ---- device memory -------------------------------------------------------------------------
 // The graph owns its images (reference: VMA allocations, managed_resources.hpp).  Allocation goes
 // through a replaceable hook so a launcher can back every image with memory it can also hand to
@@ -161,12 +176,13 @@ struct UniformBufferPool {
 
 // ---- descriptor sets ---------------------------------------------------------------------------------
 struct SetSlot {
-  enum Kind { Empty, Texture, StorageTexture, Ubo, Ssbo } kind = Empty;
+  enum Kind { Empty, Texture, StorageTexture, Ubo, Ssbo, AccelStruct } kind = Empty;
   ImageViewObject view{nullptr, {}};
   VkSampler sampler = nullptr;
   const void* host_data = nullptr;  // UBO living in the per-frame ring
   uint64_t host_size = 0;
   BufferPtr buffer;                 // UBO / SSBO living in a device buffer
+  VkAccelerationStructureKHR tlas = nullptr;  // AccelStruct: a vkr_accel*
 };
 struct DescriptorSetObject {
   std::array<SetSlot, 16> slots;
@@ -199,8 +215,8 @@ struct SSBOBinding : BaseBinding {
   SSBOBinding(uint32_t b, const BufferPtr& buf) : BaseBinding{b}, buffer{buf} {}
   BufferPtr buffer;
 };
-// gpu/descriptors.hpp:168-183: named by GTAO::add_main_rt_pass only.  No program on this path can read an
-// acceleration structure, so writing one into a set is an error, not a silent no-op.
+// gpu/descriptors.hpp:168-183: the scene's acceleration structure (GTAO::add_main_rt_pass).  The handle names the project's
+// own structure (vkr_accel of include/vkr_postfx.h, scene::SceneAccelerationStructure::tlas); a null handle is an error.
 struct AccelerationStructBinding : BaseBinding {
   AccelerationStructBinding(uint32_t b, VkAccelerationStructureKHR t) : BaseBinding{b}, tlas{t} {}
   VkAccelerationStructureKHR tlas;

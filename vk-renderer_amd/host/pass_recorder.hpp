@@ -27,7 +27,7 @@ using rendergraph::ImageResourceId;
 using rendergraph::ImageViewId;
 
 struct Binding {
-  enum Kind { Sampled, SampledWhole, Storage, StorageArray, Color, Depth, UniformBlock, UniformBuffer, StorageBuffer, GraphUniformBuffer } kind;
+  enum Kind { Sampled, SampledWhole, Storage, StorageArray, Color, Depth, UniformBlock, UniformBuffer, StorageBuffer, GraphUniformBuffer, AccelStruct } kind;
   uint32_t slot = 0;
   ImageResourceId image;
   BufferResourceId graph_buffer;
@@ -37,6 +37,7 @@ struct Binding {
   VkSampler sampler = nullptr;
   bool writable = true;
   std::vector<uint8_t> bytes;  // UniformBlock payload
+  VkAccelerationStructureKHR tlas = nullptr;  // AccelStruct
 };
 
 // texture(): all mips and layers of the image
@@ -68,6 +69,10 @@ inline Binding uniform_buffer(uint32_t slot, const gpu::BufferPtr &buf) {
 }
 inline Binding uniform_buffer(uint32_t slot, BufferResourceId buf) {
   Binding b; b.kind = Binding::GraphUniformBuffer; b.slot = slot; b.graph_buffer = buf; return b;
+}
+// the scene's acceleration structure (not a graph resource: built once per scene, outside the graph)
+inline Binding accel(uint32_t slot, VkAccelerationStructureKHR tlas) {
+  Binding b; b.kind = Binding::AccelStruct; b.slot = slot; b.tlas = tlas; return b;
 }
 inline Binding storage_buffer(uint32_t slot, BufferResourceId buf, bool writable = true) {
   Binding b; b.kind = Binding::StorageBuffer; b.slot = slot; b.graph_buffer = buf; b.writable = writable; return b;
@@ -123,6 +128,7 @@ inline VkDescriptorSet write(const std::vector<Bound> &bound, rendergraph::Rende
       case Binding::UniformBuffer: gpu::write_set(set, gpu::UBOBinding {b.slot, b.buffer}); break;
       case Binding::GraphUniformBuffer: gpu::write_set(set, gpu::UBOBinding {b.slot, resources.get_buffer(b.graph_buffer)}); break;
       case Binding::StorageBuffer: gpu::write_set(set, gpu::SSBOBinding {b.slot, resources.get_buffer(b.graph_buffer)}); break;
+      case Binding::AccelStruct: gpu::write_set(set, gpu::AccelerationStructBinding {b.slot, b.tlas}); break;
       default: break;
     }
   }

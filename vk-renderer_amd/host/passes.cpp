@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "pass_recorder.hpp"
+#include "scene/scene_as.hpp"
 
 using rendergraph::ImageResourceId;
 using rendergraph::RenderGraph;
@@ -175,8 +176,8 @@ ImageResourceId create_gtao_texture(RenderGraph &graph, uint32_t width, uint32_t
 GTAO::GTAO(RenderGraph &graph, uint32_t width, uint32_t height, bool use_ray_query, bool half_res, int pattern_n)
   : deinterleave_n {pattern_n}, pinned_jitter {std::numeric_limits<float>::quiet_NaN()}
 {
-  if (use_ray_query)
-    throw std::runtime_error {"GTAO: ray-query AO needs an acceleration structure; not available on the HIP path"};
+  if (use_ray_query && !graph.get_device_config().use_ray_query)
+    throw std::runtime_error {"GTAO: ray-query AO needs a device with ray query (construct the graph with gpu::DeviceConfig {.use_ray_query = true})"};
   if (half_res) {
     width /= 2;
     height /= 2;
@@ -200,9 +201,32 @@ GTAO::GTAO(RenderGraph &graph, uint32_t width, uint32_t height, bool use_ray_que
   main_deinterleaved_pipeline = gpu::create_compute_pipeline("main_deinterleaved");
   main_pipeline_gfx = fullscreen_pipeline("gtao_main");
   main_pipeline_gfx.set_rendersubpass({false, {graph.get_descriptor(raw).format}});
+  if (use_ray_query) {  // :57-63, :35
+    rt_main_pipeline = fullscreen_pipeline("gtao_rt_main");
+    rt_main_pipeline.set_rendersubpass({false, {graph.get_descriptor(raw).format}});
+    const auto dirs = gtao_random_directions(64);
+    random_vectors = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, sizeof(glm::vec4) * dirs.size(), VK_BUFFER_USAGE_UNIFORM_BUFFER_BIT);
+    std::memcpy(random_vectors->get_mapped_ptr(), dirs.data(), sizeof(glm::vec4) * dirs.size());
+  }
   sampler = default_sampler();
 }
 #endif
+
+std::vector<glm::vec4> gtao_random_directions(uint32_t count) {
+  std::minstd_rand0 engine;  // what std::default_random_engine is in libstdc++; default seed 1
+  std::uniform_real_distribution<float> unit {0.0f, 1.0f};
+  std::vector<glm::vec4> out;
+  out.reserve(count);
+  while (out.size() < count) {
+    const float x = float(double(unit(engine)) * 2.0 - 1.0);
+    const float y = float(double(unit(engine)) * 2.0 - 1.0);
+    const float z = unit(engine);
+    const float len = std::sqrt((x * x + y * y) + z * z);  // glm::length of (x, y, z, 0)
+    if (double(len) <= 0.00001 || len > 1.0f) continue;
+    out.push_back(glm::vec4 {x / len, y / len, z / len, 0.0f});
+  }
+  return out;
+}
 
 // the 12-entry angle table + jitter every main-pass flavour uses (:109-111, :362-364, :487-489)
 float GTAO::next_base_angle() {
@@ -265,10 +289,24 @@ void GTAO::add_main_pass_graphics(RenderGraph &graph, const GTAOParams &params, 
 }
 #endif
 
-// :150-196 (VK_KHR_ray_query against the scene's TLAS): not part of this path
+// :150-196: full-screen triangle into `raw`; bindings 0 GTAORTParams, 1 depth (view mip depth_lod), 2 normal, 3 the scene's
+// acceleration structure, 4 RandomVectors; push constant: the rotation (:162)
 #ifndef VKR_REFERENCE_PASSES  // defined by the reference's own source in the drop-in build (Makefile: refpasses)
-void GTAO::add_main_rt_pass(RenderGraph &, const GTAORTParams &, VkAccelerationStructureKHR, ImageResourceId, ImageResourceId) {
-  throw std::runtime_error {"GTAO::add_main_rt_pass: the ray-query pass needs a scene acceleration structure (out of scope: SURVEY.md section 2b)"};
+void GTAO::add_main_rt_pass(RenderGraph &graph, const GTAORTParams &params, VkAccelerationStructureKHR tlas, ImageResourceId depth,
+  ImageResourceId normal)
+{
+  static_assert(sizeof(GTAORTParams) == sizeof(vkr_gtao_rt_params), "GTAORTParams must match the C-ABI");
+  if (!rt_main_pipeline.has_program())
+    throw std::runtime_error {"GTAO::add_main_rt_pass: this GTAO was constructed without use_ray_query"};
+  if (!tlas)
+    throw std::runtime_error {"GTAO::add_main_rt_pass: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
+  const float rotation = std::isnan(pinned_jitter)? (rand()/float(RAND_MAX) - 0.5f) : pinned_jitter;
+  const vkr_gtao_rt_push pc {rotation};
+  const auto ext = graph.get_descriptor(raw);
+  rec::fullscreen(graph, "GTAO_rt_main", rt_main_pipeline,
+    {rec::uniform(0, params), rec::sampled_mips(1, depth, sampler, DEPTH, depth_lod, 1), rec::sampled(2, normal, sampler),
+     rec::accel(3, tlas), rec::uniform_buffer(4, random_vectors), rec::color_target(raw)},
+    rec::push(pc), ext.width, ext.height);
 }
 #endif
 
@@ -840,6 +878,70 @@ CompiledScene make_scene(const Vertex *vertices, uint32_t vertex_count, const ui
     out.base_nodes.push_back(BaseNode {d.transform, {}, int(i)});
   }
   return out;
+}
+
+// ---- scene/scene_as.hpp: the acceleration structure of the ray-query AO -----------------------------------------------
+SceneAccelerationStructure::~SceneAccelerationStructure() {
+  if (tlas) vkr_accel_destroy((vkr_accel*)tlas);
+}
+
+void SceneAccelerationStructure::build(gpu::TransferCmdPool &transfer_pool, const CompiledScene &source) {  // scene_as.cpp:19-24
+  blas_triangles.clear();
+  for (const auto &mesh : source.root_meshes) build_blas(transfer_pool, mesh, source);
+  build_tlas(transfer_pool, source);
+}
+
+void SceneAccelerationStructure::build_blas(gpu::TransferCmdPool &, const BaseMesh &mesh, const CompiledScene &source) {
+  const auto *vertices = (const Vertex *)source.vertex_buffer->host_data();
+  const auto *indices = (const uint32_t *)source.index_buffer->host_data();
+  const uint64_t vertex_count = vertices ? source.vertex_buffer->get_size() / sizeof(Vertex) : 0;
+  const uint64_t index_count = indices ? source.index_buffer->get_size() / sizeof(uint32_t) : 0;
+  std::vector<float> tris;
+  for (const auto &prim : mesh.primitives) {  // scene_as.cpp:60-70: primitiveCount = index_count / 3, firstVertex = vertex_offset
+    if (uint64_t(prim.index_offset) + prim.index_count > index_count)
+      throw std::runtime_error {"SceneAccelerationStructure: a primitive's indices lie outside the index buffer"};
+    for (uint32_t j = 0; j + 3 <= prim.index_count; j += 3)
+      for (uint32_t k = 0; k < 3; k++) {
+        const uint64_t v = uint64_t(prim.vertex_offset) + indices[prim.index_offset + j + k];
+        if (v >= vertex_count) throw std::runtime_error {"SceneAccelerationStructure: an index names a vertex outside the vertex buffer"};
+        tris.insert(tris.end(), {vertices[v].pos.x, vertices[v].pos.y, vertices[v].pos.z});
+      }
+  }
+  blas_triangles.push_back(std::move(tris));
+}
+
+namespace {
+struct FlatNode { glm::mat4 transform; int mesh; };
+void flatten_nodes(std::vector<FlatNode> &out, const BaseNode &node, const glm::mat4 &pre_transform) {  // scene_as.cpp:144-157
+  const glm::mat4 transform = pre_transform * node.transform;
+  if (node.mesh_index >= 0) out.push_back(FlatNode {transform, node.mesh_index});
+  for (const auto &child : node.children) flatten_nodes(out, child, transform);
+}
+}  // namespace
+
+void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const CompiledScene &source) {
+  std::vector<FlatNode> nodes;
+  for (const auto &node : source.base_nodes) flatten_nodes(nodes, node, glm::mat4 {1.f});
+  world_triangles.clear();
+  for (const auto &n : nodes) {
+    if (size_t(n.mesh) >= blas_triangles.size()) throw std::runtime_error {"SceneAccelerationStructure: a node names a mesh without a structure (build_blas first)"};
+    const glm::mat4 &m = n.transform;  // m[column][row]
+    const auto &obj = blas_triangles[n.mesh];
+    for (size_t i = 0; i + 3 <= obj.size(); i += 3) {
+      const float x = obj[i], y = obj[i + 1], z = obj[i + 2];
+      for (int row = 0; row < 3; row++) {
+        const float p0 = m[0][row] * x, p1 = m[1][row] * y, p2 = m[2][row] * z;
+        const float s01 = p0 + p1, s012 = s01 + p2;
+        world_triangles.push_back(s012 + m[3][row]);
+      }
+    }
+  }
+  if (tlas) vkr_accel_destroy((vkr_accel*)tlas);
+  tlas = nullptr;
+  vkr_accel *accel = nullptr;
+  if (vkr_accel_create(world_triangles.data(), uint32_t(world_triangles.size() / 9), &accel) != 0)
+    throw std::runtime_error {std::string {"SceneAccelerationStructure: "} + vkr_last_error()};
+  tlas = (VkAccelerationStructureKHR)accel;
 }
 
 }  // namespace scene

@@ -234,8 +234,9 @@ private:
 // gtao_accumulate, and the variants it ships but never records: graphics
 // main pass ("gtao_main"), static reprojection ("gtao_reproject"), deinterleaved depth + main pass
 // ("deinterleave_depth", "main_deinterleaved").  The ray-query pass (add_main_rt_pass,
-// gtao.cpp:150-196) needs a scene acceleration structure and is not part of this path: the
-// constructor throws when use_ray_query is set.
+// gtao.cpp:150-196, program "gtao_rt_main") traces the scene's acceleration structure
+// (scene/scene_as.hpp) in software; the constructor accepts use_ray_query only on a graph whose
+// device has ray query (gpu::DeviceConfig) and throws otherwise.
 
 
 rendergraph::ImageResourceId create_gtao_texture(rendergraph::RenderGraph &graph, uint32_t width, uint32_t height);
@@ -256,6 +257,11 @@ struct GTAORTParams {  // gtao.hpp:20-26 (ray-query pass; named by add_main_rt_p
   float zfar;
 };
 
+// gtao.cpp:415-443 create_random_vectors: `count` unit vectors of the upper hemisphere (z >= 0) drawn from a default-constructed
+// std::default_random_engine through uniform_real_distribution<float>(0, 1), x and y mapped to [-1, 1] in double; vectors of
+// length <= 1e-5 or > 1 are rejected, the others divided by their length.  Deterministic under libstdc++ (minstd_rand0, seed 1).
+std::vector<glm::vec4> gtao_random_directions(uint32_t count);
+
 struct GTAOReprojection {
   glm::mat4 camera_to_prev_frame;
   float fovy;
@@ -275,8 +281,9 @@ struct GTAO {
     rendergraph::ImageResourceId material,
     rendergraph::ImageResourceId preintegrated_pdf);
 
-  // gtao.cpp:150-196: needs VK_KHR_ray_query and the scene's TLAS (compiled out of the reference's own frame loop,
-  // main.cpp:40 USE_RAY_QUERY 0; SURVEY.md section 2b: out of scope).  Declared for source compatibility; throws.
+  // gtao.cpp:150-196: 64 rays of 0.2 per pixel against the scene's acceleration structure (`tlas`, built by
+  // scene::SceneAccelerationStructure).  Needs a GTAO constructed with use_ray_query; rotation = rand()/RAND_MAX - 0.5
+  // per call as in the reference, or the pinned jitter (pin_angle_jitter).
   void add_main_rt_pass(
     rendergraph::RenderGraph &graph,
     const GTAORTParams &params,
@@ -341,8 +348,8 @@ private:
   float next_base_angle();
 
   gpu::GraphicsPipeline main_pipeline_gfx;
-  gpu::GraphicsPipeline rt_main_pipeline;  // never bound: the ray-query program is not part of this path
-  gpu::BufferPtr random_vectors;           // gtao.cpp:35: consumed by the ray-query pass only
+  gpu::GraphicsPipeline rt_main_pipeline;  // use_ray_query only
+  gpu::BufferPtr random_vectors;           // gtao.cpp:35: 64 x vec4, consumed by the ray-query pass only (use_ray_query)
   gpu::ComputePipeline reproject_pipeline;
   gpu::ComputePipeline deinterleave_pipeline;
   gpu::ComputePipeline main_deinterleaved_pipeline;

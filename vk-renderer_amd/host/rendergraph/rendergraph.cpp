@@ -93,6 +93,7 @@ VkImageView RenderResources::get_view(const ImageViewId& ref) {
 
 // ---- graph ---------------------------------------------------------------------------------------------
 RenderGraph::RenderGraph(void* stream) : cmd{stream}, main_stream{stream} { gpu::register_hot_path_programs(); }
+RenderGraph::RenderGraph(void* stream, const gpu::DeviceConfig& device) : RenderGraph{stream} { device_config = device; }
 ImageResourceId RenderGraph::get_backbuffer() {
   if (!has_backbuffer) {
     backbuffer = create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, win_w ? win_w : 1u, win_h ? win_h : 1u},

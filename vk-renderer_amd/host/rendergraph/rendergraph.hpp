@@ -155,7 +155,10 @@ template <typename TaskData> struct Task : BaseTask {
 struct RenderGraph {  // rendergraph.hpp:112-158
   // `stream`: the HIP stream every task is recorded on (nullptr = the default stream)
   explicit RenderGraph(void* stream = nullptr);
+  // the same on a device described by `device` (gpu/driver.hpp DeviceConfig): ray query on or off for this graph's passes
+  RenderGraph(void* stream, const gpu::DeviceConfig& device);
   ~RenderGraph();
+  const gpu::DeviceConfig& get_device_config() const { return device_config; }
 
   template <typename TaskData>
   void add_task(const std::string& name, TaskCreateCB<TaskData> create_cb, TaskRunCB<TaskData> run_cb) {
@@ -207,6 +210,7 @@ struct RenderGraph {  // rendergraph.hpp:112-158
   std::vector<TaskTime> collect_task_times();
 
  private:
+  gpu::DeviceConfig device_config;
   GraphResources resources;
   gpu::CmdContext cmd;
   std::vector<std::unique_ptr<BaseTask>> tasks;

@@ -1,0 +1,42 @@
+// scene/scene_as.hpp — the scene's acceleration structure, interface of src/scene/scene_as.hpp:8-24.
+//
+// The reference builds one bottom-level structure per mesh and a top-level one over the flattened node tree
+// (scene_as.cpp:144-157) for VK_KHR_ray_query.  MI355X has no ray-tracing hardware; the ray query is a software traversal of
+// the project's own structure (include/vkr_postfx.h vkr_accel, csrc/accel.hip).  For an any-hit query of a static scene two
+// levels add nothing, so build_blas() only gathers each mesh's triangles in object space and build_tlas() flattens every node
+// into ONE world-space structure:
+//   * node transforms are composed as flattern_nodes does: pre_transform * node.transform, children after their parent;
+//   * triangle j of primitive p reads vertices vertex_offset + indices[index_offset + 3j + k] (firstVertex of the build
+//     range); every triangle is opaque and double-sided, alpha clipping is ignored (scene_as.cpp:57,172);
+//   * a vertex goes to world space in fp32 on the host as ((m00 x + m01 y) + m02 z) + m03 per row (each product and sum
+//     rounded, no fused multiply-add) — vk-renderer_amd/abi.py scene_triangles() restates it in numpy.
+// `tlas` names the structure (a vkr_accel*) that gtao_rt_main binds at binding 3.
+#ifndef SCENE_AS_HPP_INCLUDED
+#define SCENE_AS_HPP_INCLUDED
+
+#include <vector>
+
+#include "../passes.hpp"
+
+namespace scene {
+
+struct SceneAccelerationStructure {
+  SceneAccelerationStructure() = default;
+  SceneAccelerationStructure(const SceneAccelerationStructure &) = delete;
+  SceneAccelerationStructure &operator=(const SceneAccelerationStructure &) = delete;
+  ~SceneAccelerationStructure();
+
+  void build(gpu::TransferCmdPool &transfer_pool, const CompiledScene &source);
+  void build_blas(gpu::TransferCmdPool &transfer_pool, const BaseMesh &mesh, const CompiledScene &source);
+  void build_tlas(gpu::TransferCmdPool &transfer_pool, const CompiledScene &source);
+
+  // object-space triangles of each mesh, in build_blas() order (9 floats per triangle)
+  std::vector<std::vector<float>> blas_triangles;
+  // the world-space triangles build_tlas() put into the structure (9 floats per triangle)
+  std::vector<float> world_triangles;
+  VkAccelerationStructureKHR tlas {nullptr};
+};
+
+}  // namespace scene
+
+#endif
