@@ -47,8 +47,9 @@ typedef enum vkr_format {
   VKR_FMT_R16_SFLOAT     = 8,  /* 1 x fp16                                         */
   VKR_FMT_R32_SFLOAT     = 9,  /* 1 x fp32                                         */
   VKR_FMT_R8_UNORM       = 10, /* 1 x uint8 (create_gtao_texture, gtao.cpp:10)     */
-  VKR_FMT_RGBA32_SFLOAT  = 11  /* 4 x fp32: AdvancedSSR::tile_planes (advanced_ssr.cpp:85), allocated by the reference's
+  VKR_FMT_RGBA32_SFLOAT  = 11, /* 4 x fp32: AdvancedSSR::tile_planes (advanced_ssr.cpp:85), allocated by the reference's
                                   constructor, bound by no program of this path       */
+  VKR_FMT_R16_UNORM      = 12  /* 1 x uint16: the octahedral probe depth (probe_renderer.cpp:284,302) */
 } vkr_format;
 
 /* bytes per texel of a vkr_format (0 for unknown) */
@@ -494,6 +495,36 @@ typedef struct vkr_gtao_rt_push { float rotation; } vkr_gtao_rt_push;  /* rt_mai
  * 2 PI (rotation + k / 16) are evaluated on the host.  One wave per pixel, one lane per direction.                        */
 int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel,
                      const float* directions, const vkr_img* out_raw, const vkr_gtao_rt_push* push, void* stream);
+
+/* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cube2oct, probe_downsample, trace_probe) ------------------------
+ * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
+ * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one
+ * per-mip stride (the layout of an array image).  A cube is 6 layers in face order +X, -X, +Y, -Y, +Z, -Z, sampled with the
+ * frozen seamless rules of DESIGN_NUMERICS.md (face ties x over y over z; a corner tap is the average of its three texels).  */
+#define VKR_PROBE_ZNEAR 0.05f  /* cube2oct/shader.comp:10-11, trace_probe/shader.comp:117-118 */
+#define VKR_PROBE_ZFAR  80.0f
+/* program "cube2oct": probe_renderer.cpp:171-202 + cube2oct/shader.comp.  cube_color: 6 RGBA8_SRGB layers, cube_distance: 6
+ * R16F layers (one square extent); oct_color RGBA8_UNORM and oct_depth R16_UNORM (mip 0 is written) of one extent.  Only the
+ * dispatch extent floor(w/8)*8 x floor(h/4)*4 is written, with uv = pixel / that extent.                                     */
+int vkr_cube2oct(const vkr_img* cube_color, const vkr_img* cube_distance, const vkr_img* oct_color, const vkr_img* oct_depth,
+                 void* stream);
+/* program "probe_downsample": probe_renderer.cpp:204-236 + probe_downsample/shader.frag.  Mip i >= 1 of the R16_UNORM view is
+ * the min of the 2 x 2 texels of mip i - 1 at min(2 * pixel + o, size) (not size - 1: a fetch past the edge reads 0).        */
+int vkr_probe_downsample(const vkr_img* depth_layer_all_mips, void* stream);
+/* Constants, probe_renderer.cpp:332-341 / trace_probe/shader.comp:12-22 (116 bytes) */
+typedef struct vkr_probe_trace_consts {
+  vkr_mat4 inverse_view;       /* camera -> world */
+  float    probe_min[4], probe_max[4];
+  uint32_t grid_size;
+  float    fovy, aspect, znear, zfar;
+} vkr_probe_trace_consts;
+/* program "trace_probe": probe_renderer.cpp:323-394 + trace_probe/shader.comp:48-82, 101-115, 175-347, 410-441.  Bindings 0
+ * depth (D24, full resolution, mip 0), 1 normal (RG16_UNORM), 2 the probe colour array (RGBA8_UNORM), 3 the probe depth array
+ * (R16_UNORM, all mips), 4 consts, 5 out (RGBA8_UNORM).  layer_count >= grid_size^2, grid_size >= 2.  Only the dispatch extent
+ * floor(w/8)*8 x floor(h/4)*4 of `out` is written.  A hit stores the bilinear probe colour, a miss, an unresolved trace and sky
+ * store 0.  Single-GPU images only (no windows).                                                                              */
+int vkr_trace_probe(const vkr_img* depth, const vkr_img* normal, const vkr_img* color_layers, const vkr_img* depth_layers,
+                    uint32_t layer_count, const vkr_probe_trace_consts* consts, const vkr_img* out, void* stream);
 
 /* Multi-GPU exchange helper (the reference is single-GPU, so there is no program this
  * replaces): copies `count` pitch-linear byte rectangles on `stream`, VKR_MAX_RECTS per launch.  Used to pack

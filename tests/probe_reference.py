@@ -1,0 +1,421 @@
+"""Numpy restatement of the octahedral probe programs (csrc/probe.hip): the helpers of octahedral.glsl, the frozen seamless
+cube sampling, cube2oct, probe_downsample and trace_probe — the checker of tests/test_probe_gpu.py.
+
+Test infrastructure, like gtao_rt_reference.py, whose Arith it reuses for the fused operations of numeric contract 2: every
+fp32 operation is written in the order the kernels use.  The GPU tests feed it the images the kernels read, downloaded from
+the device, so the comparison is bit for bit.
+"""
+import os
+import re
+
+import numpy as np
+
+from gtao_rt_reference import Arith, d24_to_float, decode_normal, fma32, sample, unorm16_to_float
+
+F32 = np.float32
+ZNEAR, ZFAR = F32(0.05), F32(80.0)
+MISS, HIT, UNKNOWN = 0, 1, 2
+MAX_T = F32(3.402823466e38)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- storage codecs -------------------------------------------------------------------------------------------------------
+def _srgb_decode_table():
+    txt = open(os.path.join(ROOT, "vk-renderer_amd", "csrc", "srgb_tables.inc")).read()
+    body = re.search(r"k_srgb_decode_bits\[256\] = \{(.*?)\};", txt, re.S).group(1)
+    bits = np.array([int(v, 16) for v in re.findall(r"0x([0-9a-f]+)u", body)], np.uint32)
+    return bits.view(F32)
+
+
+SRGB = _srgb_decode_table()
+
+
+def unorm8_to_float(v):
+    x = np.asarray(v).astype(F32) * F32(2.0 ** -8)
+    return fma32(x, np.array([0x3B808081], np.uint32).view(F32)[0], x)  # 0x1.010102p-8
+
+
+def float_to_unorm(f, bits):
+    with np.errstate(invalid="ignore"):
+        c = np.fmin(np.fmax(np.asarray(f, F32), F32(0.0)), F32(1.0))
+        return np.rint(c * F32(2 ** bits - 1)).astype(np.uint32)
+
+
+def f2i_index(x):
+    """v_cvt_i32_f32: truncate toward zero, NaN -> 0, saturate"""
+    with np.errstate(invalid="ignore"):
+        t = np.where(np.isnan(x), F32(0.0), np.trunc(x)).astype(np.float64)
+    return np.clip(t, -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+
+
+# ---- octahedral.glsl ------------------------------------------------------------------------------------------------------
+def _sign_nz(k):
+    return np.where(k >= 0, F32(1.0), F32(-1.0)).astype(F32)
+
+
+def oct_fold(uvx, uvy):
+    u = F32(2.0) * (np.asarray(uvx, F32) - F32(0.5))
+    v = F32(2.0) * (np.asarray(uvy, F32) - F32(0.5))
+    z = (F32(1.0) - np.abs(u)) - np.abs(v)
+    nx = np.where(z < 0, (F32(1.0) - np.abs(v)) * _sign_nz(u), u)
+    ny = np.where(z < 0, (F32(1.0) - np.abs(u)) * _sign_nz(v), v)
+    return np.stack([nx, ny, z], axis=-1).astype(F32)
+
+
+def normalize(ar, v):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return ar.normalize(v)
+
+
+def oct_decode(ar, uvx, uvy):
+    return normalize(ar, oct_fold(uvx, uvy))
+
+
+def oct_center(ar, uvx, uvy):
+    return normalize(ar, np.sign(oct_fold(uvx, uvy)).astype(F32))
+
+
+def oct_encode(ar, v):
+    l1 = (np.abs(v[..., 0]) + np.abs(v[..., 1])) + np.abs(v[..., 2])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = F32(1.0) / l1
+        rx, ry = v[..., 0] * inv, v[..., 1] * inv
+    neg = v[..., 2] < 0
+    fx = np.where(neg, (F32(1.0) - np.abs(ry)) * _sign_nz(rx), rx)
+    fy = np.where(neg, (F32(1.0) - np.abs(rx)) * _sign_nz(ry), ry)
+    return ar.cfma(F32(0.5), fx, F32(0.5)), ar.cfma(F32(0.5), fy, F32(0.5))
+
+
+def encode_oct_depth(z, n=ZNEAR, f=ZFAR):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (f / (f - n) + (f * n) / ((-np.asarray(z, F32)) * (f - n))).astype(F32)
+
+
+def decode_oct_depth(ar, d, n=ZNEAR, f=ZFAR):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (-(n * f) / ar.cfma(d, f - n, -f)).astype(F32)
+
+
+# ---- the frozen seamless cube sampling ------------------------------------------------------------------------------------
+def _face_dir(f, sc, tc, n):
+    N = np.full_like(sc, n)
+    x = np.select([f == 0, f == 1, f == 2, f == 3, f == 4], [N, -N, sc, sc, sc], -sc)
+    y = np.select([f == 0, f == 1, f == 2, f == 3, f == 4], [-tc, -tc, N, -N, -tc], -tc)
+    z = np.select([f == 0, f == 1, f == 2, f == 3, f == 4], [-sc, sc, tc, -tc, N], -N)
+    return x, y, z
+
+
+def _face_coords(f, x, y, z):
+    sc = np.select([f == 0, f == 1, f == 2, f == 3, f == 4], [-z, z, x, x, x], -x)
+    tc = np.select([f == 0, f == 1, f == 2, f == 3, f == 4], [-y, -y, z, -z, -y], -y)
+    return sc, tc
+
+
+def _edge_index(v, n):
+    return np.where(v >= n, n - 1, np.where(v <= -n, 0, (v + n - 1) >> 1))
+
+
+def across_edge(f, i, j, n):
+    """texel (i, j) of face f, one coordinate one past an edge -> the touching texel (face, i, j) of the neighbouring face"""
+    x, y, z = _face_dir(f, 2 * i + 1 - n, 2 * j + 1 - n, n)
+    nf = np.where(np.abs(x) > n, np.where(x > 0, 0, 1), np.where(np.abs(y) > n, np.where(y > 0, 2, 3), np.where(z > 0, 4, 5)))
+    sc, tc = _face_coords(nf, x, y, z)
+    return nf, _edge_index(sc, n), _edge_index(tc, n)
+
+
+def cube_tap(tex, f, i, j):
+    """tex: [6, n, n, C] decoded float32 faces; the frozen seamless tap of texel (i, j) of face f, i, j in [-1, n]"""
+    n = tex.shape[1]
+    out_i, out_j = (i < 0) | (i >= n), (j < 0) | (j >= n)
+    ci, cj = np.clip(i, 0, n - 1), np.clip(j, 0, n - 1)
+    g, gi, gj = across_edge(f, i, j, n)
+    edge = np.where((out_i & ~out_j)[..., None] | (out_j & ~out_i)[..., None], tex[g, gj, gi], tex[f, cj, ci])
+    t0 = tex[f, cj, ci]
+    g1, i1, j1 = across_edge(f, i, cj, n)
+    g2, i2, j2 = across_edge(f, ci, j, n)
+    corner = ((t0 + tex[g1, j1, i1]) + tex[g2, j2, i2]) / F32(3.0)
+    return np.where((out_i & out_j)[..., None], corner, edge).astype(F32)
+
+
+def sample_cube(ar, tex, d):
+    """texture(samplerCube, d) on decoded faces tex [6, n, n, C]: face by the largest |component| (ties x, y, z)"""
+    ax, ay, az = np.abs(d[..., 0]), np.abs(d[..., 1]), np.abs(d[..., 2])
+    use_x = (ax >= ay) & (ax >= az)
+    use_y = ~use_x & (ay >= az)
+    fx_ = np.where(d[..., 0] < 0, 1, 0)
+    fy_ = np.where(d[..., 1] < 0, 3, 2)
+    fz_ = np.where(d[..., 2] < 0, 5, 4)
+    f = np.where(use_x, fx_, np.where(use_y, fy_, fz_))
+    ma = np.where(use_x, ax, np.where(use_y, ay, az))
+    sc = np.where(use_x, np.where(f == 0, -d[..., 2], d[..., 2]), np.where(use_y, d[..., 0], np.where(f == 4, d[..., 0], -d[..., 0])))
+    tc = np.where(use_x, -d[..., 1], np.where(use_y, np.where(f == 2, d[..., 2], -d[..., 2]), -d[..., 1]))
+    s = ar.cfma(F32(0.5), (sc / ma).astype(F32), F32(0.5))
+    t = ar.cfma(F32(0.5), (tc / ma).astype(F32), F32(0.5))
+    n = tex.shape[1]
+    x = ar.cfma(s, F32(n), F32(-0.5))
+    y = ar.cfma(t, F32(n), F32(-0.5))
+    x0f, y0f = np.floor(x), np.floor(y)
+    fx, fy = (x - x0f)[..., None], (y - y0f)[..., None]
+    x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+    t00, t10 = cube_tap(tex, f, x0, y0), cube_tap(tex, f, x0 + 1, y0)
+    t01, t11 = cube_tap(tex, f, x0, y0 + 1), cube_tap(tex, f, x0 + 1, y0 + 1)
+    top = ar.mixf(t00, t10, np.broadcast_to(fx, t00.shape))
+    bot = ar.mixf(t01, t11, np.broadcast_to(fx, t01.shape))
+    return ar.mixf(top, bot, np.broadcast_to(fy, top.shape))
+
+
+def decode_cube(color_codes, distance_half):
+    """color_codes: [6, n, n, 4] uint8 RGBA8_SRGB; distance_half: [6, n, n] float16 -> [6, n, n, 5] float32 (r, g, b, a, d)"""
+    rgb = SRGB[color_codes[..., :3]]
+    a = unorm8_to_float(color_codes[..., 3])
+    return np.concatenate([rgb, a[..., None], distance_half.astype(F32)[..., None]], axis=-1).astype(F32)
+
+
+# ---- cube2oct -------------------------------------------------------------------------------------------------------------
+def cube2oct(ar, color_codes, distance_half, width, height):
+    """-> (RGBA8 codes [th, tw, 4] uint8, R16_UNORM codes [th, tw] uint16) of the dispatch extent tw x th"""
+    tw, th = width // 8 * 8, height // 4 * 4
+    tex = decode_cube(color_codes, distance_half)
+    gy, gx = np.mgrid[0:th, 0:tw]
+    uvx, uvy = (gx.astype(F32) / F32(tw)).astype(F32), (gy.astype(F32) / F32(th)).astype(F32)
+    d = oct_decode(ar, uvx, uvy)
+    c = sample_cube(ar, tex, d)
+    view_dir = d * c[..., 4:5]
+    front = oct_center(ar, uvx, uvy)
+    depth = encode_oct_depth(np.fmin(np.fmax(ar.dot(view_dir, front), ZNEAR), ZFAR))
+    return float_to_unorm(c[..., :4], 8).astype(np.uint8), float_to_unorm(depth, 16).astype(np.uint16)
+
+
+# ---- probe_downsample -----------------------------------------------------------------------------------------------------
+def probe_downsample(mip0_codes, mips):
+    """mip0_codes: [h, w] uint16 -> list of `mips` levels; level i is the min of the 2 x 2 texels of level i - 1 at
+    min(2 p + o, size), where a fetch past the edge reads 0"""
+    out = [np.asarray(mip0_codes, np.uint16)]
+    h, w = out[0].shape
+    for m in range(1, mips):
+        src = unorm16_to_float(out[-1])
+        sh, sw = src.shape
+        dh, dw = h >> m, w >> m
+        pad = np.zeros((sh + 1, sw + 1), F32)
+        pad[:sh, :sw] = src
+        gy, gx = np.mgrid[0:dh, 0:dw]
+        acc = np.full((dh, dw), F32(1000.0))
+        for oy, ox in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            acc = np.fmin(pad[np.minimum(2 * gy + oy, sh), np.minimum(2 * gx + ox, sw)], acc)
+        out.append(float_to_unorm(acc, 16).astype(np.uint16))
+    return out
+
+
+# ---- trace_probe ----------------------------------------------------------------------------------------------------------
+class ProbeArrays:
+    """the probe colour array (RGBA8 codes [L, S, S, 4]) and depth array (R16_UNORM codes per mip, [L, h_m, w_m])"""
+
+    def __init__(self, color_codes, depth_mips):
+        self.color = np.asarray(color_codes, np.uint8)
+        self.mips = len(depth_mips)
+        self.layers = self.color.shape[0]
+        self.w = np.array([d.shape[2] for d in depth_mips] + [1] * 32, np.int64)
+        self.h = np.array([d.shape[1] for d in depth_mips] + [1] * 32, np.int64)
+        self.off = np.zeros(self.mips + 32, np.int64)
+        flat = [unorm16_to_float(d).reshape(-1) for d in depth_mips]
+        acc = 0
+        for m, f in enumerate(flat):
+            self.off[m] = acc
+            acc += f.size
+        self.flat = np.concatenate(flat + [np.zeros(1, F32)])  # the last entry: the 0 of a fetch out of range
+        self.zero = acc
+        self.mip0 = unorm16_to_float(depth_mips[0])
+
+    def fetch(self, px, py, layer, mip):
+        x, y = f2i_index(px), f2i_index(py)
+        m = np.minimum(mip, self.mips + 31)
+        w, h = self.w[m], self.h[m]
+        ok = (mip < self.mips) & (x >= 0) & (y >= 0) & (x < w) & (y < h)
+        idx = np.where(ok, self.off[m] + (layer * h + np.where(ok, y, 0)) * w + np.where(ok, x, 0), self.zero)
+        return self.flat[idx]
+
+    def bilinear_depth(self, ar, u, v, layer):
+        h, w = self.mip0.shape[1:]
+        x, y = ar.cfma(u, F32(w), F32(-0.5)), ar.cfma(v, F32(h), F32(-0.5))
+        x0f, y0f = np.floor(x), np.floor(y)
+        fx, fy = x - x0f, y - y0f
+        x0, y0 = f2i_index(x0f), f2i_index(y0f)
+        xa, xb = np.clip(x0, 0, w - 1), np.clip(x0 + 1, 0, w - 1)
+        ya, yb = np.clip(y0, 0, h - 1), np.clip(y0 + 1, 0, h - 1)
+        t = self.mip0
+        return ar.mixf(ar.mixf(t[layer, ya, xa], t[layer, ya, xb], fx), ar.mixf(t[layer, yb, xa], t[layer, yb, xb], fx), fy)
+
+    def color_sample(self, ar, u, v, layer):
+        h, w = self.color.shape[1:3]
+        x, y = ar.cfma(u, F32(w), F32(-0.5)), ar.cfma(v, F32(h), F32(-0.5))
+        x0f, y0f = np.floor(x), np.floor(y)
+        fx, fy = (x - x0f)[..., None], (y - y0f)[..., None]
+        x0, y0 = f2i_index(x0f), f2i_index(y0f)
+        xa, xb = np.clip(x0, 0, w - 1), np.clip(x0 + 1, 0, w - 1)
+        ya, yb = np.clip(y0, 0, h - 1), np.clip(y0 + 1, 0, h - 1)
+        c = self.color
+        t00, t10 = unorm8_to_float(c[layer, ya, xa]), unorm8_to_float(c[layer, ya, xb])
+        t01, t11 = unorm8_to_float(c[layer, yb, xa]), unorm8_to_float(c[layer, yb, xb])
+        fx4, fy4 = np.broadcast_to(fx, t00.shape), np.broadcast_to(fy, t00.shape)
+        v4 = ar.mixf(ar.mixf(t00, t10, fx4), ar.mixf(t01, t11, fx4), fy4)
+        return float_to_unorm(v4, 8).astype(np.uint8)
+
+
+def madd(ar, a, s, b):  # a + s * b for per-lane scalars s
+    return ar.cfma(np.asarray(s, F32)[..., None], b, a)
+
+
+def hierarchical_raymarch(ar, pa, layer, origin, direction):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv = np.where(direction != 0, F32(1.0) / np.where(direction != 0, direction, F32(1.0)), MAX_T).astype(F32)
+        S = F32(pa.w[0]), F32(pa.h[0])
+        res = [np.full(layer.shape, S[0], F32), np.full(layer.shape, S[1], F32)]
+        res_inv = [np.full(layer.shape, F32(1.0) / S[0], F32), np.full(layer.shape, F32(1.0) / S[1], F32)]
+        uvo = [F32(0.005) / S[0], F32(0.005) / S[1]]
+        uv_offset = [np.where(direction[..., k] < 0, -uvo[k], uvo[k]).astype(F32) for k in range(2)]
+        floor_offset = [np.where(direction[..., k] < 0, F32(0.0), F32(1.0)).astype(F32) for k in range(2)]
+        planes = [ar.cfma(np.floor(res[k] * origin[..., k]) + floor_offset[k], res_inv[k], uv_offset[k]) for k in range(2)]
+        current_t = np.fmin((planes[0] - origin[..., 0]) * inv[..., 0], (planes[1] - origin[..., 1]) * inv[..., 1])
+        position = madd(ar, origin, current_t, direction)
+        mip = np.zeros(layer.shape, np.int64)
+        for _ in range(25):
+            act = mip >= 0
+            if not act.any():
+                break
+            mp = [res[k] * position[..., k] for k in range(2)]
+            surface_z = pa.fetch(mp[0], mp[1], layer, np.maximum(mip, 0))
+            pl = [ar.cfma(np.floor(mp[k]) + floor_offset[k], res_inv[k], uv_offset[k]) for k in range(2)]
+            tx = (pl[0] - origin[..., 0]) * inv[..., 0]
+            ty = (pl[1] - origin[..., 1]) * inv[..., 1]
+            tz = (surface_z - origin[..., 2]) * inv[..., 2]
+            tz = np.where(direction[..., 2] > 0, tz, MAX_T)
+            t_min = np.fmin(np.fmin(np.fmin(tx, ty), tz), F32(1.0))
+            above = surface_z > position[..., 2]
+            skipped = (t_min != tz) & above
+            new_t = np.where(above, t_min, current_t)
+            current_t = np.where(act, new_t, current_t)
+            position = np.where(act[..., None], madd(ar, origin, current_t, direction), position)
+            mip = np.where(act, mip + np.where(skipped, 1, -1), mip)
+            for k in range(2):
+                res[k] = np.where(act, res[k] * np.where(skipped, F32(0.5), F32(2.0)), res[k]).astype(F32)
+                res_inv[k] = np.where(act, res_inv[k] * np.where(skipped, F32(2.0), F32(0.5)), res_inv[k]).astype(F32)
+    return position
+
+
+def trace_segment_hi(ar, pa, o, d, t0, t1, layer):
+    """-> (result, tmin, stop_u, stop_v) for lanes of one segment"""
+    start = madd(ar, o, t0 + F32(0.001), d)
+    end = madd(ar, o, t1 - F32(0.001), d)
+    diff = start - end
+    start = np.where((ar.dot(diff, diff) < F32(0.001))[..., None], d, start)
+    su, sv = oct_encode(ar, normalize(ar, start))
+    eu, ev = oct_encode(ar, normalize(ar, end))
+    front = oct_center(ar, (su + eu) * F32(0.5), (sv + ev) * F32(0.5))
+    sd = encode_oct_depth(ar.dot(start, front)) - F32(0.0005)
+    ed = encode_oct_depth(ar.dot(end, front))
+    p_start = np.stack([su, sv, sd], axis=-1).astype(F32)
+    p_end = np.stack([eu, ev, ed], axis=-1).astype(F32)
+    stop = hierarchical_raymarch(ar, pa, layer, p_start, (p_end - p_start).astype(F32))
+    stop_dir = oct_decode(ar, stop[..., 0], stop[..., 1])
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        coef = decode_oct_depth(ar, stop[..., 2]) / ar.dot(stop_dir, front)
+        ray_stop = stop_dir * coef[..., None]
+        dd = ray_stop - o
+        tmin = np.sqrt(ar.dot(dd, dd))
+    sampled = pa.bilinear_depth(ar, stop[..., 0], stop[..., 1], layer)
+    z = stop[..., 2]
+    res = np.where(z > F32(1.0), MISS, np.where(z > sampled + F32(0.0005), UNKNOWN, np.where(z > sampled - F32(0.0005), HIT, MISS)))
+    return res, tmin.astype(F32), stop[..., 0], stop[..., 1]
+
+
+def trace_one_probe(ar, pa, grid, pmin, pstep, ray_origin, ray_dir, probe, tmin, tmax):
+    px, py = (probe % grid).astype(F32), (probe // grid).astype(F32)
+    porig = np.stack([ar.cfma(px, pstep[0], pmin[0]), ar.cfma(np.zeros_like(px), pstep[1], pmin[1]), ar.cfma(py, pstep[2], pmin[2])], axis=-1)
+    o = (ray_origin - porig).astype(F32)
+    d = normalize(ar, ray_dir)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = o * -(F32(1.0) / d)
+    tx, ty, tz = t[..., 0], t[..., 1], t[..., 2]
+    m = np.fmin(tx, ty); ty = np.fmax(tx, ty); tx = m
+    m = np.fmin(ty, tz); tz = np.fmax(ty, tz); ty = m
+    m = np.fmin(tx, ty); ty = np.fmax(tx, ty); tx = m
+    clamp = lambda v: np.fmin(np.fmax(v, tmin), tmax)
+    seg = [tmin.copy(), clamp(tx), clamp(ty), clamp(tz), np.full_like(tmin, tmax)]
+    result = np.full(probe.shape, MISS)
+    hu, hv = np.zeros_like(tmin), np.zeros_like(tmin)
+    for i in range(4):
+        sel = (result == MISS) & (np.abs(seg[i + 1] - seg[i]) >= F32(0.002))
+        if not sel.any():
+            continue
+        idx = np.nonzero(sel)[0]
+        r, tm, u, v = trace_segment_hi(ar, pa, o[idx], d[idx], seg[i][idx], seg[i + 1][idx], probe[idx])
+        result[idx] = r
+        tmin[idx] = tm
+        hu[idx], hv[idx] = u, v
+    return result, tmin, hu, hv
+
+
+def tan_half(fovy):
+    from gtao_rt_reference import _LIBM
+
+    return F32(_LIBM.tanf(float(F32(fovy) / F32(2.0))))
+
+
+def trace_probe(ar, depth_bits, normal_codes, pa, inverse_view, probe_min, probe_max, grid, fovy, aspect, znear, zfar, width, height):
+    """-> (RGBA8 codes [th, tw, 4], final result [th, tw], number of probes traced [th, tw]) on the dispatch extent tw x th.
+    depth_bits: raw D24 [h, w]; normal_codes: RG16_UNORM [h, w, 2]; inverse_view: 4x4 maths-convention float32."""
+    tw, th = width // 8 * 8, height // 4 * 4
+    gy, gx = np.mgrid[0:th, 0:tw]
+    uvx = (gx.astype(F32) / F32(tw)).astype(F32).reshape(-1)
+    uvy = (gy.astype(F32) / F32(th)).astype(F32).reshape(-1)
+    depth = d24_to_float(depth_bits.reshape(depth_bits.shape[0], depth_bits.shape[1], 1))
+    dpx = sample(ar, depth, uvx, uvy, 1)[..., 0]
+    sky = dpx >= F32(1.0)
+    tg = tan_half(fovy)
+    n_, f_ = F32(znear), F32(zfar)
+    z = (n_ * f_) / ar.cfma(dpx, f_ - n_, -f_)
+    xd, yd = ar.cfma(F32(2.0), uvx, F32(-1.0)), ar.cfma(F32(2.0), uvy, F32(-1.0))
+    vx = -xd * ((z * F32(aspect)) * tg)
+    vy = -yd * (z * tg)
+    M = np.asarray(inverse_view, F32)
+    one = F32(1.0)
+    world = np.stack([ar.cfma(M[r, 3], one, ar.cfma(M[r, 2], z, ar.cfma(M[r, 1], vy, M[r, 0] * vx))) for r in range(3)], axis=-1)
+    zero = np.zeros(1, F32)
+    cam = np.stack([ar.cfma(M[r, 3], one, ar.cfma(M[r, 2], zero, ar.cfma(M[r, 1], zero, M[r, 0] * zero))) for r in range(3)], axis=-1)
+    N = decode_normal(ar, sample(ar, unorm16_to_float(normal_codes), uvx, uvy, 2))
+    world = madd(ar, world, F32(1e-6), N)
+    V = normalize(ar, world - cam)
+    world = madd(ar, world, F32(-1e-6), V)
+    R = madd(ar, V, -(F32(2.0) * ar.dot(N, V)), N)
+
+    pmin = np.asarray(probe_min[:3], F32)
+    gm1 = F32(grid - 1)
+    pstep = ((np.asarray(probe_max[:3], F32) - pmin) / gm1).astype(F32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cx = np.fmin(np.fmax((world[..., 0] - pmin[0]) / pstep[0], F32(0.0)), F32(grid - 2))
+        cz = np.fmin(np.fmax((world[..., 2] - pmin[2]) / pstep[2], F32(0.0)), F32(grid - 2))
+    bx, by = np.floor(cx).astype(np.int64), np.floor(cz).astype(np.int64)
+
+    P = uvx.size
+    out = np.zeros((P, 4), np.uint8)
+    result = np.full(P, UNKNOWN)
+    probes_traced = np.zeros(P, np.int64)
+    live = np.nonzero(~sky)[0]
+    tmin = np.zeros(P, F32)
+    i = np.zeros(P, np.int64)
+    probe = np.zeros(P, np.int64)
+    hu, hv = np.zeros(P, F32), np.zeros(P, F32)
+    for _ in range(4):
+        if live.size == 0:
+            break
+        probe[live] = (by[live] + ((i[live] >> 1) & 1)) * grid + bx[live] + (i[live] & 1)
+        r, tm, u, v = trace_one_probe(ar, pa, grid, pmin, pstep, world[live], R[live], probe[live], tmin[live].copy(), F32(30.0))
+        result[live], tmin[live], hu[live], hv[live] = r, tm, u, v
+        probes_traced[live] += 1
+        i[live] = (i[live] + 3) & 3
+        live = live[r == UNKNOWN]
+    hit = np.nonzero((result == HIT) & ~sky)[0]
+    if hit.size:
+        out[hit] = pa.color_sample(ar, hu[hit], hv[hit], probe[hit])
+    result[sky] = -1
+    return out.reshape(th, tw, 4), result.reshape(th, tw), probes_traced.reshape(th, tw)

@@ -28,7 +28,8 @@ FMT_R16_SFLOAT = 8
 FMT_R32_SFLOAT = 9
 FMT_R8_UNORM = 10
 FMT_RGBA32_SFLOAT = 11
-FORMAT_BYTES = {1: 4, 2: 4, 3: 4, 4: 4, 5: 4, 6: 8, 7: 8, 8: 2, 9: 4, 10: 1, 11: 16}
+FMT_R16_UNORM = 12
+FORMAT_BYTES = {1: 4, 2: 4, 3: 4, 4: 4, 5: 4, 6: 8, 7: 8, 8: 2, 9: 4, 10: 1, 11: 16, 12: 2}
 
 NORMALIZE_REFLECTIONS = 1
 ACCUMULATE_REFLECTIONS = 2
@@ -218,6 +219,12 @@ class GtaoRtPush(C.Structure):  # vkr_gtao_rt_push
     _fields_ = [("rotation", C.c_float)]
 
 
+# ---- octahedral probes: programs cube2oct, probe_downsample, trace_probe ----
+class ProbeTraceConsts(C.Structure):  # vkr_probe_trace_consts == Constants (probe_renderer.cpp:332-341), 116 bytes
+    _fields_ = [("inverse_view", Mat4), ("probe_min", C.c_float * 4), ("probe_max", C.c_float * 4), ("grid_size", C.c_uint32),
+                ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
+
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -341,6 +348,12 @@ def product():
         lib.vkr_accel_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.vkr_gtao_rt_main.argtypes = [P(GtaoRtParams), _IMG, _IMG, C.c_void_p, C.c_void_p, _IMG, P(GtaoRtPush), C.c_void_p]
         for name in ("accel_layout", "accel_create", "accel_destroy", "accel_info", "accel_query", "gtao_rt_main"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
+        # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
+        lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
+        lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
+        lib.vkr_trace_probe.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_uint32, P(ProbeTraceConsts), _IMG, C.c_void_p]
+        for name in ("cube2oct", "probe_downsample", "trace_probe"):
             getattr(lib, "vkr_" + name).restype = C.c_int
         _product = lib
     return _product

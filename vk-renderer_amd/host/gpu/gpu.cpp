@@ -74,6 +74,7 @@ uint32_t to_vkr_format(VkFormat fmt) {
     case VK_FORMAT_R16G16B16A16_UNORM: return VKR_FMT_RGBA16_UNORM;
     case VK_FORMAT_R16G16B16A16_SFLOAT: return VKR_FMT_RGBA16_SFLOAT;
     case VK_FORMAT_R16_SFLOAT: return VKR_FMT_R16_SFLOAT;
+    case VK_FORMAT_R16_UNORM: return VKR_FMT_R16_UNORM;
     case VK_FORMAT_R32_SFLOAT: return VKR_FMT_R32_SFLOAT;
     case VK_FORMAT_R8_UNORM: return VKR_FMT_R8_UNORM;
     case VK_FORMAT_R32G32B32A32_SFLOAT: return VKR_FMT_RGBA32_SFLOAT;

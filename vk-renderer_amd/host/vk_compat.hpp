@@ -18,7 +18,7 @@ typedef uint64_t VkDeviceSize;
 #define VK_FALSE 0u
 enum VkFormat {
   VK_FORMAT_UNDEFINED = 0, VK_FORMAT_R8_UNORM = 9, VK_FORMAT_R8G8B8A8_UNORM = 37, VK_FORMAT_R8G8B8A8_SRGB = 43,
-  VK_FORMAT_R16_SFLOAT = 76, VK_FORMAT_R16G16_UNORM = 77, VK_FORMAT_R16G16_SFLOAT = 83,
+  VK_FORMAT_R16_UNORM = 70, VK_FORMAT_R16_SFLOAT = 76, VK_FORMAT_R16G16_UNORM = 77, VK_FORMAT_R16G16_SFLOAT = 83,
   VK_FORMAT_R16G16B16A16_UNORM = 91, VK_FORMAT_R16G16B16A16_SFLOAT = 97, VK_FORMAT_R32_UINT = 98, VK_FORMAT_R32_SFLOAT = 100,
   VK_FORMAT_R32G32B32A32_SFLOAT = 109, VK_FORMAT_D24_UNORM_S8_UINT = 129
 };

@@ -108,6 +108,8 @@ class ImageBuf:
             return np.ascontiguousarray(rows).view(np.float16).reshape(h, w, 4)
         if f == abi.FMT_R16_SFLOAT:
             return np.ascontiguousarray(rows).view(np.float16).reshape(h, w, 1)
+        if f == abi.FMT_R16_UNORM:
+            return np.ascontiguousarray(rows).view(np.uint16).reshape(h, w, 1)
         if f == abi.FMT_R32_SFLOAT:
             return np.ascontiguousarray(rows).view(np.float32).reshape(h, w, 1)
         if f == abi.FMT_R8_UNORM:
@@ -130,7 +132,7 @@ class ImageBuf:
         f = self.format
         if f == abi.FMT_D24_UNORM_S8:
             return ((r & 0xFFFFFF).astype(np.float32) / np.float32(16777215.0)).astype(np.float32)
-        if f in (abi.FMT_RG16_UNORM, abi.FMT_RGBA16_UNORM):
+        if f in (abi.FMT_RG16_UNORM, abi.FMT_RGBA16_UNORM, abi.FMT_R16_UNORM):
             return (r.astype(np.float32) / np.float32(65535.0)).astype(np.float32)
         if f in (abi.FMT_RGBA8_UNORM, abi.FMT_R8_UNORM):
             return (r.astype(np.float32) / np.float32(255.0)).astype(np.float32)
@@ -140,6 +142,70 @@ class ImageBuf:
             lin[..., 3] = c[..., 3]
             return lin.astype(np.float32)
         return r.astype(np.float32)
+
+
+class ArrayImageBuf:
+    """An array image, mip-major: per mip, the layers one after another (rows 256-B aligned), so layer l of mip m lies at
+    layer 0's plus l * pitch[m] * height[m].  That is how the host mirror's gpu::Image allocates an array; the mirror does not
+    yet hand out per-layer views of a mipped array (Image::describe_layer takes single-mip arrays only), so this layout is
+    the one its probe arrays are to use.  `descs()` gives the per-layer descriptors of the C-ABI's array arguments
+    (vkr_trace_probe's probe arrays).  raw() knows the formats of those arrays: RGBA8_UNORM and R16_UNORM."""
+
+    def __init__(self, fmt, width, height, layers, mips=1, device=None, fill=0):
+        self.format, self.width, self.height, self.layers, self.mips = fmt, int(width), int(height), int(layers), int(mips)
+        self.bpp = abi.FORMAT_BYTES[fmt]
+        self.pitch, self.offset = [], []
+        off = 0
+        for i in range(self.mips):
+            p = _align(mip_extent(self.width, i) * self.bpp, ROW_ALIGN)
+            self.pitch.append(p)
+            self.offset.append(off)
+            off += _align(p * mip_extent(self.height, i) * self.layers, ROW_ALIGN)
+        self.nbytes = off
+        if device is None:
+            self.host, self.tensor = np.full(self.nbytes, fill, dtype=np.uint8), None
+            self.ptr = self.host.ctypes.data
+        else:
+            import torch
+
+            self.host, self.tensor = None, torch.full((self.nbytes,), fill, dtype=torch.uint8, device=device)
+            self.ptr = self.tensor.data_ptr()
+
+    def layer_offset(self, layer, mip):
+        return self.offset[mip] + layer * self.pitch[mip] * mip_extent(self.height, mip)
+
+    def desc(self, layer):
+        d = abi.VkrImg()
+        d.base = self.ptr + self.layer_offset(layer, 0)
+        d.format, d.mip_count = self.format, self.mips
+        d.width = d.full_width = self.width
+        d.height = d.full_height = self.height
+        d.origin_x = d.origin_y = 0
+        for i in range(self.mips):
+            d.pitch_bytes[i] = self.pitch[i]
+            d.mip_offset[i] = self.layer_offset(layer, i) - self.layer_offset(layer, 0)
+        return d
+
+    def descs(self):
+        """(vkr_img * layers) array, one descriptor per layer"""
+        arr = (abi.VkrImg * self.layers)()
+        for layer in range(self.layers):
+            arr[layer] = self.desc(layer)
+        return arr
+
+    def to_host(self):
+        return self.host if self.host is not None else self.tensor.cpu().numpy()
+
+    def raw(self, mip=0, host=None):
+        """raw storage of one mip of every layer: [layers, h, w, channels] in the storage dtype"""
+        dtypes = {abi.FMT_RGBA8_UNORM: np.uint8, abi.FMT_R16_UNORM: np.uint16}
+        if self.format not in dtypes:
+            raise ValueError(f"ArrayImageBuf.raw: format {self.format}")
+        host = self.to_host() if host is None else host
+        w, h = mip_extent(self.width, mip), mip_extent(self.height, mip)
+        rows = host[self.offset[mip]: self.offset[mip] + self.pitch[mip] * h * self.layers]
+        rows = np.ascontiguousarray(rows.reshape(self.layers, h, self.pitch[mip])[:, :, : w * self.bpp])
+        return rows.view(dtypes[self.format]).reshape(self.layers, h, w, -1)
 
 
 def depth_mip_count(width, height):
