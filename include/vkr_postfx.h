@@ -496,7 +496,7 @@ typedef struct vkr_gtao_rt_push { float rotation; } vkr_gtao_rt_push;  /* rt_mai
 int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel,
                      const float* directions, const vkr_img* out_raw, const vkr_gtao_rt_push* push, void* stream);
 
-/* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cube2oct, probe_downsample, trace_probe) ------------------------
+/* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
  * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one
  * per-mip stride (the layout of an array image).  A cube is 6 layers in face order +X, -X, +Y, -Y, +Z, -Z, sampled with the
@@ -508,6 +508,20 @@ int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, con
  * dispatch extent floor(w/8)*8 x floor(h/4)*4 is written, with uv = pixel / that extent.                                     */
 int vkr_cube2oct(const vkr_img* cube_color, const vkr_img* cube_distance, const vkr_img* oct_color, const vkr_img* oct_depth,
                  void* stream);
+/* program "cubemap_probe": ProbeRenderer::render_cubemap / render_side (probe_renderer.cpp:72-160) + cubemap_probe/shader.{vert,
+ * frag} as a compute rasteriser: the six faces of the cube at `pos` from one set of launches.  Face f (+X, -X, +Y, -Y, +Z, -Z) is
+ * drawn with view = lookAt(pos, pos + fwd, up) of calc_matrix (up (0,-1,0); +Y: (0,0,1), -Y: (0,0,-1)) and projection =
+ * perspective(radians(90), 1, 0.05, 80), both evaluated on the host in fp32; the vertex stage is view_pos = (view * model) * pos,
+ * clip = projection * view_pos.  A draw whose albedo_index is 0xFFFFFFFF is skipped.  The raster rules are those of
+ * vkr_raster_gbuffer (pixel centres, top-left fill rule, 8 sub-pixel bits, cull none, D24 LESS_OR_EQUAL with the later triangle
+ * winning a tie, near-plane clip, implicit LOD, the alpha-0 discard at coverage time, VKR_RASTER_DRAW_OPAQUE_ALBEDO).  Colour: the
+ * trilinear sRGB albedo as RGBA8_SRGB; distance: length of the interpolated view-space position as fp16 (round to nearest even).
+ * Clears: colour codes (255, 0, 0, 0) (the reference clears to (100, 0, 0, 0)), distance 100.0.  cube_color / cube_distance: 6
+ * descriptors each, the layers of one regular array (one square extent, one pitch, one stride between consecutive layers).
+ * `scratch`: vkr_cubemap_probe_scratch_bytes(cube size, triangles summed over ALL draws of the scene) of device memory. */
+uint64_t vkr_cubemap_probe_scratch_bytes(uint32_t cube_size, uint32_t triangle_count);
+int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[3], const vkr_img* cube_color /* 6 x RGBA8_SRGB */,
+                      const vkr_img* cube_distance /* 6 x R16_SFLOAT */, void* scratch, uint64_t scratch_bytes, void* stream);
 /* program "probe_downsample": probe_renderer.cpp:204-236 + probe_downsample/shader.frag.  Mip i >= 1 of the R16_UNORM view is
  * the min of the 2 x 2 texels of mip i - 1 at min(2 * pixel + o, size) (not size - 1: a fetch past the edge reads 0).        */
 int vkr_probe_downsample(const vkr_img* depth_layer_all_mips, void* stream);

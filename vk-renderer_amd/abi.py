@@ -355,6 +355,11 @@ def product():
         lib.vkr_trace_probe.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_uint32, P(ProbeTraceConsts), _IMG, C.c_void_p]
         for name in ("cube2oct", "probe_downsample", "trace_probe"):
             getattr(lib, "vkr_" + name).restype = C.c_int
+        # the cube-face bake (checked against the numpy restatement tests/cubemap_reference.py)
+        lib.vkr_cubemap_probe_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.vkr_cubemap_probe_scratch_bytes.restype = C.c_uint64
+        lib.vkr_cubemap_probe.argtypes = [P(RasterScene), P(C.c_float * 3), _IMG, _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.vkr_cubemap_probe.restype = C.c_int
         _product = lib
     return _product
 
@@ -365,6 +370,22 @@ def check(rc, lib=None):
         if lib is not None and hasattr(lib, "vkr_last_error"):
             msg = (lib.vkr_last_error() or b"").decode()
         raise RuntimeError(f"vkr call failed with code {rc}: {msg}")
+
+
+def cubemap_probe_scratch_bytes(cube_size, triangle_count):
+    """vkr_cubemap_probe_scratch_bytes: device scratch of one bake (triangles summed over all draws of the scene)"""
+    return int(product().vkr_cubemap_probe_scratch_bytes(int(cube_size), int(triangle_count)))
+
+
+def cubemap_probe(scene, pos, cube_color, cube_distance, scratch, scratch_bytes, stream=None):
+    """vkr_cubemap_probe: bakes the six cube faces at `pos`.  scene: RasterScene; cube_color / cube_distance: (VkrImg * 6)
+    arrays, the layers of one regular array image each (images.ArrayImageBuf.descs()); scratch: device pointer.  Raises
+    RuntimeError with the library's message on a refusal."""
+    lib = product()
+    if len(cube_color) < 6 or len(cube_distance) < 6:
+        raise RuntimeError("cubemap_probe: a cube has 6 layers")
+    p = (C.c_float * 3)(float(pos[0]), float(pos[1]), float(pos[2]))
+    check(lib.vkr_cubemap_probe(C.byref(scene), C.byref(p), cube_color, cube_distance, scratch, int(scratch_bytes), stream), lib)
 
 
 COMM_ID_BYTES = 128

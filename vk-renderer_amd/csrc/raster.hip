@@ -26,12 +26,9 @@
 // the oracle's immediate-mode rasterizer; colour / normal / velocity follow the frozen fp32 contract.
 #include <vector>
 
-#include "vkr_host.hpp"
+#include "raster_common.hpp"
 
 namespace vkr {
-
-#define RASTER_MAX_TEXTURES 32
-#define RASTER_GUARD_PX 1048576.0f  // |screen coordinate| beyond this: the triangle is dropped (documented limit)
 
 struct DrawDev {  // one draw call, matrices premultiplied on the host exactly as the vertex shader does
   Mat4 mvp, prev_mvp, normal_mat;
@@ -89,15 +86,6 @@ struct ScreenTri {
   bool valid;
 };
 
-// differences of 24.8 coordinates fit 32 bits, their products need 64 (v_mad_i64_i32)
-VKR_DEV long long edge_fn(int ax, int ay, int bx, int by, int px, int py) {
-  return (long long)(bx - ax) * (long long)(py - ay) - (long long)(by - ay) * (long long)(px - ax);
-}
-// top-left rule for an edge a->b of a triangle with positive area2 under edge_fn (y down)
-VKR_DEV bool is_top_left(int ax, int ay, int bx, int by) {
-  const int dx = bx - ax, dy = by - ay;
-  return dy < 0 || (dy == 0 && dx > 0);
-}
 
 // Vertex shader on the three corners + near-plane clip (z_clip >= 0) -> sub-triangle `sub` (0 or 1).
 // Returns the number of sub-triangles the clipped polygon has (0, 1 or 2) in *count.
@@ -123,17 +111,8 @@ VKR_DEV ScreenTri setup_triangle(const RasterArgs& a, const DrawDev& d, uint32_t
   *count = n < 3 ? 0 : n - 2;
   if (sub >= *count) return t;
   t.v[0] = poly[0]; t.v[1] = poly[1 + sub]; t.v[2] = poly[2 + sub];
-  for (int k = 0; k < 3; k++) {
-    const f4 p = t.v[k].position;
-    if (!(p.w > 0.0f)) return t;
-    const float xs = ((p.x / p.w) * 0.5f + 0.5f) * (float)a.width;
-    const float ys = ((p.y / p.w) * 0.5f + 0.5f) * (float)a.height;
-    if (!(fabsf(xs) <= RASTER_GUARD_PX && fabsf(ys) <= RASTER_GUARD_PX)) return t;
-    t.x[k] = (int)rintf(xs * 256.0f);
-    t.y[k] = (int)rintf(ys * 256.0f);
-    t.w[k] = p.w;
-    t.z[k] = p.z / p.w;
-  }
+  for (int k = 0; k < 3; k++)
+    if (!snap_vertex(t.v[k].position, a.width, a.height, &t.x[k], &t.y[k], &t.w[k], &t.z[k])) return t;
   t.area2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], t.x[2], t.y[2]);
   if (t.area2 == 0) return t;
   if (t.area2 < 0) {  // cull none: both windings are drawn; normalise the orientation
@@ -158,78 +137,7 @@ struct CoverTri {
   VKR_DEV CoverTri() {}
   VKR_DEV explicit CoverTri(const ScreenTri& t) : x {t.x[0], t.x[1], t.x[2]}, y {t.y[0], t.y[1], t.y[2]}, z {t.z[0], t.z[1], t.z[2]}, inv_area2 {t.inv_area2} {}
 };
-// coverage + depth of pixel (px, py); lambda: screen-space barycentrics
-template <class T> VKR_DEV bool cover(const T& t, int px, int py, float lambda[3], uint32_t* d24) {
-  const int X = (px << 8) + 128, Y = (py << 8) + 128;
-  const long long e0 = edge_fn(t.x[1], t.y[1], t.x[2], t.y[2], X, Y);
-  const long long e1 = edge_fn(t.x[2], t.y[2], t.x[0], t.y[0], X, Y);
-  const long long e2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], X, Y);
-  if (e0 < 0 || e1 < 0 || e2 < 0) return false;
-  if (e0 == 0 && !is_top_left(t.x[1], t.y[1], t.x[2], t.y[2])) return false;
-  if (e1 == 0 && !is_top_left(t.x[2], t.y[2], t.x[0], t.y[0])) return false;
-  if (e2 == 0 && !is_top_left(t.x[0], t.y[0], t.x[1], t.y[1])) return false;
-  const double inv = t.inv_area2;
-  lambda[0] = (float)((double)e0 * inv);
-  lambda[1] = (float)((double)e1 * inv);
-  lambda[2] = (float)((double)e2 * inv);
-  const float depth = (lambda[0] * t.z[0] + lambda[1] * t.z[1]) + lambda[2] * t.z[2];
-  if (!(depth >= 0.0f && depth <= 1.0f)) return false;  // depth clipping (far plane; near was clipped)
-  *d24 = (uint32_t)rintf(depth * 16777215.0f);
-  return true;
-}
-// barycentrics at an arbitrary (possibly uncovered) pixel, for the forward differences of uv
-VKR_DEV void lambda_at(const ScreenTri& t, int px, int py, float lambda[3]) {
-  const int X = (px << 8) + 128, Y = (py << 8) + 128;
-  const double inv = t.inv_area2;
-  lambda[0] = (float)((double)edge_fn(t.x[1], t.y[1], t.x[2], t.y[2], X, Y) * inv);
-  lambda[1] = (float)((double)edge_fn(t.x[2], t.y[2], t.x[0], t.y[0], X, Y) * inv);
-  lambda[2] = (float)((double)edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], X, Y) * inv);
-}
-VKR_DEV void perspective(const ScreenTri& t, const float lambda[3], float b[3]) {
-  const float q0 = lambda[0] / t.w[0], q1 = lambda[1] / t.w[1], q2 = lambda[2] / t.w[2];
-  const float s = (q0 + q1) + q2;
-  b[0] = q0 / s; b[1] = q1 / s; b[2] = q2 / s;
-}
 #define BARY(F) ((b[0] * t.v[0].F + b[1] * t.v[1].F) + b[2] * t.v[2].F)
-
-VKR_DEV int wrap_repeat(int i, int n) {
-  if ((n & (n - 1)) == 0) return i & (n - 1);  // power-of-two extent (every mip of the usual texture): no integer division
-  const int m = i % n;
-  return m < 0 ? m + n : m;
-}
-// texture(sampler2D, uv) of an RGBA8_SRGB mip chain: REPEAT, bilinear, linear between the two mips of `lod`
-// `lut`: the sRGB decode table (srgb_lut_stage), in LDS where the caller has staged it
-VKR_DEV f4 sample_level_repeat(const Tex& t, f2 uv, const float* lut) {
-  const float x = cfma(uv.x, (float)t.fw, -0.5f), y = cfma(uv.y, (float)t.fh, -0.5f);
-  const float x0f = floorf(x), y0f = floorf(y);
-  const float fx = x - x0f, fy = y - y0f;
-  const int x0 = wrap_repeat(f2i(x0f), t.fw), y0 = wrap_repeat(f2i(y0f), t.fh);
-  const int x1 = wrap_repeat(x0 + 1, t.fw), y1 = wrap_repeat(y0 + 1, t.fh);
-  auto dec = [&](int tx, int ty) {
-    const uint32_t v = *texel_ptr<const uint32_t>(t, tx, ty);
-    return mk4(lut[v & 0xFFu], lut[(v >> 8) & 0xFFu], lut[(v >> 16) & 0xFFu], unorm8_to_float(v >> 24));
-  };
-  return mix4(mix4(dec(x0, y0), dec(x1, y0), fx), mix4(dec(x0, y1), dec(x1, y1), fx), fy);
-}
-VKR_DEV f4 sample_trilinear(const Pyramid& p, f2 uv, f2 duvdx, f2 duvdy, const float* lut) {
-  const float w = (float)p.mip[0].fw, h = (float)p.mip[0].fh;
-  // rho^2 = max squared footprint; lod = log2(rho).  The level pair comes from the exponent of rho^2
-  // (exact), only the blend factor from log2f (smooth) — a libm ulp must not flip the pair.
-  const float rx2 = (duvdx.x * w) * (duvdx.x * w) + (duvdx.y * h) * (duvdx.y * h);
-  const float ry2 = (duvdy.x * w) * (duvdy.x * w) + (duvdy.y * h) * (duvdy.y * h);
-  const float r2 = vmax(rx2, ry2);
-  int l0 = 0;
-  float f = 0.0f;
-  if (r2 > 1.0f && r2 < 3.0e38f) {
-    l0 = ilogbf(r2) >> 1;  // floor(log2(rho))
-    f = vclamp(0.5f * log2f(r2) - (float)l0, 0.0f, 1.0f);
-  }
-  if (l0 >= p.count - 1) { l0 = p.count - 1; f = 0.0f; }  // sampler LOD range [0, 10] and the chain length
-  const int l1 = min(l0 + 1, p.count - 1);
-  const f4 a = sample_level_repeat(p.mip[l0], uv, lut);
-  if (f == 0.0f || l1 == l0) return a;
-  return mix4(a, sample_level_repeat(p.mip[l1], uv, lut), f);
-}
 
 
 // uv and its forward differences at pixel (px, py) of triangle t (lambda: its screen-space barycentrics there):
@@ -266,18 +174,6 @@ __global__ void k_raster_clear(unsigned long long* vis, size_t n) {
   if (i < n) vis[i] = ~0ull;
 }
 
-// pixel bounding box (centres that can be covered), clipped to the viewport; false when empty
-template <class T> VKR_DEV bool tri_bbox(const T& t, int width, int height, int* x0, int* y0, int* x1, int* y1) {
-  const int minx = min(t.x[0], min(t.x[1], t.x[2])), maxx = max(t.x[0], max(t.x[1], t.x[2]));
-  const int miny = min(t.y[0], min(t.y[1], t.y[2])), maxy = max(t.y[0], max(t.y[1], t.y[2]));
-  *x0 = max((minx - 128) >> 8, 0); *x1 = min((maxx - 128) >> 8, width - 1);
-  *y0 = max((miny - 128) >> 8, 0); *y1 = min((maxy - 128) >> 8, height - 1);
-  return *x0 <= *x1 && *y0 <= *y1;
-}
-#define RASTER_SMALL_BLOCKS 64  // sub-triangles whose bounding box has more 8x8 blocks go to the shared-work kernel
-#define RASTER_LARGE_CHUNK 16   // blocks per work item of the shared-work kernel
-#define RASTER_LARGE_GRID 2048  // its blocks of four waves: chunk c goes to wave c mod (4 x grid)
-struct LargeEntry { uint32_t rec, first_chunk; };  // a listed sub-triangle and the index of its first chunk
 
 // one thread per triangle; a large sub-triangle takes a list slot AND its range of chunks with one 64-bit atomicAdd on
 // *large_state (entries << 32 | chunks), so the list is sorted by first_chunk
@@ -314,22 +210,11 @@ __global__ __launch_bounds__(256) void k_raster_setup(RasterArgs a, uint32_t tot
   }
 }
 
-// Largest value edge a->b takes over the pixel centres X in [X0, X1], Y in [Y0, Y1] (24.8): when it is negative no pixel of
-// the block is inside the triangle (an edge function is linear, its maximum over a box sits at a corner)
-VKR_DEV long long edge_max(int ax, int ay, int bx, int by, int X0, int Y0, int X1, int Y1) {
-  const int dx = bx - ax, dy = by - ay;
-  return (long long)dx * (long long)((dx > 0 ? Y1 : Y0) - ay) - (long long)dy * (long long)((dy > 0 ? X0 : X1) - ax);
-}
 // 8x8 pixel block `b` (row-major inside the bounding box) of record `rec`, one pixel per lane
 VKR_DEV void raster_block(const RasterArgs& a, const CoverTri& t, uint32_t alpha_tex, uint32_t rec, int x0, int y0, int x1, int y1, int b, int lane) {
   const int bw = (x1 >> 3) - (x0 >> 3) + 1;
   const int bx0 = ((x0 >> 3) + b % bw) << 3, by0 = ((y0 >> 3) + b / bw) << 3;
-  {  // the whole block outside one edge (half the blocks of a large triangle's bounding box): nothing to test per pixel
-    const int X0 = (bx0 << 8) + 128, Y0 = (by0 << 8) + 128, X1 = X0 + 7 * 256, Y1 = Y0 + 7 * 256;
-    if (edge_max(t.x[1], t.y[1], t.x[2], t.y[2], X0, Y0, X1, Y1) < 0 || edge_max(t.x[2], t.y[2], t.x[0], t.y[0], X0, Y0, X1, Y1) < 0 ||
-        edge_max(t.x[0], t.y[0], t.x[1], t.y[1], X0, Y0, X1, Y1) < 0)
-      return;
-  }
+  if (block_outside(t, bx0, by0)) return;
   const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
   if (px < x0 || px > x1 || py < y0 || py > y1) return;
   float lambda[3];
@@ -369,12 +254,7 @@ __global__ __launch_bounds__(256) void k_raster_large(RasterArgs a, const unsign
   const int lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
   for (uint32_t c = wave; c < chunks; c += waves) {
-    uint32_t lo = 0, hi = n - 1;  // the last entry with first_chunk <= c
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1) >> 1;
-      if (large_list[mid].first_chunk <= c) lo = mid; else hi = mid - 1;
-    }
-    const LargeEntry e = large_list[lo];
+    const LargeEntry e = large_entry_of(large_list, n, c);
     const CoverTri t(a.setup[e.rec]);
     const uint32_t alpha_tex = a.setup[e.rec].alpha_tex;
     int x0, y0, x1, y1;
@@ -436,21 +316,11 @@ __global__ __launch_bounds__(256) void k_raster_resolve(ResolveArgs a) {
   *texel_ptr<uint32_t>(a.depth, lx, ly) = o_depth;
 }
 
-// c = a * b with GLSL's mat4 * mat4 (column-major, each element a dot product accumulated left to right)
-static void mat_mul(Mat4& c, const vkr_mat4& a, const vkr_mat4& b) {
-  for (int col = 0; col < 4; col++)
-    for (int row = 0; row < 4; row++) {
-      float s = a.m[0 * 4 + row] * b.m[col * 4 + 0];
-      for (int k = 1; k < 4; k++) s = s + a.m[k * 4 + row] * b.m[col * 4 + k];
-      c.m[col * 4 + row] = s;
-    }
-}
 
 }  // namespace vkr
 
 using namespace vkr;
 
-static uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 extern "C" uint64_t vkr_raster_scratch_bytes(uint32_t width, uint32_t height, uint32_t triangle_count) {
   return align_up((uint64_t)width * height * 8u, 256) + align_up(sizeof(DrawDev) * 1024u, 256) + align_up(sizeof(Pyramid) * RASTER_MAX_TEXTURES, 256) +

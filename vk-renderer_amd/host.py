@@ -16,6 +16,7 @@ STAGE_GTAO_GRAPHICS, STAGE_GTAO_DEINTERLEAVED, STAGE_SCREEN_TRACE = 2048, 4096, 
 STAGE_SSR_CLASSIFIED, STAGE_SSR_TRACE, STAGE_SSR_RESOLVE = 16384, 32768, 65536
 STAGE_RASTER = 131072
 STAGE_GTAO_RT = 1 << 21  # ray-traced AO (main.cpp:379-388 use_rt_ao): needs load_scene(); not with STAGE_GTAO, not tiled
+STAGE_PROBE_TRACE = 1 << 22  # ProbeTracePass::run through the grid of bake_probes() -> image "probe_trace"; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -121,7 +122,9 @@ def lib():
         # frames that never ask for them must still load it.  Calling one that is missing raises AttributeError.
         for name, args in (("vkrh_gtao_rt_params", [C.c_void_p, C.POINTER(abi.GtaoRtParams)]),
                            ("vkrh_gtao_directions", [C.c_void_p, C.c_uint32]),
-                           ("vkrh_selftest_ray_query", [C.c_char_p, C.c_uint32])):
+                           ("vkrh_selftest_ray_query", [C.c_char_p, C.c_uint32]),
+                           # the probe bake (same rule: typed where exported)
+                           ("vkrh_bake_probes", [C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_uint32, C.c_uint32, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -283,6 +286,12 @@ class HostFrame:
     def pin_screen_trace(self, angle_jitter=0.0, random_offset=0.25, frame_count=0):
         self._check(lib().vkrh_pin_screen_trace(self.h, angle_jitter, random_offset, frame_count))
 
+    def bake_probes(self, pmin, pmax, grid_size=4, probe_size=256, cube_size=128):
+        """vkrh_bake_probes: a grid_size x grid_size grid of octahedral probes from the loaded scene, in x and z between pmin and
+        pmax at pmin's y.  Leaves images "probe_color" / "probe_depth" (download(name, layer)) for STAGE_PROBE_TRACE."""
+        lo, hi = (C.c_float * 3)(*[float(v) for v in pmin]), (C.c_float * 3)(*[float(v) for v in pmax])
+        self._check(lib().vkrh_bake_probes(self.h, C.byref(lo), C.byref(hi), int(grid_size), int(probe_size), int(cube_size)))
+
     def run(self, mask):
         self._check(lib().vkrh_run(self.h, mask))
 
@@ -347,9 +356,18 @@ class HostFrame:
             d = abi.VkrImg()
             self._check(lib().vkrh_image_layer(self.h, name.encode(), layer, C.byref(d)))
         buf = ImageBuf(d.format, d.width, d.height, d.mip_count, full=(d.full_width, d.full_height), origin=(d.origin_x, d.origin_y))
+        t, off = self.allocator.tensor_at(d.base)
+        if layer is not None and d.mip_count > 1:
+            # a layer of a mipped array: its mips lie an array's mip apart (arrays are mip-major), copied level by level
+            from .images import mip_extent
+
+            for i in range(d.mip_count):
+                assert buf.pitch[i] == d.pitch_bytes[i], "layout rules diverged"
+                n = buf.pitch[i] * mip_extent(d.height, i)
+                buf.host[buf.offset[i]: buf.offset[i] + n] = t[off + d.mip_offset[i]: off + d.mip_offset[i] + n].cpu().numpy()
+            return buf
         for i in range(d.mip_count):
             assert buf.pitch[i] == d.pitch_bytes[i] and buf.offset[i] == d.mip_offset[i], "layout rules diverged"
-        t, off = self.allocator.tensor_at(d.base)
         buf.upload(t[off: off + buf.nbytes].cpu().numpy())
         return buf
 

@@ -21,6 +21,7 @@
 #include "downsample_pass.hpp"
 #include "gtao.hpp"
 #include "image_readback.hpp"
+#include "probe_renderer.hpp"
 #include "scene/scene_as.hpp"
 #include "scene_renderer.hpp"
 #include "screen_trace.hpp"
@@ -57,6 +58,13 @@ struct PostFxFrame {
   std::unique_ptr<scene::CompiledScene> loaded_scene;
   std::unique_ptr<SceneRenderer> scene_renderer;
   std::unique_ptr<scene::SceneAccelerationStructure> scene_as;  // main.cpp:257-258, built by vkrh_load_scene
+
+  // the probe grid of the last vkrh_bake_probes
+  std::unique_ptr<ProbeRenderer> probe_renderer;
+  std::unique_ptr<OctahedralProbeGrid> probe_grid;
+  ProbeTracePass probe_trace_pass;
+  rendergraph::ImageResourceId probe_trace_out;
+  bool has_probe_trace_out = false;
 
   DrawTAAParams draw_params{};
   glm::mat4 projection, view, prev_view;
@@ -99,6 +107,23 @@ struct PostFxFrame {
     return GTAORTParams{glm::inverse(view), fazz.x, fazz.y, fazz.z, fazz.w};
   }
 
+  void bake_probes(const float* mn, const float* mx, uint32_t grid_size, uint32_t probe_size, uint32_t cube_size) {
+    // refused before anything is recorded
+    if (!mn || !mx) throw std::runtime_error{"vkrh_bake_probes: NULL argument"};
+    if (cfg.tiled) throw std::runtime_error{"vkrh_bake_probes: on a tiled frame (probes are baked on one GPU)"};
+    if (grid_size < 2 || grid_size > 64) throw std::runtime_error{"vkrh_bake_probes: grid_size " + std::to_string(grid_size) + ", needs 2..64"};
+    if (probe_size == 0 || probe_size % 8 || probe_size > 4096) throw std::runtime_error{"vkrh_bake_probes: probe_size must be a multiple of 8 in 8..4096"};
+    if (cube_size == 0 || cube_size % 8 || cube_size > 4096) throw std::runtime_error{"vkrh_bake_probes: cube_size must be a multiple of 8 in 8..4096"};
+    if (!scene_renderer) throw std::runtime_error{"vkrh_bake_probes: without a loaded scene (vkrh_load_scene)"};
+    probe_grid.reset();
+    probe_renderer.reset(new ProbeRenderer(graph, cube_size));
+    probe_grid.reset(new OctahedralProbeGrid(graph, grid_size, probe_size));
+    probe_renderer->render_probe_grid(graph, *scene_renderer, glm::vec3{mn[0], mn[1], mn[2]}, glm::vec3{mx[0], mx[1], mx[2]}, *probe_grid);
+    graph.submit();
+    task_names.clear();
+    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
+  }
+
   void run(uint32_t mask) {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
     if (mask & VKRH_STAGE_GTAO_RT) {  // refused before anything is recorded
@@ -109,6 +134,10 @@ struct PostFxFrame {
         throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
     }
     const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
+    if (mask & VKRH_STAGE_PROBE_TRACE) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE on a tiled frame (probes are traced on one GPU)"};
+      if (!probe_grid) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE without baked probes (vkrh_bake_probes)"};
+    }
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
     if (mask & VKRH_STAGE_BRDF_LUT) ssr.preintegrate_brdf(graph);
     if (mask & VKRH_STAGE_PREV_DEPTH) {
@@ -159,6 +188,15 @@ struct PostFxFrame {
       gtao.add_accumulate_pass(graph, draw_params, gbuffer);
     }
     // ---- passes the reference ships but never records ----
+    if (mask & VKRH_STAGE_PROBE_TRACE) {
+      if (!has_probe_trace_out) {
+        probe_trace_out = graph.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, cfg.width, cfg.height},
+                                             VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT | VK_IMAGE_USAGE_SAMPLED_BIT);
+        has_probe_trace_out = true;
+      }
+      const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
+      probe_trace_pass.run(graph, *probe_grid, gbuffer.depth, gbuffer.normal, probe_trace_out, ProbeTraceParams{glm::inverse(view), fazz.x, fazz.y, fazz.z, fazz.w});
+    }
     if (mask & VKRH_STAGE_GTAO_GRAPHICS) {
       gtao.add_main_pass_graphics(graph, gtao_params, gbuffer.depth, gbuffer.normal);
       gtao.add_filter_pass(graph, gtao_params, gbuffer.depth);
@@ -225,7 +263,8 @@ struct PostFxFrame {
         {"raw", 8}, {"filtered", 9}, {"acc_ao", 10}, {"acc_hist", 11}, {"rays", 12}, {"reflections", 13}, {"blurred", 14},
         {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
-        {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}};
+        {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
+        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -239,6 +278,11 @@ struct PostFxFrame {
       case 22: return color_out_tex; case 23: return ssr.get_preintegrated_brdf(); case 24: return gtao.prev_frame;
       case 25: return gtao.output; case 26: return gtao.deinterleaved_depth; case 27: return screen_trace.raw;
       case 28: return screen_trace.filtered;
+      case 31: if (!has_probe_trace_out) throw std::runtime_error{"vkrh_image: 'probe_trace' only exists after VKRH_STAGE_PROBE_TRACE"}; return probe_trace_out;
+      case 32: case 33: case 34: case 35:
+        if (!probe_grid) throw std::runtime_error{"vkrh_image: '" + name + "' only exists after vkrh_bake_probes"};
+        return it->second == 32 ? probe_grid->color_array : it->second == 33 ? probe_grid->depth_array
+               : it->second == 34 ? probe_renderer->get_cubemap_color() : probe_renderer->get_cubemap_distance();
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -971,6 +1015,9 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
     f->scene_as->build(transfer_pool, *f->loaded_scene);
   });
 }
+int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32_t grid_size, uint32_t probe_size, uint32_t cube_size) {
+  return guarded([&] { frame_ref(frame).bake_probes(min, max, grid_size, probe_size, cube_size); });
+}
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {
     auto* f = &frame_ref(frame);
@@ -1046,7 +1093,8 @@ int vkrh_image_layer(void* frame, const char* name, uint32_t layer, vkr_img* out
   return guarded([&] {
     auto* f = &frame_ref(frame);
     if (!f || !name || !out) throw std::runtime_error{"NULL argument"};
-    *out = f->graph.get_image(f->lookup(name))->describe_layer(layer);
+    auto& img = f->graph.get_image(f->lookup(name));
+    *out = img->describe_layer(layer, 0, img->get_mip_levels());
   });
 }
 int vkrh_capture(void* frame, const char* name, uint32_t mip, uint32_t kind, const char* path) {

@@ -55,6 +55,9 @@ enum {
    * vkrh_load_scene), add_filter_pass, add_accumulate_pass.  One GPU only (not on a tiled frame), not together with
    * VKRH_STAGE_GTAO (both write GTAO's images), and only after vkrh_load_scene.                                           */
   VKRH_STAGE_GTAO_RT            = 1u << 21,
+  /* ProbeTracePass::run on the G-buffer's depth and normal through the probe grid of the last vkrh_bake_probes -> image
+   * "probe_trace" (RGBA8_UNORM, full resolution).  One GPU only (not on a tiled frame), and only after a bake.            */
+  VKRH_STAGE_PROBE_TRACE        = 1u << 22,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -85,6 +88,12 @@ typedef struct vkrh_scene_texture {
 } vkrh_scene_texture;
 int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
                     const vkrh_scene_draw* draws, uint32_t draw_count, const vkrh_scene_texture* textures, uint32_t texture_count);
+/* Bakes a grid_size x grid_size grid of octahedral probes (probe_size^2, from cube_size^2 cube faces) from the scene of
+ * vkrh_load_scene through ProbeRenderer::render_probe_grid: probes in x and z between min and max, at min.y; array layer
+ * y * grid_size + x.  The grid stays in the frame until the next bake: images "probe_color", "probe_depth" (vkrh_image_layer, all
+ * mips), and the cube of the last probe "cubemap_color", "cubemap_distance".  Refused: no scene, grid_size < 2, probe_size or
+ * cube_size 0 or not a multiple of 8. */
+int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32_t grid_size, uint32_t probe_size, uint32_t cube_size);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */
@@ -110,7 +119,7 @@ int vkrh_image(void* frame, const char* name, uint32_t base_mip, uint32_t mip_co
 /* copies a named device buffer ("reflective_tiles", "glossy_tiles", "reflective_indirect",
  * "glossy_indirect") to host memory after synchronising the stream; returns its size in *bytes */
 int vkrh_read_buffer(void* frame, const char* name, void* dst, uint64_t capacity, uint64_t* bytes);
-/* one layer of a named array image ("deinterleaved_depth") */
+/* one layer (all its mips) of a named array image ("deinterleaved_depth", "probe_color", "probe_depth", "cubemap_color", ...) */
 int vkrh_image_layer(void* frame, const char* name, uint32_t layer, vkr_img* out);
 /* Reads `name` (mip) back through ReadBackSystem and writes it with the reference's capture writers
  * (main.cpp:118-176): kind 0 = depth CSV (24-bit hex), 1 = depth PNG, 2 = RGBA8 PNG (alpha 255). */

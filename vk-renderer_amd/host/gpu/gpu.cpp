@@ -136,10 +136,12 @@ vkr_img Image::describe_store(uint32_t base_mip, uint32_t count) const {
   return d;
 }
 
-vkr_img Image::describe_layer(uint32_t layer) const {
-  if (layer >= get_array_layers() || info.mip_levels != 1) throw std::runtime_error{"Image layer view outside the array"};
-  vkr_img d = describe(0, 1);
-  d.base = (uint8_t*)d.base + uint64_t(pitch[0]) * info.height * layer;
+vkr_img Image::describe_layer(uint32_t layer, uint32_t base_mip, uint32_t count) const {
+  if (layer >= get_array_layers()) throw std::runtime_error{"Image layer view outside the array"};
+  vkr_img d = describe(base_mip, count);
+  auto layer_offset = [&](uint32_t m) { return offset[m] + uint64_t(pitch[m]) * mip_dim(info.height, m) * layer; };
+  d.base = (uint8_t*)base + layer_offset(base_mip);
+  for (uint32_t m = 0; m < count; m++) d.mip_offset[m] = layer_offset(base_mip + m) - layer_offset(base_mip);
   return d;
 }
 
@@ -521,6 +523,104 @@ void register_hot_path_programs() {
       return vkr_raster_gbuffer(&scene, ubo<vkr_gbuf_const>(st, 0, P), &albedo, &normal, &material, &velocity, &depth,
                                 st.scratch, st.scratch_bytes, st.stream);
     });
+    // ---- octahedral probes (probe_renderer.cpp): cubemap_probe, cube2oct, probe_downsample, trace_probe ----
+    // a view of one layer of an array image (or of a plain image) as the C-ABI descriptor of its mips
+    auto layer_view = [](const ImageViewObject& v) {
+      return v.image->get_array_layers() > 1 ? v.image->describe_layer(v.range.base_layer, v.range.base_mip, v.range.mips_count)
+                                             : v.image->describe(v.range.base_mip, v.range.mips_count);
+    };
+    auto bound_view = [](const LaunchState& st, uint32_t slot, SetSlot::Kind kind, const char* prog) -> const ImageViewObject& {
+      if (!st.set || st.set->slots[slot].kind != kind || !st.set->slots[slot].view.image)
+        throw std::runtime_error{std::string{prog} + ": binding " + std::to_string(slot) + " is not bound as expected"};
+      return st.set->slots[slot].view;
+    };
+    // cubemap_probe/shader.{vert,frag}: set 0 {0 ShaderUbo {projection, camera}, 1 transforms, 2 material textures[], 3 sampler};
+    // vertex + index buffers; one draw_indexed per primitive with PushData {transform, albedo}; attachments {cube colour layer,
+    // cube distance layer, depth}, cleared to (100, 0, 0, 0) and 1.  One render pass per face, faces 0..5 in order.
+    create_program("cubemap_probe", [=](LaunchState& st) {
+      const char* P = "cubemap_probe";
+      struct ShaderUbo { float projection[16], camera[16]; };
+      if (st.attachments.size() != 3) throw std::runtime_error{"cubemap_probe: expects colour, distance and depth attachments"};
+      if (!st.cleared_color || !st.cleared_depth || st.clear_color[0] != 100.f)
+        throw std::runtime_error{"cubemap_probe: attachments must be cleared (colour (100, 0, 0, 0), depth 1)"};
+      if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{"cubemap_probe: vertex / index buffer not bound"};
+      const ImageViewObject &color = st.attachments[0], &distance = st.attachments[1];
+      const uint32_t side = color.range.base_layer;
+      if (color.image->get_array_layers() != 6 || distance.image->get_array_layers() != 6 || distance.range.base_layer != side || side >= 6)
+        throw std::runtime_error{"cubemap_probe: the colour and distance attachments must be the same layer of two cube images"};
+      const ShaderUbo* u = ubo<ShaderUbo>(st, 0, P);
+      // the view of face `side` is lookAt(pos, pos + fwd, up) of calc_matrix: a signed permutation R and t = -R pos, so pos = -R^T t
+      float pos[3];
+      for (int k = 0; k < 3; k++) pos[k] = 0.f - ((u->camera[4 * k + 0] * u->camera[12] + u->camera[4 * k + 1] * u->camera[13]) + u->camera[4 * k + 2] * u->camera[14]);
+      if (side == 0) { st.cube = LaunchState::CubeBatch{}; std::memcpy(st.cube.pos, pos, sizeof(pos)); st.cube.color = color.image; st.cube.distance = distance.image; st.cube.draws = st.indexed_draws.size(); }
+      if (st.cube.faces != side || st.cube.color != color.image || st.cube.distance != distance.image || st.cube.draws != st.indexed_draws.size() ||
+          pos[0] != st.cube.pos[0] || pos[1] != st.cube.pos[1] || pos[2] != st.cube.pos[2])
+        throw std::runtime_error{"cubemap_probe: the six faces of a cube are drawn in order 0..5, from one position, with the same draws"};
+      st.cube.faces = side + 1;
+      if (side != 5) return 0;
+      st.cube.faces = 0;
+      Buffer* transforms = ssbo(st, 1, P);
+      if (!transforms->host_data()) throw std::runtime_error{"cubemap_probe: the transform buffer must be host-visible on this path"};
+      std::vector<vkr_img> textures;
+      for (const auto& v : st.set->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
+      std::vector<vkr_raster_draw> draws;
+      for (const auto& d : st.indexed_draws) {
+        if (d.push.size() < 8) throw std::runtime_error{"cubemap_probe: push constants missing"};
+        vkr_raster_draw r{};
+        std::memcpy(&r, d.push.data(), 8);  // PushData {transform_index, albedo_index}
+        r.mr_index = 0xFFFFFFFFu;
+        r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
+        if (r.albedo_index < st.set->image_array.size() && st.set->image_array[r.albedo_index].image->alpha_never_zero)
+          r.reserved |= VKR_RASTER_DRAW_OPAQUE_ALBEDO;  // the discard of shader.frag cannot fire
+        draws.push_back(r);
+      }
+      vkr_raster_scene scene{};
+      scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
+      scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
+      scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
+      scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
+      scene.transforms = (const vkr_raster_transform*)transforms->host_data();
+      scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
+      scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
+      scene.textures = textures.data(); scene.texture_count = (uint32_t)textures.size();
+      vkr_img cc[6], cd[6];
+      for (uint32_t f = 0; f < 6; f++) { cc[f] = color.image->describe_layer(f); cd[f] = distance.image->describe_layer(f); }
+      return vkr_cubemap_probe(&scene, pos, cc, cd, st.scratch, st.scratch_bytes, st.stream);
+    });
+    // cube2oct/shader.comp: set {0 cube colour (cube view), 1 cube distance (cube view), 2 oct colour (storage, one layer), 3 oct
+    // depth (storage, mip 0 of one layer)}
+    create_program("cube2oct", [=](LaunchState& st) {
+      const char* P = "cube2oct";
+      const ImageViewObject &c = bound_view(st, 0, T, P), &d = bound_view(st, 1, T, P);
+      if (c.image->get_array_layers() != 6 || d.image->get_array_layers() != 6) throw std::runtime_error{"cube2oct: bindings 0 and 1 must be cube images"};
+      vkr_img cc[6], cd[6];
+      for (uint32_t f = 0; f < 6; f++) { cc[f] = c.image->describe_layer(f); cd[f] = d.image->describe_layer(f); }
+      vkr_img oc = layer_view(bound_view(st, 2, S, P)), od = layer_view(bound_view(st, 3, S, P));
+      return vkr_cube2oct(cc, cd, &oc, &od, st.stream);
+    });
+    // probe_downsample/shader.frag: set {0 depth mip i - 1 of one layer}; colour attachment: mip i of the same layer
+    create_program("probe_downsample", [=](LaunchState& st) {
+      const char* P = "probe_downsample";
+      if (st.attachments.size() != 1) throw std::runtime_error{"probe_downsample: expects one colour attachment"};
+      const ImageViewObject &src = bound_view(st, 0, T, P), &dst = st.attachments[0];
+      if (src.image != dst.image || dst.range.base_mip != src.range.base_mip + 1 || dst.range.base_layer != src.range.base_layer)
+        throw std::runtime_error{"probe_downsample: the attachment must be the next mip of the sampled layer"};
+      vkr_img two = src.image->get_array_layers() > 1 ? src.image->describe_layer(src.range.base_layer, src.range.base_mip, 2)
+                                                      : src.image->describe(src.range.base_mip, 2);
+      return vkr_probe_downsample(&two, st.stream);
+    });
+    // trace_probe/shader.comp: set {0 depth, 1 normal, 2 probe colour array, 3 probe depth array (all mips), 4 Constants, 5 out}
+    create_program("trace_probe", [=](LaunchState& st) {
+      const char* P = "trace_probe";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 5, S, P);
+      const ImageViewObject &pc = bound_view(st, 2, T, P), &pd = bound_view(st, 3, T, P);
+      const uint32_t layers = pc.image->get_array_layers();
+      if (pd.image->get_array_layers() != layers) throw std::runtime_error{"trace_probe: the probe colour and depth arrays differ in layers"};
+      std::vector<vkr_img> cl(layers), dl(layers);
+      for (uint32_t l = 0; l < layers; l++) { cl[l] = pc.image->describe_layer(l, 0, 1); dl[l] = pd.image->describe_layer(l, 0, pd.image->get_mip_levels()); }
+      static_assert(sizeof(vkr_probe_trace_consts) == 116, "Constants of trace_probe/shader.comp");
+      return vkr_trace_probe(&depth, &normal, cl.data(), dl.data(), layers, ubo<vkr_probe_trace_consts>(st, 4, P), &out, st.stream);
+    });
     // ---- dormant GTAO variants ----
     // gtao/main.frag: set {0 depth, 1 GTAOParams, 2 normal}; colour attachment raw
     create_program("gtao_main", [=](LaunchState& st) {
@@ -639,8 +739,11 @@ void* CmdContext::require_scratch(uint64_t bytes) {
   return state.scratch;
 }
 void CmdContext::clear_color_attachments(float r, float g, float b, float a) {
-  if (r != 0.f || g != 0.f || b != 0.f || a != 0.f) throw std::runtime_error{"Only a clear to 0 is implemented on this path"};
+  // the programs clear their own attachments: to 0, or (cubemap_probe, probe_renderer.cpp:121) to (100, 0, 0, 0)
+  const bool zero = r == 0.f && g == 0.f && b == 0.f && a == 0.f, probe = r == 100.f && g == 0.f && b == 0.f && a == 0.f;
+  if (!zero && !probe) throw std::runtime_error{"Only a clear to 0 or to (100, 0, 0, 0) is implemented on this path"};
   state.cleared_color = true;
+  state.clear_color[0] = r; state.clear_color[1] = g; state.clear_color[2] = b; state.clear_color[3] = a;
 }
 void CmdContext::clear_depth_attachment(float depth) {
   if (depth != 1.f) throw std::runtime_error{"Only a depth clear to 1 is implemented on this path"};
@@ -659,10 +762,17 @@ void CmdContext::draw_indexed(uint32_t index_count, uint32_t instance_count, uin
   state.indexed_draws.push_back(LaunchState::IndexedDraw{push_data, index_count, first_index, vertex_offset});
 }
 void CmdContext::end_renderpass() {
-  if (!state.indexed_draws.empty()) {  // the recorded geometry is one pass of the bound raster program
+  const bool cube_face = bound_program && *bound_program == "cubemap_probe" && !state.attachments.empty();  // cleared even without a draw
+  if (!state.indexed_draws.empty() || cube_face) {  // the recorded geometry is one pass of the bound raster program
     uint32_t triangles = 0;
     for (const auto& d : state.indexed_draws) triangles += d.index_count / 3u;
-    require_scratch(vkr_raster_scratch_bytes(state.fb_width, state.fb_height, triangles));
+    if (cube_face) {
+      // one face of a cube: the draws are kept with their attachments, the six faces are baked by one vkr_cubemap_probe when
+      // the last one ends (host/probe_renderer.hpp)
+      require_scratch(vkr_cubemap_probe_scratch_bytes(state.fb_width, triangles));
+    } else {
+      require_scratch(vkr_raster_scratch_bytes(state.fb_width, state.fb_height, triangles));
+    }
     launch();
   }
   state.indexed_draws.clear();

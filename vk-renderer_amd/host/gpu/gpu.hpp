@@ -55,6 +55,10 @@ struct TraceRange { explicit TraceRange(const char* name) { trace_push(name); } 
 void device_free(void* ptr);
 
 // ---- images --------------------------------------------------------------------------------------
+// gpu/resources.hpp:16-20.  Here an array image is an array image whatever it is created as; Cubemap requires six square layers
+// (the probe renderer's cube colour and distance).
+enum class ImageCreateOptions { None, Cubemap, Array2D };
+
 struct ImageInfo {  // gpu/resources.hpp:22-42
   VkFormat format = VK_FORMAT_UNDEFINED;
   VkImageAspectFlags aspect = 0;
@@ -92,8 +96,9 @@ struct Image {
   size_t size_bytes() const { return bytes; }
   // C-ABI view of mips [base_mip, base_mip + count)
   vkr_img describe(uint32_t base_mip, uint32_t count) const;
-  // one layer of a (single-mip) array image
-  vkr_img describe_layer(uint32_t layer) const;
+  // mips [base_mip, base_mip + count) of one layer of an array image.  Arrays are mip-major: per mip, the layers one after
+  // another, so layer l of mip m lies l * pitch[m] * height[m] bytes after layer 0 of that mip.
+  vkr_img describe_layer(uint32_t layer, uint32_t base_mip = 0, uint32_t count = 1) const;
   // Multi-GPU strips (host/frame.cpp): of a window image that a pass writes, only rows [row0, row0 + rows) of mip 0 are ever
   // read — by the passes downstream in the same frame, or as the rank's own share of a history whose halo rows arrive from the
   // neighbours.  A program that binds the image as its storage OUTPUT gets the view describe_store() returns: the same memory,
@@ -246,6 +251,7 @@ struct LaunchState {
   Buffer* vertex_buffer = nullptr;
   Buffer* index_buffer = nullptr;
   bool cleared_color = false, cleared_depth = false;
+  float clear_color[4] = {0.f, 0.f, 0.f, 0.f};  // what clear_color_attachments asked for; the program checks it is its own clear
   void* scratch = nullptr;                    // device scratch owned by the command context
   uint64_t scratch_bytes = 0;
   void* stream = nullptr;
@@ -254,6 +260,9 @@ struct LaunchState {
   void* workspace = nullptr;
   uint64_t workspace_bytes = 0;
   void* require_workspace(uint64_t bytes);
+  // program "cubemap_probe": ProbeRenderer::render_side draws one face per render pass, the kernels bake the six faces of a cube
+  // together, so faces 0..4 are only checked and remembered here and face 5 launches (gpu.cpp)
+  struct CubeBatch { uint32_t faces = 0; float pos[3] = {0.f, 0.f, 0.f}; const struct Image* color = nullptr; const struct Image* distance = nullptr; size_t draws = 0; } cube;
 };
 using ProgramFn = std::function<int(LaunchState&)>;
 // Registers `name` -> C-ABI thunk.  The hot-path programs of src/shaders/config.json are

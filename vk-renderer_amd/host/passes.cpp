@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "pass_recorder.hpp"
+#include "probe_renderer.hpp"
 #include "scene/scene_as.hpp"
 
 using rendergraph::ImageResourceId;
@@ -1035,5 +1036,253 @@ void SceneRenderer::draw_taa(RenderGraph &graph, const Gbuffer &gbuffer, const D
         }
       }
       cmd.end_renderpass();
+    });
+}
+
+// ==== probe renderer (probe_renderer.hpp; reference: src/probe_renderer.cpp, whose render_side is a commented-out body: here it draws)
+// Every task executes through the programs cubemap_probe, cube2oct, probe_downsample and trace_probe registered in gpu/gpu.cpp.
+using rendergraph::ImageViewId;
+static uint32_t full_mip_chain(uint32_t size) { return uint32_t(std::floor(std::log2(float(size)))) + 1u; }
+
+ProbeRenderer::ProbeRenderer(RenderGraph &graph, uint32_t cubemap_res) {
+  rendergraph::ImageDescriptor desc {};
+  desc.type = VK_IMAGE_TYPE_2D;
+  desc.width = desc.height = cubemap_res;
+  desc.format = VK_FORMAT_R8G8B8A8_SRGB;
+  desc.array_layers = 6;
+  desc.mip_levels = 1;
+  desc.aspect = COLOR;
+  desc.tiling = VK_IMAGE_TILING_OPTIMAL;
+  desc.usage = VK_IMAGE_USAGE_COLOR_ATTACHMENT_BIT|VK_IMAGE_USAGE_SAMPLED_BIT;
+  cubemap_color = graph.create_image(desc, gpu::ImageCreateOptions::Cubemap);
+  desc.format = VK_FORMAT_R16_SFLOAT;
+  cubemap_distance = graph.create_image(desc, gpu::ImageCreateOptions::Cubemap);
+
+  // the depth attachment of a face: the programs keep their own depth (the visibility buffer), the image is only declared
+  rt_depth = graph.create_frame_image(gpu::ImageInfo {VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT|VK_IMAGE_ASPECT_STENCIL_BIT, cubemap_res, cubemap_res, 1, 1, 1});
+
+  gpu::Registers regs {};
+  regs.depth_stencil.depthTestEnable = VK_TRUE;
+  regs.depth_stencil.depthWriteEnable = VK_TRUE;
+  cubemap_pass = gpu::create_graphics_pipeline();
+  cubemap_pass.set_program("cubemap_probe");
+  cubemap_pass.set_registers(regs);
+  cubemap_pass.set_vertex_input({});
+  cubemap_pass.set_rendersubpass({true, {VK_FORMAT_R8G8B8A8_SRGB, VK_FORMAT_R16_SFLOAT, VK_FORMAT_D24_UNORM_S8_UINT}});
+
+  octprobe_pass = gpu::create_compute_pipeline();
+  octprobe_pass.set_program("cube2oct");
+
+  downsample_pass = gpu::create_graphics_pipeline();
+  downsample_pass.set_program("probe_downsample");
+  downsample_pass.set_registers({});
+  downsample_pass.set_vertex_input({});
+  downsample_pass.set_rendersubpass({false, {VK_FORMAT_R16_UNORM}});
+
+  sampler = gpu::create_sampler(gpu::DEFAULT_SAMPLER);
+}
+
+// forward / up of the six faces: up is (0, -1, 0) except on the two faces that look along y
+static glm::mat4 face_view(uint32_t side, glm::vec3 pos) {
+  glm::vec3 fwd {0.f, 0.f, -1.f}, up {0.f, -1.f, 0.f};
+  switch (side) {
+    case 0: fwd = glm::vec3 {1.f, 0.f, 0.f}; break;
+    case 1: fwd = glm::vec3 {-1.f, 0.f, 0.f}; break;
+    case 2: fwd = glm::vec3 {0.f, 1.f, 0.f}; up = glm::vec3 {0.f, 0.f, 1.f}; break;
+    case 3: fwd = glm::vec3 {0.f, -1.f, 0.f}; up = glm::vec3 {0.f, 0.f, -1.f}; break;
+    case 4: fwd = glm::vec3 {0.f, 0.f, 1.f}; break;
+    default: break;
+  }
+  return glm::lookAt(pos, pos + fwd, up);
+}
+
+void ProbeRenderer::render_cubemap(RenderGraph &graph, SceneRenderer &scene_renderer, const glm::vec3 pos) {
+  for (uint32_t side = 0; side < 6; side++) render_side(graph, scene_renderer, side, face_view(side, pos));
+}
+
+void ProbeRenderer::render_side(RenderGraph &graph, SceneRenderer &scene_renderer, uint32_t side, glm::mat4 view) {
+  struct Res { ImageViewId color, distance, depth; };
+  struct ShaderUbo { glm::mat4 projection, camera; };
+  struct PushData { uint32_t transform_index, albedo_index; };
+
+  graph.add_task<Res>("CubemapSide",
+    [&](Res &res, rendergraph::RenderGraphBuilder &builder) {
+      res.color = builder.use_color_attachment(cubemap_color, 0, side);
+      res.distance = builder.use_color_attachment(cubemap_distance, 0, side);
+      res.depth = builder.use_depth_attachment(rt_depth, 0, 0);
+      builder.use_storage_buffer(scene_renderer.get_scene_transforms(), VK_SHADER_STAGE_VERTEX_BIT);
+    },
+    [=, &scene_renderer](Res &res, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      const auto extent = resources.get_image(res.color)->get_info().extent2D();
+      auto blk = cmd.allocate_ubo<ShaderUbo>();
+      blk.ptr->projection = glm::perspective(glm::radians(90.f), 1.f, 0.05f, 80.f);
+      blk.ptr->camera = view;
+
+      cmd.set_framebuffer(extent.width, extent.height, {resources.get_image_range(res.color), resources.get_image_range(res.distance), resources.get_image_range(res.depth)});
+      auto &target = scene_renderer.get_target();
+      cmd.bind_pipeline(cubemap_pass);
+      cmd.clear_depth_attachment(1.f);
+      cmd.clear_color_attachments(100.f, 0.f, 0.f, 0.f);
+      cmd.bind_viewport(0.f, 0.f, float(extent.width), float(extent.height), 0.f, 1.f);
+      cmd.bind_scissors(0, 0, extent.width, extent.height);
+      cmd.bind_vertex_buffers(0, {target.vertex_buffer->api_buffer()}, {0ul});
+      cmd.bind_index_buffer(target.index_buffer->api_buffer(), 0, VK_INDEX_TYPE_UINT32);
+
+      auto set = resources.allocate_set(cubemap_pass.get_layout(0));
+      gpu::write_set(set,
+        gpu::UBOBinding {0, cmd.get_ubo_pool(), blk},
+        gpu::SSBOBinding {1, resources.get_buffer(scene_renderer.get_scene_transforms())},
+        gpu::ArrayOfImagesBinding {2, scene_renderer.get_images()});
+      cmd.bind_descriptors_graphics(0, {set}, {blk.offset});
+
+      const uint32_t ntex = uint32_t(scene_renderer.get_images().size());
+      for (const auto &draw_call : scene_renderer.get_drawcalls()) {
+        for (const auto &prim : target.root_meshes[draw_call.mesh].primitives) {
+          const auto &material = target.materials[prim.material_index];
+          if (material.albedo_tex_index == scene::INVALID_TEXTURE || material.albedo_tex_index >= ntex) continue;
+          const PushData pc {draw_call.transform, material.albedo_tex_index};
+          cmd.push_constants_graphics(VK_SHADER_STAGE_VERTEX_BIT|VK_SHADER_STAGE_FRAGMENT_BIT, 0, sizeof(PushData), &pc);
+          cmd.draw_indexed(prim.index_count, 1, prim.index_offset, int32_t(prim.vertex_offset), 0);
+        }
+      }
+      cmd.end_renderpass();
+    });
+}
+
+void ProbeRenderer::render_octahedral(RenderGraph &graph, ImageResourceId probe_color, ImageResourceId probe_depth, uint32_t array_layer) {
+  struct Input { ImageViewId cube_color, cube_distance, oct_color, oct_depth; };
+  graph.add_task<Input>("Cubemap2Octahedral",
+    [&](Input &input, rendergraph::RenderGraphBuilder &builder) {
+      input.cube_color = builder.sample_cubemap(cubemap_color, VK_SHADER_STAGE_COMPUTE_BIT);
+      input.cube_distance = builder.sample_cubemap(cubemap_distance, VK_SHADER_STAGE_COMPUTE_BIT);
+      input.oct_color = builder.use_storage_image(probe_color, VK_SHADER_STAGE_COMPUTE_BIT, 0, array_layer);
+      input.oct_depth = builder.use_storage_image(probe_depth, VK_SHADER_STAGE_COMPUTE_BIT, 0, array_layer);
+    },
+    [=](Input &input, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      const auto desc = resources.get_image(input.oct_color)->get_extent();
+      auto set = resources.allocate_set(octprobe_pass, 0);
+      gpu::write_set(set,
+        gpu::TextureBinding {0, resources.get_view(input.cube_color), sampler},
+        gpu::TextureBinding {1, resources.get_view(input.cube_distance), sampler},
+        gpu::StorageTextureBinding {2, resources.get_view(input.oct_color)},
+        gpu::StorageTextureBinding {3, resources.get_view(input.oct_depth)});
+      cmd.bind_pipeline(octprobe_pass);
+      cmd.bind_descriptors_compute(0, {set});
+      cmd.dispatch(desc.width/8, desc.height/4, 1);
+    });
+}
+
+void ProbeRenderer::probe_downsample(RenderGraph &graph, ImageResourceId probe_depth, uint32_t array_layer) {
+  const auto desc = graph.get_descriptor(probe_depth);
+  struct Input { ImageViewId depth_tex, depth_rt; };
+  for (uint32_t i = 1; i < desc.mip_levels; i++) {
+    graph.add_task<Input>("DownsampleProbe",
+      [&](Input &input, rendergraph::RenderGraphBuilder &builder) {
+        input.depth_rt = builder.use_color_attachment(probe_depth, i, array_layer);
+        input.depth_tex = builder.sample_image(probe_depth, VK_SHADER_STAGE_FRAGMENT_BIT, COLOR, i - 1, 1, array_layer, 1);
+      },
+      [=](Input &input, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+        auto set = resources.allocate_set(downsample_pass, 0);
+        gpu::write_set(set, gpu::TextureBinding {0, resources.get_view(input.depth_tex), sampler});
+        const uint32_t w = desc.width/(1u << i), h = desc.height/(1u << i);
+        cmd.set_framebuffer(w, h, {resources.get_image_range(input.depth_rt)});
+        cmd.bind_pipeline(downsample_pass);
+        cmd.bind_descriptors_graphics(0, {set});
+        cmd.bind_viewport(0.f, 0.f, float(w), float(h), 0.f, 1.f);
+        cmd.bind_scissors(0, 0, w, h);
+        cmd.draw(3, 1, 0, 0);
+        cmd.end_renderpass();
+      });
+  }
+}
+
+void ProbeRenderer::render_probe(RenderGraph &graph, SceneRenderer &scene_renderer, const glm::vec3 pos, OctahedralProbe &probe) {
+  render_cubemap(graph, scene_renderer, pos);
+  render_octahedral(graph, probe.color, probe.depth);
+  probe_downsample(graph, probe.depth);
+  probe.pos = pos;
+}
+
+void ProbeRenderer::render_probe_grid(RenderGraph &graph, SceneRenderer &scene_renderer, glm::vec3 min, glm::vec3 max, OctahedralProbeGrid &probe_grid) {
+  for (int k = 0; k < 3; k++) {
+    const float lo = std::min(min[k], max[k]), hi = std::max(min[k], max[k]);
+    min[k] = lo; max[k] = hi;
+  }
+  probe_grid.min = min;
+  probe_grid.max = max;
+  if (probe_grid.grid_size < 2) throw std::runtime_error {"ProbeRenderer::render_probe_grid: a probe grid needs grid_size >= 2"};
+
+  const float cells = float(probe_grid.grid_size - 1);
+  const glm::vec3 step {(max.x - min.x)/cells, (max.y - min.y)/cells, (max.z - min.z)/cells};
+  for (uint32_t y = 0; y < probe_grid.grid_size; y++) {
+    for (uint32_t x = 0; x < probe_grid.grid_size; x++) {
+      const glm::vec3 pos {min.x + step.x * float(x), min.y + step.y * 0.f, min.z + step.z * float(y)};  // probes in x and z, at min.y
+      const uint32_t array_layer = y * probe_grid.grid_size + x;
+      render_cubemap(graph, scene_renderer, pos);
+      render_octahedral(graph, probe_grid.color_array, probe_grid.depth_array, array_layer);
+      probe_downsample(graph, probe_grid.depth_array, array_layer);
+    }
+  }
+}
+
+// (probe images are never windows of a tiled frame, whatever their extent: create_frame_image)
+OctahedralProbe::OctahedralProbe(RenderGraph &graph, uint32_t size) {
+  gpu::ImageInfo desc {VK_FORMAT_R8G8B8A8_UNORM, COLOR, size, size};
+  color = graph.create_frame_image(desc);
+  desc.mip_levels = full_mip_chain(size);
+  desc.format = VK_FORMAT_R16_UNORM;
+  depth = graph.create_frame_image(desc);
+}
+
+OctahedralProbeGrid::OctahedralProbeGrid(RenderGraph &graph, uint32_t grid_sz, uint32_t size) : grid_size {grid_sz} {
+  gpu::ImageInfo desc {VK_FORMAT_R8G8B8A8_UNORM, COLOR, size, size};
+  desc.array_layers = grid_sz * grid_sz;
+  color_array = graph.create_frame_image(desc);
+  desc.mip_levels = full_mip_chain(size);
+  desc.format = VK_FORMAT_R16_UNORM;
+  depth_array = graph.create_frame_image(desc);
+}
+
+ProbeTracePass::ProbeTracePass() {
+  trace_pass = gpu::create_compute_pipeline();
+  trace_pass.set_program("trace_probe");
+  sampler = gpu::create_sampler(gpu::DEFAULT_SAMPLER);
+}
+
+void ProbeTracePass::run(RenderGraph &graph, OctahedralProbeGrid &probe, ImageResourceId gbuffer_depth, ImageResourceId gbuffer_norm, ImageResourceId out_image,
+                         const ProbeTraceParams &params) {
+  struct Input { ImageViewId depth, normal, probe_color, probe_depth, out_tex; };
+  static_assert(sizeof(vkr_probe_trace_consts) == sizeof(glm::mat4) + 2 * sizeof(glm::vec4) + 5 * sizeof(uint32_t), "Constants must match the C-ABI");
+  vkr_probe_trace_consts consts {};
+  std::memcpy(consts.inverse_view.m, &params.inv_view, sizeof(consts.inverse_view.m));
+  const glm::vec4 pmin {probe.min.x, probe.min.y, probe.min.z, 1.f}, pmax {probe.max.x, probe.max.y, probe.max.z, 1.f};
+  std::memcpy(consts.probe_min, &pmin, sizeof(consts.probe_min));
+  std::memcpy(consts.probe_max, &pmax, sizeof(consts.probe_max));
+  consts.grid_size = probe.grid_size;
+  consts.fovy = params.fovy; consts.aspect = params.aspect; consts.znear = params.znear; consts.zfar = params.zfar;
+
+  graph.add_task<Input>("TraceProbe",
+    [&](Input &input, rendergraph::RenderGraphBuilder &builder) {
+      input.depth = builder.sample_image(gbuffer_depth, VK_SHADER_STAGE_COMPUTE_BIT, VK_IMAGE_ASPECT_DEPTH_BIT, 0, 1, 0, 1);
+      input.normal = builder.sample_image(gbuffer_norm, VK_SHADER_STAGE_COMPUTE_BIT);
+      input.probe_color = builder.sample_image(probe.color_array, VK_SHADER_STAGE_COMPUTE_BIT);
+      input.probe_depth = builder.sample_image(probe.depth_array, VK_SHADER_STAGE_COMPUTE_BIT);
+      input.out_tex = builder.use_storage_image(out_image, VK_SHADER_STAGE_COMPUTE_BIT, 0, 0);
+    },
+    [=](Input &input, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      const auto desc = resources.get_image(input.out_tex)->get_extent();
+      auto blk = cmd.allocate_ubo<vkr_probe_trace_consts>();
+      *blk.ptr = consts;
+      auto set = resources.allocate_set(trace_pass, 0);
+      gpu::write_set(set,
+        gpu::TextureBinding {0, resources.get_view(input.depth), sampler},
+        gpu::TextureBinding {1, resources.get_view(input.normal), sampler},
+        gpu::TextureBinding {2, resources.get_view(input.probe_color), sampler},
+        gpu::TextureBinding {3, resources.get_view(input.probe_depth), sampler},
+        gpu::UBOBinding {4, cmd.get_ubo_pool(), blk},
+        gpu::StorageTextureBinding {5, resources.get_view(input.out_tex)});
+      cmd.bind_pipeline(trace_pass);
+      cmd.bind_descriptors_compute(0, {set}, {blk.offset});
+      cmd.dispatch(desc.width/8, desc.height/4, 1);
     });
 }

@@ -180,6 +180,9 @@ struct SceneRenderer {
 
   const std::vector<DrawCall> &get_drawcalls() const { return draw_calls; }
   rendergraph::BufferResourceId get_scene_transforms() const { return transform_buffer; }
+  // what another raster pass over the same scene needs (ProbeRenderer::render_side): the scene and its bindless texture table
+  scene::CompiledScene &get_target() { return target; }
+  const std::vector<std::pair<VkImageView, VkSampler>> &get_images() const { return scene_textures; }
 
 private:
   scene::CompiledScene &target;

@@ -78,6 +78,14 @@ ImageViewId RenderGraphBuilder::sample_image(ImageResourceId id, VkShaderStageFl
   const auto& info = resources.get_image(id)->get_info();
   return sample_image(id, stages, aspect ? aspect : info.aspect, 0, info.mip_levels, 0, info.array_layers);
 }
+ImageViewId RenderGraphBuilder::sample_cubemap(ImageResourceId id, VkShaderStageFlags, VkImageAspectFlags aspect) {
+  const auto& info = resources.get_image(id)->get_info();
+  if (info.array_layers != 6) throw std::runtime_error{"sample_cubemap: not a cube image"};
+  resources.declare(id, 0, info.mip_levels, Usage::Sampled, task_index, log);
+  auto r = make_range(aspect ? aspect : info.aspect, 0, info.mip_levels, 0, 6);
+  r.type = VK_IMAGE_VIEW_TYPE_CUBE;
+  return {id, r};
+}
 void RenderGraphBuilder::transfer_read(ImageResourceId id, uint32_t base_mip, uint32_t mip_count, uint32_t, uint32_t) {
   resources.declare(id, base_mip, mip_count, Usage::TransferRead, task_index, log);
 }
@@ -141,8 +149,12 @@ void RenderGraph::set_frame_window(uint32_t fw, uint32_t fh, int32_t ox, int32_t
   full_w = fw; full_h = fh; org_x = ox; org_y = oy; win_w = ww; win_h = wh;
 }
 
-ImageResourceId RenderGraph::create_image(VkImageType type, const gpu::ImageInfo& info, VkImageTiling, VkImageUsageFlags) {
+ImageResourceId RenderGraph::create_image(VkImageType type, const gpu::ImageInfo& info, VkImageTiling, VkImageUsageFlags, gpu::ImageCreateOptions options) {
   if (type != VK_IMAGE_TYPE_2D) throw std::runtime_error{"Only 2D images exist on this path"};
+  if (options == gpu::ImageCreateOptions::Cubemap) {
+    if (info.array_layers != 6 || info.width != info.height) throw std::runtime_error{"A cube image has six square layers"};
+    return resources.create_image(info, gpu::FrameWindow{});  // never a window of the frame, whatever its extent
+  }
   gpu::FrameWindow w;
   if (has_window) {
     for (uint32_t k = 0; k < 2; k++) {
@@ -243,6 +255,9 @@ void RenderGraph::submit() {
       t->write_commands(res, cmd);
     }
     cmd.pop_label();
+    // a task's uniform blocks are read by its programs while it is recorded (they travel as launch arguments), so the ring is free
+    // again once the task is written: a long submission (96 cube faces of a probe grid) does not run out of the 16 KiB
+    cmd.get_ubo_pool().reset();
     if (spread) {
       hip_check(hipEventRecord((hipEvent_t)sync_events[i], (hipStream_t)cmd.get_stream()), "hipEventRecord");
       for (const auto& a : t->accesses) {

@@ -59,6 +59,17 @@ struct ImageViewId {
   gpu::ImageViewRange range;
 };
 
+// resources.hpp:15-39
+struct ImageDescriptor {
+  VkImageType type = VK_IMAGE_TYPE_2D;
+  VkFormat format = VK_FORMAT_UNDEFINED;
+  VkImageAspectFlags aspect = 0;
+  VkImageTiling tiling = VK_IMAGE_TILING_OPTIMAL;
+  VkImageUsageFlags usage = 0;
+  uint32_t width = 0, height = 0, depth = 1, mip_levels = 1, array_layers = 1;
+  gpu::ImageInfo get_vk_info() const { return {format, aspect, width, height, depth, mip_levels, array_layers}; }
+};
+
 enum class Usage : uint8_t { None, Sampled, Storage, ColorAttachment, DepthAttachment, TransferRead, TransferWrite };
 
 struct GraphResources {
@@ -94,6 +105,8 @@ struct RenderGraphBuilder {  // rendergraph.hpp:17-55
   ImageViewId sample_image(ImageResourceId id, VkShaderStageFlags stages, VkImageAspectFlags aspect, uint32_t base_mip,
                            uint32_t mip_count, uint32_t base_layer, uint32_t layer_count);
   ImageViewId sample_image(ImageResourceId id, VkShaderStageFlags stages, VkImageAspectFlags aspect = 0);
+  // the six layers of a cube image as one cube view (every mip)
+  ImageViewId sample_cubemap(ImageResourceId id, VkShaderStageFlags stages, VkImageAspectFlags aspect = 0);
   void use_uniform_buffer(BufferResourceId id, VkShaderStageFlags) { GraphResources::declare(id, false, log); }
   void use_storage_buffer(BufferResourceId id, VkShaderStageFlags, bool readonly = true) { GraphResources::declare(id, !readonly, log); }
   void use_indirect_buffer(BufferResourceId id) { GraphResources::declare(id, false, log); }
@@ -171,7 +184,11 @@ struct RenderGraph {  // rendergraph.hpp:112-158
 
   void submit();
 
-  ImageResourceId create_image(VkImageType type, const gpu::ImageInfo& info, VkImageTiling tiling, VkImageUsageFlags usage);
+  ImageResourceId create_image(VkImageType type, const gpu::ImageInfo& info, VkImageTiling tiling, VkImageUsageFlags usage,
+                               gpu::ImageCreateOptions options = gpu::ImageCreateOptions::None);
+  ImageResourceId create_image(const ImageDescriptor& desc, gpu::ImageCreateOptions options = gpu::ImageCreateOptions::None) {
+    return create_image(desc.type, desc.get_vk_info(), desc.tiling, desc.usage, options);
+  }
   BufferResourceId create_buffer(VmaMemoryUsage mem, uint64_t size, VkBufferUsageFlags usage) { return resources.create_buffer(mem, size, usage); }
   gpu::ImageInfo get_descriptor(ImageResourceId id) const { return resources.get_image(id)->get_info(); }
   void remap(ImageResourceId src, ImageResourceId dst) { resources.remap(src, dst); }

@@ -146,10 +146,10 @@ class ImageBuf:
 
 class ArrayImageBuf:
     """An array image, mip-major: per mip, the layers one after another (rows 256-B aligned), so layer l of mip m lies at
-    layer 0's plus l * pitch[m] * height[m].  That is how the host mirror's gpu::Image allocates an array; the mirror does not
-    yet hand out per-layer views of a mipped array (Image::describe_layer takes single-mip arrays only), so this layout is
-    the one its probe arrays are to use.  `descs()` gives the per-layer descriptors of the C-ABI's array arguments
-    (vkr_trace_probe's probe arrays).  raw() knows the formats of those arrays: RGBA8_UNORM and R16_UNORM."""
+    layer 0's plus l * pitch[m] * height[m].  That is how the host mirror's gpu::Image allocates an array (Image::describe_layer hands
+    out the per-layer views), so a probe array baked by the mirror and one allocated here are laid out alike.  `descs()` gives the per-layer descriptors of the C-ABI's array arguments
+    (vkr_trace_probe's probe arrays, vkr_cubemap_probe's cubes).  raw() knows the formats of those arrays: RGBA8_UNORM and
+    R16_UNORM (probes), RGBA8_SRGB and R16_SFLOAT (cubes)."""
 
     def __init__(self, fmt, width, height, layers, mips=1, device=None, fill=0):
         self.format, self.width, self.height, self.layers, self.mips = fmt, int(width), int(height), int(layers), int(mips)
@@ -198,7 +198,7 @@ class ArrayImageBuf:
 
     def raw(self, mip=0, host=None):
         """raw storage of one mip of every layer: [layers, h, w, channels] in the storage dtype"""
-        dtypes = {abi.FMT_RGBA8_UNORM: np.uint8, abi.FMT_R16_UNORM: np.uint16}
+        dtypes = {abi.FMT_RGBA8_UNORM: np.uint8, abi.FMT_R16_UNORM: np.uint16, abi.FMT_RGBA8_SRGB: np.uint8, abi.FMT_R16_SFLOAT: np.float16}
         if self.format not in dtypes:
             raise ValueError(f"ArrayImageBuf.raw: format {self.format}")
         host = self.to_host() if host is None else host
