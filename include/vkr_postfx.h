@@ -441,6 +441,24 @@ int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_const* cons
                        const vkr_img* normal, const vkr_img* material, const vkr_img* velocity, const vkr_img* depth,
                        void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* program "default_shadow": SceneRenderer::render_shadow (scene_renderer.cpp:222-274) + shadows/default.{vert,frag} as a
+ * depth-only compute rasteriser: layer l of `layers` is the scene's depth seen through mvps[l], with the vertex stage
+ * clip = (mvps[l] * model) * vec4(pos, 1) and an empty fragment stage.  Each layer is cleared to depth 1, stencil 0 (the word
+ * 0x00FFFFFF) and then drawn; every stored word has its top byte 0.  The raster rules are those of vkr_raster_gbuffer (pixel
+ * centres, vertices snapped to 8 sub-pixel bits, top-left fill rule, cull none, near-plane clip in clip space, per-fragment depth
+ * clip, D24 = rint(z * (2^24 - 1)), LESS_OR_EQUAL), so a layer equals the depth attachment of vkr_raster_gbuffer run with
+ * view_projection = mvps[l], zero jitter and no textures.  Only pos, the indices, the model matrices and transform_index /
+ * index_offset / index_count / vertex_offset of each draw are read: textures, albedo_index, mr_index, flags and reserved are
+ * ignored (textures == NULL with texture_count == 0 is valid), and a cutout casts a solid shadow as the empty fragment shader
+ * makes it.  A triangle with an index outside the vertex buffer is not drawn.  There is no visibility buffer and no resolve:
+ * coverage issues atomic mins of the 24-bit depth straight into the layers.  layers: layer_count (1..8) D24_UNORM_S8 descriptors,
+ * square, of one extent, not windowed (single-GPU pass); they need not be the layers of one array.  All layers go through one set
+ * of launches.  `scratch`: vkr_default_shadow_scratch_bytes(edge of a layer, layer_count, triangles summed over all draws) of
+ * device memory.  At most 1024 draws. */
+uint64_t vkr_default_shadow_scratch_bytes(uint32_t size, uint32_t layer_count, uint32_t triangle_count);
+int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4* mvps /* [layer_count] */, const vkr_img* layers /* [layer_count] */,
+                       uint32_t layer_count, void* scratch, uint64_t scratch_bytes, void* stream);
+
 /* synthetic G-buffer generator (no reference program).  Any of the
  * colour outputs may be NULL when VKR_SYNTH_DEPTH_ONLY is set.                          */
 int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, const vkr_img* albedo,

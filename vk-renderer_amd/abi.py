@@ -360,6 +360,11 @@ def product():
         lib.vkr_cubemap_probe_scratch_bytes.restype = C.c_uint64
         lib.vkr_cubemap_probe.argtypes = [P(RasterScene), P(C.c_float * 3), _IMG, _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.vkr_cubemap_probe.restype = C.c_int
+        # the shadow-map pass (checked against the oracle's G-buffer rasteriser: its depth attachment under the light's matrix)
+        lib.vkr_default_shadow_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.vkr_default_shadow_scratch_bytes.restype = C.c_uint64
+        lib.vkr_default_shadow.argtypes = [P(RasterScene), P(Mat4), _IMG, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.vkr_default_shadow.restype = C.c_int
         _product = lib
     return _product
 
@@ -386,6 +391,24 @@ def cubemap_probe(scene, pos, cube_color, cube_distance, scratch, scratch_bytes,
         raise RuntimeError("cubemap_probe: a cube has 6 layers")
     p = (C.c_float * 3)(float(pos[0]), float(pos[1]), float(pos[2]))
     check(lib.vkr_cubemap_probe(C.byref(scene), C.byref(p), cube_color, cube_distance, scratch, int(scratch_bytes), stream), lib)
+
+
+def default_shadow_scratch_bytes(size, layer_count, triangle_count):
+    """vkr_default_shadow_scratch_bytes: device scratch of one call (edge of a layer, layers, triangles summed over all draws)"""
+    return int(product().vkr_default_shadow_scratch_bytes(int(size), int(layer_count), int(triangle_count)))
+
+
+def default_shadow(scene, mvps, layers, scratch, scratch_bytes, stream=None):
+    """vkr_default_shadow: layer l := the depth of `scene` (RasterScene) seen through mvps[l].  mvps: a sequence of 4x4 arrays
+    (maths convention, as camera.shadow_mvp returns them); layers: a (VkrImg * n) array or a sequence of VkrImg, one square
+    D24_UNORM_S8 descriptor per matrix; scratch: device pointer.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    n = len(mvps)
+    if len(layers) != n:
+        raise RuntimeError(f"default_shadow: {n} matrices for {len(layers)} layers")
+    mats = (Mat4 * max(1, n))(*[Mat4.from_np(m) for m in mvps])
+    descs = (VkrImg * max(1, n))(*list(layers))
+    check(lib.vkr_default_shadow(C.byref(scene), mats, descs, n, scratch, int(scratch_bytes), stream), lib)
 
 
 COMM_ID_BYTES = 128

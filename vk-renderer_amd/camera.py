@@ -55,6 +55,52 @@ def camera_view(pos, yaw_deg=90.0, pitch_deg=0.0, world_up=(0.0, -1.0, 0.0)):
     return look_at_rh(pos, pos + f, up)
 
 
+LIGHT_POS = (-1.85867, 5.81832, -0.247114)  # main.cpp:295; LIGHT_POS of defered_shading/shader.frag
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def look_at(eye, center, up):
+    """glm::lookAt (RH) as a 4x4 float32 array (maths convention: m[row, column]): the components of eye, center and up rounded to
+    float32, every entry evaluated in float64 — plain scalar arithmetic in one fixed order, so that the C++ host mirror
+    (host/frame.cpp) reproduces it bit for bit — and rounded once."""
+    e, c, u = ([_f32(x) for x in v] for v in (eye, center, up))
+    dot = lambda a, b: a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+    cross = lambda a, b: [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+    def unit(a):
+        n = math.sqrt(dot(a, a))
+        return [a[0] / n, a[1] / n, a[2] / n]
+
+    f = unit([c[0] - e[0], c[1] - e[1], c[2] - e[2]])
+    s = unit(cross(f, u))
+    t = cross(s, f)
+    m = np.zeros((4, 4), dtype=np.float64)
+    m[0, :3], m[1, :3], m[2, :3] = s, t, [-f[0], -f[1], -f[2]]
+    m[0, 3], m[1, 3], m[2, 3], m[3, 3] = -dot(s, e), -dot(t, e), dot(f, e), 1.0
+    return m.astype(np.float32)
+
+
+def shadow_mvp(eye=LIGHT_POS, center=(0.0, 2.0, 1.0), up=(0.0, -1.0, 0.0), fovy_deg=90.0, near=0.05, far=80.0):
+    """The light matrix of the shadow pass, perspective(radians(fovy), 1, near, far) * lookAt(eye, center, up) (main.cpp:295 with
+    the defaults), under this module's rule: fovy (in radians), near, far and the vectors rounded to float32, the two factors
+    evaluated in float64 and rounded to float32, their product evaluated in float64 and rounded once.  Bit-equal to the default
+    light of the host frame (vkrh_shadow_lights).  -> 4x4 float32, maths convention."""
+    fovy = _f32(np.float32(fovy_deg) * np.float32(0.01745329251994329576923690768489))
+    p = perspective_rh_zo(fovy, 1.0, _f32(near), _f32(far)).astype(np.float32)
+    v = look_at(eye, center, up)
+    out = np.zeros((4, 4), dtype=np.float32)
+    for r in range(4):
+        for c in range(4):
+            acc = 0.0
+            for k in range(4):
+                acc += float(p[r, k]) * float(v[k, c])
+            out[r, c] = np.float32(acc)
+    return out
+
+
 class FrameSetup:
     """All per-frame uniforms of the frozen benchmark frame: current camera at
     (0,1,-1) yaw 90; previous frame = eye + (0.02,0,0.01), yaw + 0.2 deg; jitter 0;

@@ -17,6 +17,7 @@ STAGE_SSR_CLASSIFIED, STAGE_SSR_TRACE, STAGE_SSR_RESOLVE = 16384, 32768, 65536
 STAGE_RASTER = 131072
 STAGE_GTAO_RT = 1 << 21  # ray-traced AO (main.cpp:379-388 use_rt_ao): needs load_scene(); not with STAGE_GTAO, not tiled
 STAGE_PROBE_TRACE = 1 << 22  # ProbeTracePass::run through the grid of bake_probes() -> image "probe_trace"; not tiled
+STAGE_SHADOW = 1 << 23  # SceneRenderer::render_shadow per configured light -> layers of image "shadows"; needs load_scene(); not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -124,7 +125,10 @@ def lib():
                            ("vkrh_gtao_directions", [C.c_void_p, C.c_uint32]),
                            ("vkrh_selftest_ray_query", [C.c_char_p, C.c_uint32]),
                            # the probe bake (same rule: typed where exported)
-                           ("vkrh_bake_probes", [C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_uint32, C.c_uint32, C.c_uint32])):
+                           ("vkrh_bake_probes", [C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_uint32, C.c_uint32, C.c_uint32]),
+                           # the shadow pass (same rule)
+                           ("vkrh_set_shadow_lights", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32]),
+                           ("vkrh_shadow_lights", [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -291,6 +295,20 @@ class HostFrame:
         pmax at pmin's y.  Leaves images "probe_color" / "probe_depth" (download(name, layer)) for STAGE_PROBE_TRACE."""
         lo, hi = (C.c_float * 3)(*[float(v) for v in pmin]), (C.c_float * 3)(*[float(v) for v in pmax])
         self._check(lib().vkrh_bake_probes(self.h, C.byref(lo), C.byref(hi), int(grid_size), int(probe_size), int(cube_size)))
+
+    def set_shadow_lights(self, mvps, size=0):
+        """vkrh_set_shadow_lights: 1..4 light matrices (4x4, maths convention, e.g. camera.shadow_mvp(...)) for STAGE_SHADOW, light l
+        -> layer l of image "shadows" (download("shadows", l)); size: edge of the map, 0 keeps 1024."""
+        flat = (C.c_float * (16 * len(mvps)))()
+        for i, m in enumerate(mvps):
+            flat[16 * i: 16 * i + 16] = list(_mat16(m))
+        self._check(lib().vkrh_set_shadow_lights(self.h, flat, len(mvps), int(size)))
+
+    def shadow_lights(self):
+        """vkrh_shadow_lights: the light matrices in use as 4x4 float32 arrays (maths convention)"""
+        out, n = (C.c_float * 64)(), C.c_uint32(0)
+        self._check(lib().vkrh_shadow_lights(self.h, out, C.byref(n)))
+        return [np.array(out[16 * i: 16 * i + 16], dtype=np.float32).reshape(4, 4).T.copy() for i in range(n.value)]
 
     def run(self, mask):
         self._check(lib().vkrh_run(self.h, mask))

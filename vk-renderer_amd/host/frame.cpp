@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +39,40 @@ struct GraphInit {  // orders construction: the frame window must be set before 
   }
 };
 
+// main.cpp:295: perspective(radians(90), 1, 0.05, 80) * lookAt((-1.85867, 5.81832, -0.247114), (0, 2, 1), (0, -1, 0)), the light
+// the shading pass calls LIGHT_POS.  Evaluated under the rule of vk-renderer_amd/camera.py (shadow_mvp): the inputs are floats,
+// each factor is evaluated in double — plain scalar arithmetic in one fixed order — and rounded to float, the product is
+// accumulated in double and rounded once.  Python and C++ hand the kernels the same 16 words.
+glm::mat4 default_shadow_mvp() {
+  const double e[3] = {(double)-1.85867f, (double)5.81832f, (double)-0.247114f}, c[3] = {0.0, 2.0, 1.0}, up[3] = {0.0, -1.0, 0.0};
+  auto dot = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+  auto cross = [](const double* a, const double* b, double* o) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+  auto unit = [&](double* a) { const double n = std::sqrt(dot(a, a)); a[0] = a[0] / n; a[1] = a[1] / n; a[2] = a[2] / n; };
+  double f[3] = {c[0] - e[0], c[1] - e[1], c[2] - e[2]}, s[3], t[3];
+  unit(f);
+  cross(f, up, s);
+  unit(s);
+  cross(s, f, t);
+  glm::mat4 v{1.f}, p{0.f};  // m[column][row]
+  for (int k = 0; k < 3; k++) { v[k][0] = (float)s[k]; v[k][1] = (float)t[k]; v[k][2] = (float)-f[k]; }
+  v[3][0] = (float)-dot(s, e); v[3][1] = (float)-dot(t, e); v[3][2] = (float)dot(f, e);
+  const double fovy = (double)(90.f * 0.01745329251994329576923690768489f), znear = (double)0.05f, zfar = 80.0;
+  const double tg = std::tan(fovy / 2.0);
+  p[0][0] = (float)(1.0 / (1.0 * tg));
+  p[1][1] = (float)(1.0 / tg);
+  p[2][2] = (float)(zfar / (znear - zfar));
+  p[2][3] = -1.f;
+  p[3][2] = (float)(-(zfar * znear) / (zfar - znear));
+  glm::mat4 out{0.f};
+  for (int col = 0; col < 4; col++)
+    for (int row = 0; row < 4; row++) {
+      double acc = 0.0;
+      for (int k = 0; k < 4; k++) acc += (double)p[k][row] * (double)v[col][k];
+      out[col][row] = (float)acc;
+    }
+  return out;
+}
+
 struct PostFxFrame {
   vkrh_config cfg;
   rendergraph::RenderGraph graph;
@@ -65,6 +100,12 @@ struct PostFxFrame {
   ProbeTracePass probe_trace_pass;
   rendergraph::ImageResourceId probe_trace_out;
   bool has_probe_trace_out = false;
+
+  // the shadow maps of VKRH_STAGE_SHADOW: main.cpp:279-287 (1024^2, 4 layers, D24S8), one layer per configured light
+  rendergraph::ImageResourceId shadows;
+  bool has_shadows = false, shadows_rendered = false;
+  uint32_t shadow_size = 1024;
+  std::vector<glm::mat4> shadow_lights{default_shadow_mvp()};
 
   DrawTAAParams draw_params{};
   glm::mat4 projection, view, prev_view;
@@ -124,8 +165,36 @@ struct PostFxFrame {
     for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
   }
 
+  void set_shadow_lights(const float* mvps, uint32_t count, uint32_t size) {
+    if (!mvps) throw std::runtime_error{"vkrh_set_shadow_lights: NULL argument"};
+    if (count < 1 || count > 4) throw std::runtime_error{"vkrh_set_shadow_lights: count " + std::to_string(count) + ", needs 1..4 (the layers of the shadow image)"};
+    if (size > 8192) throw std::runtime_error{"vkrh_set_shadow_lights: size " + std::to_string(size) + ", at most 8192"};
+    shadow_lights.resize(count);
+    for (uint32_t i = 0; i < count; i++) std::memcpy((void*)&shadow_lights[i], mvps + 16 * i, 64);
+    shadow_size = size ? size : 1024;
+  }
+
+  // the `shadows` image, created on first use (main.cpp:279-287) and again when the size changes
+  void ensure_shadows() {
+    if (has_shadows && graph.get_descriptor(shadows).width == shadow_size) return;
+    const gpu::ImageInfo info{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT | VK_IMAGE_ASPECT_STENCIL_BIT, shadow_size, shadow_size, 1, 1, 4};
+    if (has_shadows) {
+      // the graph's resource table only grows: the new image takes the old one's place, so that its memory is returned
+      if (hipStreamSynchronize((hipStream_t)cfg.stream) != hipSuccess) throw std::runtime_error{"shadow map: stream synchronisation failed"};
+      graph.get_image(shadows) = std::make_shared<gpu::Image>(info, gpu::FrameWindow{});
+    } else {
+      shadows = graph.create_frame_image(info);  // never a window of the frame, whatever the frame's extent
+      has_shadows = true;
+    }
+    shadows_rendered = false;
+  }
+
   void run(uint32_t mask) {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
+    if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
+      if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
+    }
     if (mask & VKRH_STAGE_GTAO_RT) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT on a tiled frame (ray-traced AO runs on one GPU)"};
       if (mask & VKRH_STAGE_GTAO)
@@ -150,6 +219,11 @@ struct PostFxFrame {
     if (mask & VKRH_STAGE_RASTER) {  // main.cpp:345
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_RASTER without a loaded scene"};
       scene_renderer->draw_taa(graph, gbuffer, draw_params);
+    }
+    if (mask & VKRH_STAGE_SHADOW) {  // main.cpp:346, for every configured light
+      ensure_shadows();
+      for (uint32_t l = 0; l < shadow_lights.size(); l++) scene_renderer->render_shadow(graph, shadow_lights[l], shadows, l);
+      shadows_rendered = true;
     }
     if (mask & VKRH_STAGE_DOWNSAMPLE)  // main.cpp:347
       downsample_pass.run(graph, gbuffer.normal, gbuffer.velocity_vectors, gbuffer.depth, gbuffer.downsampled_normals,
@@ -217,8 +291,10 @@ struct PostFxFrame {
     // resolves.  Without the shading stage TAA resolves the albedo attachment (the headline
     // composite of BASELINE.json is the nine passes without shading).
     if (mask & VKRH_STAGE_SHADING) {
-      shading_pass.update_params(view, glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
-      shading_pass.draw(graph, gbuffer, shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
+      // main.cpp:339,390: once VKRH_STAGE_SHADOW has filled it, layer 0 of `shadows` and its matrix; until then the dummy
+      const bool lit = has_shadows && shadows_rendered;
+      shading_pass.update_params(view, lit ? shadow_lights[0] : glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
+      shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
     }
     if (mask & VKRH_STAGE_TAA) taa_pass.run(graph, gbuffer, (mask & VKRH_STAGE_SHADING) ? color_out_tex : gbuffer.albedo, draw_params);
     graph.submit();
@@ -264,7 +340,7 @@ struct PostFxFrame {
         {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
-        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}};
+        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -283,6 +359,7 @@ struct PostFxFrame {
         if (!probe_grid) throw std::runtime_error{"vkrh_image: '" + name + "' only exists after vkrh_bake_probes"};
         return it->second == 32 ? probe_grid->color_array : it->second == 33 ? probe_grid->depth_array
                : it->second == 34 ? probe_renderer->get_cubemap_color() : probe_renderer->get_cubemap_distance();
+      case 36: if (!has_shadows) throw std::runtime_error{"vkrh_image: 'shadows' only exists after VKRH_STAGE_SHADOW"}; return shadows;
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1017,6 +1094,17 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
 }
 int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32_t grid_size, uint32_t probe_size, uint32_t cube_size) {
   return guarded([&] { frame_ref(frame).bake_probes(min, max, grid_size, probe_size, cube_size); });
+}
+int vkrh_set_shadow_lights(void* frame, const float* mvps, uint32_t count, uint32_t size) {
+  return guarded([&] { frame_ref(frame).set_shadow_lights(mvps, count, size); });
+}
+int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    if (!out || !count) throw std::runtime_error{"vkrh_shadow_lights: NULL argument"};
+    *count = (uint32_t)f->shadow_lights.size();
+    std::memcpy(out, f->shadow_lights.data(), 64 * f->shadow_lights.size());
+  });
 }
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {

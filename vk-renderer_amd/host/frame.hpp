@@ -58,6 +58,12 @@ enum {
   /* ProbeTracePass::run on the G-buffer's depth and normal through the probe grid of the last vkrh_bake_probes -> image
    * "probe_trace" (RGBA8_UNORM, full resolution).  One GPU only (not on a tiled frame), and only after a bake.            */
   VKRH_STAGE_PROBE_TRACE        = 1u << 22,
+  /* main.cpp:346: scene_renderer.render_shadow for every configured light (vkrh_set_shadow_lights; by default the one light of
+   * main.cpp:295 on layer 0) into the layers of image "shadows" (main.cpp:279-287: 1024^2, 4 layers, D24S8; vkrh_image_layer),
+   * recorded after the raster stage and before the downsample.  Once it has run, VKRH_STAGE_SHADING binds layer 0 of "shadows" at
+   * binding 5 instead of its 16x16 dummy (the shader never reads it: color_out does not change).  One GPU only (not on a tiled
+   * frame), and only after vkrh_load_scene.                                                                              */
+  VKRH_STAGE_SHADOW             = 1u << 23,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -94,6 +100,11 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
  * mips), and the cube of the last probe "cubemap_color", "cubemap_distance".  Refused: no scene, grid_size < 2, probe_size or
  * cube_size 0 or not a multiple of 8. */
 int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32_t grid_size, uint32_t probe_size, uint32_t cube_size);
+/* The lights of VKRH_STAGE_SHADOW: `count` (1..4) light matrices of 16 floats (column-major, glm layout), light l renders into
+ * layer l of "shadows"; `size` is the edge of the map, 0 keeps 1024 (at most 8192).  Replaces the default light; a change of size
+ * reallocates the image at the next VKRH_STAGE_SHADOW.  vkrh_shadow_lights returns the matrices in use (room for 4 x 16 floats). */
+int vkrh_set_shadow_lights(void* frame, const float* mvps, uint32_t count, uint32_t size);
+int vkrh_shadow_lights(void* frame, float* out, uint32_t* count);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */
@@ -119,7 +130,7 @@ int vkrh_image(void* frame, const char* name, uint32_t base_mip, uint32_t mip_co
 /* copies a named device buffer ("reflective_tiles", "glossy_tiles", "reflective_indirect",
  * "glossy_indirect") to host memory after synchronising the stream; returns its size in *bytes */
 int vkrh_read_buffer(void* frame, const char* name, void* dst, uint64_t capacity, uint64_t* bytes);
-/* one layer (all its mips) of a named array image ("deinterleaved_depth", "probe_color", "probe_depth", "cubemap_color", ...) */
+/* one layer (all its mips) of a named array image ("deinterleaved_depth", "probe_color", "probe_depth", "cubemap_color", "shadows", ...) */
 int vkrh_image_layer(void* frame, const char* name, uint32_t layer, vkr_img* out);
 /* Reads `name` (mip) back through ReadBackSystem and writes it with the reference's capture writers
  * (main.cpp:118-176): kind 0 = depth CSV (24-bit hex), 1 = depth PNG, 2 = RGBA8 PNG (alpha 255). */

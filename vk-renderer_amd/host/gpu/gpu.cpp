@@ -523,6 +523,45 @@ void register_hot_path_programs() {
       return vkr_raster_gbuffer(&scene, ubo<vkr_gbuf_const>(st, 0, P), &albedo, &normal, &material, &velocity, &depth,
                                 st.scratch, st.scratch_bytes, st.stream);
     });
+    // ---- shadow map (scene_renderer.cpp:222-274): shadows/default.{vert,frag} ----
+    // set 0 {0 ShadowConst {mat4 mvp}, 1 transforms (pairs of mat4: model, normal)}; vertex + index buffers; one recorded
+    // draw_indexed per primitive with a 4-byte push constant transform_index; one depth attachment (a layer of a square D24S8
+    // image), cleared to 1.
+    create_program("default_shadow", [=](LaunchState& st) {
+      const char* P = "default_shadow";
+      if (st.attachments.size() != 1) throw std::runtime_error{"default_shadow: expects one depth attachment"};
+      if (!st.cleared_depth) throw std::runtime_error{"default_shadow: the depth attachment must be cleared (depth 1)"};
+      if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{"default_shadow: vertex / index buffer not bound"};
+      Buffer* transforms = ssbo(st, 1, P);
+      if (!transforms->host_data()) throw std::runtime_error{"default_shadow: the transform buffer must be host-visible on this path"};
+      const ImageViewObject& depth = st.attachments[0];
+      if (depth.range.base_mip != 0) throw std::runtime_error{"default_shadow: the depth attachment must be mip 0 of a layer"};
+      if (st.fb_width != depth.image->get_info().width || st.fb_height != depth.image->get_info().height)
+        throw std::runtime_error{"default_shadow: the framebuffer must cover the (square) depth attachment"};
+      const vkr_img layer = depth.image->get_array_layers() > 1 ? depth.image->describe_layer(depth.range.base_layer, 0, 1) : depth.image->describe(0, 1);
+      std::vector<vkr_raster_draw> draws;
+      uint32_t triangles = 0;
+      for (const auto& d : st.indexed_draws) {
+        if (d.push.size() < 4) throw std::runtime_error{"default_shadow: push constants missing"};
+        vkr_raster_draw r{};
+        std::memcpy(&r.transform_index, d.push.data(), 4);
+        r.albedo_index = r.mr_index = 0xFFFFFFFFu;
+        r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
+        triangles += d.index_count / 3u;
+        draws.push_back(r);
+      }
+      vkr_raster_scene scene{};
+      scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
+      scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
+      scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
+      scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
+      scene.transforms = (const vkr_raster_transform*)transforms->host_data();
+      scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
+      scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
+      static_assert(sizeof(vkr_mat4) == 64, "ShadowConst of shadows/default.vert");
+      if (st.scratch_bytes < vkr_default_shadow_scratch_bytes(layer.width, 1, triangles)) throw std::runtime_error{"default_shadow: no scratch (CmdContext::require_scratch)"};
+      return vkr_default_shadow(&scene, ubo<vkr_mat4>(st, 0, P), &layer, 1, st.scratch, st.scratch_bytes, st.stream);
+    });
     // ---- octahedral probes (probe_renderer.cpp): cubemap_probe, cube2oct, probe_downsample, trace_probe ----
     // a view of one layer of an array image (or of a plain image) as the C-ABI descriptor of its mips
     auto layer_view = [](const ImageViewObject& v) {
@@ -763,10 +802,13 @@ void CmdContext::draw_indexed(uint32_t index_count, uint32_t instance_count, uin
 }
 void CmdContext::end_renderpass() {
   const bool cube_face = bound_program && *bound_program == "cubemap_probe" && !state.attachments.empty();  // cleared even without a draw
-  if (!state.indexed_draws.empty() || cube_face) {  // the recorded geometry is one pass of the bound raster program
+  const bool shadow_layer = bound_program && *bound_program == "default_shadow" && !state.attachments.empty();  // likewise
+  if (!state.indexed_draws.empty() || cube_face || shadow_layer) {  // the recorded geometry is one pass of the bound raster program
     uint32_t triangles = 0;
     for (const auto& d : state.indexed_draws) triangles += d.index_count / 3u;
-    if (cube_face) {
+    if (shadow_layer) {
+      require_scratch(vkr_default_shadow_scratch_bytes(state.fb_width, 1, triangles));
+    } else if (cube_face) {
       // one face of a cube: the draws are kept with their attachments, the six faces are baked by one vkr_cubemap_probe when
       // the last one ends (host/probe_renderer.hpp)
       require_scratch(vkr_cubemap_probe_scratch_bytes(state.fb_width, triangles));

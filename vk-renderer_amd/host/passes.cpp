@@ -954,6 +954,10 @@ void SceneRenderer::init_pipeline(RenderGraph &graph, const Gbuffer &) {  // :46
   regs.depth_stencil.depthWriteEnable = VK_TRUE;
   opaque_taa_pipeline = fullscreen_pipeline("gbuf_opaque_taa", regs);
   opaque_taa_pipeline.set_rendersubpass({true, {VK_FORMAT_R8G8B8A8_SRGB, VK_FORMAT_R16G16_UNORM, VK_FORMAT_R8G8B8A8_SRGB, VK_FORMAT_R16G16_SFLOAT}});
+  shadow_pipeline = gpu::create_graphics_pipeline();  // :72-75
+  shadow_pipeline.set_program("default_shadow");
+  shadow_pipeline.set_registers(regs);
+  shadow_pipeline.set_vertex_input(scene::get_vertex_input_shadow());
   auto repeat = gpu::DEFAULT_SAMPLER;
   repeat.addressModeU = repeat.addressModeV = VK_SAMPLER_ADDRESS_MODE_REPEAT;
   sampler = gpu::create_sampler(repeat);
@@ -1009,7 +1013,7 @@ void SceneRenderer::draw_taa(RenderGraph &graph, const Gbuffer &gbuffer, const D
 
   struct Data { std::vector<rec::Bound> bound; };
   graph.add_task<Data>("GbufferPass",
-    [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(binds, builder, VK_SHADER_STAGE_VERTEX_BIT); },
+    [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(binds, builder, VK_SHADER_STAGE_VERTEX_BIT); builder.use_context_scratch(); },
     [=](Data &d, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
       std::vector<gpu::ImageViewObject> targets;
       for (const auto &r : d.bound)
@@ -1035,6 +1039,61 @@ void SceneRenderer::draw_taa(RenderGraph &graph, const Gbuffer &gbuffer, const D
           cmd.draw_indexed(prim.index_count, 1, prim.index_offset, int32_t(prim.vertex_offset), 0);
         }
       }
+      cmd.end_renderpass();
+    });
+}
+
+// :222-274, a commented-out body in the reference (it predates the scene traversal): here it draws, walking draw_calls x
+// mesh.primitives as draw_taa does.  Depth attachment (out_tex, mip 0, layer) cleared to 1, UBO mat4, SSBO transforms, a 4-byte
+// push constant transform_index, one draw_indexed per primitive.  The reference sizes the framebuffer width x width (:234-235);
+// a non-square image is refused instead of rendered wrongly.
+void SceneRenderer::render_shadow(RenderGraph &graph, const glm::mat4 &shadow_mvp, rendergraph::ImageResourceId out_tex, uint32_t layer) {
+  struct Data {
+    rendergraph::ImageViewId depth;
+  };
+  const auto desc = graph.get_descriptor(out_tex);
+  if (desc.width != desc.height)
+    throw std::runtime_error {"SceneRenderer::render_shadow: the shadow map is " + std::to_string(desc.width) + "x" + std::to_string(desc.height) + ", it must be square"};
+  if (layer >= std::max(1u, desc.array_layers)) throw std::runtime_error {"SceneRenderer::render_shadow: layer outside the shadow map"};
+  graph.add_task<Data>("ShadowPass",
+    [&](Data &input, rendergraph::RenderGraphBuilder &builder) {
+      input.depth = builder.use_depth_attachment(out_tex, 0, layer);
+      builder.use_storage_buffer(transform_buffer, VK_SHADER_STAGE_VERTEX_BIT);
+      builder.use_context_scratch();
+    },
+    [=](Data &input, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      const auto &depth_rt = resources.get_image(input.depth);
+      const uint32_t w = depth_rt->get_info().width;
+      const uint32_t h = depth_rt->get_info().width;
+
+      shadow_pipeline.set_rendersubpass({true, {depth_rt->get_info().format}});
+
+      cmd.set_framebuffer(w, h, {resources.get_image_range(input.depth)});
+      cmd.bind_pipeline(shadow_pipeline);
+      cmd.clear_color_attachments(0.f, 0.f, 0.f, 0.f);
+      cmd.clear_depth_attachment(1.f);
+      cmd.bind_viewport(0.f, 0.f, float(w), float(h), 0.f, 1.f);
+      cmd.bind_scissors(0, 0, w, h);
+      cmd.bind_vertex_buffers(0, {target.vertex_buffer->api_buffer()}, {0ul});
+      cmd.bind_index_buffer(target.index_buffer->api_buffer(), 0, VK_INDEX_TYPE_UINT32);
+
+      auto set = resources.allocate_set(shadow_pipeline.get_layout(0));
+      auto block = cmd.allocate_ubo<glm::mat4>();
+      *block.ptr = shadow_mvp;
+
+      gpu::write_set(set,
+        gpu::UBOBinding {0, cmd.get_ubo_pool(), block},
+        gpu::SSBOBinding {1, resources.get_buffer(transform_buffer)});
+
+      cmd.bind_descriptors_graphics(0, {set}, {block.offset});
+
+      for (const auto &draw_call : draw_calls) {
+        for (const auto &prim : target.root_meshes[draw_call.mesh].primitives) {
+          cmd.push_constants_graphics(VK_SHADER_STAGE_VERTEX_BIT, 0, sizeof(uint32_t), &draw_call.transform);
+          cmd.draw_indexed(prim.index_count, 1, prim.index_offset, int32_t(prim.vertex_offset), 0);
+        }
+      }
+
       cmd.end_renderpass();
     });
 }
@@ -1111,6 +1170,7 @@ void ProbeRenderer::render_side(RenderGraph &graph, SceneRenderer &scene_rendere
       res.distance = builder.use_color_attachment(cubemap_distance, 0, side);
       res.depth = builder.use_depth_attachment(rt_depth, 0, 0);
       builder.use_storage_buffer(scene_renderer.get_scene_transforms(), VK_SHADER_STAGE_VERTEX_BIT);
+      builder.use_context_scratch();
     },
     [=, &scene_renderer](Res &res, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
       const auto extent = resources.get_image(res.color)->get_info().extent2D();

@@ -105,6 +105,10 @@ struct FlatDraw {
 CompiledScene make_scene(const Vertex *vertices, uint32_t vertex_count, const uint32_t *indices, uint32_t index_count,
                          const FlatDraw *draws, uint32_t draw_count, const TextureData *textures, uint32_t texture_count);
 
+// scene/scene.cpp:46-60: one binding of stride sizeof(Vertex), attribute 0 = pos.  The vertex layout of this path is fixed
+// (vkr_raster_vertex), so the description is empty; the shadow program reads only pos
+inline gpu::VertexInput get_vertex_input_shadow() { return {}; }
+
 }
 
 
@@ -172,6 +176,8 @@ struct SceneRenderer {
   void init_pipeline(rendergraph::RenderGraph &graph, const Gbuffer &buffer);
   void update_scene();
   void draw_taa(rendergraph::RenderGraph &graph, const Gbuffer &gbuffer, const DrawTAAParams &params);
+  // the scene's depth seen through shadow_mvp into layer `layer` of the square D24S8 image out_tex (program "default_shadow")
+  void render_shadow(rendergraph::RenderGraph &graph, const glm::mat4 &shadow_mvp, rendergraph::ImageResourceId out_tex, uint32_t layer);
 
   struct DrawCall {
     uint32_t transform;
@@ -188,6 +194,7 @@ private:
   scene::CompiledScene &target;
   rendergraph::RenderGraph *owner = nullptr;
   gpu::GraphicsPipeline opaque_taa_pipeline;
+  gpu::GraphicsPipeline shadow_pipeline;
   VkSampler sampler;
   rendergraph::BufferResourceId transform_buffer;
   VkDescriptorSet bindless_textures {nullptr};

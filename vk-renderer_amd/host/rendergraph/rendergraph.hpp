@@ -80,7 +80,7 @@ struct GraphResources {
   const gpu::ImagePtr& get_image(ImageResourceId id) const;
   gpu::BufferPtr& get_buffer(BufferResourceId id);
   // usage tracking of the task being recorded; `log` receives (resource key, write?) for submit()'s lane assignment
-  struct Access { uint64_t key; bool write; };  // key: image index << 8 | mip, or 1 << 63 | buffer index
+  struct Access { uint64_t key; bool write; };  // key: image index << 8 | mip, 1 << 63 | buffer index, or 1 << 62 (the context's scratch)
   void declare(ImageResourceId id, uint32_t base_mip, uint32_t mips, Usage usage, uint32_t task_index, std::vector<Access>* log);
   static void declare(BufferResourceId id, bool write, std::vector<Access>* log) { if (log) log->push_back({(1ull << 63) | id.get_index(), write}); }
   size_t image_count() const { return images.size(); }
@@ -110,6 +110,10 @@ struct RenderGraphBuilder {  // rendergraph.hpp:17-55
   void use_uniform_buffer(BufferResourceId id, VkShaderStageFlags) { GraphResources::declare(id, false, log); }
   void use_storage_buffer(BufferResourceId id, VkShaderStageFlags, bool readonly = true) { GraphResources::declare(id, !readonly, log); }
   void use_indirect_buffer(BufferResourceId id) { GraphResources::declare(id, false, log); }
+  // The raster programs (gbuf_opaque_taa, cubemap_probe, default_shadow) keep their records in the command context's one scratch
+  // allocation (CmdContext::require_scratch).  Declared as a write of a resource of its own, so that two raster passes of one
+  // submission never run on different lanes at once (set_async).
+  void use_context_scratch() { if (log) log->push_back({1ull << 62, true}); }
   void transfer_write(BufferResourceId id) { GraphResources::declare(id, true, log); }
   void transfer_read(BufferResourceId id) { GraphResources::declare(id, false, log); }
   void transfer_read(ImageResourceId id, uint32_t base_mip, uint32_t mip_count, uint32_t base_layer, uint32_t layer_count);

@@ -149,7 +149,7 @@ class ArrayImageBuf:
     layer 0's plus l * pitch[m] * height[m].  That is how the host mirror's gpu::Image allocates an array (Image::describe_layer hands
     out the per-layer views), so a probe array baked by the mirror and one allocated here are laid out alike.  `descs()` gives the per-layer descriptors of the C-ABI's array arguments
     (vkr_trace_probe's probe arrays, vkr_cubemap_probe's cubes).  raw() knows the formats of those arrays: RGBA8_UNORM and
-    R16_UNORM (probes), RGBA8_SRGB and R16_SFLOAT (cubes)."""
+    R16_UNORM (probes), RGBA8_SRGB and R16_SFLOAT (cubes), D24_UNORM_S8 (shadow maps: whole uint32 words)."""
 
     def __init__(self, fmt, width, height, layers, mips=1, device=None, fill=0):
         self.format, self.width, self.height, self.layers, self.mips = fmt, int(width), int(height), int(layers), int(mips)
@@ -198,7 +198,8 @@ class ArrayImageBuf:
 
     def raw(self, mip=0, host=None):
         """raw storage of one mip of every layer: [layers, h, w, channels] in the storage dtype"""
-        dtypes = {abi.FMT_RGBA8_UNORM: np.uint8, abi.FMT_R16_UNORM: np.uint16, abi.FMT_RGBA8_SRGB: np.uint8, abi.FMT_R16_SFLOAT: np.float16}
+        dtypes = {abi.FMT_RGBA8_UNORM: np.uint8, abi.FMT_R16_UNORM: np.uint16, abi.FMT_RGBA8_SRGB: np.uint8, abi.FMT_R16_SFLOAT: np.float16,
+                  abi.FMT_D24_UNORM_S8: np.uint32}
         if self.format not in dtypes:
             raise ValueError(f"ArrayImageBuf.raw: format {self.format}")
         host = self.to_host() if host is None else host
