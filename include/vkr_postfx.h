@@ -558,6 +558,37 @@ typedef struct vkr_probe_trace_consts {
 int vkr_trace_probe(const vkr_img* depth, const vkr_img* normal, const vkr_img* color_layers, const vkr_img* depth_layers,
                     uint32_t layer_count, const vkr_probe_trace_consts* consts, const vkr_img* out, void* stream);
 
+/* ---- image transfers (util_passes.cpp: clear_depth, clear_color, blit_image, gen_mipmaps; scene/images.cpp:93-160) -----------------------
+ * Whole-image operations: every entry refuses, before it launches anything, a NULL descriptor, an unknown format and a descriptor
+ * that is a window of a larger frame (origin != 0 or full_* != width / height).  Conversions use the library's codecs: a texel
+ * decodes to float RGBA with absent channels 0, 0, 0, 1 (UNORM: the correctly rounded k / (2^b - 1); RGBA8_SRGB: rgb through the
+ * EOTF table, alpha linear) and is stored as that format stores: sRGB threshold rule for the rgb of RGBA8_SRGB, UNORM
+ * rint(clamp(x, 0, 1) * (2^b - 1)), fp16 round to nearest even, fp32 unchanged (DESIGN_NUMERICS.md, "Image transfers").        */
+typedef struct vkr_clear_value {
+  float    color[4];   /* colour formats                                    */
+  float    depth;      /* D24_UNORM_S8: rint(clamp(depth, 0, 1) * 16777215) */
+  uint32_t stencil;    /* ... | (stencil & 0xFF) << 24                      */
+} vkr_clear_value;
+/* vkCmdClearColorImage / vkCmdClearDepthStencilImage over every mip of the view, one launch.  Only the texels of a row are written
+ * (not the padding up to the pitch), so clearing one layer's descriptor of an array image leaves the other layers alone.          */
+int vkr_clear_image(const vkr_img* img, const vkr_clear_value* value, void* stream);
+#define VKR_FILTER_NEAREST 0u
+#define VKR_FILTER_LINEAR  1u
+/* vkCmdBlitImage of whole mip 0 of `src` onto whole mip 0 of `dst` (what both callers of the reference do, util_passes.cpp:152-179),
+ * between any two colour formats and any two extents.  Destination texel (i, j) samples the source at u = (i + 0.5) * (src_w /
+ * dst_w), v alike: NEAREST takes texel floor(u); LINEAR takes the taps floor(u - 0.5) and that plus one, clamped to the edge, with
+ * weight frac(u - 0.5), mixed like the sampler's bilinear filter.  D24_UNORM_S8 blits only to D24_UNORM_S8, only with NEAREST and
+ * only at equal extents (the stored words are copied).  src and dst must not be the same memory.                                */
+int vkr_blit_image(const vkr_img* src, const vkr_img* dst, uint32_t filter, void* stream);
+/* Levels 1 .. mip_count - 1 of the view from level 0, by the project's one mip rule (vk-renderer_amd/scene.py build_mips), which
+ * is NOT a Vulkan blit on odd extents: level extents max(1, s / 2); destination texel (X, Y) is ((a + b) + (c + d)) * 0.25 in fp32
+ * of the source texels (2X, 2Y), (min(2X + 1, w - 1), 2Y) and the same in the row min(2Y + 1, h - 1), per channel, decoded from
+ * the stored previous level and stored again (RGBA8_SRGB: rgb through the EOTF table, alpha linear).  Formats: RGBA8_SRGB,
+ * RGBA8_UNORM, RGBA16_SFLOAT, RG16_SFLOAT, R16_SFLOAT, R32_SFLOAT, R8_UNORM; D24_UNORM_S8 is refused (vkr_depth_mips is the depth
+ * pyramid).  Two schedules that leave the same bytes: one launch per level, or 64 x 64 source tiles reduced through LDS over up
+ * to six levels per launch (VKR_SWITCH_MIPS_PER_LEVEL / VKR_SWITCH_MIPS_FUSED force one).                                       */
+int vkr_gen_mipmaps(const vkr_img* img, void* stream);
+
 /* Multi-GPU exchange helper (the reference is single-GPU, so there is no program this
  * replaces): copies `count` pitch-linear byte rectangles on `stream`, VKR_MAX_RECTS per launch.  Used to pack
  * a tile's surfaces for the all-gather, to scatter the gathered tiles into the whole-frame images and to
@@ -665,7 +696,7 @@ int vkr_hit_scatter(const vkr_img* frame_albedo, const vkr_img* frame_normals, c
                     uint32_t count, void* stream);
 
 /* Measurement switches — the library's only process-wide state.  The environment (VKR_BLUR_NO_SKIP, VKR_FILTER_NO_SKIP,
- * VKR_TAA_GENERIC, VKR_SHADING_GENERIC, VKR_BLUR_GENERIC, VKR_BLUR_LANE_LOOPS, VKR_TRACE_ONE_LAUNCH) is read once, at the first launch that asks; afterwards only vkr_set_switches
+ * VKR_TAA_GENERIC, VKR_SHADING_GENERIC, VKR_BLUR_GENERIC, VKR_BLUR_LANE_LOOPS, VKR_TRACE_ONE_LAUNCH, VKR_MIPS_PER_LEVEL, VKR_MIPS_FUSED) is read once, at the first launch that asks; afterwards only vkr_set_switches
  * changes them.  NO_SKIP: evaluate every tap of the blur / filter even in tiles without a reflection / hit (a
  * content-independent time; the stored texels are the same wherever every weight is finite).  GENERIC: the TAA /
  * shading instantiations that do not assume equal window layouts.                                                  */
@@ -677,6 +708,8 @@ int vkr_hit_scatter(const vkr_img* frame_albedo, const vkr_img* frame_normals, c
 #define VKR_SWITCH_BLUR_LANE_LOOPS 64u /* waves that do not share one sigma on the per-lane tap loops of rounds 1-3 instead of the transposed packed rows (blur_rows) */
 #define VKR_SWITCH_TRACE_ONE_LAUNCH 32u /* read by the HOST layer (host/gpu): program "sssr_trace" as one launch (vkr_sssr_trace) instead of
                                           * head + resume (vkr_sssr_trace_split); the library's entries do what their names say either way */
+#define VKR_SWITCH_MIPS_PER_LEVEL 128u /* vkr_gen_mipmaps: one launch per level ... */
+#define VKR_SWITCH_MIPS_FUSED     256u /* ... or the fused tiles, whatever the default is (per level wins if both are set); same bytes */
 uint32_t vkr_get_switches(void);
 void vkr_set_switches(uint32_t mask);
 

@@ -225,6 +225,13 @@ class ProbeTraceConsts(C.Structure):  # vkr_probe_trace_consts == Constants (pro
                 ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
 
 
+# ---- image transfers: vkr_clear_image, vkr_blit_image, vkr_gen_mipmaps ----
+class ClearValue(C.Structure):  # vkr_clear_value
+    _fields_ = [("color", C.c_float * 4), ("depth", C.c_float), ("stencil", C.c_uint32)]
+
+
+FILTER_NEAREST, FILTER_LINEAR = 0, 1
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -365,6 +372,12 @@ def product():
         lib.vkr_default_shadow_scratch_bytes.restype = C.c_uint64
         lib.vkr_default_shadow.argtypes = [P(RasterScene), P(Mat4), _IMG, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.vkr_default_shadow.restype = C.c_int
+        # image transfers (checked against the numpy restatement tests/transfer_reference.py and scene.build_mips)
+        lib.vkr_clear_image.argtypes = [_IMG, P(ClearValue), C.c_void_p]
+        lib.vkr_blit_image.argtypes = [_IMG, _IMG, C.c_uint32, C.c_void_p]
+        lib.vkr_gen_mipmaps.argtypes = [_IMG, C.c_void_p]
+        for name in ("clear_image", "blit_image", "gen_mipmaps"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
         _product = lib
     return _product
 
@@ -393,6 +406,28 @@ def cubemap_probe(scene, pos, cube_color, cube_distance, scratch, scratch_bytes,
     check(lib.vkr_cubemap_probe(C.byref(scene), C.byref(p), cube_color, cube_distance, scratch, int(scratch_bytes), stream), lib)
 
 
+def clear_image(img, color=(0.0, 0.0, 0.0, 0.0), depth=1.0, stencil=0, stream=None):
+    """vkr_clear_image: every mip of the view `img` (VkrImg) to one value: `color` for colour formats (stored as the format
+    stores it), rint(depth * 16777215) | stencil << 24 for D24_UNORM_S8.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    v = ClearValue((C.c_float * 4)(*[float(c) for c in color]), float(depth), int(stencil))
+    check(lib.vkr_clear_image(C.byref(img), C.byref(v), stream), lib)
+
+
+def blit_image(src, dst, filter=FILTER_LINEAR, stream=None):
+    """vkr_blit_image: whole mip 0 of `src` onto whole mip 0 of `dst` (VkrImg), any colour formats and extents; FILTER_NEAREST or
+    FILTER_LINEAR.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    check(lib.vkr_blit_image(C.byref(src), C.byref(dst), int(filter), stream), lib)
+
+
+def gen_mipmaps(img, stream=None):
+    """vkr_gen_mipmaps: levels 1 .. mip_count - 1 of the view from level 0 by the project's mip rule (scene.build_mips).  Raises
+    RuntimeError with the library's message on a refusal."""
+    lib = product()
+    check(lib.vkr_gen_mipmaps(C.byref(img), stream), lib)
+
+
 def default_shadow_scratch_bytes(size, layer_count, triangle_count):
     """vkr_default_shadow_scratch_bytes: device scratch of one call (edge of a layer, layers, triangles summed over all draws)"""
     return int(product().vkr_default_shadow_scratch_bytes(int(size), int(layer_count), int(triangle_count)))
@@ -414,6 +449,7 @@ def default_shadow(scene, mvps, layers, scratch, scratch_bytes, stream=None):
 COMM_ID_BYTES = 128
 # measurement switches (include/vkr_postfx.h VKR_SWITCH_*): vkr_get_switches / vkr_set_switches
 SWITCH_BLUR_NO_SKIP, SWITCH_FILTER_NO_SKIP, SWITCH_TAA_GENERIC, SWITCH_SHADING_GENERIC, SWITCH_BLUR_GENERIC, SWITCH_TRACE_ONE_LAUNCH, SWITCH_BLUR_LANE_LOOPS = 1, 2, 4, 8, 16, 32, 64
+SWITCH_MIPS_PER_LEVEL, SWITCH_MIPS_FUSED = 128, 256  # vkr_gen_mipmaps: force one launch per level / the fused tiles (same bytes)
 
 
 class Comm:

@@ -28,6 +28,8 @@ uint32_t switches() {
     if (getenv("VKR_BLUR_GENERIC")) v |= VKR_SWITCH_BLUR_GENERIC;
     if (getenv("VKR_TRACE_ONE_LAUNCH")) v |= VKR_SWITCH_TRACE_ONE_LAUNCH;
     if (getenv("VKR_BLUR_LANE_LOOPS")) v |= VKR_SWITCH_BLUR_LANE_LOOPS;
+    if (getenv("VKR_MIPS_PER_LEVEL")) v |= VKR_SWITCH_MIPS_PER_LEVEL;
+    if (getenv("VKR_MIPS_FUSED")) v |= VKR_SWITCH_MIPS_FUSED;
     uint32_t expected = 0x80000000u;
     if (!g_switches.compare_exchange_strong(expected, v)) v = expected;
   }

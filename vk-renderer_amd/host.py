@@ -18,6 +18,8 @@ STAGE_RASTER = 131072
 STAGE_GTAO_RT = 1 << 21  # ray-traced AO (main.cpp:379-388 use_rt_ao): needs load_scene(); not with STAGE_GTAO, not tiled
 STAGE_PROBE_TRACE = 1 << 22  # ProbeTracePass::run through the grid of bake_probes() -> image "probe_trace"; not tiled
 STAGE_SHADOW = 1 << 23  # SceneRenderer::render_shadow per configured light -> layers of image "shadows"; needs load_scene(); not tiled
+STAGE_CLEAR_PREV_DEPTH = 1 << 24  # clear_depth(graph, gbuffer.prev_depth) (main.cpp:306), before every other stage; not tiled
+TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the host, the frame builds the others (vkr_gen_mipmaps)
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -52,7 +54,7 @@ class SceneDraw(C.Structure):
 
 
 class SceneTexture(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32), ("reserved", C.c_uint32),
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32), ("flags", C.c_uint32),
                 ("levels", C.c_void_p * 16)]
 
 
@@ -128,7 +130,11 @@ def lib():
                            ("vkrh_bake_probes", [C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_uint32, C.c_uint32, C.c_uint32]),
                            # the shadow pass (same rule)
                            ("vkrh_set_shadow_lights", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32]),
-                           ("vkrh_shadow_lights", [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)])):
+                           ("vkrh_shadow_lights", [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+                           # image transfers (same rule)
+                           ("vkrh_scene_texture_image", [C.c_void_p, C.c_uint32, C.POINTER(abi.VkrImg)]),
+                           ("vkrh_create_image", [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+                           ("vkrh_transfer", [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_float)])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -257,8 +263,9 @@ class HostFrame:
         cam.fovy, cam.aspect, cam.znear, cam.zfar = [float(v) for v in fazz]
         self._check(lib().vkrh_set_camera(self.h, C.byref(cam)))
 
-    def load_scene(self, sc):
-        """scene.Scene -> scene::CompiledScene + SceneRenderer inside the frame (main.cpp:250-259)."""
+    def load_scene(self, sc, device_mips=False):
+        """scene.Scene -> scene::CompiledScene + SceneRenderer inside the frame (main.cpp:250-259).  device_mips: only level 0 of
+        every texture is handed over (TEXTURE_GEN_MIPS); the frame builds the chain on the device, as scene/images.cpp does."""
         verts = np.ascontiguousarray(sc.vertices, dtype=np.float32)
         idx = np.ascontiguousarray(sc.indices, dtype=np.uint32)
         draws = (SceneDraw * max(1, len(sc.draws)))()
@@ -269,13 +276,47 @@ class HostFrame:
         keep = []
         for i, levels in enumerate(sc.textures):
             h, w = levels[0].shape[:2]
-            tex[i].width, tex[i].height, tex[i].mip_levels = w, h, len(levels)
-            for m, lv in enumerate(levels):
+            tex[i].width, tex[i].height, tex[i].mip_levels = w, h, 1 if device_mips else len(levels)
+            tex[i].flags = TEXTURE_GEN_MIPS if device_mips else 0
+            for m, lv in enumerate(levels[:1] if device_mips else levels):
                 a = np.ascontiguousarray(lv)
                 keep.append(a)
                 tex[i].levels[m] = a.ctypes.data
         self._check(lib().vkrh_load_scene(self.h, C.c_void_p(verts.ctypes.data), len(verts), C.c_void_p(idx.ctypes.data), len(idx),
                                           draws, len(sc.draws), tex, len(sc.textures)))
+
+    def scene_texture(self, index):
+        """vkrh_scene_texture_image: descriptor (every level) of texture `index` of the loaded scene"""
+        d = abi.VkrImg()
+        self._check(lib().vkrh_scene_texture_image(self.h, int(index), C.byref(d)))
+        return d
+
+    def download_desc(self, d):
+        """host ImageBuf with the bytes of a device image described by `d` (a descriptor of one of the frame's allocations)"""
+        from .images import ImageBuf, mip_extent
+
+        buf = ImageBuf(d.format, d.width, d.height, d.mip_count)
+        t, off = self.allocator.tensor_at(d.base)
+        for i in range(d.mip_count):
+            assert buf.pitch[i] == d.pitch_bytes[i], "layout rules diverged"
+            n = buf.pitch[i] * mip_extent(d.height, i)
+            buf.host[buf.offset[i]: buf.offset[i] + n] = t[off + d.mip_offset[i]: off + d.mip_offset[i] + n].cpu().numpy()
+        return buf
+
+    def create_image(self, name, fmt, width, height, mips=1, layers=1):
+        """vkrh_create_image: an image of the caller's own in the frame's graph (fmt: abi.FMT_*), found by image() / download()"""
+        self._check(lib().vkrh_create_image(self.h, name.encode(), int(fmt), int(width), int(height), int(mips), int(layers)))
+
+    TRANSFER_GEN_MIPMAPS, TRANSFER_CLEAR_DEPTH, TRANSFER_CLEAR_COLOR, TRANSFER_BLIT = 0, 1, 2, 3
+
+    def transfer(self, op, image, dst=None, value=None):
+        """vkrh_transfer: one helper of util_passes.hpp on named images of the frame, recorded and submitted: gen_mipmaps(image),
+        clear_depth(image, value), clear_color(image, value[4]), blit_image(image, dst)"""
+        v = None
+        if value is not None:
+            vals = [float(value)] if np.isscalar(value) else [float(c) for c in value]
+            v = (C.c_float * 4)(*(vals + [0.0] * (4 - len(vals))))
+        self._check(lib().vkrh_transfer(self.h, int(op), image.encode(), dst.encode() if dst else None, v))
 
     def gtao_rt_params(self):
         """abi.GtaoRtParams that STAGE_GTAO_RT uses for the current camera (camera_to_world = inverse(view))"""
@@ -321,11 +362,16 @@ class HostFrame:
         self._check(lib().vkrh_image(self.h, name.encode(), base_mip, mip_count, C.byref(d)))
         return d
 
-    CAPTURE_DEPTH_CSV, CAPTURE_DEPTH_PNG, CAPTURE_RGBA_PNG = 0, 1, 2
+    CAPTURE_DEPTH_CSV, CAPTURE_DEPTH_PNG, CAPTURE_RGBA_PNG, CAPTURE_FINAL_FRAME = 0, 1, 2, 3
 
     def capture(self, name, path, kind, mip=0):
         """ReadBackSystem + the capture writers of main.cpp:118-176 (SURVEY.md 8(f) #3)."""
         self._check(lib().vkrh_capture(self.h, name.encode(), mip, kind, str(path).encode()))
+
+    def capture_final(self, path, name="taa_target"):
+        """The final frame as a PNG (main.cpp:392-396): `name` is blitted into the RGBA8_SRGB image "readback" on the device, which
+        is read back and written with the RGBA PNG writer.  download("readback") shows the blitted image afterwards."""
+        self.capture(name, path, self.CAPTURE_FINAL_FRAME)
 
     def read_buffer(self, name, max_bytes=1 << 24):
         """int32 contents of a named device buffer of the SSR pass (tile lists, indirect arguments)."""

@@ -28,6 +28,7 @@
 #include "screen_trace.hpp"
 #include "synthetic_gbuffer.hpp"
 #include "taa.hpp"
+#include "util_passes.hpp"
 
 namespace {
 
@@ -106,6 +107,18 @@ struct PostFxFrame {
   bool has_shadows = false, shadows_rendered = false;
   uint32_t shadow_size = 1024;
   std::vector<glm::mat4> shadow_lights{default_shadow_mvp()};
+
+  // main.cpp:392-396: the RGBA8_SRGB image the final frame is blitted into before it is read back (capture kind 3)
+  rendergraph::ImageResourceId readback_image;
+  bool has_readback_image = false;
+  rendergraph::ImageResourceId ensure_readback_image() {
+    if (!has_readback_image) {
+      readback_image = graph.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, cfg.width, cfg.height},
+                                          VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_TRANSFER_DST_BIT | VK_IMAGE_USAGE_TRANSFER_SRC_BIT);
+      has_readback_image = true;
+    }
+    return readback_image;
+  }
 
   DrawTAAParams draw_params{};
   glm::mat4 projection, view, prev_view;
@@ -191,6 +204,8 @@ struct PostFxFrame {
 
   void run(uint32_t mask) {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
+    if ((mask & VKRH_STAGE_CLEAR_PREV_DEPTH) && cfg.tiled)  // refused before anything is recorded
+      throw std::runtime_error{"vkrh_run: VKRH_STAGE_CLEAR_PREV_DEPTH on a tiled frame (transfers take whole images)"};
     if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
@@ -207,6 +222,7 @@ struct PostFxFrame {
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE on a tiled frame (probes are traced on one GPU)"};
       if (!probe_grid) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE without baked probes (vkrh_bake_probes)"};
     }
+    if (mask & VKRH_STAGE_CLEAR_PREV_DEPTH) clear_depth(graph, gbuffer.prev_depth);  // main.cpp:306
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
     if (mask & VKRH_STAGE_BRDF_LUT) ssr.preintegrate_brdf(graph);
     if (mask & VKRH_STAGE_PREV_DEPTH) {
@@ -333,14 +349,70 @@ struct PostFxFrame {
 
   uint32_t hiz_gathered_mips = 4;  // tiled: view mips 0..3 of frame_hiz (image mips 1..4) arrive by all-gather
 
+  std::map<std::string, rendergraph::ImageResourceId> user_images;  // vkrh_create_image
+
+  static VkFormat vk_format(uint32_t format) {
+    switch (format) {
+      case VKR_FMT_D24_UNORM_S8: return VK_FORMAT_D24_UNORM_S8_UINT; case VKR_FMT_RG16_UNORM: return VK_FORMAT_R16G16_UNORM;
+      case VKR_FMT_RG16_SFLOAT: return VK_FORMAT_R16G16_SFLOAT; case VKR_FMT_RGBA8_SRGB: return VK_FORMAT_R8G8B8A8_SRGB;
+      case VKR_FMT_RGBA8_UNORM: return VK_FORMAT_R8G8B8A8_UNORM; case VKR_FMT_RGBA16_UNORM: return VK_FORMAT_R16G16B16A16_UNORM;
+      case VKR_FMT_RGBA16_SFLOAT: return VK_FORMAT_R16G16B16A16_SFLOAT; case VKR_FMT_R16_SFLOAT: return VK_FORMAT_R16_SFLOAT;
+      case VKR_FMT_R32_SFLOAT: return VK_FORMAT_R32_SFLOAT; case VKR_FMT_R8_UNORM: return VK_FORMAT_R8_UNORM;
+      case VKR_FMT_RGBA32_SFLOAT: return VK_FORMAT_R32G32B32A32_SFLOAT; case VKR_FMT_R16_UNORM: return VK_FORMAT_R16_UNORM;
+      default: throw std::runtime_error{"vkrh_create_image: unknown format " + std::to_string(format)};
+    }
+  }
+  void create_user_image(const char* name, uint32_t format, uint32_t w, uint32_t h, uint32_t mips, uint32_t layers) {
+    if (!name || !*name) throw std::runtime_error{"vkrh_create_image: NULL name"};
+    if (cfg.tiled) throw std::runtime_error{"vkrh_create_image: on a tiled frame (transfers take whole images)"};
+    bool taken = user_images.count(name) != 0;
+    if (!taken) { try { lookup(name); taken = true; } catch (const std::exception& e) { taken = std::string{e.what()}.find("unknown image") == std::string::npos; } }
+    if (taken) throw std::runtime_error{std::string{"vkrh_create_image: the name '"} + name + "' is taken"};
+    const VkFormat fmt = vk_format(format);
+    if (!w || !h || !mips || mips > VKR_MAX_MIPS || !layers) throw std::runtime_error{"vkrh_create_image: bad extent, mip or layer count"};
+    const VkImageAspectFlags aspect = format == VKR_FMT_D24_UNORM_S8 ? VK_IMAGE_ASPECT_DEPTH_BIT | VK_IMAGE_ASPECT_STENCIL_BIT : VK_IMAGE_ASPECT_COLOR_BIT;
+    user_images[name] = graph.create_frame_image(gpu::ImageInfo{fmt, aspect, w, h, 1, mips, layers});
+  }
+  void transfer(uint32_t op, const char* image, const char* dst, const float* value) {
+    if (cfg.tiled) throw std::runtime_error{"vkrh_transfer: on a tiled frame (transfers take whole images)"};
+    if (!image) throw std::runtime_error{"vkrh_transfer: NULL image name"};
+    const rendergraph::ImageResourceId id = lookup(image);
+    switch (op) {
+      case VKRH_TRANSFER_GEN_MIPMAPS: gen_mipmaps(graph, id); break;
+      case VKRH_TRANSFER_CLEAR_DEPTH: clear_depth(graph, id, value ? value[0] : 1.0f); break;
+      case VKRH_TRANSFER_CLEAR_COLOR: {
+        if (!value) throw std::runtime_error{"vkrh_transfer: clear_color needs a value"};
+        VkClearColorValue v{};
+        std::memcpy(v.float32, value, sizeof(v.float32));
+        clear_color(graph, id, v);
+        break;
+      }
+      case VKRH_TRANSFER_BLIT: {
+        if (!dst) throw std::runtime_error{"vkrh_transfer: blit_image needs a destination"};
+        const rendergraph::ImageResourceId to = lookup(dst);
+        if (to == id) throw std::runtime_error{"vkrh_transfer: blit_image onto the source"};
+        blit_image(graph, id, to);
+        break;
+      }
+      default: throw std::runtime_error{"vkrh_transfer: unknown operation " + std::to_string(op)};
+    }
+    graph.submit();
+    task_names.clear();
+    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
+  }
+
   rendergraph::ImageResourceId lookup(const std::string& name) {
+    {
+      auto user = user_images.find(name);
+      if (user != user_images.end()) return user->second;
+    }
     static const std::map<std::string, int> ids = {
         {"depth", 0}, {"prev_depth", 1}, {"normal", 2}, {"albedo", 3}, {"material", 4}, {"velocity", 5}, {"dn", 6}, {"dv", 7},
         {"raw", 8}, {"filtered", 9}, {"acc_ao", 10}, {"acc_hist", 11}, {"rays", 12}, {"reflections", 13}, {"blurred", 14},
         {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
-        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}};
+        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -360,6 +432,7 @@ struct PostFxFrame {
         return it->second == 32 ? probe_grid->color_array : it->second == 33 ? probe_grid->depth_array
                : it->second == 34 ? probe_renderer->get_cubemap_color() : probe_renderer->get_cubemap_distance();
       case 36: if (!has_shadows) throw std::runtime_error{"vkrh_image: 'shadows' only exists after VKRH_STAGE_SHADOW"}; return shadows;
+      case 37: if (!has_readback_image) throw std::runtime_error{"vkrh_image: 'readback' only exists after a final-frame capture (vkrh_capture kind 3)"}; return readback_image;
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1075,21 +1148,36 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
       flat[i].clip_alpha = draws[i].clip_alpha != 0;
     }
     std::vector<scene::TextureData> tex(texture_count);
-    for (uint32_t i = 0; i < texture_count; i++) {
-      if (textures[i].mip_levels == 0 || textures[i].mip_levels > VKR_MAX_MIPS) throw std::runtime_error{"vkrh_load_scene: bad mip count"};
-      tex[i].width = textures[i].width; tex[i].height = textures[i].height; tex[i].mip_levels = textures[i].mip_levels;
-      for (uint32_t m = 0; m < textures[i].mip_levels; m++) tex[i].levels[m] = textures[i].levels[m];
+    for (uint32_t i = 0; i < texture_count; i++) {  // refused before anything is uploaded
+      if (textures[i].flags & ~uint32_t(VKRH_TEXTURE_GEN_MIPS)) throw std::runtime_error{"vkrh_load_scene: unknown texture flag"};
+      tex[i].gen_mips = (textures[i].flags & VKRH_TEXTURE_GEN_MIPS) != 0;
+      if (tex[i].gen_mips && f->cfg.tiled) throw std::runtime_error{"vkrh_load_scene: VKRH_TEXTURE_GEN_MIPS on a tiled frame (texture mips are built on one GPU)"};
+      if (tex[i].gen_mips && (textures[i].width == 0 || textures[i].height == 0 || !textures[i].levels[0])) throw std::runtime_error{"vkrh_load_scene: VKRH_TEXTURE_GEN_MIPS needs level 0"};
+      if (!tex[i].gen_mips && (textures[i].mip_levels == 0 || textures[i].mip_levels > VKR_MAX_MIPS)) throw std::runtime_error{"vkrh_load_scene: bad mip count"};
+      tex[i].width = textures[i].width; tex[i].height = textures[i].height; tex[i].mip_levels = tex[i].gen_mips ? 1u : textures[i].mip_levels;
+      for (uint32_t m = 0; m < tex[i].mip_levels; m++) tex[i].levels[m] = textures[i].levels[m];
     }
     f->scene_renderer.reset();
     f->scene_as.reset();
     f->loaded_scene.reset(new scene::CompiledScene(scene::make_scene((const scene::Vertex*)vertices, vertex_count, indices, index_count,
-                                                                     flat.data(), draw_count, tex.data(), texture_count)));
+                                                                     flat.data(), draw_count, tex.data(), texture_count, f->graph.get_stream())));
     f->scene_renderer.reset(new SceneRenderer(*f->loaded_scene));
     f->scene_renderer->init_pipeline(f->graph, f->gbuffer);  // main.cpp:256-259
     f->scene_renderer->update_scene();
     gpu::TransferCmdPool transfer_pool{f->graph.get_stream()};  // main.cpp:257-258
     f->scene_as.reset(new scene::SceneAccelerationStructure);
     f->scene_as->build(transfer_pool, *f->loaded_scene);
+  });
+}
+int vkrh_scene_texture_image(void* frame, uint32_t index, vkr_img* out) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    if (!out) throw std::runtime_error{"vkrh_scene_texture_image: NULL argument"};
+    if (f->cfg.tiled) throw std::runtime_error{"vkrh_scene_texture_image: on a tiled frame (scene textures live on one GPU)"};
+    if (!f->loaded_scene) throw std::runtime_error{"vkrh_scene_texture_image: without a loaded scene (vkrh_load_scene)"};
+    if (index >= f->loaded_scene->images.size()) throw std::runtime_error{"vkrh_scene_texture_image: texture " + std::to_string(index) + " of " + std::to_string(f->loaded_scene->images.size())};
+    const auto& img = f->loaded_scene->images[index];
+    *out = img->describe(0, img->get_mip_levels());
   });
 }
 int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32_t grid_size, uint32_t probe_size, uint32_t cube_size) {
@@ -1189,7 +1277,16 @@ int vkrh_capture(void* frame, const char* name, uint32_t mip, uint32_t kind, con
   return guarded([&] {
     auto* f = &frame_ref(frame);
     if (!f || !name || !path) throw std::runtime_error{"NULL argument"};
-    const ReadBackID id = f->readback.read_image(f->graph, f->lookup(name), 0, mip, 0);
+    rendergraph::ImageResourceId source = f->lookup(name);
+    if (kind == 3) {  // main.cpp:392-396: the final frame through an RGBA8_SRGB image
+      if (f->cfg.tiled) throw std::runtime_error{"vkrh_capture: the final-frame capture on a tiled frame (transfers take whole images)"};
+      if (mip != 0) throw std::runtime_error{"vkrh_capture: the final-frame capture blits mip 0"};
+      const rendergraph::ImageResourceId dst = f->ensure_readback_image();
+      if (source == dst) throw std::runtime_error{"vkrh_capture: 'readback' is the destination of the final-frame capture"};
+      blit_image(f->graph, source, dst);
+      source = dst;
+    }
+    const ReadBackID id = f->readback.read_image(f->graph, source, 0, mip, 0);
     // the request matures frames_count + 1 submits later, like the reference's fenced frames
     for (uint32_t i = 0; i <= f->graph.get_frames_count() + 1 && !f->readback.is_data_available(id); i++) {
       f->graph.submit();
@@ -1204,7 +1301,7 @@ int vkrh_capture(void* frame, const char* name, uint32_t mip, uint32_t kind, con
     } else if (kind == 1) {
       if (data.texel_size != 4) throw std::runtime_error{"depth PNG capture needs 4-byte texels"};
       ok = write_depth_png(data, path);
-    } else if (kind == 2) {
+    } else if (kind == 2 || kind == 3) {
       if (data.texel_size != 4) throw std::runtime_error{"RGBA PNG capture needs 4-byte texels"};
       ok = write_rgba_png(data, path);
     } else {
@@ -1319,6 +1416,39 @@ int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
     struct Big { char b[6000]; };
     pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>();
   });
+  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
+  return 0;
+}
+
+int vkrh_create_image(void* frame, const char* name, uint32_t format, uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t array_layers) {
+  return guarded([&] { frame_ref(frame).create_user_image(name, format, width, height, mip_levels, array_layers); });
+}
+int vkrh_transfer(void* frame, uint32_t op, const char* image, const char* dst, const float* value) {
+  return guarded([&] { frame_ref(frame).transfer(op, image, dst, value); });
+}
+int vkrh_selftest_transfers(char* buf, uint32_t buf_size) {
+  std::string out;
+  const int rc = guarded([&] {
+    rendergraph::RenderGraph g;
+    const auto u = VK_IMAGE_USAGE_TRANSFER_SRC_BIT | VK_IMAGE_USAGE_TRANSFER_DST_BIT;
+    auto tex = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, 40, 24, 1, 6, 1}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto depth = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 16, 16, 1, 3, 2}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto color = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 16, 8, 1, 2, 1}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto src = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16B16A16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 32, 16}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto dst = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, 32, 16}, VK_IMAGE_TILING_OPTIMAL, u);
+    gen_mipmaps(g, tex);
+    clear_depth(g, depth);
+    VkClearColorValue red{};
+    red.float32[0] = 1.f;
+    clear_color(g, color, red);
+    blit_image(g, src, dst);
+    for (const auto& t : g.pending_tasks()) {
+      out += t.name + ":";
+      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+      out += "\n";
+    }
+  });
+  if (rc != 0) return rc;
   if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
   return 0;
 }

@@ -64,6 +64,9 @@ enum {
    * binding 5 instead of its 16x16 dummy (the shader never reads it: color_out does not change).  One GPU only (not on a tiled
    * frame), and only after vkrh_load_scene.                                                                              */
   VKRH_STAGE_SHADOW             = 1u << 23,
+  /* main.cpp:306: clear_depth(graph, gbuffer.prev_depth) — every mip of prev_depth to depth 1, stencil 0 (the word 0x00FFFFFF) —
+   * recorded before every other stage of the run.  One GPU only (not on a tiled frame: transfers take whole images).           */
+  VKRH_STAGE_CLEAR_PREV_DEPTH   = 1u << 24,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -89,11 +92,17 @@ typedef struct vkrh_scene_draw {
   uint32_t albedo_tex_index, metalic_roughness_index, clip_alpha;
 } vkrh_scene_draw;
 typedef struct vkrh_scene_texture {
-  uint32_t width, height, mip_levels, reserved;
+  uint32_t width, height, mip_levels, flags;  /* flags: VKRH_TEXTURE_* (0: every level comes from the host, as before) */
   const uint8_t* levels[16];
 } vkrh_scene_texture;
+/* images.cpp:93-160: the mip chain is built on the device.  Only levels[0] is read (mip_levels is ignored); the texture gets
+ * floor(log2(max(w, h))) + 1 levels, level 0 is uploaded and vkr_gen_mipmaps builds the others — byte for byte what
+ * vk-renderer_amd/scene.py build_mips makes on the host.  Not on a tiled frame.                                            */
+#define VKRH_TEXTURE_GEN_MIPS 1u
 int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
                     const vkrh_scene_draw* draws, uint32_t draw_count, const vkrh_scene_texture* textures, uint32_t texture_count);
+/* descriptor (every level) of texture `index` of the loaded scene.  Not on a tiled frame. */
+int vkrh_scene_texture_image(void* frame, uint32_t index, vkr_img* out);
 /* Bakes a grid_size x grid_size grid of octahedral probes (probe_size^2, from cube_size^2 cube faces) from the scene of
  * vkrh_load_scene through ProbeRenderer::render_probe_grid: probes in x and z between min and max, at min.y; array layer
  * y * grid_size + x.  The grid stays in the frame until the next bake: images "probe_color", "probe_depth" (vkrh_image_layer, all
@@ -133,7 +142,11 @@ int vkrh_read_buffer(void* frame, const char* name, void* dst, uint64_t capacity
 /* one layer (all its mips) of a named array image ("deinterleaved_depth", "probe_color", "probe_depth", "cubemap_color", "shadows", ...) */
 int vkrh_image_layer(void* frame, const char* name, uint32_t layer, vkr_img* out);
 /* Reads `name` (mip) back through ReadBackSystem and writes it with the reference's capture writers
- * (main.cpp:118-176): kind 0 = depth CSV (24-bit hex), 1 = depth PNG, 2 = RGBA8 PNG (alpha 255). */
+ * (main.cpp:118-176): kind 0 = depth CSV (24-bit hex), 1 = depth PNG, 2 = RGBA8 PNG (alpha 255).
+ * kind 3 = the final frame (main.cpp:392-396): blit_image(`name`, normally "taa_target" -> "readback") converts the image to
+ * RGBA8_SRGB on the device, then "readback" goes through the read-back and the RGBA PNG writer of kind 2.  "readback" is
+ * RGBA8_SRGB of the frame's extent, created on first use and visible through vkrh_image afterwards; mip must be 0.  Not on a
+ * tiled frame. */
 int vkrh_capture(void* frame, const char* name, uint32_t mip, uint32_t kind, const char* path);
 /* CPU-only check of the capture writers: writes <dir>/depth.csv, depth.png, color.png from a
  * width x height pattern depth = (x * 65537 + y * 257 + 0xAB000000) (top byte = stencil, must be
@@ -148,6 +161,19 @@ const char* vkrh_collect_task_times(void* frame);
 /* Exercises the rendergraph / pass error paths the reference signals with exceptions (no kernel is
  * launched; images come from the installed allocator).  Writes "case: message" lines into buf. */
 int vkrh_selftest_errors(char* buf, uint32_t buf_size);
+/* The transfer helpers of util_passes.hpp on images of the frame's graph, for launchers written against the rendergraph API.
+ * vkrh_create_image adds an image of the caller's own (format: a vkr_format; never a window of the frame) that vkrh_image /
+ * vkrh_image_layer then find under `name`; a name of the frame's own images or one already taken is refused.  vkrh_transfer records
+ * one helper and submits it on the frame's stream: GEN_MIPMAPS gen_mipmaps(image), CLEAR_DEPTH clear_depth(image, value[0]) (value
+ * NULL: 1.0), CLEAR_COLOR clear_color(image, value[0..3]), BLIT blit_image(image, dst).  Not on a tiled frame.                   */
+enum { VKRH_TRANSFER_GEN_MIPMAPS = 0, VKRH_TRANSFER_CLEAR_DEPTH = 1, VKRH_TRANSFER_CLEAR_COLOR = 2, VKRH_TRANSFER_BLIT = 3 };
+int vkrh_create_image(void* frame, const char* name, uint32_t format, uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t array_layers);
+int vkrh_transfer(void* frame, uint32_t op, const char* image, const char* dst, const float* value);
+/* The transfer helpers of util_passes.hpp, recorded and NOT submitted (no kernel is launched; images come from the installed
+ * allocator): gen_mipmaps on a 40 x 24 image of 6 levels, clear_depth on a D24S8 image of 3 levels and 2 layers, clear_color on an
+ * RGBA8 image of 2 levels, blit_image between two images.  Writes one line per recorded task into buf:
+ * "name: R<image>.<mip> ... W<image>.<mip> ..." — the declared transfer reads and writes, images numbered in creation order. */
+int vkrh_selftest_transfers(char* buf, uint32_t buf_size);
 /* names of the tasks executed by the last vkrh_run, '\n'-separated */
 const char* vkrh_last_tasks(void* frame);
 /* the stream lane (0 = the frame's stream) each of those tasks was recorded on, space separated */

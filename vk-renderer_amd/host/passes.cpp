@@ -8,11 +8,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 
 #include "pass_recorder.hpp"
 #include "probe_renderer.hpp"
 #include "scene/scene_as.hpp"
+#include "util_passes.hpp"
 
 using rendergraph::ImageResourceId;
 using rendergraph::RenderGraph;
@@ -836,11 +838,69 @@ void SyntheticGbuffer::draw_depth(RenderGraph &graph, ImageResourceId depth_targ
     rec::no_push(), desc.width, desc.height);
 }
 
+// ==== util_passes.hpp (reference: src/util_passes.cpp:42-179) — transfers through vkr_gen_mipmaps / vkr_clear_image / vkr_blit_image
+namespace {
+void transfer_status(int rc, const char *what) {
+  if (rc != 0) throw std::runtime_error {std::string {what} + ": " + vkr_last_error()};
+}
+struct MipRange { ImageResourceId image; uint32_t base_mip, mips, layers; };
+// one transfer task: the declarations the reference makes for it, and the C-ABI call on the command context's stream
+void add_transfer_task(RenderGraph &graph, const char *name, const std::vector<MipRange> &reads, const std::vector<MipRange> &writes,
+                       std::function<void(rendergraph::RenderResources &, void *stream)> run) {
+  struct Data {};
+  graph.add_task<Data>(name,
+    [&](Data &, rendergraph::RenderGraphBuilder &builder) {
+      for (const auto &r : reads) builder.transfer_read(r.image, r.base_mip, r.mips, 0, r.layers);
+      for (const auto &w : writes) builder.transfer_write(w.image, w.base_mip, w.mips, 0, w.layers);
+    },
+    [=](Data &, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) { run(resources, cmd.get_stream()); });
+}
+// every mip of every layer: a layer's descriptor covers the texels of that layer only
+void add_clear_task(RenderGraph &graph, const char *name, ImageResourceId image, const vkr_clear_value &value) {
+  const auto info = graph.get_descriptor(image);
+  add_transfer_task(graph, name, {}, {{image, 0, info.mip_levels, info.array_layers}}, [=](rendergraph::RenderResources &resources, void *stream) {
+    const gpu::Image &img = *resources.get_image(image);
+    for (uint32_t layer = 0; layer < img.get_array_layers(); layer++) {
+      const vkr_img d = img.describe_layer(layer, 0, img.get_mip_levels());
+      transfer_status(vkr_clear_image(&d, &value, stream), name);
+    }
+  });
+}
+}  // namespace
+
+void gen_mipmaps(RenderGraph &graph, ImageResourceId image) {
+  const uint32_t levels = graph.get_descriptor(image).mip_levels;
+  for (uint32_t dst_mip = 1; dst_mip < levels; dst_mip++)  // the reference's task list: one blit per level
+    add_transfer_task(graph, "Genmips", {{image, dst_mip - 1, 1, 1}}, {{image, dst_mip, 1, 1}}, [=](rendergraph::RenderResources &resources, void *stream) {
+      const vkr_img d = resources.get_image(image)->describe(dst_mip - 1, 2);  // the chain of one level
+      transfer_status(vkr_gen_mipmaps(&d, stream), "Genmips");
+    });
+}
+
+void clear_depth(RenderGraph &graph, ImageResourceId image, float val) {
+  vkr_clear_value value {};
+  value.depth = val;  // stencil 0, as a VkClearDepthStencilValue with only .depth set
+  add_clear_task(graph, "Clear_depth", image, value);
+}
+
+void clear_color(RenderGraph &graph, ImageResourceId image, VkClearColorValue val) {
+  vkr_clear_value value {};
+  std::memcpy(value.color, val.float32, sizeof(value.color));  // every format of this path is UNORM / SRGB / SFLOAT: the float member
+  add_clear_task(graph, "Clear_color", image, value);
+}
+
+void blit_image(RenderGraph &graph, ImageResourceId src, ImageResourceId dst) {
+  add_transfer_task(graph, "CopyImage", {{src, 0, 1, 1}}, {{dst, 0, 1, 1}}, [=](rendergraph::RenderResources &resources, void *stream) {
+    const vkr_img s = resources.get_image(src)->describe(0, 1), d = resources.get_image(dst)->describe(0, 1);
+    transfer_status(vkr_blit_image(&s, &d, VKR_FILTER_LINEAR, stream), "CopyImage");  // the reference blits with VK_FILTER_LINEAR
+  });
+}
+
 // ==== scene (scene/scene.cpp, scene/images.cpp) and SceneRenderer (scene_renderer.cpp:46-220) ===========================
 namespace scene {
 
 CompiledScene make_scene(const Vertex *vertices, uint32_t vertex_count, const uint32_t *indices, uint32_t index_count,
-                         const FlatDraw *draws, uint32_t draw_count, const TextureData *textures, uint32_t texture_count)
+                         const FlatDraw *draws, uint32_t draw_count, const TextureData *textures, uint32_t texture_count, void *stream)
 {
   CompiledScene out;
   auto upload = [](const void *src, uint64_t bytes) {  // scene.cpp:285-296: one vertex and one index buffer for the whole file
@@ -855,12 +915,20 @@ CompiledScene make_scene(const Vertex *vertices, uint32_t vertex_count, const ui
   out.samplers.push_back(gpu::create_sampler(repeat));
   for (uint32_t i = 0; i < texture_count; i++) {  // images.cpp:32-49: RGBA8_SRGB with a full mip chain
     const TextureData &t = textures[i];
-    auto img = std::make_shared<gpu::Image>(gpu::ImageInfo {VK_FORMAT_R8G8B8A8_SRGB, COLOR, t.width, t.height, 1, t.mip_levels, 1}, gpu::FrameWindow {});
+    // images.cpp:93-160 builds the chain on the GPU; so does gen_mips (level 0 uploaded, the rest by vkr_gen_mipmaps)
+    const uint32_t levels = t.gen_mips ? uint32_t(std::floor(std::log2(float(std::max(t.width, t.height))))) + 1u : t.mip_levels;
+    auto img = std::make_shared<gpu::Image>(gpu::ImageInfo {VK_FORMAT_R8G8B8A8_SRGB, COLOR, t.width, t.height, 1, levels, 1}, gpu::FrameWindow {});
     bool never_zero = true;
-    for (uint32_t m = 0; m < t.mip_levels; m++) {
+    // gen_mips: only level 0 is in host memory.  It decides for every level: the alpha of a mip texel is rint(255 * average) of
+    // four alphas of the level below, and an average of codes >= 1 rounds to a code >= 1
+    for (uint32_t m = 0; m < (t.gen_mips ? 1u : levels); m++) {
       img->upload_mip(m, t.levels[m]);
       const size_t texels = size_t(std::max(1u, t.width >> m)) * std::max(1u, t.height >> m);
       for (size_t k = 0; k < texels && never_zero; k++) never_zero = t.levels[m][4 * k + 3] != 0;
+    }
+    if (t.gen_mips && levels > 1) {  // upload_mip is synchronous: level 0 is in place
+      const vkr_img d = img->describe(0, levels);
+      transfer_status(vkr_gen_mipmaps(&d, stream), "make_scene: texture mips");
     }
     img->alpha_never_zero = never_zero;
     out.images.push_back(img);

@@ -10,6 +10,7 @@
 //   DeferedShadingPass                                            (src/defered_shading.hpp)
 //   ReadBackData, ReadBackSystem + capture writers                (src/image_readback.hpp, main.cpp:118-176)
 //   SyntheticGbuffer                                              (no counterpart: analytic G-buffer)
+// (the transfer helpers gen_mipmaps / clear_depth / clear_color / blit_image have their own header, util_passes.hpp)
 // The per-name headers (gtao.hpp, taa.hpp, ...) forward here.  Implementations: passes.cpp, written on
 // pass_recorder.hpp; everything executes through the C-ABI of include/vkr_postfx.h.
 #ifndef VKR_HOST_PASSES_HPP_INCLUDED
@@ -88,10 +89,12 @@ struct CompiledScene {
   std::vector<BaseNode> base_nodes;
 };
 
-// one mip chain of RGBA8 texels, level 0 first, rows tightly packed
+// one mip chain of RGBA8 texels, level 0 first, rows tightly packed.  gen_mips: only levels[0] is read, the image gets
+// floor(log2(max(w, h))) + 1 levels and the others are built on the device (vkr_gen_mipmaps), as images.cpp:93-160 does
 struct TextureData {
   uint32_t width, height, mip_levels;
   const uint8_t *levels[VKR_MAX_MIPS];
+  bool gen_mips = false;
 };
 
 // Flat description of a scene: node i draws mesh i (one primitive) with material i.
@@ -103,7 +106,8 @@ struct FlatDraw {
 };
 
 CompiledScene make_scene(const Vertex *vertices, uint32_t vertex_count, const uint32_t *indices, uint32_t index_count,
-                         const FlatDraw *draws, uint32_t draw_count, const TextureData *textures, uint32_t texture_count);
+                         const FlatDraw *draws, uint32_t draw_count, const TextureData *textures, uint32_t texture_count,
+                         void *stream = nullptr /* of the device-built mips */);
 
 // scene/scene.cpp:46-60: one binding of stride sizeof(Vertex), attribute 0 = pos.  The vertex layout of this path is fixed
 // (vkr_raster_vertex), so the description is empty; the shadow program reads only pos

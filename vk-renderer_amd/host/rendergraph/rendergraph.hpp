@@ -221,6 +221,13 @@ struct RenderGraph {  // rendergraph.hpp:112-158
   gpu::ImagePtr& get_image(ImageResourceId id) { return resources.get_image(id); }
   gpu::BufferPtr& get_buffer(BufferResourceId id) { return resources.get_buffer(id); }
   const std::vector<std::string>& last_submitted_tasks() const { return submitted_names; }
+  // the tasks recorded since the last submit(), in order: name and what create_cb declared (tests / diagnostics)
+  struct PendingTask { std::string name; std::vector<GraphResources::Access> accesses; };
+  std::vector<PendingTask> pending_tasks() const {
+    std::vector<PendingTask> out;
+    for (const auto& t : tasks) out.push_back(PendingTask{t->name, t->accesses});
+    return out;
+  }
   // Per-task device timing: HIP events recorded around every task on the graph's stream (the
   // counterpart of the reference's per-task debug labels, rendergraph.cpp:289-304).  Events are
   // only recorded, never waited on, inside submit(); collect_task_times() synchronises.

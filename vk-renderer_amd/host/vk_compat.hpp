@@ -50,6 +50,7 @@ struct VkSamplerCreateInfo {
 };
 enum VkIndexType { VK_INDEX_TYPE_UINT16 = 0, VK_INDEX_TYPE_UINT32 = 1 };
 struct VkDispatchIndirectCommand { uint32_t x, y, z; };
+union VkClearColorValue { float float32[4]; int32_t int32[4]; uint32_t uint32[4]; };  // util_passes.hpp clear_color
 typedef struct VkBuffer_T* VkBuffer;
 typedef struct VkSampler_T* VkSampler;
 typedef struct VkImageView_T* VkImageView;

@@ -99,8 +99,11 @@ class Scene:
         self.draws.append(dict(transform=transform, albedo=albedo, mr=mr, flags=flags, index_offset=i0, index_count=n, vertex_offset=v0))
 
     # ---- C-ABI view -------------------------------------------------------------------------------------
-    def upload(self, device=None):
-        """-> (abi.RasterScene, keep-alive list).  device None: host memory, else torch device."""
+    def upload(self, device=None, device_mips=False):
+        """-> (abi.RasterScene, keep-alive list).  device None: host memory, else torch device.  device_mips (needs a device): only
+        level 0 of every texture is uploaded, abi.gen_mipmaps builds the others there (the same bytes as build_mips)."""
+        if device_mips and device is None:
+            raise ValueError("device_mips needs a device")
         keep = []
 
         def dev(arr):
@@ -123,13 +126,26 @@ class Scene:
         dr = (abi.RasterDraw * max(1, len(self.draws)))()
         # VKR_RASTER_DRAW_OPAQUE_ALBEDO: no texel of any level of the albedo texture has alpha 0, so the discard of
         # opaque_taa.frag:32-34 cannot fire and the stage may skip the coverage-time alpha test
-        opaque = [all(int(lv[..., 3].min()) > 0 for lv in levels) for levels in self.textures]
+        # (an average of alpha codes >= 1 rounds to a code >= 1, so with device_mips level 0 decides for the whole chain)
+        opaque = [all(int(lv[..., 3].min()) > 0 for lv in (levels[:1] if device_mips else levels)) for levels in self.textures]
         for i, d in enumerate(self.draws):
             hint = 1 if (d["albedo"] != INVALID and opaque[d["albedo"]] and not d.get("force_alpha_test")) else 0
             dr[i] = abi.RasterDraw(d["transform"], d["albedo"], d["mr"], d["flags"], d["index_offset"], d["index_count"], d["vertex_offset"], hint)
         tx = (abi.VkrImg * max(1, len(self.textures)))()
         for i, levels in enumerate(self.textures):
             h, w = levels[0].shape[:2]
+            if device_mips:
+                import torch
+
+                count = int(math.floor(math.log2(max(w, h)))) + 1
+                host_img = ImageBuf(abi.FMT_RGBA8_SRGB, w, h, count)
+                host_img.set_raw(levels[0], 0)
+                img = ImageBuf(abi.FMT_RGBA8_SRGB, w, h, count, device=device)
+                img.upload(host_img.to_host())
+                abi.gen_mipmaps(img.desc(), torch.cuda.current_stream(device).cuda_stream)
+                keep.append(img)
+                tx[i] = img.desc()
+                continue
             img = ImageBuf(abi.FMT_RGBA8_SRGB, w, h, len(levels))
             for m, lv in enumerate(levels):
                 img.set_raw(lv, m)
