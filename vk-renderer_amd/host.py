@@ -134,7 +134,10 @@ def lib():
                            # image transfers (same rule)
                            ("vkrh_scene_texture_image", [C.c_void_p, C.c_uint32, C.POINTER(abi.VkrImg)]),
                            ("vkrh_create_image", [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
-                           ("vkrh_transfer", [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_float)])):
+                           ("vkrh_transfer", [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_float)]),
+                           # deferred shading in the tiled frame (same rule)
+                           ("vkrh_tiled_set_shading", [C.c_void_p, C.c_uint32]),
+                           ("vkrh_tiled_shading", [C.c_void_p])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -517,6 +520,17 @@ class HostFrame:
 
     def tiled_local_first(self):
         return bool(lib().vkrh_tiled_local_first(self.tiled_handle))
+
+    def tiled_set_shading(self, on=True):
+        """frame.hpp vkrh_tiled_set_shading: deferred shading at the end of the tiled frame, the TAA resolving color_out.  Needs
+        STAGE_BRDF_LUT to have run; refused while a halo refresh is in flight (call before the first frame or after tiled_flush)"""
+        self._check(lib().vkrh_tiled_set_shading(self.tiled_handle, 1 if on else 0))
+
+    def tiled_shading(self):
+        on = lib().vkrh_tiled_shading(self.tiled_handle)
+        if on < 0:
+            self._check(1)
+        return bool(on)
 
     def tiled_emulate_wire(self, comm_handle, counts):
         """frame.hpp vkrh_tiled_emulate_wire: the harness-driven frame goes on natively on an emulated communicator"""

@@ -123,6 +123,7 @@ struct PostFxFrame {
   DrawTAAParams draw_params{};
   glm::mat4 projection, view, prev_view;
   bool has_camera = false;
+  bool brdf_lut_ran = false;  // VKRH_STAGE_BRDF_LUT has filled the LUT the shading pass samples (vkrh_tiled_set_shading asks)
   std::string task_names, task_lanes;
 
   explicit PostFxFrame(const vkrh_config& c)
@@ -224,7 +225,7 @@ struct PostFxFrame {
     }
     if (mask & VKRH_STAGE_CLEAR_PREV_DEPTH) clear_depth(graph, gbuffer.prev_depth);  // main.cpp:306
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
-    if (mask & VKRH_STAGE_BRDF_LUT) ssr.preintegrate_brdf(graph);
+    if (mask & VKRH_STAGE_BRDF_LUT) { ssr.preintegrate_brdf(graph); brdf_lut_ran = true; }
     if (mask & VKRH_STAGE_PREV_DEPTH) {
       // what the previous frame left behind: its depth in `prev_depth`, including the Hi-Z mips
       synth.draw_depth(graph, gbuffer.prev_depth, prev_view, draw_params.prev_mvp, fazz);
@@ -526,15 +527,19 @@ struct TiledFrame {
   // image the trace shares with GTAO main — two rows more: the resolve reads its four neighbours (filter.comp:112-134), GTAO's
   // filter taps reach two rows (filter.comp:17-51); the request / reply round and the deferred normal test walk the same rows
   // (rays_img() etc. describe the store rows).  The downsample stays whole-window: everything above reads its halo.
-  void clip_outputs() {
-    auto& g = frame->graph;
+  // With shading on, color_out: the strip and one row either side — the TAA reads its four neighbours (resolve.comp) — clamped
+  // to the frame (the window ends there).
+  bool clipped = false;
+  void store_rows(rendergraph::ImageResourceId id, uint32_t shift, uint32_t apron) {
+    gpu::Image& img = *frame->graph.get_image(id);
     const uint32_t top = y0 - wy0;  // rows of halo above the strip inside the window
-    const auto rows = [&](rendergraph::ImageResourceId id, uint32_t shift, uint32_t apron) {
-      gpu::Image& img = *g.get_image(id);
-      const uint32_t first = top >> shift, last = (top + th) >> shift, h = img.get_info().height;
-      const uint32_t lo = first > apron ? first - apron : 0, hi = std::min(h, last + apron);
-      img.set_store_rows(lo, hi - lo);
-    };
+    const uint32_t first = top >> shift, last = (top + th) >> shift, h = img.get_info().height;
+    const uint32_t lo = first > apron ? first - apron : 0, hi = std::min(h, last + apron);
+    img.set_store_rows(lo, hi - lo);
+  }
+  void clip_outputs() {
+    clipped = true;
+    const auto rows = [&](rendergraph::ImageResourceId id, uint32_t shift, uint32_t apron) { store_rows(id, shift, apron); };
     rows(frame->taa_pass.get_output(), 0, 0); rows(frame->taa_pass.get_history(), 0, 0);
     rows(frame->gtao.accumulated_ao, 1, 0); rows(frame->gtao.accumulated_history, 1, 0); rows(frame->gtao.filtered, 1, 0);
     rows(frame->ssr.get_blurred(), 1, 0); rows(frame->ssr.get_blurred_history(), 1, 0);
@@ -972,9 +977,9 @@ struct TiledFrame {
   void phase(uint32_t p) {
     if (!tiled) throw std::runtime_error {"vkrh_tiled_phase: this frame is not tiled (one rank without force_tiled has no phases: use vkrh_tiled_step)"};
     PostFxFrame& f = *frame;
-    static const char* const names[VKRH_TILED_PHASES] = {"tiled: downsample | start gathers", "tiled: TAA | halo", "tiled: Hi-Z tail + trace",
-                                                        "tiled: GTAO | halo | hit colours", "tiled: SSR filter + blur | halo"};
-    gpu::TraceRange range {p < VKRH_TILED_PHASES ? names[p] : "tiled: ?"};
+    static const char* const names[VKRH_TILED_PHASES_SHADED] = {"tiled: downsample | start gathers", "tiled: TAA | halo", "tiled: Hi-Z tail + trace",
+                                                               "tiled: GTAO | halo | hit colours", "tiled: SSR filter + blur | halo", "tiled: halos | shading + TAA | halo"};
+    gpu::TraceRange range {p < VKRH_TILED_PHASES_SHADED ? names[p] : "tiled: ?"};
     switch (p) {
       case 0:
         f.run(VKRH_STAGE_DOWNSAMPLE);
@@ -990,7 +995,7 @@ struct TiledFrame {
           f.run(VKRH_STAGE_SSR_TRACE_HEAD);
           break;
         }
-        taa_and_halo();
+        if (!shading) taa_and_halo();  // shaded: the TAA resolves color_out, at the end of the frame (phase 5)
         break;
       case 2:
         wait(VKRH_GATHER_HIZ);
@@ -1007,7 +1012,7 @@ struct TiledFrame {
         if (by_request() && cfg.comm && !hit.speculative) hit_exchange_complete();
         copy_halo(VKRH_HALO_AO, true);
         start_halo(VKRH_HALO_AO);
-        if (local_first()) taa_and_halo();
+        if (local_first() && !shading) taa_and_halo();
         break;
       case 4:
         if (by_request() && !cfg.comm && hit.counted) throw std::runtime_error {"vkrh_tiled_phase: the harness must complete the hit-colour exchange before phase 4"};
@@ -1017,9 +1022,13 @@ struct TiledFrame {
         f.run(VKRH_STAGE_SSR_RESOLVE);
         copy_halo(VKRH_HALO_SSR, true);
         start_halo(VKRH_HALO_SSR);
-        f.end_frame(false);
+        if (!shading) f.end_frame(false);
         break;
-      default: throw std::runtime_error {"vkrh_tiled_phase: phases are 0..4"};
+      case 5:
+        if (!shading) throw std::runtime_error {"vkrh_tiled_phase: phases are 0..4"};
+        shaded_tail();
+        break;
+      default: throw std::runtime_error {shading ? "vkrh_tiled_phase: phases are 0..5" : "vkrh_tiled_phase: phases are 0..4"};
     }
   }
   void taa_and_halo() {
@@ -1053,30 +1062,32 @@ struct TiledFrame {
     if (!hit.speculative) hit_exchange_complete();  // first frame: the host round trip, with GTAO queued
     copy_halo(VKRH_HALO_AO, true);
     start_halo(VKRH_HALO_AO);
-    taa_and_halo();
+    if (!shading) taa_and_halo();
     hit_exchange_complete();
     wait(VKRH_GATHER_ALBEDO);
     finish_halo(VKRH_HALO_SSR);
     f.run(VKRH_STAGE_SSR_RESOLVE);
     copy_halo(VKRH_HALO_SSR, true);
     start_halo(VKRH_HALO_SSR);
-    f.end_frame(false);
+    if (shading) shaded_tail();
+    else f.end_frame(false);
     f.gbuffer.swap_sets(f.graph);               // what was downsampled for frame f + 1 becomes the current set
     hit_local_rows(compute);                    // its own rows of the whole-frame albedo / normals (after this frame's resolve has read them)
   }
   void step() {
-    if (!tiled) { frame->run(VKRH_STAGE_CHAIN); frame->end_frame(false); return; }
+    if (!tiled) { frame->run(VKRH_STAGE_CHAIN | (shading ? VKRH_STAGE_SHADING : 0u)); frame->end_frame(false); return; }
     if (!cfg.comm && cfg.world > 1) throw std::runtime_error {"vkrh_tiled_step: no communicator (drive vkrh_tiled_phase from a harness instead)"};
     if (pipeline_enabled && cfg.comm) { pipelined_step(); return; }
+    const uint32_t phases = shading ? VKRH_TILED_PHASES_SHADED : VKRH_TILED_PHASES;
     if (!cfg.comm) {  // one rank, no wire: the gathers degenerate to copies of the tile into the frame images
-      for (uint32_t p = 0; p < VKRH_TILED_PHASES; p++) {
+      for (uint32_t p = 0; p < phases; p++) {
         if (p == 2) local_gather(VKRH_GATHER_HIZ);
         if (p == 4) local_gather(VKRH_GATHER_ALBEDO);
         phase(p);
       }
       return;
     }
-    for (uint32_t p = 0; p < VKRH_TILED_PHASES; p++) phase(p);
+    for (uint32_t p = 0; p < phases; p++) phase(p);
   }
   void local_gather(int which) {
     vkr_gather_part p[8];
@@ -1085,6 +1096,35 @@ struct TiledFrame {
       check(hipMemcpyAsync((uint8_t*)p[i].recv + gather_offsets[which][i][cfg.rank], p[i].send, p[i].bytes, hipMemcpyDeviceToDevice, compute), "local gather");
   }
   void flush() { for (int s = 0; s < 3; s++) finish_halo(s); }
+
+  // ---- deferred shading (frame.hpp) --------------------------------------------------------------------------------------
+  bool shading = false;
+  void set_shading(bool on) {
+    // a refresh packed under one order would be unpacked under the other: the TAA rows at the wrong end of the frame
+    for (int s = 0; s < 3; s++)
+      if (halo_in_flight[s]) throw std::runtime_error {"vkrh_tiled_set_shading: a halo refresh is in flight (before the first frame, or right after vkrh_tiled_flush)"};
+    if (on && cfg.world > 1 && cfg.halo < VKRH_TILED_SHADING_MIN_HALO)
+      throw std::runtime_error {"vkrh_tiled_set_shading: halo " + std::to_string(cfg.halo) + ", the shading of a strip's last rows reads 2 half-res rows of its neighbour (halo >= " +
+                                std::to_string(VKRH_TILED_SHADING_MIN_HALO) + ")"};
+    if (on && !frame->brdf_lut_ran) throw std::runtime_error {"vkrh_tiled_set_shading: VKRH_STAGE_BRDF_LUT has not run on this frame (the shading pass samples the LUT)"};
+    shading = on;
+    if (clipped) {
+      if (on) store_rows(frame->color_out_tex, 0, 1);
+      else frame->graph.get_image(frame->color_out_tex)->set_store_rows(0, 0);
+    }
+  }
+  // The end of the shaded frame.  The AO and SSR refreshes started in THIS frame: awaited and unpacked here, into the images they
+  // were packed from (copy_halo), their rows are the neighbours' current interiors — what the one-GPU shading reads there.  The
+  // TAA refresh is last frame's.  One run() for both stages, so that the TAA resolves color_out.
+  void shaded_tail() {
+    finish_halo(VKRH_HALO_AO);
+    finish_halo(VKRH_HALO_SSR);
+    finish_halo(VKRH_HALO_TAA);
+    frame->run(VKRH_STAGE_SHADING | VKRH_STAGE_TAA);
+    copy_halo(VKRH_HALO_TAA, true);
+    start_halo(VKRH_HALO_TAA);
+    frame->end_frame(false);
+  }
 };
 
 template <typename F> int guarded(F&& f) {
@@ -1585,6 +1625,12 @@ int vkrh_tiled_emulate_wire(void* tiled, void* comm, const uint32_t* counts) {
 }
 int vkrh_tiled_pipelined(void* tiled) { return tiled && ((TiledFrame*)tiled)->pipeline_enabled ? 1 : 0; }
 int vkrh_tiled_local_first(void* tiled) { return tiled && ((TiledFrame*)tiled)->local_first() ? 1 : 0; }
+int vkrh_tiled_set_shading(void* tiled, uint32_t on) { return guarded([&] { tiled_ref(tiled, "vkrh_tiled_set_shading").set_shading(on != 0); }); }
+int vkrh_tiled_shading(void* tiled) {
+  int on = -1;
+  (void)guarded([&] { on = tiled_ref(tiled, "vkrh_tiled_shading").shading ? 1 : 0; });
+  return on;
+}
 int vkrh_tiled_time_waits(void* tiled, uint32_t on) {
   return guarded([&] {
     auto* t = &tiled_ref(tiled, "vkrh_tiled_time_waits");

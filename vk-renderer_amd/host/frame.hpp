@@ -222,12 +222,29 @@ typedef struct vkrh_tiled_config {
    * ranks whose rows differ in cost (vkrh_balance_rows); their shares travel with vkr_all_gather_v.                  */
   const uint32_t* row_bounds;
 } vkrh_tiled_config;
-enum { VKRH_TILED_PHASES = 5, VKRH_GATHER_HIZ = 0, VKRH_GATHER_ALBEDO = 1, VKRH_HALO_TAA = 0, VKRH_HALO_AO = 1, VKRH_HALO_SSR = 2 };
+enum { VKRH_TILED_PHASES = 5, VKRH_TILED_PHASES_SHADED = 6, VKRH_TILED_SHADING_MIN_HALO = 4, VKRH_GATHER_HIZ = 0, VKRH_GATHER_ALBEDO = 1, VKRH_HALO_TAA = 0, VKRH_HALO_AO = 1, VKRH_HALO_SSR = 2 };
 void* vkrh_tiled_create(const vkrh_tiled_config* cfg);
 void  vkrh_tiled_destroy(void* tiled);
 void* vkrh_tiled_frame(void* tiled);                 /* the frame inside: every vkrh_* call above works on it       */
 int   vkrh_tiled_step(void* tiled);                  /* one frame, exchanges included (comm != NULL or world == 1)  */
 int   vkrh_tiled_flush(void* tiled);                 /* completes the halo refreshes the last frame left in flight  */
+/* Deferred shading in the tiled frame (main.cpp:390-391: shading_pass.draw -> color_out_tex, which the TAA resolves).  Off by
+ * default, and off is the frame above.  On, the TAA leaves its early place and the frame gets a tail behind the SSR resolve:
+ *
+ *   ... SSR filter + blur | its halo refresh starts
+ *   the AO, SSR and TAA halo refreshes are awaited and unpacked — the AO and SSR rows in the SAME frame, into the images they were
+ *   packed from: the shading of a strip's first / last rows reads its neighbours' current accumulated AO and blurred reflections
+ *   shading + TAA (one vkrh_run: the TAA resolves color_out) | the TAA halo refresh starts; history remaps
+ *
+ * Reach: color_out is computed on the strip and one row either side (the TAA reads its four neighbours); for those rows the 3 x 3
+ * half-res footprint of sample_ocllusion_ssr (shader.frag:103-130) spans 1 half-res row above the strip's first and 2 below its
+ * last, so the halo must hold 2 half-res rows: halo >= VKRH_TILED_SHADING_MIN_HALO.  In the harness the tail is phase 5
+ * (VKRH_TILED_PHASES_SHADED phases; halo 1 moves after phase 3, halo 2 after phase 4, halo 0 after phase 5).  One untiled rank
+ * runs VKRH_STAGE_CHAIN | VKRH_STAGE_SHADING.  vkrh_tiled_set_shading is refused (vkrh_last_error): a NULL handle; while a halo
+ * refresh is in flight (allowed before the first frame and right after vkrh_tiled_flush); world > 1 with a halo below the
+ * reach; when VKRH_STAGE_BRDF_LUT has never run on the frame inside.  vkrh_tiled_shading: 1 / 0, or -1 for a NULL handle.   */
+int   vkrh_tiled_set_shading(void* tiled, uint32_t on);
+int   vkrh_tiled_shading(void* tiled);
 /* lockstep harness: phase p of the frame without the wire; what must cross ranks between phases is exposed below */
 int   vkrh_tiled_phase(void* tiled, uint32_t phase);
 int   vkrh_tiled_gather_parts(void* tiled, uint32_t which, vkr_gather_part* out, uint32_t capacity, uint32_t* count);

@@ -457,7 +457,8 @@ void register_hot_path_programs() {
       if (st.attachments.size() != 1) throw std::runtime_error{"defered_shading: expects one colour attachment"};
       vkr_img albedo = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P), depth = tex(st, 3, T, P);
       vkr_img occlusion = tex(st, 6, T, P), brdf = tex(st, 7, T, P), refl = tex(st, 8, T, P);
-      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      // (the rows the frame asked for: a tiled frame shades its strip and one row either side, Image::set_store_rows)
+      vkr_img out = st.attachments[0].image->describe_store(st.attachments[0].range.base_mip, 1);
       return vkr_defered_shading(&albedo, &normal, &material, &depth, ubo<vkr_shading_params>(st, 4, P), &occlusion, &brdf, &refl, &out,
                                  push<vkr_shading_push>(st, P), st.stream);
     });

@@ -37,6 +37,7 @@ from . import abi
 
 HALO = 48          # full-res pixels, a multiple of 16 (the gathered mips of a window must align with the frame's); the longest
                    # fixed reach is GTAO main + filter, 20 half-res = 40 full-res pixels.  Half-res surfaces carry HALO // 2
+SHADING_MIN_HALO = 4  # full-res pixels: the shading of a strip's last rows reads 2 half-res rows of the strip below (frame.hpp)
 GATHER_MIPS = 4    # at most: depth image-mips 1..4 are tile-aligned for tiles divisible by 16
 
 
@@ -123,7 +124,7 @@ class HostBackend:
 
 class TiledFrame:
     def __init__(self, setup, rank, world, cols, rows, device, backend="host", halo=HALO, force_tiled=False, native=False, comm=None,
-                 row_bounds=None, gather_mode=1):
+                 row_bounds=None, gather_mode=1, shading=False):
         """native (strips on the host backend only): the frame order, the pack / unpack launches and the exchanges run in
         C++ (host/frame.cpp TiledFrame: grouped RCCL launches on its own stream, ordered with events) — step() is one
         call.  comm: abi.Comm, or None to drive the C++ phases from a harness (tests) / to rehearse on one rank.
@@ -131,7 +132,10 @@ class TiledFrame:
         strips of different heights balance ranks whose rows differ in cost (host.balance_rows).
         gather_mode (this Python driver; the C++ frame has its own, host.HostFrame): 1 = albedo and downsampled normals
         all-gathered (the default here); 0 = hit colours and hit normals by request / reply, 2 = only the hit colours —
-        strips only, on a backend that exposes the hit_* steps (the oracle's: that is how the CPU tests run them)."""
+        strips only, on a backend that exposes the hit_* steps (the oracle's: that is how the CPU tests run them).
+        shading: deferred shading, the TAA resolving color_out (main.cpp:390-391).  On one GPU it is the stage plan
+        [STAGE_CHAIN | STAGE_SHADING]; on a tiled frame only the C++ frame has it (native=True: host/frame.cpp shaded_tail) —
+        this Python driver, which gloo runs, keeps the TAA ahead of the gather and refuses.  prepare() runs the BRDF LUT."""
         assert cols * rows == world
         self.setup, self.rank, self.world, self.cols, self.rows_n = setup, rank, world, cols, rows
         W, H = setup.width, setup.height
@@ -160,6 +164,9 @@ class TiledFrame:
             assert self.halo % 2 == 0 and self.halo <= min(self.tw, self.th)
         # force_tiled: run the multi-GPU code path (gathers, whole-frame Hi-Z, staged frame) on one rank
         self.tiled = world > 1 or force_tiled
+        self.shading = bool(shading)
+        if self.shading and (backend != "host" or (self.tiled and not native)):
+            raise ValueError("shading: only on the host backend, and on a tiled frame only with native=True (the C++ tiled frame)")
         # "host": the C++ host mirror on the GPU; anything else: a class with HostBackend's interface
         self.native = bool(native) and self.tiled
         if self.native:
@@ -185,10 +192,17 @@ class TiledFrame:
         self._halo_packed = {}   # surface -> plan whose send buffers are filled and whose receive is outstanding
         self._halo_works = {}
         self.stage_plan = None  # single-GPU only: list of stage masks run per step instead of STAGE_CHAIN
+        if self.shading and not self.tiled:
+            h = self.backend.host
+            self.stage_plan = [h.STAGE_CHAIN | h.STAGE_SHADING]
 
     # ---- set-up ---------------------------------------------------------------------------------
     def prepare(self):
         self.backend.prepare()
+        if self.shading:
+            self.frame.run(self.backend.host.STAGE_BRDF_LUT)
+            if self.native:
+                self.frame.tiled_set_shading(True)
         if self.frame is not None:  # GPU: seed the histories as SURVEY.md 8(d) says
             self._seed_histories_gpu()
         self.backend.sync()
@@ -633,27 +647,40 @@ def _hit_exchange(ranks, in_capacities=False):
     return matrix
 
 
-def native_lockstep_frame(ranks, hit_in_capacities=False):
+def native_lockstep_frame(ranks, hit_in_capacities=False, skip_halos=()):
     """One frame of every in-process rank of a strip grid (C++ tiled frames made with native=True, comm=None), advanced
-    phase by phase; between phases the harness copies exactly the buffers the RCCL calls would move."""
+    phase by phase; between phases the harness copies exactly the buffers the RCCL calls would move.
+    Shaded ranks (TiledFrame(shading=True)) have six phases: the TAA runs in the last, behind the shading, and the AO and SSR
+    refreshes (halo 1 after phase 3, halo 2 after phase 4) are unpacked in the same frame; halo 0 moves after phase 5.
+    skip_halos: halo surfaces (0 TAA, 1 AO, 2 SSR) the harness does NOT move in this frame — the ranks then unpack what their
+    receive buffers still hold (tests: a shaded frame whose neighbours' rows did not arrive must differ)."""
     by_gather = ranks[0].frame.albedo_by_gather or len(ranks) == 1
+    shaded = ranks[0].frame.tiled_shading()
+    assert all(t.frame.tiled_shading() == shaded for t in ranks), "every rank of a frame is shaded, or none"
     taa_after_gtao = ranks[0].frame.tiled_local_first()  # the C++ frame then resolves the TAA in phase 3 (frame.cpp: local rows first)
-    for p in range(5):
+
+    def move_halo(surface):
+        if surface not in skip_halos:
+            _move_halo(ranks, surface)
+
+    for p in range(6 if shaded else 5):
         for t in ranks:
             t.frame.tiled_phase(p)
         if p == 0:      # the gathers start after the downsample; the harness completes them at once
             _move_gather(ranks, 0)
             if by_gather:
                 _move_gather(ranks, 1)
-        elif p == 1 and not taa_after_gtao:
-            _move_halo(ranks, 0)
+        elif p == 1 and not taa_after_gtao and not shaded:
+            move_halo(0)
         elif p == 3:
-            if taa_after_gtao:
-                _move_halo(ranks, 0)
-            _move_halo(ranks, 1)
+            if taa_after_gtao and not shaded:
+                move_halo(0)
+            move_halo(1)
             if not by_gather:
                 ranks[0].hit_matrix = _hit_exchange(ranks, hit_in_capacities)
         elif p == 4:
-            _move_halo(ranks, 2)
+            move_halo(2)
+        elif p == 5:
+            move_halo(0)
     for t in ranks:
         t._frame_no += 1
