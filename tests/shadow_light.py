@@ -55,6 +55,18 @@ def expected(scene, m, n):
     return oracle_depth(strip(scene), m, n)
 
 
+def add_backdrop(scene, m, z=0.999, reach=1.5):
+    """Adds to `scene` an untextured quad (two triangles, identity model) that fills the target seen through m behind everything
+    else: the corners (+-reach, +-reach, z) of NDC unprojected.  The bounding box of each triangle is the whole target, so both
+    go to a rasteriser's large list whatever the extent.  Returns the scene."""
+    ndc = np.array([[-reach, -reach, z, 1.0], [reach, -reach, z, 1.0], [reach, reach, z, 1.0], [-reach, reach, z, 1.0]])
+    w = ndc @ np.linalg.inv(np.asarray(m, dtype=np.float64)).T
+    pos = (w[:, :3] / w[:, 3:4]).astype(np.float32)
+    mesh = scene.add_mesh(pos, np.array([[0, 0, 1]] * 4, np.float32), np.zeros((4, 2), np.float32), np.array([0, 1, 2, 0, 2, 3], np.uint32))
+    scene.add_draw(scene.add_transform(np.eye(4, dtype=np.float32)), mesh)
+    return scene
+
+
 def unproject(texels, depth, m):
     """world positions (float64 [k, 3]) of the centres of texels [k, 2] (x, y) of an n x n map with D24 words depth[n, n]"""
     n = depth.shape[0]

@@ -82,10 +82,16 @@ def _decode_color(codes):
 
 def _scenes():
     suz = scn.load_gltf(SUZANNE)
-    return {"procedural": scn.procedural_scene(detail=DETAIL, cutout=True), "suzanne": suz}
+    return {"procedural": scn.procedural_scene(detail=DETAIL, cutout=True), "suzanne": suz, "room": room.room_scene()}
 
 
 def _positions(name, sc):
+    if name == "room":
+        # The ceiling is nearer than any wall is far, so it fills face +Y: the bounding box of both its triangles is the whole face
+        # and they go to the large list.  At 72^2 that is 9 x 9 = 81 blocks of 8 x 8: 5 chunks of 16 and a last one of 1.
+        p = np.array((0.0, 1.0, 4.0))
+        assert room.ROOM_HI[1] - p[1] <= min(np.delete(p - room.ROOM_LO, 1).min(), np.delete(room.ROOM_HI - p, 1).min())
+        return [tuple(p)]
     if name == "procedural":  # the floor (y = 0) passes under every position: near-plane clipping on every side face
         return [(0.0, 1.0, 4.0), (-3.5, 0.6, 7.25), (2.5, 2.0, 1.0)]
     idx = np.concatenate([sc.indices[d["index_offset"]:d["index_offset"] + d["index_count"]].astype(np.int64) + d["vertex_offset"] for d in sc.draws])
@@ -99,7 +105,7 @@ def _positions(name, sc):
 
 
 @pytest.mark.parametrize("size", [128, 72])
-@pytest.mark.parametrize("name", ["procedural", "suzanne"])
+@pytest.mark.parametrize("name", ["procedural", "suzanne", "room"])
 def test_cubemap_probe_matches_restatement(name, size, parity_table):
     """Coverage bit-exact on all six faces; colour and distance within one storage step (or REL_TOL) of the restatement, at most
     1e-4 of the texels of a face outside."""

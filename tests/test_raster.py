@@ -194,15 +194,21 @@ def test_alpha_discard_known_answer_gpu(oracle_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("size", [(640, 360)])
+@pytest.mark.parametrize("size", [(640, 360), (200, 120)])
 def test_raster_parity_cutout(size, oracle_lib):
     """The procedural scene with a fence whose texture has alpha-0 holes, minified and magnified: coverage / depth must
     stay bit-exact against the oracle (a wrong discard shows as a depth mismatch), and a fair share of the fence must
-    actually have been discarded."""
+    actually have been discarded.  At 200 x 120 a quad that fills the frame stands behind the scene: the bounding box of each
+    of its triangles is 25 x 15 = 375 blocks of 8 x 8, 23 chunks of 16 and a last one of 7 for the large kernel."""
     W, H = size
     ref = PostFxChain(W, H, backend="oracle")
     gpu = PostFxChain(W, H, backend="product", device="cuda")
     solid, cut = scn.procedural_scene(), scn.procedural_scene(cutout=True)
+    if size == (200, 120):
+        import shadow_light as sl
+
+        assert ((W + 7) // 8) * ((H + 7) // 8) % 16 != 0
+        solid, cut = sl.add_backdrop(solid, ref.setup.mvp), sl.add_backdrop(cut, ref.setup.mvp)
     ref.raster(solid)
     d_solid = ref.depth.raw(0)[..., 0] & 0xFFFFFF
     for c in (ref, gpu):
@@ -210,6 +216,7 @@ def test_raster_parity_cutout(size, oracle_lib):
     gpu.sync()
     a, b = gpu.depth.raw(0)[..., 0] & 0xFFFFFF, ref.depth.raw(0)[..., 0] & 0xFFFFFF
     assert np.array_equal(a, b), f"depth: {int((a != b).sum())} texels differ"
+    assert size != (200, 120) or (b != 0xFFFFFF).all(), "the quad fills the frame"
     fence = b != d_solid
     print(f"[parity] cutout: fence covers {int(fence.sum())} px")
     assert fence.sum() > 0.01 * W * H

@@ -12,15 +12,14 @@
 //                      box of at most 64 blocks of 8x8 texels) or to the large list (chunks of 16 blocks).
 //   k_cubemap_small    the waves of the launch walk the small list, one record per wave at a time, one texel per lane
 //   k_cubemap_large    the chunks of the large list, dealt round-robin to all waves (a wall that fills a face is 16 chunks)
-//                      both: cover() of raster_common.hpp, atomicMin of (D24 << 32 | ~submission index) into the face's slice
+//                      both: walk_blocks() of raster_common.hpp; the fragment is the alpha test and the atomicMin of
+//                      (D24 << 32 | ~submission index) into the face's slice
 //   k_cubemap_resolve  one thread per (texel, face): the winning record, perspective-correct uv and view-space position,
 //                      implicit LOD from forward differences, the trilinear sRGB albedo -> RGBA8_SRGB, length(view_pos) -> fp16
 //
 // shader.frag discards a fragment whose albedo alpha is 0; as in raster.hip the discard is evaluated at coverage time (the very
 // expression the resolve evaluates again) and skipped for draws that carry VKR_RASTER_DRAW_OPAQUE_ALBEDO.  A draw without an
 // albedo texture is not drawn at all (probe_renderer.cpp:136-138).
-#include <vector>
-
 #define VKR_FORCE_GLM_COMPAT  // lookAt / perspective of the host mirror, the same code on every machine
 #include "../host/glm_compat.hpp"
 #include "raster_common.hpp"
@@ -61,43 +60,6 @@ struct CubeArgs {
 // the vertex shader's outputs as the floats clip_near() interpolates: clip position, view-space position, uv
 enum { CV_X, CV_Y, CV_Z, CV_W, CV_VX, CV_VY, CV_VZ, CV_U, CV_V, CV_N };
 
-VKR_DEV uint32_t cube_draw_of(const CubeArgs& a, uint32_t gtri) {
-  uint32_t lo = 0, hi = a.draw_count - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (a.draws[mid].tri_base <= gtri) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// uv and its forward differences at texel (px, py): what texture() of shader.frag sees
-struct CubeFrag { f2 uv, ddx, ddy; float b[3]; };
-VKR_DEV CubeFrag cube_fragment(const CubeTri& t, int px, int py, const float lambda[3]) {
-  CubeFrag f;
-  perspective(t, lambda, f.b);
-  const float* b = f.b;
-  const float u[3] = {t.uv[0].x, t.uv[1].x, t.uv[2].x}, v[3] = {t.uv[0].y, t.uv[1].y, t.uv[2].y};
-  f.uv = mk2((b[0] * u[0] + b[1] * u[1]) + b[2] * u[2], (b[0] * v[0] + b[1] * v[1]) + b[2] * v[2]);
-  float lx1[3], ly1[3], bx1[3], by1[3];
-  lambda_at(t, px + 1, py, lx1);
-  lambda_at(t, px, py + 1, ly1);
-  perspective(t, lx1, bx1);
-  perspective(t, ly1, by1);
-  const f2 uvx = mk2((bx1[0] * u[0] + bx1[1] * u[1]) + bx1[2] * u[2], (bx1[0] * v[0] + bx1[1] * v[1]) + bx1[2] * v[2]);
-  const f2 uvy = mk2((by1[0] * u[0] + by1[1] * u[1]) + by1[2] * u[2], (by1[0] * v[0] + by1[1] * v[1]) + by1[2] * v[2]);
-  f.ddx = uvx - f.uv; f.ddy = uvy - f.uv;
-  return f;
-}
-
-struct CubeDrawChunk { CubeDraw d[8]; };
-__global__ void k_cubemap_store_draws(CubeDrawChunk c, CubeDraw* dst, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = c.d[threadIdx.x];
-}
-struct CubeTexChunk { Pyramid p[4]; };
-__global__ void k_cubemap_store_textures(CubeTexChunk c, Pyramid* dst, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = c.p[threadIdx.x];
-}
-
 __global__ void k_cubemap_clear(unsigned long long* vis, size_t n, unsigned long long* state) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) vis[i] = ~0ull;
@@ -109,7 +71,7 @@ __global__ __launch_bounds__(256) void k_cubemap_setup(CubeArgs a) {
   const uint32_t gtri = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t face = blockIdx.y;
   if (gtri >= a.total_tris) return;
-  const CubeDraw& d = a.draws[cube_draw_of(a, gtri)];
+  const CubeDraw& d = a.draws[draw_of(a.draws, a.draw_count, gtri)];
   const uint32_t tri = gtri - d.tri_base;
   float in[3][CV_N], poly[4][CV_N];
   uint32_t out_mask = 0x1Fu;  // planes every corner so far lies outside of: x < -w, x > w, y < -w, y > w, z < 0
@@ -121,7 +83,7 @@ __global__ __launch_bounds__(256) void k_cubemap_setup(CubeArgs a) {
     in[k][CV_X] = p.x; in[k][CV_Y] = p.y; in[k][CV_Z] = p.z; in[k][CV_W] = p.w;
     in[k][CV_VX] = view_pos.x; in[k][CV_VY] = view_pos.y; in[k][CV_VZ] = view_pos.z;
     in[k][CV_U] = v.uv[0]; in[k][CV_V] = v.uv[1];
-    out_mask &= (p.x < -p.w ? 1u : 0u) | (p.x > p.w ? 2u : 0u) | (p.y < -p.w ? 4u : 0u) | (p.y > p.w ? 8u : 0u) | (p.z < 0.0f ? 16u : 0u);
+    out_mask &= frustum_out_mask(p);
   }
   if (out_mask) return;  // wholly outside the face's frustum: no texel centre of the face can be covered
   const int n = clip_near<CV_N, CV_Z>(in, poly);
@@ -129,21 +91,10 @@ __global__ __launch_bounds__(256) void k_cubemap_setup(CubeArgs a) {
   // the fan of the clipped polygon: (0, 1, 2) and, for a quad, (0, 2, 3); constant indices keep the polygon in registers
   auto emit = [&](const float (&c0)[CV_N], const float (&c1)[CV_N], const float (&c2)[CV_N], uint32_t sub) {
     CubeTri t;
-    bool ok = snap_vertex(mk4(c0[CV_X], c0[CV_Y], c0[CV_Z], c0[CV_W]), a.size, a.size, &t.x[0], &t.y[0], &t.w[0], &t.z[0]);
-    ok = snap_vertex(mk4(c1[CV_X], c1[CV_Y], c1[CV_Z], c1[CV_W]), a.size, a.size, &t.x[1], &t.y[1], &t.w[1], &t.z[1]) && ok;
-    ok = snap_vertex(mk4(c2[CV_X], c2[CV_Y], c2[CV_Z], c2[CV_W]), a.size, a.size, &t.x[2], &t.y[2], &t.w[2], &t.z[2]) && ok;
-    if (!ok) return;
-    long long area2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], t.x[2], t.y[2]);
-    if (area2 == 0) return;
-    const bool flip = area2 < 0;  // cull none: both windings are drawn; normalise the orientation
-    if (flip) {
-      int ti = t.x[1]; t.x[1] = t.x[2]; t.x[2] = ti;
-      ti = t.y[1]; t.y[1] = t.y[2]; t.y[2] = ti;
-      float tf = t.w[1]; t.w[1] = t.w[2]; t.w[2] = tf;
-      tf = t.z[1]; t.z[1] = t.z[2]; t.z[2] = tf;
-      area2 = -area2;
-    }
-    t.inv_area2 = 1.0 / (double)area2;
+    bool flip;
+    const f4 p0 = mk4(c0[CV_X], c0[CV_Y], c0[CV_Z], c0[CV_W]), p1 = mk4(c1[CV_X], c1[CV_Y], c1[CV_Z], c1[CV_W]);
+    const f4 p2 = mk4(c2[CV_X], c2[CV_Y], c2[CV_Z], c2[CV_W]);
+    if (!snap_orient(p0, p1, p2, a.size, a.size, t.x, t.y, t.z, t.w, &t.inv_area2, &flip)) return;
     // (values first, then selects: a select between the two arrays' addresses would put the polygon in memory)
     const float u1 = c1[CV_U], v1 = c1[CV_V], u2 = c2[CV_U], v2 = c2[CV_V];
     const float x1 = c1[CV_VX], y1 = c1[CV_VY], z1 = c1[CV_VZ], x2 = c2[CV_VX], y2 = c2[CV_VY], z2 = c2[CV_VZ];
@@ -158,75 +109,45 @@ __global__ __launch_bounds__(256) void k_cubemap_setup(CubeArgs a) {
     if (!tri_bbox(t, a.size, a.size, &bx0, &by0, &bx1, &by1)) return;  // no texel centre inside the bounding box
     const uint32_t rec = face * 2u * a.total_tris + gtri * 2u + sub;
     a.setup[rec] = t;
-    const int nb = bbox_blocks(bx0, by0, bx1, by1);
-    if (nb > RASTER_SMALL_BLOCKS) {
-      const uint32_t chunks = (uint32_t)(nb + RASTER_LARGE_CHUNK - 1) / RASTER_LARGE_CHUNK;
-      const unsigned long long v = atomicAdd(&a.state[0], (1ull << 32) | (unsigned long long)chunks);
-      a.large_list[(uint32_t)(v >> 32)] = LargeEntry {rec, (uint32_t)v};
-    } else {
-      a.small_list[(uint32_t)atomicAdd(&a.state[1], 1ull)] = rec;
-    }
+    list_append(rec, bbox_blocks(bx0, by0, bx1, by1), &a.state[0], a.large_list, &a.state[1], a.small_list);
   };
   if (n >= 3) emit(poly[0], poly[1], poly[2], 0u);
   if (n >= 4) emit(poly[0], poly[2], poly[3], 1u);
 }
 
-// What coverage needs of a record, in registers (the waves issue atomics between their reads of it)
-struct CubeCover {
-  int x[3], y[3];
-  float z[3];
-  double inv_area2;
-  VKR_DEV explicit CubeCover(const CubeTri& t) : x {t.x[0], t.x[1], t.x[2]}, y {t.y[0], t.y[1], t.y[2]}, z {t.z[0], t.z[1], t.z[2]}, inv_area2 {t.inv_area2} {}
-};
-
-// 8x8 texel block `b` (row-major inside the bounding box) of record `rec`, one texel per lane
-VKR_DEV void cube_block(const CubeArgs& a, const CubeCover& t, uint32_t alpha_tex, uint32_t rec, int x0, int y0, int x1, int y1, int b, int lane) {
-  const int bw = (x1 >> 3) - (x0 >> 3) + 1;
-  const int bx0 = ((x0 >> 3) + b % bw) << 3, by0 = ((y0 >> 3) + b / bw) << 3;
-  if (block_outside(t, bx0, by0)) return;
-  const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
-  if (px < x0 || px > x1 || py < y0 || py > y1) return;
-  float lambda[3];
-  uint32_t d24;
-  if (!cover(t, px, py, lambda, &d24)) return;
-  if (alpha_tex != 0xFFFFFFFFu) {  // shader.frag:26-28: out_albedo.a == 0 -> discard (no depth, no colour, no distance)
-    const CubeFrag f = cube_fragment(a.setup[rec], px, py, lambda);
-    if (sample_trilinear(a.tex[alpha_tex], f.uv, f.ddx, f.ddy, (const float*)k_srgb_decode_bits).w == 0.0f) return;
-  }
-  const uint32_t per_face = 2u * a.total_tris;
-  const uint32_t face = rec / per_face, order = rec - face * per_face;  // order: the submission index, later wins a depth tie
-  atomicMin(&a.vis[((size_t)face * a.size + py) * a.size + px], ((unsigned long long)d24 << 32) | (0xFFFFFFFFull - (unsigned long long)order));
+// the fragment of record `rec` at a covered texel
+VKR_DEV auto cube_fragment(const CubeArgs& a, uint32_t rec) {
+  const uint32_t alpha_tex = a.setup[rec].alpha_tex;
+  return [&a, rec, alpha_tex](int px, int py, const float lambda[3], uint32_t d24) {
+    if (alpha_tex != 0xFFFFFFFFu) {  // shader.frag:26-28: out_albedo.a == 0 -> discard (no depth, no colour, no distance)
+      const CubeTri& t = a.setup[rec];
+      const FragUv f = fragment_uv(t, t.uv[0], t.uv[1], t.uv[2], px, py, lambda);
+      if (sample_trilinear(a.tex[alpha_tex], f.uv, f.ddx, f.ddy, (const float*)k_srgb_decode_bits).w == 0.0f) return;
+    }
+    const uint32_t per_face = 2u * a.total_tris;
+    const uint32_t face = rec / per_face, order = rec - face * per_face;  // order: the submission index, later wins a depth tie
+    atomicMin(&a.vis[((size_t)face * a.size + py) * a.size + px], ((unsigned long long)d24 << 32) | (0xFFFFFFFFull - (unsigned long long)order));
+  };
 }
 
-__global__ __launch_bounds__(256) void k_cubemap_small(CubeArgs a) {
+__global__ __launch_bounds__(COVER_BLOCK) void k_cubemap_small(CubeArgs a) {
   const uint32_t n = (uint32_t)a.state[1];
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t i = wave; i < n; i += waves) {
+  for (uint32_t i = wave_index(); i < n; i += wave_count()) {
     const uint32_t rec = a.small_list[i];
-    const CubeCover t(a.setup[rec]);
-    const uint32_t alpha_tex = a.setup[rec].alpha_tex;
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.size, a.size, &x0, &y0, &x1, &y1)) continue;
-    const int nb = bbox_blocks(x0, y0, x1, y1);
-    for (int b = 0; b < nb; b++) cube_block(a, t, alpha_tex, rec, x0, y0, x1, y1, b, lane);
+    const CoverTri t(a.setup[rec]);
+    walk_blocks(t, a.size, a.size, 0, INT_MAX, INT_MAX, lane, cube_fragment(a, rec));
   }
 }
 
-__global__ __launch_bounds__(256) void k_cubemap_large(CubeArgs a) {
+__global__ __launch_bounds__(COVER_BLOCK) void k_cubemap_large(CubeArgs a) {
   const unsigned long long st = a.state[0];
   const uint32_t n = (uint32_t)(st >> 32), chunks = (uint32_t)st;
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t c = wave; c < chunks; c += waves) {
+  for (uint32_t c = wave_index(); c < chunks; c += wave_count()) {
     const LargeEntry e = large_entry_of(a.large_list, n, c);
-    const CubeCover t(a.setup[e.rec]);
-    const uint32_t alpha_tex = a.setup[e.rec].alpha_tex;
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.size, a.size, &x0, &y0, &x1, &y1)) continue;
-    const int nb = bbox_blocks(x0, y0, x1, y1);
-    const int b0 = (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, b1 = min(b0 + RASTER_LARGE_CHUNK, nb);
-    for (int b = b0; b < b1; b++) cube_block(a, t, alpha_tex, e.rec, x0, y0, x1, y1, b, lane);
+    const CoverTri t(a.setup[e.rec]);
+    walk_blocks(t, a.size, a.size, (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, RASTER_LARGE_CHUNK, INT_MAX, lane, cube_fragment(a, e.rec));
   }
 }
 
@@ -257,7 +178,7 @@ __global__ __launch_bounds__(256) void k_cubemap_resolve(CubeResolveArgs a) {
     float lambda[3];
     uint32_t d24 = 0;
     cover(t, px, py, lambda, &d24);
-    const CubeFrag fu = cube_fragment(t, px, py, lambda);
+    const FragUv fu = fragment_uv(t, t.uv[0], t.uv[1], t.uv[2], px, py, lambda);
     const float* b = fu.b;
     const f3 pos = mk3((b[0] * t.vp[0].x + b[1] * t.vp[1].x) + b[2] * t.vp[2].x, (b[0] * t.vp[0].y + b[1] * t.vp[1].y) + b[2] * t.vp[2].y,
                        (b[0] * t.vp[0].z + b[1] * t.vp[1].z) + b[2] * t.vp[2].z);
@@ -295,12 +216,24 @@ using namespace vkr;
 #define CUBE_MAX_DRAWS 1024u
 #define CUBE_RASTER_GRID 1024  // blocks of four waves of the small and the large kernel
 
-static uint64_t cube_records(uint32_t triangle_count) { return 12ull * triangle_count; }  // 6 faces x 2 sub-triangles
+struct CubeLayout {  // offsets of the parts of the scratch, and its size
+  uint64_t vis, draws, tex, setup, state, small_list, large_list, total;
+  CubeLayout(uint32_t cube_size, uint32_t triangle_count) {
+    const uint64_t recs = 12ull * triangle_count;  // 6 faces x 2 sub-triangles
+    ScratchCarver c;
+    vis = c.take(6ull * cube_size * cube_size * 8u);
+    draws = c.take(sizeof(CubeDraw) * CUBE_MAX_DRAWS);
+    tex = c.take(sizeof(Pyramid) * RASTER_MAX_TEXTURES);
+    setup = c.take(sizeof(CubeTri) * recs);
+    state = c.take(256);
+    small_list = c.take(sizeof(uint32_t) * recs);
+    large_list = c.take(sizeof(LargeEntry) * recs);
+    total = c.at;
+  }
+};
 
 extern "C" uint64_t vkr_cubemap_probe_scratch_bytes(uint32_t cube_size, uint32_t triangle_count) {
-  return align_up(6ull * cube_size * cube_size * 8u, 256) + align_up(sizeof(CubeDraw) * CUBE_MAX_DRAWS, 256) + align_up(sizeof(Pyramid) * RASTER_MAX_TEXTURES, 256) +
-         align_up(sizeof(CubeTri) * cube_records(triangle_count), 256) + 256u + align_up(sizeof(uint32_t) * cube_records(triangle_count), 256) +
-         align_up(sizeof(LargeEntry) * cube_records(triangle_count), 256);
+  return CubeLayout(cube_size, triangle_count).total;
 }
 
 extern "C" int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[3], const vkr_img* cube_color, const vkr_img* cube_distance,
@@ -336,19 +269,14 @@ extern "C" int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[
   ra.color = color[0]; ra.distance = distance[0];
   ra.color_stride = (uint32_t)cs; ra.distance_stride = (uint32_t)ds;
   const int S = color[0].w;
-  std::vector<Pyramid> tex(scene->texture_count);
-  for (uint32_t i = 0; i < scene->texture_count; i++) {
-    const vkr_img& t = scene->textures[i];
-    if (t.mip_count < 1 || t.mip_count > VKR_MAX_MIPS) { set_error("cubemap_probe: texture %u: bad mip count", i); return VKR_ERR_MIPS; }
-    tex[i].count = (int)t.mip_count;
-    for (int m = 0; m < (int)t.mip_count; m++) VKR_TRY(make_tex(&t, m, VKR_FMT_RGBA8_SRGB, "cubemap_probe.texture", &tex[i].mip[m]));
-    for (int m = (int)t.mip_count; m < 16; m++) tex[i].mip[m] = tex[i].mip[0];
-  }
+  std::vector<Pyramid> tex;
+  VKR_TRY(make_pyramids(scene, "cubemap_probe", &tex));
   // scratch is sized by every triangle of the scene (what the caller knows); only draws with an albedo texture are drawn
   uint64_t scene_tris = 0;
-  for (uint32_t i = 0; i < scene->draw_count; i++) scene_tris += scene->draws[i].index_count / 3u;
+  VKR_TRY(check_scene("cubemap_probe", scene, true, &scene_tris));
   if (scene_tris >= (1ull << 28)) { set_error("cubemap_probe: too many triangles"); return VKR_ERR_EXTENT; }
-  if (scratch_bytes < vkr_cubemap_probe_scratch_bytes((uint32_t)S, (uint32_t)scene_tris)) { set_error("cubemap_probe: scratch too small"); return VKR_ERR_EXTENT; }
+  const CubeLayout lay((uint32_t)S, (uint32_t)scene_tris);
+  if (scratch_bytes < lay.total) { set_error("cubemap_probe: scratch too small"); return VKR_ERR_EXTENT; }
   const glm::mat4 proj = glm::perspective(glm::radians(90.f), 1.f, 0.05f, 80.f);
   vkr_mat4 views[6];
   for (uint32_t f = 0; f < 6; f++) {
@@ -360,11 +288,6 @@ extern "C" int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[
   uint32_t tri_base = 0;
   for (uint32_t i = 0; i < scene->draw_count; i++) {
     const vkr_raster_draw& s = scene->draws[i];
-    if (s.transform_index >= scene->transform_count || (s.albedo_index != 0xFFFFFFFFu && s.albedo_index >= scene->texture_count) ||
-        s.index_offset + s.index_count > scene->index_count) {
-      set_error("cubemap_probe: draw %u references data outside the scene", i);
-      return VKR_ERR_EXTENT;
-    }
     if (s.albedo_index == 0xFFFFFFFFu || s.index_count < 3) continue;  // probe_renderer.cpp:136-138
     CubeDraw d;
     for (int f = 0; f < 6; f++) mat_mul(d.view_model[f], views[f], scene->transforms[s.transform_index].model);
@@ -377,36 +300,27 @@ extern "C" int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[
   }
   CubeArgs r;
   r.vertices = scene->vertices; r.indices = scene->indices;
-  uint8_t* at = (uint8_t*)scratch;
-  r.vis = (unsigned long long*)at; at += align_up(6ull * S * S * 8u, 256);
-  r.draws = (const CubeDraw*)at; at += align_up(sizeof(CubeDraw) * CUBE_MAX_DRAWS, 256);
-  r.tex = (const Pyramid*)at; at += align_up(sizeof(Pyramid) * RASTER_MAX_TEXTURES, 256);
-  r.setup = (CubeTri*)at; at += align_up(sizeof(CubeTri) * cube_records((uint32_t)scene_tris), 256);
-  r.state = (unsigned long long*)at; at += 256;
-  r.small_list = (uint32_t*)at; at += align_up(sizeof(uint32_t) * cube_records((uint32_t)scene_tris), 256);
-  r.large_list = (LargeEntry*)at;
+  uint8_t* const at = (uint8_t*)scratch;
+  r.vis = (unsigned long long*)(at + lay.vis);
+  r.draws = (const CubeDraw*)(at + lay.draws);
+  r.tex = (const Pyramid*)(at + lay.tex);
+  r.setup = (CubeTri*)(at + lay.setup);
+  r.state = (unsigned long long*)(at + lay.state);
+  r.small_list = (uint32_t*)(at + lay.small_list);
+  r.large_list = (LargeEntry*)(at + lay.large_list);
   std::memcpy(r.projection.m, &proj, sizeof(r.projection.m));
   r.draw_count = (uint32_t)draws.size(); r.total_tris = tri_base; r.size = S;
-  for (uint32_t i = 0; i < r.draw_count; i += 8) {
-    CubeDrawChunk c;
-    const uint32_t n = r.draw_count - i < 8u ? r.draw_count - i : 8u;
-    for (uint32_t k = 0; k < 8; k++) c.d[k] = draws[i + (k < n ? k : 0)];
-    hipLaunchKernelGGL(k_cubemap_store_draws, dim3(1), dim3(64), 0, stream, c, const_cast<CubeDraw*>(r.draws) + i, n);
-  }
-  for (uint32_t i = 0; i < scene->texture_count; i += 4) {
-    CubeTexChunk c;
-    const uint32_t n = scene->texture_count - i < 4u ? scene->texture_count - i : 4u;
-    for (uint32_t k = 0; k < 4; k++) c.p[k] = tex[i + (k < n ? k : 0)];
-    hipLaunchKernelGGL(k_cubemap_store_textures, dim3(1), dim3(64), 0, stream, c, const_cast<Pyramid*>(r.tex) + i, n);
-  }
+  store_table<8>(draws, r.draws, stream);
+  store_table<4>(tex, r.tex, stream);
   const size_t npx = 6u * (size_t)S * S;
   hipLaunchKernelGGL(k_cubemap_clear, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, r.vis, npx, r.state);
   if (tri_base) {
     hipLaunchKernelGGL(k_cubemap_setup, dim3((tri_base + 255) / 256, 6), dim3(256), 0, stream, r);
-    const uint64_t waves = cube_records(tri_base);
-    const unsigned grid = (unsigned)(waves / 4 + 1 < CUBE_RASTER_GRID ? waves / 4 + 1 : CUBE_RASTER_GRID);
-    hipLaunchKernelGGL(k_cubemap_small, dim3(grid), dim3(256), 0, stream, r);
-    hipLaunchKernelGGL(k_cubemap_large, dim3(grid), dim3(256), 0, stream, r);
+    const uint64_t waves = 12ull * tri_base;  // one per record: 6 faces x 2 sub-triangles
+    const uint64_t blocks = waves / COVER_BLOCK_WAVES + 1;
+    const unsigned grid = (unsigned)(blocks < CUBE_RASTER_GRID ? blocks : CUBE_RASTER_GRID);
+    hipLaunchKernelGGL(k_cubemap_small, dim3(grid), dim3(COVER_BLOCK), 0, stream, r);
+    hipLaunchKernelGGL(k_cubemap_large, dim3(grid), dim3(COVER_BLOCK), 0, stream, r);
   }
   ra.r = r;
   dim3 block(64, 4);

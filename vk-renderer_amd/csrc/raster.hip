@@ -9,7 +9,8 @@
 //   k_raster_small    one wave per triangle walks the (<= 64) blocks of its bounding box, one pixel per lane
 //   k_raster_large    the listed triangles, their bounding boxes cut into chunks of 16 blocks that are dealt to all
 //                     waves of the launch (a screen-filling quad does not serialise on a few waves)
-//                     both: fill rule on exact 64-bit edge functions of 24.8 coordinates, D24 depth, atomicMin
+//                     both: walk_blocks() of raster_common.hpp — fill rule on exact 64-bit edge functions of 24.8
+//                     coordinates, D24 depth; the fragment is the alpha test and the atomicMin
 //                     of (depth << 32 | ~record) — LESS_OR_EQUAL with later triangles winning ties
 //                     (gpu/pipelines.hpp:128)
 //   k_raster_resolve  one thread per pixel: the winning triangle's record, perspective-correct attributes,
@@ -24,8 +25,6 @@
 //
 // Coverage and depth are integer-exact functions of the snapped vertices, so they are bit-equal to
 // the oracle's immediate-mode rasterizer; colour / normal / velocity follow the frozen fp32 contract.
-#include <vector>
-
 #include "raster_common.hpp"
 
 namespace vkr {
@@ -128,46 +127,7 @@ VKR_DEV ScreenTri setup_triangle(const RasterArgs& a, const DrawDev& d, uint32_t
   return t;
 }
 
-// What coverage and depth need of a ScreenTri, copied into registers once per triangle: the rasterising waves issue
-// atomics between their reads of the record, and the compiler must otherwise assume those change it and reload.
-struct CoverTri {
-  int x[3], y[3];
-  float z[3];
-  double inv_area2;
-  VKR_DEV CoverTri() {}
-  VKR_DEV explicit CoverTri(const ScreenTri& t) : x {t.x[0], t.x[1], t.x[2]}, y {t.y[0], t.y[1], t.y[2]}, z {t.z[0], t.z[1], t.z[2]}, inv_area2 {t.inv_area2} {}
-};
 #define BARY(F) ((b[0] * t.v[0].F + b[1] * t.v[1].F) + b[2] * t.v[2].F)
-
-
-// uv and its forward differences at pixel (px, py) of triangle t (lambda: its screen-space barycentrics there):
-// what the fragment shader's texture() calls see (implicit derivatives as differences to the right / lower pixel)
-struct FragUv { f2 uv, ddx, ddy; float b[3]; };
-VKR_DEV FragUv fragment_uv(const ScreenTri& t, int px, int py, const float lambda[3]) {
-  FragUv f;
-  perspective(t, lambda, f.b);
-  const float* b = f.b;
-  f.uv = mk2(BARY(uv.x), BARY(uv.y));
-  float lx1[3], ly1[3], bx1[3], by1[3];
-  lambda_at(t, px + 1, py, lx1);
-  lambda_at(t, px, py + 1, ly1);
-  perspective(t, lx1, bx1);
-  perspective(t, ly1, by1);
-  const f2 uvx = mk2((bx1[0] * t.v[0].uv.x + bx1[1] * t.v[1].uv.x) + bx1[2] * t.v[2].uv.x, (bx1[0] * t.v[0].uv.y + bx1[1] * t.v[1].uv.y) + bx1[2] * t.v[2].uv.y);
-  const f2 uvy = mk2((by1[0] * t.v[0].uv.x + by1[1] * t.v[1].uv.x) + by1[2] * t.v[2].uv.x, (by1[0] * t.v[0].uv.y + by1[1] * t.v[1].uv.y) + by1[2] * t.v[2].uv.y);
-  f.ddx = uvx - f.uv; f.ddy = uvy - f.uv;
-  return f;
-}
-// the per-draw constants travel as kernel arguments (8 per launch) into the draw table in scratch: no host
-// staging memory has to outlive the call and nothing synchronises
-struct DrawChunk { DrawDev d[8]; };
-__global__ void k_raster_store_draws(DrawChunk c, DrawDev* dst, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = c.d[threadIdx.x];
-}
-struct TexChunk { Pyramid p[4]; };
-__global__ void k_raster_store_textures(TexChunk c, Pyramid* dst, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = c.p[threadIdx.x];
-}
 
 __global__ void k_raster_clear(unsigned long long* vis, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,20 +137,11 @@ __global__ void k_raster_clear(unsigned long long* vis, size_t n) {
 
 // one thread per triangle; a large sub-triangle takes a list slot AND its range of chunks with one 64-bit atomicAdd on
 // *large_state (entries << 32 | chunks), so the list is sorted by first_chunk
-// the draw that owns global triangle `gtri` (draws are consecutive ranges [tri_base, tri_base + tri_count))
-VKR_DEV uint32_t draw_of(const RasterArgs& a, uint32_t gtri) {
-  uint32_t lo = 0, hi = a.draw_count - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (a.draws[mid].tri_base <= gtri) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 // (every draw of the frame in one launch: a draw of a few thousand triangles does not fill the chip on its own)
 __global__ __launch_bounds__(256) void k_raster_setup(RasterArgs a, uint32_t total_tris, unsigned long long* large_state, LargeEntry* large_list) {
   const uint32_t gtri = blockIdx.x * blockDim.x + threadIdx.x;
   if (gtri >= total_tris) return;
-  const DrawDev d = a.draws[draw_of(a, gtri)];
+  const DrawDev d = a.draws[draw_of(a.draws, a.draw_count, gtri)];
   const uint32_t tri = gtri - d.tri_base;
   for (int sub = 0; sub < 2; sub++) {
     int count;
@@ -200,7 +151,7 @@ __global__ __launch_bounds__(256) void k_raster_setup(RasterArgs a, uint32_t tot
     a.setup[rec] = t;
     int x0, y0, x1, y1;
     if (t.valid && tri_bbox(t, a.width, a.height, &x0, &y0, &x1, &y1)) {
-      const int nb = ((x1 >> 3) - (x0 >> 3) + 1) * ((y1 >> 3) - (y0 >> 3) + 1);
+      const int nb = bbox_blocks(x0, y0, x1, y1);
       if (nb > RASTER_SMALL_BLOCKS) {
         const uint32_t chunks = (uint32_t)(nb + RASTER_LARGE_CHUNK - 1) / RASTER_LARGE_CHUNK;
         const unsigned long long v = atomicAdd(large_state, (1ull << 32) | (unsigned long long)chunks);
@@ -210,58 +161,44 @@ __global__ __launch_bounds__(256) void k_raster_setup(RasterArgs a, uint32_t tot
   }
 }
 
-// 8x8 pixel block `b` (row-major inside the bounding box) of record `rec`, one pixel per lane
-VKR_DEV void raster_block(const RasterArgs& a, const CoverTri& t, uint32_t alpha_tex, uint32_t rec, int x0, int y0, int x1, int y1, int b, int lane) {
-  const int bw = (x1 >> 3) - (x0 >> 3) + 1;
-  const int bx0 = ((x0 >> 3) + b % bw) << 3, by0 = ((y0 >> 3) + b / bw) << 3;
-  if (block_outside(t, bx0, by0)) return;
-  const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
-  if (px < x0 || px > x1 || py < y0 || py > y1) return;
-  float lambda[3];
-  uint32_t d24;
-  if (!cover(t, px, py, lambda, &d24)) return;
-  if (alpha_tex != 0xFFFFFFFFu) {  // opaque_taa.frag:32-34: out_albedo.a == 0 -> discard (no depth, no colour)
-    const FragUv f = fragment_uv(a.setup[rec], px, py, lambda);
-    if (sample_trilinear(a.tex[alpha_tex], f.uv, f.ddx, f.ddy, (const float*)k_srgb_decode_bits).w == 0.0f) return;  // only alpha is used: the colour decodes fold away
-  }
-  atomicMin(&a.vis[(size_t)py * a.width + px], ((unsigned long long)d24 << 32) | (0xFFFFFFFFull - (unsigned long long)rec));
+// the fragment of record `rec` at a covered pixel
+VKR_DEV auto raster_fragment(const RasterArgs& a, uint32_t rec) {
+  const uint32_t alpha_tex = a.setup[rec].alpha_tex;
+  return [&a, rec, alpha_tex](int px, int py, const float lambda[3], uint32_t d24) {
+    if (alpha_tex != 0xFFFFFFFFu) {  // opaque_taa.frag:32-34: out_albedo.a == 0 -> discard (no depth, no colour)
+      const ScreenTri& t = a.setup[rec];
+      const FragUv f = fragment_uv(t, t.v[0].uv, t.v[1].uv, t.v[2].uv, px, py, lambda);
+      // only alpha is used: the colour decodes fold away
+      if (sample_trilinear(a.tex[alpha_tex], f.uv, f.ddx, f.ddy, (const float*)k_srgb_decode_bits).w == 0.0f) return;
+    }
+    atomicMin(&a.vis[(size_t)py * a.width + px], ((unsigned long long)d24 << 32) | (0xFFFFFFFFull - (unsigned long long)rec));
+  };
 }
 
-// small triangles: one wave per triangle walks its (at most 64) blocks
-__global__ __launch_bounds__(256) void k_raster_small(RasterArgs a, uint32_t total_tris) {
-  const uint32_t gtri = blockIdx.x * 4u + (threadIdx.x >> 6);
+// small triangles: one wave per triangle walks its (at most 64) blocks; a larger sub-triangle is left to k_raster_large
+__global__ __launch_bounds__(COVER_BLOCK) void k_raster_small(RasterArgs a, uint32_t total_tris) {
+  const uint32_t gtri = wave_index();
   const int lane = threadIdx.x & 63;
   if (gtri >= total_tris) return;
   for (uint32_t sub = 0; sub < 2; sub++) {
     const uint32_t rec = gtri * 2u + sub;
     if (!a.setup[rec].valid) continue;
     const CoverTri t(a.setup[rec]);
-    const uint32_t alpha_tex = a.setup[rec].alpha_tex;
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.width, a.height, &x0, &y0, &x1, &y1)) continue;
-    const int nb = ((x1 >> 3) - (x0 >> 3) + 1) * ((y1 >> 3) - (y0 >> 3) + 1);
-    if (nb > RASTER_SMALL_BLOCKS) continue;
-    for (int b = 0; b < nb; b++) raster_block(a, t, alpha_tex, rec, x0, y0, x1, y1, b, lane);
+    walk_blocks(t, a.width, a.height, 0, INT_MAX, RASTER_SMALL_BLOCKS, lane, raster_fragment(a, rec));
   }
 }
 
 // large triangles: their bounding boxes are cut into chunks of RASTER_LARGE_CHUNK blocks, all chunks of all listed
 // triangles are dealt round-robin to the waves of the launch (a screen-filling quad is 4096 chunks at 4K: every wave
 // of the launch works on it, none serialises)
-__global__ __launch_bounds__(256) void k_raster_large(RasterArgs a, const unsigned long long* large_state, const LargeEntry* large_list) {
+__global__ __launch_bounds__(COVER_BLOCK) void k_raster_large(RasterArgs a, const unsigned long long* large_state, const LargeEntry* large_list) {
   const unsigned long long st = *large_state;
   const uint32_t n = (uint32_t)(st >> 32), chunks = (uint32_t)st;
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t c = wave; c < chunks; c += waves) {
+  for (uint32_t c = wave_index(); c < chunks; c += wave_count()) {
     const LargeEntry e = large_entry_of(large_list, n, c);
     const CoverTri t(a.setup[e.rec]);
-    const uint32_t alpha_tex = a.setup[e.rec].alpha_tex;
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.width, a.height, &x0, &y0, &x1, &y1)) continue;
-    const int nb = ((x1 >> 3) - (x0 >> 3) + 1) * ((y1 >> 3) - (y0 >> 3) + 1);
-    const int b0 = (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, b1 = min(b0 + RASTER_LARGE_CHUNK, nb);
-    for (int b = b0; b < b1; b++) raster_block(a, t, alpha_tex, e.rec, x0, y0, x1, y1, b, lane);
+    walk_blocks(t, a.width, a.height, (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, RASTER_LARGE_CHUNK, INT_MAX, lane, raster_fragment(a, e.rec));
   }
 }
 
@@ -284,12 +221,12 @@ __global__ __launch_bounds__(256) void k_raster_resolve(ResolveArgs a) {
   if (key != ~0ull) {
     const uint32_t gid2 = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
     const uint32_t gid = gid2 >> 1;
-    const DrawDev& d = a.r.draws[draw_of(a.r, gid)];
+    const DrawDev& d = a.r.draws[draw_of(a.r.draws, a.r.draw_count, gid)];
     const ScreenTri& t = a.r.setup[gid2];
     float lambda[3];
     uint32_t d24 = 0;
     cover(t, px, py, lambda, &d24);
-    const FragUv fu = fragment_uv(t, px, py, lambda);
+    const FragUv fu = fragment_uv(t, t.v[0].uv, t.v[1].uv, t.v[2].uv, px, py, lambda);
     const float* b = fu.b;
     const f3 in_normal = mk3(BARY(normal.x), BARY(normal.y), BARY(normal.z));
     const f2 in_uv = fu.uv;
@@ -322,9 +259,24 @@ __global__ __launch_bounds__(256) void k_raster_resolve(ResolveArgs a) {
 using namespace vkr;
 
 
+#define RASTER_MAX_DRAWS 1024u
+
+struct RasterLayout {  // offsets of the parts of the scratch, and its size
+  uint64_t vis, draws, tex, setup, large_state, large_list, total;
+  RasterLayout(uint32_t width, uint32_t height, uint32_t triangle_count) {
+    ScratchCarver c;
+    vis = c.take((uint64_t)width * height * 8u);
+    draws = c.take(sizeof(DrawDev) * RASTER_MAX_DRAWS);
+    tex = c.take(sizeof(Pyramid) * RASTER_MAX_TEXTURES);
+    setup = c.take(sizeof(ScreenTri) * 2u * (uint64_t)triangle_count);
+    large_state = c.take(256);
+    large_list = c.take(sizeof(LargeEntry) * 2u * (uint64_t)triangle_count);
+    total = c.at;
+  }
+};
+
 extern "C" uint64_t vkr_raster_scratch_bytes(uint32_t width, uint32_t height, uint32_t triangle_count) {
-  return align_up((uint64_t)width * height * 8u, 256) + align_up(sizeof(DrawDev) * 1024u, 256) + align_up(sizeof(Pyramid) * RASTER_MAX_TEXTURES, 256) +
-         align_up(sizeof(ScreenTri) * 2u * (uint64_t)triangle_count, 256) + 256u + align_up(sizeof(LargeEntry) * 2u * (uint64_t)triangle_count, 256);
+  return RasterLayout(width, height, triangle_count).total;
 }
 
 extern "C" int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_const* consts, const vkr_img* albedo,
@@ -332,8 +284,8 @@ extern "C" int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_
                                   void* scratch, uint64_t scratch_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!scene || !consts || !scratch) { set_error("gbuf_opaque_taa: NULL argument"); return VKR_ERR_NULL; }
-  if (scene->draw_count > 1024 || scene->texture_count > RASTER_MAX_TEXTURES) {
-    set_error("gbuf_opaque_taa: at most 1024 draws and %d textures", RASTER_MAX_TEXTURES);
+  if (scene->draw_count > RASTER_MAX_DRAWS || scene->texture_count > RASTER_MAX_TEXTURES) {
+    set_error("gbuf_opaque_taa: at most %u draws and %d textures", RASTER_MAX_DRAWS, RASTER_MAX_TEXTURES);
     return VKR_ERR_EXTENT;
   }
   ResolveArgs ra;
@@ -349,27 +301,17 @@ extern "C" int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_
   }
   const int W = ra.albedo.fw, H = ra.albedo.fh;
   uint64_t total_tris = 0;
-  for (uint32_t i = 0; i < scene->draw_count; i++) total_tris += scene->draws[i].index_count / 3u;
+  VKR_TRY(check_scene("gbuf_opaque_taa", scene, true, &total_tris));
   if (total_tris >= 0x7FFFFFFFull) { set_error("gbuf_opaque_taa: too many triangles"); return VKR_ERR_EXTENT; }
-  if (scratch_bytes < vkr_raster_scratch_bytes((uint32_t)W, (uint32_t)H, (uint32_t)total_tris)) { set_error("gbuf_opaque_taa: scratch too small"); return VKR_ERR_EXTENT; }
-  std::vector<Pyramid> tex(scene->texture_count);
-  for (uint32_t i = 0; i < scene->texture_count; i++) {
-    const vkr_img& t = scene->textures[i];
-    if (t.mip_count < 1 || t.mip_count > VKR_MAX_MIPS) { set_error("gbuf_opaque_taa: texture %u: bad mip count", i); return VKR_ERR_MIPS; }
-    tex[i].count = (int)t.mip_count;
-    for (int m = 0; m < (int)t.mip_count; m++) VKR_TRY(make_tex(&t, m, VKR_FMT_RGBA8_SRGB, "gbuf_opaque_taa.texture", &tex[i].mip[m]));
-    for (int m = (int)t.mip_count; m < 16; m++) tex[i].mip[m] = tex[i].mip[0];
-  }
+  const RasterLayout lay((uint32_t)W, (uint32_t)H, (uint32_t)total_tris);
+  if (scratch_bytes < lay.total) { set_error("gbuf_opaque_taa: scratch too small"); return VKR_ERR_EXTENT; }
+  std::vector<Pyramid> tex;
+  VKR_TRY(make_pyramids(scene, "gbuf_opaque_taa", &tex));
   // per-draw constants: view_projection * model exactly as opaque_taa.vert:39,44 multiplies them
   std::vector<DrawDev> draws(scene->draw_count);
   uint32_t tri_base = 0;
   for (uint32_t i = 0; i < scene->draw_count; i++) {
     const vkr_raster_draw& s = scene->draws[i];
-    if (s.transform_index >= scene->transform_count || (s.albedo_index != 0xFFFFFFFFu && s.albedo_index >= scene->texture_count) ||
-        (s.mr_index != 0xFFFFFFFFu && s.mr_index >= scene->texture_count) || s.index_offset + s.index_count > scene->index_count) {
-      set_error("gbuf_opaque_taa: draw %u references data outside the scene", i);
-      return VKR_ERR_EXTENT;
-    }
     DrawDev& d = draws[i];
     mat_mul(d.mvp, consts->view_projection, scene->transforms[s.transform_index].model);
     mat_mul(d.prev_mvp, consts->prev_view_projection, scene->transforms[s.transform_index].model);
@@ -381,31 +323,20 @@ extern "C" int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_
     d.pad1 = 0;
     tri_base += d.tri_count;
   }
-  if (tri_base >= 0x7FFFFFFFu) { set_error("gbuf_opaque_taa: too many triangles"); return VKR_ERR_EXTENT; }
   RasterArgs r;
   r.vertices = scene->vertices; r.indices = scene->indices;
-  r.vis = (unsigned long long*)scratch;
-  r.draws = (const DrawDev*)((uint8_t*)scratch + align_up((uint64_t)W * H * 8u, 256));
-  r.tex = (const Pyramid*)((uint8_t*)r.draws + align_up(sizeof(DrawDev) * 1024u, 256));
-  r.setup = (ScreenTri*)((uint8_t*)r.tex + align_up(sizeof(Pyramid) * RASTER_MAX_TEXTURES, 256));
-  unsigned long long* large_state = (unsigned long long*)((uint8_t*)r.setup + align_up(sizeof(ScreenTri) * 2u * total_tris, 256));
-  LargeEntry* large_list = (LargeEntry*)((uint8_t*)large_state + 256);
+  uint8_t* const at = (uint8_t*)scratch;
+  r.vis = (unsigned long long*)(at + lay.vis);
+  r.draws = (const DrawDev*)(at + lay.draws);
+  r.tex = (const Pyramid*)(at + lay.tex);
+  r.setup = (ScreenTri*)(at + lay.setup);
+  unsigned long long* large_state = (unsigned long long*)(at + lay.large_state);
+  LargeEntry* large_list = (LargeEntry*)(at + lay.large_list);
   r.draw_count = scene->draw_count;
   r.width = W; r.height = H;
   r.jitter_x = consts->jitter[0]; r.jitter_y = consts->jitter[1];
-  for (uint32_t i = 0; i < scene->draw_count; i += 8) {
-    DrawChunk c;
-    const uint32_t n = scene->draw_count - i < 8u ? scene->draw_count - i : 8u;
-    for (uint32_t k = 0; k < n; k++) c.d[k] = draws[i + k];
-    for (uint32_t k = n; k < 8; k++) c.d[k] = draws[i];
-    hipLaunchKernelGGL(k_raster_store_draws, dim3(1), dim3(64), 0, stream, c, const_cast<DrawDev*>(r.draws) + i, n);
-  }
-  for (uint32_t i = 0; i < scene->texture_count; i += 4) {
-    TexChunk c;
-    const uint32_t n = scene->texture_count - i < 4u ? scene->texture_count - i : 4u;
-    for (uint32_t k = 0; k < 4; k++) c.p[k] = tex[i + (k < n ? k : 0)];
-    hipLaunchKernelGGL(k_raster_store_textures, dim3(1), dim3(64), 0, stream, c, const_cast<Pyramid*>(r.tex) + i, n);
-  }
+  store_table<8>(draws, r.draws, stream);
+  store_table<4>(tex, r.tex, stream);
   const size_t npx = (size_t)W * H;
   hipLaunchKernelGGL(k_raster_clear, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, r.vis, npx);
   {
@@ -414,10 +345,10 @@ extern "C" int vkr_raster_gbuffer(const vkr_raster_scene* scene, const vkr_gbuf_
   }
   if (tri_base) {
     hipLaunchKernelGGL(k_raster_setup, dim3((tri_base + 255) / 256), dim3(256), 0, stream, r, tri_base, large_state, large_list);
-    hipLaunchKernelGGL(k_raster_small, dim3((tri_base + 3) / 4), dim3(256), 0, stream, r, tri_base);
+    hipLaunchKernelGGL(k_raster_small, dim3((tri_base + COVER_BLOCK_WAVES - 1) / COVER_BLOCK_WAVES), dim3(COVER_BLOCK), 0, stream, r, tri_base);
   }
   // every draw's large triangles in one launch: submission order is carried by the record index in the key
-  hipLaunchKernelGGL(k_raster_large, dim3(RASTER_LARGE_GRID), dim3(256), 0, stream, r, large_state, large_list);
+  hipLaunchKernelGGL(k_raster_large, dim3(RASTER_LARGE_GRID), dim3(COVER_BLOCK), 0, stream, r, large_state, large_list);
   ra.r = r;
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_raster_resolve, grid2d(ra.albedo.w, ra.albedo.h, block), block, 0, stream, ra);

@@ -1,8 +1,15 @@
-// raster_common.hpp — what the compute rasterisers share (raster.hip: program "gbuf_opaque_taa", cubemap.hip: program
-// "cubemap_probe"): the frozen raster rules — exact 64-bit edge functions of 24.8 coordinates, the top-left fill rule, the
-// 8-bit sub-pixel snap, the near-plane clip, D24 depth — the small / large split of the work, and the scene sampler
-// (REPEAT, trilinear, sRGB).  One definition, so the two programs cannot drift apart.
+// raster_common.hpp — what the three compute rasterisers share (raster.hip: program "gbuf_opaque_taa", cubemap.hip: program
+// "cubemap_probe", shadow.hip: program "default_shadow").  Device side: the frozen raster rules — exact 64-bit edge functions
+// of 24.8 coordinates, the top-left fill rule, the 8-bit sub-pixel snap, the near-plane clip, D24 depth — the scene sampler
+// (REPEAT, trilinear, sRGB), the uv of a fragment, the tail of triangle setup (snap, orientation, small / large lists) and
+// the coverage stage: CoverTri and walk_blocks(), which hand every covered texel to the calling program's fragment functor.
+// Host side: scene validation, the texture table, the upload of a table through kernel arguments and the carving of scratch.
+// One definition of each, so the programs cannot drift apart; a program keeps its records, its vertex shader and its fragment.
 #pragma once
+#include <climits>
+#include <string>
+#include <vector>
+
 #include "vkr_host.hpp"
 
 namespace vkr {
@@ -92,6 +99,25 @@ template <class T> VKR_DEV void perspective(const T& t, const float lambda[3], f
   b[0] = q0 / s; b[1] = q1 / s; b[2] = q2 / s;
 }
 
+// uv and its forward differences at pixel (px, py) of record t with the uv corners uv0..uv2 (lambda: its screen-space
+// barycentrics there): what the fragment shader's texture() calls see (implicit derivatives as differences to the right /
+// lower pixel).  b: the perspective-correct barycentrics, for the caller's other attributes
+struct FragUv { f2 uv, ddx, ddy; float b[3]; };
+template <class T>
+VKR_DEV FragUv fragment_uv(const T& t, const f2& uv0, const f2& uv1, const f2& uv2, int px, int py, const float lambda[3]) {
+  FragUv f;
+  perspective(t, lambda, f.b);
+  float lx1[3], ly1[3], bx1[3], by1[3];
+  lambda_at(t, px + 1, py, lx1);
+  lambda_at(t, px, py + 1, ly1);
+  perspective(t, lx1, bx1);
+  perspective(t, ly1, by1);
+  auto at = [&](const float b[3]) { return mk2((b[0] * uv0.x + b[1] * uv1.x) + b[2] * uv2.x, (b[0] * uv0.y + b[1] * uv1.y) + b[2] * uv2.y); };
+  f.uv = at(f.b);
+  f.ddx = at(bx1) - f.uv; f.ddy = at(by1) - f.uv;
+  return f;
+}
+
 VKR_DEV int wrap_repeat(int i, int n) {
   if ((n & (n - 1)) == 0) return i & (n - 1);  // power-of-two extent (every mip of the usual texture): no integer division
   const int m = i % n;
@@ -169,6 +195,95 @@ VKR_DEV LargeEntry large_entry_of(const LargeEntry* list, uint32_t n, uint32_t c
   return list[lo];
 }
 
+// the draw that owns global triangle `gtri` (draws are consecutive ranges [tri_base, tri_base + tri_count))
+template <class D> VKR_DEV uint32_t draw_of(const D* draws, uint32_t count, uint32_t gtri) {
+  uint32_t lo = 0, hi = count - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (draws[mid].tri_base <= gtri) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ---- the tail of triangle setup (cubemap.hip, shadow.hip) ----
+// planes of the clip volume that p lies outside of: x < -w, x > w, y < -w, y > w, z < 0.  A triangle whose three masks share a
+// bit cannot cover a texel centre
+VKR_DEV uint32_t frustum_out_mask(f4 p) {
+  return (p.x < -p.w ? 1u : 0u) | (p.x > p.w ? 2u : 0u) | (p.y < -p.w ? 4u : 0u) | (p.y > p.w ? 8u : 0u) | (p.z < 0.0f ? 16u : 0u);
+}
+// Snaps the clip positions of three clipped corners and normalises the orientation (cull none: both windings are drawn):
+// fills x, y, z, w and inv_area2 of a record.  false: a corner is behind the eye or beyond the guard band, or the area is 0.
+// *flip: corners 1 and 2 were exchanged; the caller exchanges its other attributes likewise.
+VKR_DEV bool snap_orient(f4 c0, f4 c1, f4 c2, int width, int height, int (&x)[3], int (&y)[3], float (&z)[3], float (&w)[3],
+                         double* inv_area2, bool* flip) {
+  bool ok = snap_vertex(c0, width, height, &x[0], &y[0], &w[0], &z[0]);
+  ok = snap_vertex(c1, width, height, &x[1], &y[1], &w[1], &z[1]) && ok;
+  ok = snap_vertex(c2, width, height, &x[2], &y[2], &w[2], &z[2]) && ok;
+  if (!ok) return false;
+  long long area2 = edge_fn(x[0], y[0], x[1], y[1], x[2], y[2]);
+  if (area2 == 0) return false;
+  *flip = area2 < 0;
+  if (*flip) {
+    int ti = x[1]; x[1] = x[2]; x[2] = ti;
+    ti = y[1]; y[1] = y[2]; y[2] = ti;
+    float tf = w[1]; w[1] = w[2]; w[2] = tf;
+    tf = z[1]; z[1] = z[2]; z[2] = tf;
+    area2 = -area2;
+  }
+  *inv_area2 = 1.0 / (double)area2;
+  return true;
+}
+// Lists record `rec`, whose bounding box touches nb blocks.  A large record takes a list slot AND its range of chunks with
+// one 64-bit atomicAdd on *large_state (entries << 32 | chunks), so the large list is sorted by first_chunk
+VKR_DEV void list_append(uint32_t rec, int nb, unsigned long long* large_state, LargeEntry* large_list, unsigned long long* small_count,
+                         uint32_t* small_list) {
+  if (nb > RASTER_SMALL_BLOCKS) {
+    const uint32_t chunks = (uint32_t)(nb + RASTER_LARGE_CHUNK - 1) / RASTER_LARGE_CHUNK;
+    const unsigned long long v = atomicAdd(large_state, (1ull << 32) | (unsigned long long)chunks);
+    large_list[(uint32_t)(v >> 32)] = LargeEntry {rec, (uint32_t)v};
+  } else {
+    small_list[(uint32_t)atomicAdd(small_count, 1ull)] = rec;
+  }
+}
+
+// ---- the coverage stage ----
+// What coverage and depth need of a record, copied into registers once per triangle: the rasterising waves issue atomics
+// between their reads of the record, and the compiler must otherwise assume those change it and reload.
+struct CoverTri {
+  int x[3], y[3];
+  float z[3];
+  double inv_area2;
+  template <class T> VKR_DEV explicit CoverTri(const T& t) : x {t.x[0], t.x[1], t.x[2]}, y {t.y[0], t.y[1], t.y[2]}, z {t.z[0], t.z[1], t.z[2]}, inv_area2 {t.inv_area2} {}
+};
+// One wave walks the 8x8 texel blocks [first, first + count) of t's bounding box in the width x height viewport (row-major
+// inside the box, cut off at its last block), one texel per lane, and calls frag(px, py, lambda, d24) for every covered
+// texel; what a fragment does (alpha test, which atomic, where) is the program's.  A box of more than max_blocks is not walked.
+template <class F>
+VKR_DEV void walk_blocks(const CoverTri& t, int width, int height, int first, int count, int max_blocks, int lane, const F& frag) {
+  int x0, y0, x1, y1;
+  if (!tri_bbox(t, width, height, &x0, &y0, &x1, &y1)) return;
+  const int nb = bbox_blocks(x0, y0, x1, y1);
+  if (nb > max_blocks) return;
+  const int bw = (x1 >> 3) - (x0 >> 3) + 1;
+  const int end = count < nb - first ? first + count : nb;
+  for (int b = first; b < end; b++) {
+    const int bx0 = ((x0 >> 3) + b % bw) << 3, by0 = ((y0 >> 3) + b / bw) << 3;
+    if (block_outside(t, bx0, by0)) continue;
+    const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
+    if (px < x0 || px > x1 || py < y0 || py > y1) continue;  // the bounding box is clipped to the viewport: the texel exists
+    float lambda[3];
+    uint32_t d24;
+    if (cover(t, px, py, lambda, &d24)) frag(px, py, lambda, d24);
+  }
+}
+// The coverage kernels are launched with COVER_BLOCK threads (the kernels' launch bounds and the entry points' launches both
+// use the constant).  This wave's index among the waves of such a launch, and their number: the stride of a loop over a list
+#define COVER_BLOCK_WAVES 4u
+#define COVER_BLOCK (64u * COVER_BLOCK_WAVES)
+VKR_DEV uint32_t wave_index() { return blockIdx.x * COVER_BLOCK_WAVES + (threadIdx.x >> 6); }
+VKR_DEV uint32_t wave_count() { return gridDim.x * COVER_BLOCK_WAVES; }
+
+// ---- host side ----
 // c = a * b with GLSL's mat4 * mat4 (column-major, each element a dot product accumulated left to right)
 inline void mat_mul(Mat4& c, const vkr_mat4& a, const vkr_mat4& b) {
   for (int col = 0; col < 4; col++)
@@ -180,5 +295,79 @@ inline void mat_mul(Mat4& c, const vkr_mat4& a, const vkr_mat4& b) {
 }
 
 inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+// A program's scratch is its parts one after the other, each padded to 256 bytes.  The program writes the sequence of take()
+// calls once, in its layout struct; the size function reads `at` of it, the entry point the offsets: they cannot disagree.
+struct ScratchCarver {
+  uint64_t at = 0;
+  uint64_t take(uint64_t bytes) { const uint64_t offset = at; at += align_up(bytes, 256); return offset; }
+};
+
+// A table (draw constants, texture pyramids) travels as kernel arguments, N elements per launch, into scratch: no host staging
+// memory has to outlive the call and nothing synchronises
+template <class T, int N> struct TableChunk { T e[N]; };
+template <class T, int N> __global__ void k_store_table(TableChunk<T, N> c, T* dst, uint32_t n) {
+  if (threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
+}
+template <int N, class T> inline void store_table(const std::vector<T>& src, const T* dst, hipStream_t stream) {
+  const uint32_t count = (uint32_t)src.size();
+  for (uint32_t i = 0; i < count; i += N) {
+    TableChunk<T, N> c;
+    const uint32_t n = count - i < (uint32_t)N ? count - i : (uint32_t)N;
+    for (uint32_t k = 0; k < (uint32_t)N; k++) c.e[k] = src[i + (k < n ? k : 0)];  // the tail repeats an element: defined bytes
+    hipLaunchKernelGGL((k_store_table<T, N>), dim3(1), dim3(64), 0, stream, c, const_cast<T*>(dst) + i, n);
+  }
+}
+
+// the mip chains of scene->textures as the sampler reads them
+inline int make_pyramids(const vkr_raster_scene* scene, const char* program, std::vector<Pyramid>* out) {
+  if (scene->texture_count && !scene->textures) {
+    set_error("%s: scene: %u textures but a NULL texture array", program, scene->texture_count);
+    return VKR_ERR_NULL;
+  }
+  const std::string what = std::string(program) + ".texture";
+  out->resize(scene->texture_count);
+  for (uint32_t i = 0; i < scene->texture_count; i++) {
+    const vkr_img& t = scene->textures[i];
+    Pyramid& p = (*out)[i];
+    if (t.mip_count < 1 || t.mip_count > VKR_MAX_MIPS) { set_error("%s: texture %u: bad mip count", program, i); return VKR_ERR_MIPS; }
+    p.count = (int)t.mip_count;
+    for (int m = 0; m < (int)t.mip_count; m++) VKR_TRY(make_tex(&t, m, VKR_FMT_RGBA8_SRGB, what.c_str(), &p.mip[m]));
+    for (int m = (int)t.mip_count; m < 16; m++) p.mip[m] = p.mip[0];
+  }
+  return VKR_OK;
+}
+
+// What every entry point checks of a scene before it launches anything: the arrays exist when there are draws, and every draw
+// stays inside them (the index range in 64 bits: offset + count of two uint32_t can wrap).  wants_textures: the program reads
+// the textures, so both texture indices of a draw are checked too (0xFFFFFFFF: none) — also the material index for the cube
+// bake, which samples only albedo: a scene is valid or not, whichever program sees it.  *total_tris: every triangle of the scene.
+inline int check_scene(const char* program, const vkr_raster_scene* scene, bool wants_textures, uint64_t* total_tris) {
+  if (scene->draw_count && (!scene->draws || !scene->transforms || !scene->vertices || !scene->indices)) {
+    set_error("%s: scene: %u draws but a NULL vertex, index, transform or draw array", program, scene->draw_count);
+    return VKR_ERR_NULL;
+  }
+  *total_tris = 0;
+  for (uint32_t i = 0; i < scene->draw_count; i++) {
+    const vkr_raster_draw& s = scene->draws[i];
+    if (s.transform_index >= scene->transform_count) {
+      set_error("%s: scene: draw %u: transform_index %u outside the %u transforms", program, i, s.transform_index, scene->transform_count);
+      return VKR_ERR_EXTENT;
+    }
+    if ((uint64_t)s.index_offset + s.index_count > scene->index_count) {
+      set_error("%s: scene: draw %u: indices [%u, +%u) outside the %u indices", program, i, s.index_offset, s.index_count, scene->index_count);
+      return VKR_ERR_EXTENT;
+    }
+    const bool bad_albedo = s.albedo_index != 0xFFFFFFFFu && s.albedo_index >= scene->texture_count;
+    const bool bad_material = s.mr_index != 0xFFFFFFFFu && s.mr_index >= scene->texture_count;
+    if (wants_textures && (bad_albedo || bad_material)) {
+      set_error("%s: scene: draw %u: texture index (albedo %u, material %u) outside the %u textures", program, i, s.albedo_index, s.mr_index,
+                scene->texture_count);
+      return VKR_ERR_EXTENT;
+    }
+    *total_tris += s.index_count / 3u;
+  }
+  return VKR_OK;
+}
 
 }  // namespace vkr

@@ -8,7 +8,7 @@
 // 24-bit depth and unsigned min is LESS_OR_EQUAL).  All layers of one call go through ONE set of launches, the layer is a
 // dimension of every grid, and each layer has its own lists.
 //
-//   k_shadow_store_draws  per-(layer, draw) constants (mvp = light matrix * model, multiplied on the host) -> scratch
+//   k_store_table          per-(layer, draw) constants (mvp = light matrix * model, multiplied on the host) -> scratch
 //   k_shadow_clear        grid (texels, layer): every texel of the layer := 0x00FFFFFF (depth 1, stencil 0); list counters := 0
 //   k_shadow_setup        one thread per (triangle, layer): vertex shader on the three corners, frustum rejection, near-plane
 //                         clip (up to two sub-triangles), snap, orientation -> ShadowTri records (48 B: snapped positions, z / w,
@@ -17,9 +17,7 @@
 //                         (bounding box of at most 64 blocks of 8x8 texels) or to its large list (chunks of 16 blocks).
 //   k_shadow_small        grid (waves, layer): the waves walk the layer's small list, one record per wave at a time
 //   k_shadow_large        grid (waves, layer): the chunks of the layer's large list, dealt round-robin to the waves
-//                         both: cover() of raster_common.hpp, then the atomicMin of the D24 word
-#include <vector>
-
+//                         both: walk_blocks() of raster_common.hpp, the fragment is the atomicMin of the D24 word
 #include "raster_common.hpp"
 
 namespace vkr {
@@ -58,20 +56,6 @@ struct ShadowArgs {
   int size;
 };
 
-VKR_DEV uint32_t shadow_draw_of(const ShadowDraw* draws, uint32_t draw_count, uint32_t gtri) {
-  uint32_t lo = 0, hi = draw_count - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (draws[mid].tri_base <= gtri) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-struct ShadowDrawChunk { ShadowDraw d[32]; };
-__global__ void k_shadow_store_draws(ShadowDrawChunk c, ShadowDraw* dst, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = c.d[threadIdx.x];
-}
-
 // grid (ceil(size * size / 256), layer)
 __global__ __launch_bounds__(256) void k_shadow_clear(ShadowArgs a) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,7 +76,7 @@ __global__ __launch_bounds__(256) void k_shadow_setup(ShadowArgs a) {
   const uint32_t layer = blockIdx.y;
   if (gtri >= a.total_tris) return;
   const ShadowDraw* draws = a.draws + (size_t)layer * a.draw_count;
-  const ShadowDraw& d = draws[shadow_draw_of(draws, a.draw_count, gtri)];
+  const ShadowDraw& d = draws[draw_of(draws, a.draw_count, gtri)];
   const uint32_t tri = gtri - d.tri_base;
   float in[3][SV_N], poly[4][SV_N];
   uint32_t out_mask = 0x1Fu;  // planes every corner so far lies outside of: x < -w, x > w, y < -w, y > w, z < 0
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(256) void k_shadow_setup(ShadowArgs a) {
     const vkr_raster_vertex v = a.vertices[vi];
     const f4 p = mul(d.mvp, mk4(v.pos[0], v.pos[1], v.pos[2], 1.0f));
     in[k][SV_X] = p.x; in[k][SV_Y] = p.y; in[k][SV_Z] = p.z; in[k][SV_W] = p.w;
-    out_mask &= (p.x < -p.w ? 1u : 0u) | (p.x > p.w ? 2u : 0u) | (p.y < -p.w ? 4u : 0u) | (p.y > p.w ? 8u : 0u) | (p.z < 0.0f ? 16u : 0u);
+    out_mask &= frustum_out_mask(p);
   }
   if (out_mask) return;  // wholly outside the layer's frustum: no texel centre can be covered
   const int n = clip_near<SV_N, SV_Z>(in, poly);
@@ -111,96 +95,58 @@ __global__ __launch_bounds__(256) void k_shadow_setup(ShadowArgs a) {
   // the fan of the clipped polygon: (0, 1, 2) and, for a quad, (0, 2, 3); constant indices keep the polygon in registers
   auto emit = [&](const float (&c0)[SV_N], const float (&c1)[SV_N], const float (&c2)[SV_N], uint32_t sub) {
     ShadowTri t;
-    float w;  // clip w: depth has no perspective-correct attribute to divide by it
-    bool ok = snap_vertex(mk4(c0[SV_X], c0[SV_Y], c0[SV_Z], c0[SV_W]), a.size, a.size, &t.x[0], &t.y[0], &w, &t.z[0]);
-    ok = snap_vertex(mk4(c1[SV_X], c1[SV_Y], c1[SV_Z], c1[SV_W]), a.size, a.size, &t.x[1], &t.y[1], &w, &t.z[1]) && ok;
-    ok = snap_vertex(mk4(c2[SV_X], c2[SV_Y], c2[SV_Z], c2[SV_W]), a.size, a.size, &t.x[2], &t.y[2], &w, &t.z[2]) && ok;
-    if (!ok) return;
-    long long area2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], t.x[2], t.y[2]);
-    if (area2 == 0) return;
-    if (area2 < 0) {  // cull none: both windings are drawn; normalise the orientation
-      int ti = t.x[1]; t.x[1] = t.x[2]; t.x[2] = ti;
-      ti = t.y[1]; t.y[1] = t.y[2]; t.y[2] = ti;
-      const float tf = t.z[1]; t.z[1] = t.z[2]; t.z[2] = tf;
-      area2 = -area2;
-    }
+    float w[3];  // clip w: depth has no perspective-correct attribute to divide by it
+    bool flip;   // and none to exchange with the corners
+    const f4 p0 = mk4(c0[SV_X], c0[SV_Y], c0[SV_Z], c0[SV_W]), p1 = mk4(c1[SV_X], c1[SV_Y], c1[SV_Z], c1[SV_W]);
+    const f4 p2 = mk4(c2[SV_X], c2[SV_Y], c2[SV_Z], c2[SV_W]);
+    if (!snap_orient(p0, p1, p2, a.size, a.size, t.x, t.y, t.z, w, &t.inv_area2, &flip)) return;
     t.pad = 0u;
-    t.inv_area2 = 1.0 / (double)area2;
     int bx0, by0, bx1, by1;
     if (!tri_bbox(t, a.size, a.size, &bx0, &by0, &bx1, &by1)) return;  // no texel centre inside the bounding box
     const uint32_t rec = gtri * 2u + sub;
     a.setup[layer * per_layer + rec] = t;
-    const int nb = bbox_blocks(bx0, by0, bx1, by1);
-    if (nb > RASTER_SMALL_BLOCKS) {
-      const uint32_t chunks = (uint32_t)(nb + RASTER_LARGE_CHUNK - 1) / RASTER_LARGE_CHUNK;
-      const unsigned long long v = atomicAdd(&a.state[layer * 2u], (1ull << 32) | (unsigned long long)chunks);
-      a.large_list[layer * per_layer + (uint32_t)(v >> 32)] = LargeEntry {rec, (uint32_t)v};
-    } else {
-      a.small_list[layer * per_layer + (uint32_t)atomicAdd(&a.state[layer * 2u + 1u], 1ull)] = rec;
-    }
+    unsigned long long* state = a.state + layer * 2u;  // [0] large, [1] small
+    list_append(rec, bbox_blocks(bx0, by0, bx1, by1), &state[0], a.large_list + layer * per_layer, &state[1], a.small_list + layer * per_layer);
   };
   if (n >= 3) emit(poly[0], poly[1], poly[2], 0u);
   if (n >= 4) emit(poly[0], poly[2], poly[3], 1u);
 }
 
-// a record in registers (the waves issue atomics between their reads of it)
-struct ShadowCover {
-  int x[3], y[3];
-  float z[3];
-  double inv_area2;
-  VKR_DEV explicit ShadowCover(const ShadowTri& t) : x {t.x[0], t.x[1], t.x[2]}, y {t.y[0], t.y[1], t.y[2]}, z {t.z[0], t.z[1], t.z[2]}, inv_area2 {t.inv_area2} {}
-};
-
-// 8x8 texel block `b` (row-major inside the bounding box) of a record, one texel per lane
-VKR_DEV void shadow_block(const ShadowLayer& L, const ShadowCover& t, int x0, int y0, int x1, int y1, int b, int lane) {
-  const int bw = (x1 >> 3) - (x0 >> 3) + 1;
-  const int bx0 = ((x0 >> 3) + b % bw) << 3, by0 = ((y0 >> 3) + b / bw) << 3;
-  if (block_outside(t, bx0, by0)) return;
-  const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
-  if (px < x0 || px > x1 || py < y0 || py > y1) return;  // the bounding box is clipped to the layer: the texel exists
-  float lambda[3];
-  uint32_t d24;
-  if (!cover(t, px, py, lambda, &d24)) return;
-  uint32_t* texel = (uint32_t*)(L.p + (size_t)py * (size_t)L.pitch) + px;
-  // No read of the texel first.  A plain (cacheable, possibly stale) load could skip the atomic when d24 >= loaded — a texel only
-  // decreases during a call, so a stale value is >= the current one and the skip would be right — but the load's latency then
-  // sits in every iteration of the wave's loop over its blocks, which a no-return atomic does not: measured 10 - 16 % slower on
-  // the procedural scene.
-  atomicMin(texel, d24);  // result unused: a no-return atomic.  A tie stores the same word, so LESS and LESS_OR_EQUAL agree
+// the fragment of a covered texel of layer L: its depth
+VKR_DEV auto shadow_fragment(const ShadowLayer& L) {
+  return [&L](int px, int py, const float*, uint32_t d24) {
+    uint32_t* texel = (uint32_t*)(L.p + (size_t)py * (size_t)L.pitch) + px;
+    // No read of the texel first.  A plain (cacheable, possibly stale) load could skip the atomic when d24 >= loaded — a texel only
+    // decreases during a call, so a stale value is >= the current one and the skip would be right — but the load's latency then
+    // sits in every iteration of the wave's loop over its blocks, which a no-return atomic does not: measured 10 - 16 % slower on
+    // the procedural scene.
+    atomicMin(texel, d24);  // result unused: a no-return atomic.  A tie stores the same word, so LESS and LESS_OR_EQUAL agree
+  };
 }
 
-__global__ __launch_bounds__(256) void k_shadow_small(ShadowArgs a) {
+__global__ __launch_bounds__(COVER_BLOCK) void k_shadow_small(ShadowArgs a) {
   const uint32_t layer = blockIdx.y;
   const size_t base = (size_t)layer * 2u * a.total_tris;
   const ShadowLayer L = a.layer[layer];
   const uint32_t n = (uint32_t)a.state[layer * 2u + 1u];
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t i = wave; i < n; i += waves) {
-    const ShadowCover t(a.setup[base + a.small_list[base + i]]);
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.size, a.size, &x0, &y0, &x1, &y1)) continue;
-    const int nb = bbox_blocks(x0, y0, x1, y1);
-    for (int b = 0; b < nb; b++) shadow_block(L, t, x0, y0, x1, y1, b, lane);
+  for (uint32_t i = wave_index(); i < n; i += wave_count()) {
+    const CoverTri t(a.setup[base + a.small_list[base + i]]);
+    walk_blocks(t, a.size, a.size, 0, INT_MAX, INT_MAX, lane, shadow_fragment(L));
   }
 }
 
-__global__ __launch_bounds__(256) void k_shadow_large(ShadowArgs a) {
+__global__ __launch_bounds__(COVER_BLOCK) void k_shadow_large(ShadowArgs a) {
   const uint32_t layer = blockIdx.y;
   const size_t base = (size_t)layer * 2u * a.total_tris;
   const ShadowLayer L = a.layer[layer];
   const unsigned long long st = a.state[layer * 2u];
   const uint32_t n = (uint32_t)(st >> 32), chunks = (uint32_t)st;
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t c = wave; c < chunks; c += waves) {
+  for (uint32_t c = wave_index(); c < chunks; c += wave_count()) {
     const LargeEntry e = large_entry_of(a.large_list + base, n, c);
-    const ShadowCover t(a.setup[base + e.rec]);
-    int x0, y0, x1, y1;
-    if (!tri_bbox(t, a.size, a.size, &x0, &y0, &x1, &y1)) continue;
-    const int nb = bbox_blocks(x0, y0, x1, y1);
-    const int b0 = (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, b1 = min(b0 + RASTER_LARGE_CHUNK, nb);
-    for (int b = b0; b < b1; b++) shadow_block(L, t, x0, y0, x1, y1, b, lane);
+    const CoverTri t(a.setup[base + e.rec]);
+    walk_blocks(t, a.size, a.size, (int)(c - e.first_chunk) * RASTER_LARGE_CHUNK, RASTER_LARGE_CHUNK, INT_MAX, lane, shadow_fragment(L));
   }
 }
 
@@ -208,15 +154,25 @@ __global__ __launch_bounds__(256) void k_shadow_large(ShadowArgs a) {
 
 using namespace vkr;
 
-static uint64_t shadow_records(uint32_t layer_count, uint32_t triangle_count) { return 2ull * layer_count * triangle_count; }
+struct ShadowLayout {  // offsets of the parts of the scratch, and its size
+  uint64_t draws, state, setup, small_list, large_list, total;
+  ShadowLayout(uint32_t layer_count, uint32_t triangle_count) {
+    const uint64_t recs = 2ull * layer_count * triangle_count;
+    ScratchCarver c;
+    draws = c.take(sizeof(ShadowDraw) * SHADOW_MAX_DRAWS * (uint64_t)layer_count);
+    state = c.take(256);
+    setup = c.take(sizeof(ShadowTri) * recs);
+    small_list = c.take(sizeof(uint32_t) * recs);
+    large_list = c.take(sizeof(LargeEntry) * recs);
+    total = c.at;
+  }
+};
 
 // (`size` takes no part today: the pass has no per-texel scratch.  It stays in the signature so that a caller sizes this pass
 // as it sizes the other rasterisers.)
 extern "C" uint64_t vkr_default_shadow_scratch_bytes(uint32_t size, uint32_t layer_count, uint32_t triangle_count) {
   (void)size;
-  const uint64_t recs = shadow_records(layer_count, triangle_count);
-  return align_up(sizeof(ShadowDraw) * SHADOW_MAX_DRAWS * (uint64_t)layer_count, 256) + 256u + align_up(sizeof(ShadowTri) * recs, 256) +
-         align_up(sizeof(uint32_t) * recs, 256) + align_up(sizeof(LargeEntry) * recs, 256);
+  return ShadowLayout(layer_count, triangle_count).total;
 }
 
 extern "C" int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4* mvps, const vkr_img* layers, uint32_t layer_count,
@@ -228,10 +184,6 @@ extern "C" int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4*
   if (!scratch) { set_error("default_shadow: scratch is NULL"); return VKR_ERR_NULL; }
   if (layer_count < 1 || layer_count > SHADOW_MAX_LAYERS) { set_error("default_shadow: layer_count %u, expected 1..%u", layer_count, SHADOW_MAX_LAYERS); return VKR_ERR_EXTENT; }
   if (scene->draw_count > SHADOW_MAX_DRAWS) { set_error("default_shadow: scene has %u draws, at most %u", scene->draw_count, SHADOW_MAX_DRAWS); return VKR_ERR_EXTENT; }
-  if (scene->draw_count && (!scene->draws || !scene->transforms || !scene->vertices || !scene->indices)) {
-    set_error("default_shadow: scene has draws but a NULL vertex, index, transform or draw array");
-    return VKR_ERR_NULL;
-  }
   ShadowArgs r;
   std::memset(&r, 0, sizeof(r));
   Tex first;
@@ -249,20 +201,10 @@ extern "C" int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4*
   }
   const int S = first.w;
   uint64_t total_tris = 0;
-  for (uint32_t i = 0; i < scene->draw_count; i++) {
-    const vkr_raster_draw& s = scene->draws[i];
-    if (s.transform_index >= scene->transform_count) {
-      set_error("default_shadow: scene: draw %u: transform_index %u outside the %u transforms", i, s.transform_index, scene->transform_count);
-      return VKR_ERR_EXTENT;
-    }
-    if ((uint64_t)s.index_offset + s.index_count > scene->index_count) {
-      set_error("default_shadow: scene: draw %u: indices [%u, +%u) outside the %u indices", i, s.index_offset, s.index_count, scene->index_count);
-      return VKR_ERR_EXTENT;
-    }
-    total_tris += s.index_count / 3u;
-  }
+  VKR_TRY(check_scene("default_shadow", scene, false, &total_tris));  // default.frag reads no texture
   if (total_tris * 2u * SHADOW_MAX_LAYERS >= (1ull << 31)) { set_error("default_shadow: scene: too many triangles"); return VKR_ERR_EXTENT; }
-  const uint64_t need = vkr_default_shadow_scratch_bytes((uint32_t)S, layer_count, (uint32_t)total_tris);
+  const ShadowLayout lay(layer_count, (uint32_t)total_tris);
+  const uint64_t need = lay.total;
   if (scratch_bytes < need) { set_error("default_shadow: scratch too small (%llu bytes, %llu needed)", (unsigned long long)scratch_bytes, (unsigned long long)need); return VKR_ERR_EXTENT; }
   // per-(layer, draw) constants: mvp * model exactly as default.vert multiplies them; draws without a triangle are left out
   std::vector<ShadowDraw> draws;
@@ -281,30 +223,25 @@ extern "C" int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4*
     }
     if (l == 0) draw_count = (uint32_t)draws.size();
   }
-  const uint64_t recs = shadow_records(layer_count, (uint32_t)total_tris);
   r.vertices = scene->vertices; r.indices = scene->indices;
-  uint8_t* at = (uint8_t*)scratch;
-  r.draws = (const ShadowDraw*)at; at += align_up(sizeof(ShadowDraw) * SHADOW_MAX_DRAWS * (uint64_t)layer_count, 256);
-  r.state = (unsigned long long*)at; at += 256;
-  r.setup = (ShadowTri*)at; at += align_up(sizeof(ShadowTri) * recs, 256);
-  r.small_list = (uint32_t*)at; at += align_up(sizeof(uint32_t) * recs, 256);
-  r.large_list = (LargeEntry*)at;
+  uint8_t* const at = (uint8_t*)scratch;
+  r.draws = (const ShadowDraw*)(at + lay.draws);
+  r.state = (unsigned long long*)(at + lay.state);
+  r.setup = (ShadowTri*)(at + lay.setup);
+  r.small_list = (uint32_t*)(at + lay.small_list);
+  r.large_list = (LargeEntry*)(at + lay.large_list);
   r.draw_count = draw_count; r.total_tris = (uint32_t)total_tris; r.vertex_count = scene->vertex_count;
   r.size = S;
-  for (uint32_t i = 0; i < (uint32_t)draws.size(); i += 32) {
-    ShadowDrawChunk c;
-    const uint32_t n = (uint32_t)draws.size() - i < 32u ? (uint32_t)draws.size() - i : 32u;
-    for (uint32_t k = 0; k < 32; k++) c.d[k] = draws[i + (k < n ? k : 0)];
-    hipLaunchKernelGGL(k_shadow_store_draws, dim3(1), dim3(64), 0, stream, c, const_cast<ShadowDraw*>(r.draws) + i, n);
-  }
+  store_table<32>(draws, r.draws, stream);
   const uint32_t npx = (uint32_t)S * (uint32_t)S;
   hipLaunchKernelGGL(k_shadow_clear, dim3((npx + 255u) / 256u, layer_count), dim3(256), 0, stream, r);
   if (total_tris && draw_count) {
     hipLaunchKernelGGL(k_shadow_setup, dim3(((uint32_t)total_tris + 255u) / 256u, layer_count), dim3(256), 0, stream, r);
     const uint64_t waves = 2ull * total_tris;
-    const unsigned grid = (unsigned)(waves / 4 + 1 < SHADOW_RASTER_GRID ? waves / 4 + 1 : SHADOW_RASTER_GRID);
-    hipLaunchKernelGGL(k_shadow_small, dim3(grid, layer_count), dim3(256), 0, stream, r);
-    hipLaunchKernelGGL(k_shadow_large, dim3(grid, layer_count), dim3(256), 0, stream, r);
+    const uint64_t blocks = waves / COVER_BLOCK_WAVES + 1;
+    const unsigned grid = (unsigned)(blocks < SHADOW_RASTER_GRID ? blocks : SHADOW_RASTER_GRID);
+    hipLaunchKernelGGL(k_shadow_small, dim3(grid, layer_count), dim3(COVER_BLOCK), 0, stream, r);
+    hipLaunchKernelGGL(k_shadow_large, dim3(grid, layer_count), dim3(COVER_BLOCK), 0, stream, r);
   }
   return launch_status("default_shadow");
 }
