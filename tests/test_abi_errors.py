@@ -233,3 +233,47 @@ def test_emulated_communicator_rules(lib):
     scratch = (C.c_uint8 * 16)()
     assert lib.vkr_comm_selfcheck(h, scratch, None) != 0 and b"emulated" in lib.vkr_last_error()
     assert lib.vkr_comm_destroy(h) == 0
+
+
+# ---- the whole-frame depth pyramid of the Hi-Z tracers (bind_depth_pyramid, csrc/vkr_host.hpp) ---------------------------
+def _trace_call(lib, program, depth):
+    """the tracer `program` with valid 64x64 bindings around the given pyramid descriptor"""
+    w = h = 64
+    normal, material = img(abi.FMT_RG16_UNORM, w, h), img(abi.FMT_RGBA8_SRGB, w, h)
+    rays, occ = img(abi.FMT_RGBA16_UNORM, w, h), img(abi.FMT_RGBA16_SFLOAT, w, h)
+    halton = (C.c_float * (4 * abi.HALTON_SEQ_SIZE + 4))()
+    hp = (C.addressof(halton) + 15) & ~15
+    params = abi.TraceParams()
+    if program == "sssr_trace":
+        pdf, push = img(abi.FMT_R32_SFLOAT, 64, 64), abi.TracePush(1.0)
+        rc = lib.vkr_sssr_trace(C.byref(depth), C.byref(normal), C.byref(material), C.byref(params), hp, C.byref(rays), C.byref(occ),
+                                C.byref(pdf), C.byref(push), None)
+    elif program == "sssr_trace_indirect":
+        push = abi.TraceIndirectPush(0, 1.0)
+        rc = lib.vkr_sssr_trace_indirect(C.byref(depth), C.byref(normal), C.byref(material), C.byref(params), hp, C.byref(rays), FAKE, FAKE,
+                                         64, C.byref(push), None)
+    else:
+        frame, out, sp = img(abi.FMT_RGBA8_SRGB, w, h), img(abi.FMT_RGBA8_UNORM, w, h), abi.SsrParams()
+        rc = lib.vkr_ssr(C.byref(normal), C.byref(depth), C.byref(frame), C.byref(sp), C.byref(material), C.byref(out), None)
+    return rc, (lib.vkr_last_error() or b"").decode()
+
+
+def _pyramid_with_mip_count(n):
+    d = img(abi.FMT_D24_UNORM_S8, 64, 64, mips=1)
+    d.mip_count = n
+    return d
+
+
+@pytest.mark.parametrize("program", ["sssr_trace", "sssr_trace_indirect", "ssr"])
+@pytest.mark.parametrize("case,depth,code", [
+    ("no mips", lambda: _pyramid_with_mip_count(0), ERR_MIPS),
+    ("too many mips", lambda: _pyramid_with_mip_count(abi.VKR_MAX_MIPS + 1), ERR_MIPS),
+    ("a window of a larger frame", lambda: img(abi.FMT_D24_UNORM_S8, 64, 32, full=(64, 64), origin=(0, 16)), ERR_EXTENT),
+    ("level 0 of 65536 texels", lambda: img(abi.FMT_D24_UNORM_S8, 65536, 4), ERR_EXTENT),
+])
+def test_tracers_refuse_a_bad_depth_pyramid(lib, program, case, depth, code):
+    """One rule for the three Hi-Z tracers: 1 .. VKR_MAX_MIPS levels, every level the whole frame and at most 65535 texels a
+    side; the message names the program and the binding."""
+    rc, msg = _trace_call(lib, program, depth())
+    assert rc == code, (case, rc, msg)
+    assert f"{program}.depth" in msg, (case, msg)

@@ -31,6 +31,10 @@ HOT = {
     # the resume launch is latency-bound (a tenth of the rays, 3 blocks per CU): registers are not what limits it
     "k_sssr_trace_resume<false, false>": ("ssr.hip", 256, 96, 0, 1024, 5),      # <WINDOWED, COMPACT>: single GPU, every lane its own ray
     "k_sssr_trace_resume<true, true>": ("ssr.hip", 256, 96, 0, 23 * 1024, 5),   # multi-GPU resume: compacted rounds
+    # the deferred hit-normal test of the windowed trace and the two dormant Hi-Z tracers, which share the march's set-up and hit tests
+    "k_sssr_validate": ("ssr.hip", 256, 24, 0, 0, 8),
+    "k_sssr_trace_indirect": ("ssr_indirect.hip", 64, 48, 0, 1280, 8),
+    "k_ssr_simple": ("ssr_simple.hip", 256, 56, 0, 1280, 8),
     "k_sssr_filter": ("ssr.hip", 256, 64, 0, 12 * 1024 + 256, 8),
     "k_sssr_blur": ("ssr.hip", 512, 128, 16, 48 * 1024, 4),
     "k_gtao_main<true, true>": ("gtao.hip", 1024, 64, 0, 21 * 1024, 8),   # 16-wave blocks: > 64 VGPRs means ONE block per CU
@@ -43,6 +47,8 @@ HOT = {
     "k_taa_resolve<true, false>": ("taa.hip", 256, 64, 0, 2048, 8),
     "k_taa_resolve<false, false>": ("taa.hip", 256, 64, 0, 2048, 8),
 }
+
+NO_SPILLS = {"k_sssr_validate", "k_sssr_trace_indirect", "k_ssr_simple"}  # neither VGPRs to scratch nor SGPRs to VGPRs
 
 
 def resident_waves_per_simd(threads, vgprs, lds_bytes):
@@ -75,6 +81,8 @@ def test_hot_kernel_resources(res, kernel):
     assert r["vgprs"] <= max_vgprs, f"{kernel}: {r['vgprs']} VGPRs > {max_vgprs}"
     assert r["scratch_bytes"] <= max_scratch, f"{kernel}: {r['scratch_bytes']} B of scratch per lane (limit {max_scratch}): a spill on the hot path"
     assert r["lds_bytes"] <= max_lds, f"{kernel}: {r['lds_bytes']} B of LDS per block > {max_lds}"
+    if kernel in NO_SPILLS:
+        assert (r.get("vgpr_spill", 0), r.get("sgpr_spill", 0)) == (0, 0), f"{kernel}: spills {r.get('vgpr_spill')} VGPRs / {r.get('sgpr_spill')} SGPRs"
     waves = resident_waves_per_simd(threads, r["vgprs"], r["lds_bytes"])
     assert waves >= min_waves, f"{kernel}: {waves} resident waves per SIMD < {min_waves} ({r['vgprs']} VGPRs, {r['lds_bytes']} B LDS, {threads} threads per block)"
 

@@ -385,8 +385,7 @@ extern "C" int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img*
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "gtao_rt_main.out", &a.out));
   if (((uintptr_t)directions & 15u) != 0) { set_error("gtao_rt_main: directions must be 16-byte aligned"); return VKR_ERR_LAYOUT; }
   load_mat(a.camera_to_world, params->camera_to_world);
-  a.pr.tg = tanf(params->fovy / 2.0f);
-  a.pr.aspect = params->aspect; a.pr.znear = params->znear; a.pr.zfar = params->zfar;
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   const float PI = 3.1415926535897932384626433832795f;
   for (int k = 0; k < 16; k++) {  // rt_main.frag:89: angle = 2 PI (rotation + gtao_direction(pixel))
     const float angle = (2.0f * PI) * (push->rotation + (1.0f / 16.0f) * (float)k);

@@ -313,8 +313,7 @@ extern "C" int vkr_gtao_main(const vkr_img* depth, const vkr_gtao_params* params
   VKR_TRY(make_tex(pdf_tex, 0, VKR_FMT_R32_SFLOAT, "gtao_main.pdf", &a.pdf));
   VKR_TRY(make_tex(gtao_inout, 0, VKR_FMT_RGBA16_SFLOAT, "gtao_main.gtao_out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
-  a.pr.tg = tanf(params->fovy / 2.0f);
-  a.pr.aspect = params->aspect; a.pr.znear = params->znear; a.pr.zfar = params->zfar;
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   a.tex_w = (a.out.fw / 8) * 8;
   a.tex_h = (a.out.fh / 4) * 4;
   a.weight_ratio = push->weight_ratio;
@@ -368,10 +367,7 @@ extern "C" int vkr_gtao_accumulate(const vkr_img* depth, const vkr_img* prev_dep
   VKR_TRY(make_tex(history, 0, VKR_FMT_RG16_SFLOAT, "gtao_accumulate.history", &a.history));
   load_mat(a.prev_inverse_camera, params->prev_inverse_camera);
   load_mat(a.mvp, params->mvp);
-  a.pr.tg = tanf(params->fovy_aspect_znear_zfar[0] / 2.0f);
-  a.pr.aspect = params->fovy_aspect_znear_zfar[1];
-  a.pr.znear = params->fovy_aspect_znear_zfar[2];
-  a.pr.zfar = params->fovy_aspect_znear_zfar[3];
+  load_proj(a.pr, params->fovy_aspect_znear_zfar);
   a.clear_history = push->clear_history;
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_gtao_accumulate, grid2d(a.out.w, a.out.h, block), block, 0, (hipStream_t)stream, a);

@@ -30,6 +30,38 @@ struct MarchEnv {
   int local_levels = 0;
 };
 enum { MARCH_END = 0, MARCH_MORE = 1, MARCH_PARK = 2 };
+// The quotients of a march that are the same for every ray of a frame, divided once on the host (IEEE, as a thread would):
+// 1 / screen_size and 0.005 * 2^min_mip / screen_size (screen_trace.glsl:10,20 at most_detailed_mip = min_mip).
+struct MarchQuotients { f2 screen_size_inv, uv_offset_abs; };
+inline void load_march_quotients(MarchQuotients& q, const Tex& level0, int min_mip) {
+  const float sw = (float)level0.fw, sh = (float)level0.fh, uvo = 0.005f * ldexpf(1.0f, min_mip);
+  q.screen_size_inv.x = 1.0f / sw; q.screen_size_inv.y = 1.0f / sh;
+  q.uv_offset_abs.x = uvo / sw; q.uv_offset_abs.y = uvo / sh;
+}
+// the environment of a whole-frame march (a LOCAL one adds win_table and local_levels); horizon_d2 is 0 where there is no horizon
+VKR_DEV MarchEnv march_env(const uint4* mip_table, int mip_count, const Tex& level0, const Proj& pr, const MarchQuotients& q, int min_mip,
+                           float horizon_d2) {
+  MarchEnv env;
+  env.mip_table = mip_table;
+  env.mip_count = mip_count;
+  env.screen_size = mk2((float)level0.fw, (float)level0.fh);
+  env.screen_size_inv = q.screen_size_inv;
+  env.uv_offset_abs = q.uv_offset_abs;
+  env.pr = pr;
+  env.horizon_d2 = horizon_d2;
+  env.min_mip = min_mip;
+  return env;
+}
+
+// The cell exit of advance_ray / initial_advance_ray (screen_trace.glsl:10-11,18-19): the uv planes on which the ray leaves the
+// texel of `mip_pos` on the level whose texel size is res_inv, moved uv_offset_abs beyond them along the ray.
+VKR_DEV f2 cell_exit(const MarchEnv& env, const RayConst& rc, f2 mip_pos, f2 res_inv) {
+  const f2 uv_offset = mk2(rc.direction.x < 0.0f ? -env.uv_offset_abs.x : env.uv_offset_abs.x,
+                           rc.direction.y < 0.0f ? -env.uv_offset_abs.y : env.uv_offset_abs.y);
+  const f2 floor_offset = mk2(rc.direction.x < 0.0f ? 0.0f : 1.0f, rc.direction.y < 0.0f ? 0.0f : 1.0f);
+  const f2 xy_plane = mk2(floorf(mip_pos.x), floorf(mip_pos.y)) + floor_offset;
+  return mk2(cfma(xy_plane.x, res_inv.x, uv_offset.x), cfma(xy_plane.y, res_inv.y, uv_offset.y));
+}
 
 // The horizon update of trace.comp:253-262: v = reconstruct_view_vec(uv, surface_z) - camera_start, h = max(h, cos) iff
 // |v| < 0.3.  z stays on the exact quotient (div_normal): v is a small difference of two view-space positions, so a
@@ -73,11 +105,7 @@ VKR_DEV int march_step_ex(const MarchEnv& env, const RayConst& rc, RayState& st,
     }
   }
   // advance_ray (screen_trace.glsl:17-45)
-  const f2 uv_offset = mk2(rc.direction.x < 0.0f ? -env.uv_offset_abs.x : env.uv_offset_abs.x,
-                           rc.direction.y < 0.0f ? -env.uv_offset_abs.y : env.uv_offset_abs.y);
-  const f2 floor_offset = mk2(rc.direction.x < 0.0f ? 0.0f : 1.0f, rc.direction.y < 0.0f ? 0.0f : 1.0f);
-  f2 xy_plane = mk2(floorf(mip_pos.x), floorf(mip_pos.y)) + floor_offset;
-  xy_plane = mk2(cfma(xy_plane.x, res_inv.x, uv_offset.x), cfma(xy_plane.y, res_inv.y, uv_offset.y));
+  const f2 xy_plane = cell_exit(env, rc, mip_pos, res_inv);
   f3 t = (mk3(xy_plane.x, xy_plane.y, surface_z) - rc.origin) * rc.inv_direction;
   t.z = rc.direction.z > 0.0f ? t.z : 3.402823466e+38f;
   const float t_min = vmin(vmin(t.x, t.y), t.z);
@@ -113,11 +141,7 @@ VKR_DEV bool march_step_pinned0(const MarchEnv& env, const RayConst& rc, RayStat
   } else {
     fetch0(f2i_index(mip_pos.x), f2i_index(mip_pos.y), &surface_z);
   }
-  const f2 uv_offset = mk2(rc.direction.x < 0.0f ? -env.uv_offset_abs.x : env.uv_offset_abs.x,
-                           rc.direction.y < 0.0f ? -env.uv_offset_abs.y : env.uv_offset_abs.y);
-  const f2 floor_offset = mk2(rc.direction.x < 0.0f ? 0.0f : 1.0f, rc.direction.y < 0.0f ? 0.0f : 1.0f);
-  f2 xy_plane = mk2(floorf(mip_pos.x), floorf(mip_pos.y)) + floor_offset;
-  xy_plane = mk2(cfma(xy_plane.x, env.screen_size_inv.x, uv_offset.x), cfma(xy_plane.y, env.screen_size_inv.y, uv_offset.y));
+  const f2 xy_plane = cell_exit(env, rc, mip_pos, env.screen_size_inv);
   f3 t = (mk3(xy_plane.x, xy_plane.y, surface_z) - rc.origin) * rc.inv_direction;
   t.z = rc.direction.z > 0.0f ? t.z : 3.402823466e+38f;
   const float t_min = vmin(vmin(t.x, t.y), t.z);
@@ -132,18 +156,19 @@ VKR_DEV uint4 mip_descriptor(const Tex& m) {
   const uint64_t base = (uint64_t)m.p;
   return make_uint4((uint32_t)base, (uint32_t)(base >> 32), (uint32_t)m.pitch, (uint32_t)m.w | ((uint32_t)m.h << 16));
 }
+// the level table of a block whose pyramid is whole-frame: the first 16 threads write it, the caller's barrier publishes it
+// (the descriptor is a load from the kernel arguments: every lane, with the others)
+VKR_DEV void stage_mip_table(const Pyramid& depth, int tid, uint4* s_mip) {
+  const int l = tid & 15;
+  const uint4 d = mip_descriptor(depth.mip[l < depth.count ? l : 0]);
+  if (tid < 16) s_mip[tid] = d;
+}
 // initial_advance_ray (screen_trace.glsl:8-15) on the resolution of most_detailed_mip (env.min_mip)
 VKR_DEV float initial_advance(const MarchEnv& env, const RayConst& rc) {
-  const f2 uv_offset = mk2(rc.direction.x < 0.0f ? -env.uv_offset_abs.x : env.uv_offset_abs.x,
-                           rc.direction.y < 0.0f ? -env.uv_offset_abs.y : env.uv_offset_abs.y);
-  const f2 floor_offset = mk2(rc.direction.x < 0.0f ? 0.0f : 1.0f, rc.direction.y < 0.0f ? 0.0f : 1.0f);
   const float scale = __builtin_ldexpf(1.0f, -env.min_mip), scale_inv = __builtin_ldexpf(1.0f, env.min_mip);
   const f2 res = mk2(env.screen_size.x * scale, env.screen_size.y * scale);
   const f2 res_inv = mk2(env.screen_size_inv.x * scale_inv, env.screen_size_inv.y * scale_inv);
-  const f2 cur_pos = res * xy(rc.origin);
-  f2 xy_plane = mk2(floorf(cur_pos.x), floorf(cur_pos.y)) + floor_offset;
-  xy_plane = mk2(cfma(xy_plane.x, res_inv.x, uv_offset.x), cfma(xy_plane.y, res_inv.y, uv_offset.y));
-  const f2 t = (xy_plane - xy(rc.origin)) * xy(rc.inv_direction);
+  const f2 t = (cell_exit(env, rc, res * xy(rc.origin), res_inv) - xy(rc.origin)) * xy(rc.inv_direction);
   return vmin(t.x, t.y);
 }
 VKR_DEV f3 safe_inverse(f3 d) {  // screen_trace.glsl:54-57

@@ -486,8 +486,7 @@ extern "C" int vkr_trace_probe(const vkr_img* depth, const vkr_img* normal, cons
   a.probe_step.x = (consts->probe_max[0] - consts->probe_min[0]) / gm1;
   a.probe_step.y = (consts->probe_max[1] - consts->probe_min[1]) / gm1;
   a.probe_step.z = (consts->probe_max[2] - consts->probe_min[2]) / gm1;
-  a.pr.tg = tanf(consts->fovy / 2.0f);
-  a.pr.aspect = consts->aspect; a.pr.znear = consts->znear; a.pr.zfar = consts->zfar;
+  load_proj(a.pr, consts->fovy, consts->aspect, consts->znear, consts->zfar);
   a.tex_w = (a.out.w / 8) * 8;
   a.tex_h = (a.out.h / 4) * 4;
   if (a.tex_w == 0 || a.tex_h == 0) return VKR_OK;

@@ -212,8 +212,7 @@ extern "C" int vkr_defered_shading(const vkr_img* albedo, const vkr_img* normal,
   VKR_TRY(make_tex(reflections, 0, VKR_FMT_RGBA8_UNORM, "defered_shading.reflections", &a.reflections));
   VKR_TRY(make_tex(out, 0, VKR_FMT_RGBA8_SRGB, "defered_shading.out", &a.out));
   load_mat(a.inverse_camera, consts->inverse_camera);
-  a.pr.tg = tanf(consts->fovy / 2.0f);
-  a.pr.aspect = consts->aspect; a.pr.znear = consts->znear; a.pr.zfar = consts->zfar;
+  load_proj(a.pr, consts->fovy, consts->aspect, consts->znear, consts->zfar);
   a.min_roughness = push->min_max_roughness[0];
   a.max_roughness = push->min_max_roughness[1];
   a.show_ao = push->show_ao;

@@ -7,8 +7,6 @@
 // march is a chain of <= 80 dependent texel fetches per ray and the blur up to 23x23 taps,
 // so trace is latency-bound and blur ALU/LDS-bound.
 #include <cstdlib>
-#include "vkr_host.hpp"
-#include "hiz_march.hpp"
 #include "ssr_sampling.hpp"
 
 namespace vkr {
@@ -47,9 +45,9 @@ struct TraceArgs {
   uint32_t frame_random;
   float max_roughness;
   float horizon_d2;    // host-computed: smallest float x with sqrtf(x) >= 0.3f (trace.comp:257)
-  // quotients that are the same for every ray, divided once on the host (IEEE, as the kernel would): 1 / screen_size,
-  // 0.005 / screen_size (screen_trace.glsl:10,20 at most_detailed_mip 0) and zfar / (zfar - znear) (gbuffer_encode.glsl:77)
-  f2 screen_size_inv, uv_offset_abs;
+  // quotients that are the same for every ray, divided once on the host (IEEE, as the kernel would): those of the march at
+  // most_detailed_mip 0 and zfar / (zfar - znear) (gbuffer_encode.glsl:77)
+  MarchQuotients mq;
   float f_over_fn;
   // windowed (multi-GPU, vkr_sssr_trace_windowed): `normal` holds only rows [nrm_row0, nrm_row1) of the frame when the march
   // ends; a ray whose hit-normal footprint leaves them is stored as a provisional hit and its test is left to
@@ -198,41 +196,20 @@ VKR_DEV void queue_store(uint4* r, const RayConst& c, const RayState& s, f3 R, f
 // the part of trace.comp after the march (:94-139): validity tests, the two stores
 template <bool WINDOWED>
 VKR_DEV void trace_epilogue(const TraceArgs& a, const Tex& depth0, const RayConst& rc, const RayState& st, f3 R, float roughness, float pixel_depth, int lx, int ly) {
-  const Proj pr = a.pr;
   const f2 tex_size = mk2((float)a.out_ray.fw, (float)a.out_ray.fh);
-  const f3 ray_start = rc.origin;
   const f3 out_ray = madd(rc.origin, st.t, rc.direction);
   const float h = st.h;
   const f3 pixel_normal = rc.normal, view_vec = rc.view_vec;
-  bool valid_hit = true;  // i <= 80 always (trace.comp:265)
-
-  // trace.comp:94-118
-  {
-    const f2 ray_step = mk2(fabsf(out_ray.x - ray_start.x) * tex_size.x, fabsf(out_ray.y - ray_start.y) * tex_size.y);
-    if (vmax(ray_step.x, ray_step.y) < 2.0f) valid_hit = false;
-  }
+  // trace.comp:94-118; i <= 80 always (:265)
+  bool valid_hit = ray_moved(out_ray, rc.origin, tex_size);
   if (!WINDOWED) {
-    if (valid_hit) {
-      const f3 hnw = decode_normal(sample<FmtRG16U>(a.normal, xy(out_ray)));
-      const f3 hit_normal = xyz(mul(a.normal_mat, mk4(hnw.x, hnw.y, hnw.z, 0.0f)));
-      if (dot(hit_normal, R) > 0.0f || dot(pixel_normal, R) < 0.0f) valid_hit = false;
-    }
-    if (valid_hit) {
-      const float hit_depth = sample<FmtD24>(depth0, xy(out_ray));
-      const float hit_z = linearize_depth2_unorm(hit_depth, pr.znear, pr.zfar);
-      const float ray_z = linearize_depth2(out_ray.z, pr.znear, pr.zfar);
-      if (ray_z > hit_z + 0.3f || ray_z < hit_z - 0.1f) valid_hit = false;
-    }
+    if (valid_hit && (hit_faces_away(a.normal, a.normal_mat, xy(out_ray), R) || dot(pixel_normal, R) < 0.0f)) valid_hit = false;
+    if (valid_hit) valid_hit = hit_depth_in_window(depth0, out_ray, a.pr);
   } else {
     // The same conjunction with the tests that need nothing remote first (the pyramid is whole-frame): a ray is only left
     // pending when every other test has passed and its hit-normal footprint has a row outside the rows of `normal` held here.
     if (valid_hit && dot(pixel_normal, R) < 0.0f) valid_hit = false;
-    if (valid_hit) {
-      const float hit_depth = sample<FmtD24>(depth0, xy(out_ray));
-      const float hit_z = linearize_depth2_unorm(hit_depth, pr.znear, pr.zfar);
-      const float ray_z = linearize_depth2(out_ray.z, pr.znear, pr.zfar);
-      if (ray_z > hit_z + 0.3f || ray_z < hit_z - 0.1f) valid_hit = false;
-    }
+    if (valid_hit) valid_hit = hit_depth_in_window(depth0, out_ray, a.pr);
     bool pending = false;
     if (valid_hit) {
       // rows of the bilinear footprint of texture(normal, hit uv): sample<>() clamps y0 and y0 + 1 to the frame
@@ -240,9 +217,7 @@ VKR_DEV void trace_epilogue(const TraceArgs& a, const Tex& depth0, const RayCons
       const int r0 = iclamp(y0, 0, a.normal.fh - 1), r1 = iclamp(y0 + 1, 0, a.normal.fh - 1);
       pending = r0 < a.nrm_row0 || r1 >= a.nrm_row1;
       if (!pending) {
-        const f3 hnw = decode_normal(sample<FmtRG16U>(a.normal, xy(out_ray)));
-        const f3 hit_normal = xyz(mul(a.normal_mat, mk4(hnw.x, hnw.y, hnw.z, 0.0f)));
-        if (dot(hit_normal, R) > 0.0f) valid_hit = false;
+        valid_hit = !hit_faces_away(a.normal, a.normal_mat, xy(out_ray), R);
       } else {
         float4* pd = texel_ptr<float4>(a.pend_data, 2 * lx, ly);
         pd[0] = make_float4(R.x, R.y, R.z, 0.0f);
@@ -251,12 +226,7 @@ VKR_DEV void trace_epilogue(const TraceArgs& a, const Tex& depth0, const RayCons
     }
     *texel_ptr<uint8_t>(a.pend_mask, lx, ly) = pending ? 1u : 0u;
   }
-  {  // RGBA16_UNORM store (advanced_ssr.cpp:62)
-    uint2 o;
-    o.x = float_to_unorm16(out_ray.x) | (float_to_unorm16(out_ray.y) << 16);
-    o.y = float_to_unorm16(out_ray.z) | (float_to_unorm16(valid_hit ? pixel_depth : 1.0f) << 16);
-    *texel_ptr<uint2>(a.out_ray, lx, ly) = o;
-  }
+  store_ray(a.out_ray, lx, ly, out_ray, valid_hit, pixel_depth);
   // trace.comp:123-139: (occlusion, pdf) into gtao.raw.  h was reset to 0 inside the march,
   // so the `no_occlusion` (h == -1) case of the reference never fires.
   {
@@ -281,31 +251,21 @@ VKR_DEV void trace_epilogue(const TraceArgs& a, const Tex& depth0, const RayCons
 }
 
 VKR_DEV MarchEnv trace_env(const TraceArgs& a, const uint4* s_mip) {
-  MarchEnv env;
-  env.mip_table = s_mip;
-  env.mip_count = a.depth.count;
-  env.screen_size = mk2((float)a.depth.mip[0].fw, (float)a.depth.mip[0].fh);
-  env.screen_size_inv = a.screen_size_inv;
-  env.uv_offset_abs = a.uv_offset_abs;  // most_detailed_mip = 0
-  env.pr = a.pr;
-  env.horizon_d2 = a.horizon_d2;
-  return env;
+  return march_env(s_mip, a.depth.count, a.depth.mip[0], a.pr, a.mq, 0, a.horizon_d2);
 }
 
 // the level table of a block: levels of `depth` (whole-frame extents), bases of `local` where the march is LOCAL
 template <bool LOCAL>
 VKR_DEV void stage_mip_tables(const TraceArgs& a, int tid, uint4* s_mip, uint2* s_win) {
+  if (!LOCAL) { stage_mip_table(a.depth, tid, s_mip); return; }
   const int l = tid & 15;
-  const Tex& f = a.depth.mip[l < a.depth.count ? l : 0];  // (a load from the kernel arguments: every lane, with the others)
-  uint4 d = mip_descriptor(f);
-  uint2 w = make_uint2(0u, 0u);
-  if (LOCAL) {
-    const Tex& t = a.local.mip[l < a.local.count ? l : 0];
-    const uint64_t base = (uint64_t)t.p;
-    d = make_uint4((uint32_t)base, (uint32_t)(base >> 32), (uint32_t)t.pitch, (uint32_t)f.w | ((uint32_t)f.h << 16));
-    w = make_uint2((uint32_t)t.oy, (uint32_t)t.h);
+  const Tex& f = a.depth.mip[l < a.depth.count ? l : 0];  // (loads from the kernel arguments: every lane, with the others)
+  const Tex& t = a.local.mip[l < a.local.count ? l : 0];
+  const uint64_t base = (uint64_t)t.p;
+  if (tid < 16) {
+    s_mip[tid] = make_uint4((uint32_t)base, (uint32_t)(base >> 32), (uint32_t)t.pitch, (uint32_t)f.w | ((uint32_t)f.h << 16));
+    s_win[tid] = make_uint2((uint32_t)t.oy, (uint32_t)t.h);
   }
-  if (tid < 16) { s_mip[tid] = d; if (LOCAL) s_win[tid] = w; }
 }
 
 // LOCAL epilogue guard: does the hit-depth sample of trace.comp:111-117 (texture(depth, hit uv) on level 0) touch a row of the
@@ -313,9 +273,7 @@ VKR_DEV void stage_mip_tables(const TraceArgs& a, int tid, uint4* s_mip, uint2* 
 VKR_DEV bool hit_depth_rows_missing(const TraceArgs& a, const RayConst& rc, const RayState& st, f3 R) {
   const f2 tex_size = mk2((float)a.out_ray.fw, (float)a.out_ray.fh);
   const f3 out_ray = madd(rc.origin, st.t, rc.direction);
-  const f2 ray_step = mk2(fabsf(out_ray.x - rc.origin.x) * tex_size.x, fabsf(out_ray.y - rc.origin.y) * tex_size.y);
-  if (vmax(ray_step.x, ray_step.y) < 2.0f) return false;
-  if (dot(rc.normal, R) < 0.0f) return false;
+  if (!ray_moved(out_ray, rc.origin, tex_size) || dot(rc.normal, R) < 0.0f) return false;
   const Tex& l0 = a.local.mip[0];
   const int y0 = f2i(floorf(cfma(out_ray.y, (float)l0.fh, -0.5f)));
   const int r0 = iclamp(y0, 0, l0.fh - 1), r1 = iclamp(y0 + 1, 0, l0.fh - 1);
@@ -373,33 +331,7 @@ __global__ __launch_bounds__(TRACE_THREADS) void k_sssr_trace(TraceArgs a) {
     rc.normal = normalize(xyz(mul(a.normal_mat, mk4(pixel_normal_world.x, pixel_normal_world.y, pixel_normal_world.z, 0.0f))));
     rc.view_vec = reconstruct_view_vec(screen_uv, pixel_depth, pr);
 
-    // trace.comp:61-63,156-158: rand() -> Halton index; sin evaluated in double
-    const float rdot = dot(screen_uv, mk2(12.9898f, 78.233f));
-    const float rnd01 = fractf(sin_hash_arg(rdot) * 43758.5453f);
-    const uint32_t base_index = f2u(rnd01 * (float)VKR_HALTON_SEQ_SIZE);
-    const uint32_t index = (base_index + a.frame_random) & (VKR_HALTON_SEQ_SIZE - 1);
-    const float4 hv = a.halton[index];
-
-    // trace.comp:65-77
-    f3 tangent = get_tangent(rc.normal);
-    const f3 bitangent = normalize(cross(rc.normal, tangent));
-    tangent = normalize(cross(bitangent, rc.normal));
-    f3 view_dir = -normalize(rc.view_vec);
-    view_dir = mk3(dot(view_dir, tangent), dot(view_dir, bitangent), dot(view_dir, rc.normal));
-    const f3 brdf_norm = sampleGGXVNDF(view_dir, roughness, roughness, hv.x, hv.z, hv.w);
-    const f3 N = (brdf_norm.x * tangent + brdf_norm.y * bitangent) + brdf_norm.z * rc.normal;
-    R = reflect(rc.view_vec, N);
-
-    // trace.comp:79-84
-    f3 ray_start = project_view_vec(rc.view_vec + 0.001f * rc.normal, pr, a.f_over_fn);
-    ray_start.z -= 0.0001f;
-    f3 ray_dir = project_view_vec(rc.view_vec + R, pr, a.f_over_fn);
-    ray_dir = ray_dir - ray_start;
-    ray_dir = ray_dir * ((1.0f - ray_start.z) / ray_dir.z);
-
-    rc.origin = ray_start;
-    rc.direction = ray_dir;
-    rc.inv_direction = safe_inverse(ray_dir);
+    R = setup_ray(rc, screen_uv, roughness, a.halton, a.frame_random, pr, a.f_over_fn);  // trace.comp:61-84
     st.t = initial_advance(env, rc);
     st.h = 0.0f;  // trace.comp:239
     st.mip = 0;
@@ -553,9 +485,7 @@ __global__ __launch_bounds__(256) void k_sssr_validate(Tex rays, Tex pend_mask, 
   if (*texel_ptr<uint8_t>(pend_mask, lx, ly) == 0u) return;
   const float4* pd = texel_ptr<float4>(pend_data, 2 * lx, ly);
   const float4 Rv = pd[0], hv = pd[1];
-  const f3 hnw = decode_normal(sample<FmtRG16U>(normal, mk2(hv.x, hv.y)));
-  const f3 hit_normal = xyz(mul(normal_mat, mk4(hnw.x, hnw.y, hnw.z, 0.0f)));
-  if (dot(hit_normal, mk3(Rv.x, Rv.y, Rv.z)) > 0.0f)
+  if (hit_faces_away(normal, normal_mat, mk2(hv.x, hv.y), mk3(Rv.x, Rv.y, Rv.z)))
     *(uint16_t*)(const_cast<uint8_t*>(rays.p) + toff(rays, lx, ly, 8) + 6u) = (uint16_t)0xFFFFu;  // w = 1.0: not a hit (filter.comp:93-95)
 }
 
@@ -1186,45 +1116,29 @@ extern "C" int vkr_pdf_preintegrate(const vkr_img* out_pdf, void* stream) {
   return launch_status("pdf_preintegrate");
 }
 
-static void load_proj(Proj& pr, float fovy, float aspect, float znear, float zfar) {
-  pr.tg = tanf(fovy / 2.0f);
-  pr.aspect = aspect; pr.znear = znear; pr.zfar = zfar;
-}
+// blocks of a trace launch: 32 x (8 TRACE_WY) pixels of the rays' window each
+static dim3 trace_grid(const TraceArgs& a) { return dim3((a.out_ray.w + 31) / 32, (a.out_ray.h + 8 * TRACE_WY - 1) / (8 * TRACE_WY)); }
 
 static int make_trace_args(TraceArgs& a, const vkr_img* depth, const vkr_img* normal, const vkr_img* material, const vkr_trace_params* params,
                            const float* halton_vec4, const vkr_img* out_ray, const vkr_img* out_occlusion, const vkr_img* pdf_tex,
                            const vkr_trace_push* push) {
   if (!params || !push || !halton_vec4 || !depth) { set_error("sssr_trace: NULL argument"); return VKR_ERR_NULL; }
   if (((uintptr_t)halton_vec4 % 16) != 0) { set_error("sssr_trace: halton buffer must be 16-byte aligned"); return VKR_ERR_LAYOUT; }
-  if (depth->mip_count < 1 || depth->mip_count > VKR_MAX_MIPS) { set_error("sssr_trace: bad depth mip count"); return VKR_ERR_MIPS; }
-  a.depth.count = (int)depth->mip_count;
-  for (int i = 0; i < a.depth.count; i++) VKR_TRY(make_tex(depth, i, VKR_FMT_D24_UNORM_S8, "sssr_trace.depth", &a.depth.mip[i]));
-  for (int i = a.depth.count; i < 16; i++) a.depth.mip[i] = a.depth.mip[0];
+  VKR_TRY(bind_depth_pyramid(depth, "sssr_trace", "depth", &a.depth));
   VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "sssr_trace.normal", &a.normal));
   VKR_TRY(make_tex(material, 0, VKR_FMT_RGBA8_SRGB, "sssr_trace.material", &a.material));
   VKR_TRY(make_tex(pdf_tex, 0, VKR_FMT_R32_SFLOAT, "sssr_trace.pdf", &a.pdf));
   VKR_TRY(make_tex(out_ray, 0, VKR_FMT_RGBA16_UNORM, "sssr_trace.out_ray", &a.out_ray));
   VKR_TRY(make_tex(out_occlusion, 0, VKR_FMT_RGBA16_SFLOAT, "sssr_trace.out_occlusion", &a.out_occ));
   if (!same_window(a.out_ray, a.out_occ)) { set_error("sssr_trace: ray / occlusion outputs differ in extent"); return VKR_ERR_EXTENT; }
-  for (int i = 0; i < a.depth.count; i++) {
-    const Tex& m = a.depth.mip[i];
-    if (m.ox != 0 || m.oy != 0 || m.w != m.fw || m.h != m.fh || m.w > 65535 || m.h > 65535) {
-      set_error("sssr_trace: the Hi-Z pyramid must cover the whole frame (rays have unbounded reach)");
-      return VKR_ERR_EXTENT;
-    }
-  }
   a.halton = (const float4*)halton_vec4;
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   a.frame_random = params->frame_random;
   a.max_roughness = push->max_roughness;
   a.horizon_d2 = horizon_threshold_d2();
-  {
-    const float sw = (float)a.depth.mip[0].fw, sh = (float)a.depth.mip[0].fh;
-    a.screen_size_inv.x = 1.0f / sw; a.screen_size_inv.y = 1.0f / sh;
-    a.uv_offset_abs.x = 0.005f / sw; a.uv_offset_abs.y = 0.005f / sh;
-    a.f_over_fn = a.pr.zfar / (a.pr.zfar - a.pr.znear);
-  }
+  load_march_quotients(a.mq, a.depth.mip[0], 0);
+  a.f_over_fn = a.pr.zfar / (a.pr.zfar - a.pr.znear);
   a.nrm_row0 = 0; a.nrm_row1 = a.normal.fh;
   a.pend_mask = a.out_ray; a.pend_data = a.out_ray;  // unused unless windowed
   a.q.records = nullptr; a.q.counters = nullptr; a.q.capacity = 0; a.park_after = 0;
@@ -1240,8 +1154,7 @@ extern "C" int vkr_sssr_trace(const vkr_img* depth, const vkr_img* normal, const
   TraceArgs a;
   VKR_TRY(make_trace_args(a, depth, normal, material, params, halton_vec4, out_ray, out_occlusion, pdf_tex, push));
   dim3 block(TRACE_THREADS, 1);
-  dim3 grid((a.out_ray.w + 31) / 32, (a.out_ray.h + 8 * TRACE_WY - 1) / (8 * TRACE_WY));
-  hipLaunchKernelGGL((k_sssr_trace<false, false, false>), grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_sssr_trace<false, false, false>), trace_grid(a), block, 0, (hipStream_t)stream, a);
   return launch_status("sssr_trace");
 }
 
@@ -1279,11 +1192,10 @@ extern "C" int vkr_sssr_trace_split(const vkr_img* depth, const vkr_img* normal,
   if (park_after_rounds > 4) { set_error("sssr_trace_split: park_after_rounds %u (0..4: a march has at most four compacted rounds)", park_after_rounds); return VKR_ERR_EXTENT; }
   a.park_after = (int)park_after_rounds;
   dim3 block(TRACE_THREADS, 1);
-  dim3 grid((a.out_ray.w + 31) / 32, (a.out_ray.h + 8 * TRACE_WY - 1) / (8 * TRACE_WY));
   // the queue's counter: zeroed on the stream ahead of the head launch (a reset by the resume launch itself needs every one of
   // its blocks to report that it has read the count: 2048 atomics on one word, 11 ns each, measured as 22 us)
   if (hipMemsetAsync(a.q.counters, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) { set_error("sssr_trace_split: memset failed"); return VKR_ERR_LAYOUT; }
-  hipLaunchKernelGGL((k_sssr_trace<false, true, false>), grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_sssr_trace<false, true, false>), trace_grid(a), block, 0, (hipStream_t)stream, a);
   VKR_TRY(launch_status("sssr_trace_split (head)"));
   hipLaunchKernelGGL((k_sssr_trace_resume<false, false>), resume_grid(a), dim3(RESUME_BLOCK), 0, (hipStream_t)stream, a);
   return launch_status("sssr_trace_split (resume)");
@@ -1320,8 +1232,7 @@ extern "C" int vkr_sssr_trace_windowed(const vkr_img* depth, const vkr_img* norm
   TraceArgs a;
   VKR_TRY(make_windowed_args(a, depth, normal, material, params, halton_vec4, out_ray, out_occlusion, pdf_tex, pending_mask, pending_data, push, "sssr_trace_windowed"));
   dim3 block(TRACE_THREADS, 1);
-  dim3 grid((a.out_ray.w + 31) / 32, (a.out_ray.h + 8 * TRACE_WY - 1) / (8 * TRACE_WY));
-  hipLaunchKernelGGL((k_sssr_trace<true, false, false>), grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_sssr_trace<true, false, false>), trace_grid(a), block, 0, (hipStream_t)stream, a);
   return launch_status("sssr_trace_windowed");
 }
 
@@ -1365,8 +1276,7 @@ extern "C" int vkr_sssr_trace_windowed_head(const vkr_img* local_depth, const vk
   }
   if (hipMemsetAsync(a.q.counters, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) { set_error("%s: memset failed", P); return VKR_ERR_LAYOUT; }
   dim3 block(TRACE_THREADS, 1);
-  dim3 grid((a.out_ray.w + 31) / 32, (a.out_ray.h + 8 * TRACE_WY - 1) / (8 * TRACE_WY));
-  hipLaunchKernelGGL((k_sssr_trace<true, true, true>), grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((k_sssr_trace<true, true, true>), trace_grid(a), block, 0, (hipStream_t)stream, a);
   return launch_status(P);
 }
 
@@ -1438,8 +1348,7 @@ static int make_blur_args(BlurArgs& a, const vkr_img* depth, const vkr_img* norm
   VKR_TRY(make_tex(out_blurred, 0, VKR_FMT_RGBA8_UNORM, "sssr_blur.out", &a.out));
   load_mat(a.inverse_camera, params->inverse_camera);
   load_mat(a.prev_inverse_camera, params->prev_inverse_camera);
-  load_proj(a.pr, params->fovy_aspect_znear_zfar[0], params->fovy_aspect_znear_zfar[1], params->fovy_aspect_znear_zfar[2],
-            params->fovy_aspect_znear_zfar[3]);
+  load_proj(a.pr, params->fovy_aspect_znear_zfar);
   a.max_roughness = push->max_roughness;
   a.accumulate = push->accumulate;
   a.disable_blur = push->disable_blur;

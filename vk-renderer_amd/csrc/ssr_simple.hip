@@ -14,6 +14,7 @@ struct SsrArgs {
   Tex normal, frame, material, out;
   Mat4 camera_normal;
   Proj pr;
+  MarchQuotients mq;
   uint32_t frame_format;  // VKR_FMT_RGBA8_SRGB or VKR_FMT_RGBA8_UNORM
 };
 
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void k_ssr_simple(SsrArgs a) {
   __shared__ float s_lut[VKR_SRGB_LUT_SIZE];
   const int tid = threadIdx.x;
   srgb_lut_stage(s_lut, tid, 256);
-  if (tid < 16) s_mip[tid] = mip_descriptor(a.depth.mip[tid < a.depth.count ? tid : 0]);
+  stage_mip_table(a.depth, tid, s_mip);
   __syncthreads();
   const int wave = tid >> 6, lane = tid & 63;
   const int lx = (blockIdx.x * 4 + wave) * 8 + (lane & 7);
@@ -83,14 +84,7 @@ __global__ __launch_bounds__(256) void k_ssr_simple(SsrArgs a) {
     t_bound = vmin(t_bound, vmin(u_bound, v_bound));
     const f3 end = start + t_bound * delta;
 
-    MarchEnv env;
-    env.mip_table = s_mip;
-    env.mip_count = a.depth.count;
-    env.screen_size = mk2((float)depth0.fw, (float)depth0.fh);
-    env.screen_size_inv = mk2(1.0f / env.screen_size.x, 1.0f / env.screen_size.y);
-    env.uv_offset_abs = mk2(0.005f / env.screen_size.x, 0.005f / env.screen_size.y);
-    env.pr = pr;
-    env.horizon_d2 = 0.0f;
+    const MarchEnv env = march_env(s_mip, a.depth.count, depth0, pr, a.mq, 0, 0.0f);
     RayConst rc;
     rc.origin = start;
     rc.direction = end - start;
@@ -133,17 +127,7 @@ extern "C" int vkr_ssr(const vkr_img* normal, const vkr_img* depth, const vkr_im
                        const vkr_img* material, const vkr_img* out, void* stream) {
   if (!params || !depth || !frame) { set_error("ssr: NULL argument"); return VKR_ERR_NULL; }
   SsrArgs a;
-  if (depth->mip_count < 1 || depth->mip_count > VKR_MAX_MIPS) { set_error("ssr: bad depth mip count"); return VKR_ERR_MIPS; }
-  a.depth.count = (int)depth->mip_count;
-  for (int i = 0; i < a.depth.count; i++) {
-    VKR_TRY(make_tex(depth, i, VKR_FMT_D24_UNORM_S8, "ssr.depth", &a.depth.mip[i]));
-    const Tex& m = a.depth.mip[i];
-    if (m.ox != 0 || m.oy != 0 || m.w != m.fw || m.h != m.fh || m.w > 65535 || m.h > 65535) {
-      set_error("ssr: the depth pyramid must cover the whole frame");
-      return VKR_ERR_EXTENT;
-    }
-  }
-  for (int i = a.depth.count; i < 16; i++) a.depth.mip[i] = a.depth.mip[0];
+  VKR_TRY(bind_depth_pyramid(depth, "ssr", "depth", &a.depth));
   VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "ssr.normal", &a.normal));
   a.frame_format = frame->format;
   if (frame->format != VKR_FMT_RGBA8_SRGB && frame->format != VKR_FMT_RGBA8_UNORM) { set_error("ssr: frame must be RGBA8 (sRGB or UNORM)"); return VKR_ERR_FORMAT; }
@@ -151,8 +135,8 @@ extern "C" int vkr_ssr(const vkr_img* normal, const vkr_img* depth, const vkr_im
   VKR_TRY(make_tex(material, 0, VKR_FMT_RGBA8_SRGB, "ssr.material", &a.material));
   VKR_TRY(make_tex(out, 0, VKR_FMT_RGBA8_UNORM, "ssr.out", &a.out));
   load_mat(a.camera_normal, params->normal_mat);
-  a.pr.tg = tanf(params->fovy / 2.0f);
-  a.pr.aspect = params->aspect; a.pr.znear = params->znear; a.pr.zfar = params->zfar;
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
+  load_march_quotients(a.mq, a.depth.mip[0], 0);
   dim3 grid((a.out.w + 31) / 32, (a.out.h + 7) / 8);
   hipLaunchKernelGGL(k_ssr_simple, grid, dim3(256), 0, (hipStream_t)stream, a);
   return launch_status("ssr");

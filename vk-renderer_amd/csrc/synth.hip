@@ -222,8 +222,7 @@ extern "C" int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, co
   load_mat(a.c2w, params->camera_to_world);
   load_mat(a.prev_mvp, params->prev_mvp);
   load_mat(a.mvp, params->mvp);
-  a.pr.tg = tanf(params->fovy / 2.0f);
-  a.pr.aspect = params->aspect; a.pr.znear = params->znear; a.pr.zfar = params->zfar;
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   a.seed = params->seed;
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_synth_gbuffer, grid2d(a.depth.w, a.depth.h, block), block, 0, (hipStream_t)stream, a);

@@ -223,10 +223,7 @@ extern "C" int vkr_taa_resolve(const vkr_img* history_color, const vkr_img* hist
   VKR_TRY(make_tex(out_color, 0, VKR_FMT_RGBA16_SFLOAT, "taa_resolve.out", &a.out));
   load_mat(a.inverse_camera, params->inverse_camera);
   load_mat(a.prev_inverse_camera, params->prev_inverse_camera);
-  a.pr.tg = tanf(params->fovy_aspect_znear_zfar[0] / 2.0f);
-  a.pr.aspect = params->fovy_aspect_znear_zfar[1];
-  a.pr.znear = params->fovy_aspect_znear_zfar[2];
-  a.pr.zfar = params->fovy_aspect_znear_zfar[3];
+  load_proj(a.pr, params->fovy_aspect_znear_zfar);
   a.still_d2 = sqrt_threshold(0.005f);
   const bool shared = same_layout(a.color, a.velocity) && same_layout(a.color, a.cur_depth) && !(switches() & VKR_SWITCH_TAA_GENERIC);
   // the block's footprint tile needs texture(., screen_uv) to land next to the pixel: the images' full extent is the output's

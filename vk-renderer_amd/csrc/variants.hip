@@ -344,10 +344,6 @@ static void fill_slice_table(float (*cs)[2], float angle_offset) {
     cs[k][1] = sinf(angle);
   }
 }
-static void fill_proj(Proj& pr, float fovy, float aspect, float znear, float zfar) {
-  pr.tg = tanf(fovy / 2.0f);
-  pr.aspect = aspect; pr.znear = znear; pr.zfar = zfar;
-}
 static int make_layers(const vkr_img* layers, uint32_t count, const char* what, Tex* first, LayerSet* set) {
   if (!layers || count == 0 || count > 64) { set_error("%s: needs 1..64 array layers", what); return VKR_ERR_NULL; }
   VKR_TRY(make_tex(&layers[0], 0, VKR_FMT_R32_SFLOAT, what, first));
@@ -376,7 +372,7 @@ extern "C" int vkr_gtao_main_graphics(const vkr_img* depth, const vkr_gtao_param
   VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "gtao_main.normal", &a.normal));
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "gtao_main.out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
-  fill_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   fill_slice_table(a.slice_cs, push->angle_offset);
   a.inv_w = a.out.fw; a.inv_h = a.out.fh;
   a.scale = 1; a.off_x = 0; a.off_y = 0;
@@ -397,7 +393,7 @@ extern "C" int vkr_gtao_reproject(const vkr_gtao_reprojection* params, const vkr
   VKR_TRY(make_tex(prev_ao, 0, VKR_FMT_R16_SFLOAT, "gtao_reproject.prev_ao", &prev));
   VKR_TRY(make_tex(out_img, 0, VKR_FMT_R16_SFLOAT, "gtao_reproject.out", &out));
   Proj pr;
-  fill_proj(pr, params->fovy, params->aspect, params->znear, params->zfar);
+  load_proj(pr, params->fovy, params->aspect, params->znear, params->zfar);
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_gtao_reproject, grid2d(out.w, out.h, block), block, 0, (hipStream_t)stream, d, pd, cur, prev, out, pr,
                      (out.fw / 8) * 8, (out.fh / 4) * 4);
@@ -433,7 +429,7 @@ extern "C" int vkr_gtao_main_deinterleaved(const vkr_img* layers, uint32_t layer
   VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "main_deinterleaved.normal", &a.normal));
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "main_deinterleaved.out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
-  fill_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   fill_slice_table(a.slice_cs, push->angle_offset);
   const int scale = 1 << push->pattern_n;
   a.inv_w = (a.out.fw / 8) * 8; a.inv_h = (a.out.fh / 4) * 4;
@@ -466,7 +462,7 @@ extern "C" int vkr_screen_trace_main(const vkr_img* depth, const vkr_img* normal
     return VKR_ERR_EXTENT;
   }
   load_mat(a.normal_mat, params->normal_mat);
-  fill_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
+  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   fill_slice_table(a.slice_cs, params->angle_offset);
   a.random_offset = params->random_offset;
   const int groups_x = a.out.fw / ST_TILE, groups_y = a.out.fh / ST_TILE;

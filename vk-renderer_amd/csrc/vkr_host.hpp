@@ -68,7 +68,36 @@ inline bool same_window(const Tex& a, const Tex& b) {
 // same window AND row pitch: texel (x, y) has the same byte offset in both (4-byte formats share bilinear footprints)
 inline bool same_layout(const Tex& a, const Tex& b) { return same_window(a, b) && a.pitch == b.pitch; }
 
+// A whole-frame D24 depth pyramid as the Hi-Z marches bind it: 1 .. VKR_MAX_MIPS levels, every one the whole frame (rays have
+// unbounded reach) and at most 65535 texels wide and high (the LDS level table keeps w | h << 16); padded to 16 entries.
+inline int bind_depth_pyramid(const vkr_img* d, const char* program, const char* binding, Pyramid* out) {
+  char what[96];
+  std::snprintf(what, sizeof what, "%s.%s", program, binding);
+  if (!d) { set_error("%s: NULL image", what); return VKR_ERR_NULL; }
+  if (d->mip_count < 1 || d->mip_count > VKR_MAX_MIPS) { set_error("%s: %u mips (1 .. %d)", what, d->mip_count, VKR_MAX_MIPS); return VKR_ERR_MIPS; }
+  out->count = (int)d->mip_count;
+  for (int i = 0; i < out->count; i++) {
+    Tex& m = out->mip[i];
+    int rc = make_tex(d, i, VKR_FMT_D24_UNORM_S8, what, &m);
+    if (rc != VKR_OK) return rc;
+    if (m.ox != 0 || m.oy != 0 || m.w != m.fw || m.h != m.fh || m.w > 65535 || m.h > 65535) {
+      set_error("%s: level %d (%dx%d at (%d,%d) of %dx%d) must cover the whole frame, at most 65535 texels a side", what, i, m.w, m.h, m.ox, m.oy, m.fw, m.fh);
+      return VKR_ERR_EXTENT;
+    }
+  }
+  for (int i = out->count; i < 16; i++) out->mip[i] = out->mip[0];
+  return VKR_OK;
+}
+
 inline void load_mat(Mat4& dst, const vkr_mat4& src) { std::memcpy(dst.m, src.m, sizeof(float) * 16); }
+
+inline void load_proj(Proj& pr, float fovy, float aspect, float znear, float zfar) {
+  pr.tg = tanf(fovy / 2.0f);
+  pr.aspect = aspect; pr.znear = znear; pr.zfar = zfar;
+}
+inline void load_proj(Proj& pr, const float fovy_aspect_znear_zfar[4]) {
+  load_proj(pr, fovy_aspect_znear_zfar[0], fovy_aspect_znear_zfar[1], fovy_aspect_znear_zfar[2], fovy_aspect_znear_zfar[3]);
+}
 
 inline int launch_status(const char* what) {
   hipError_t e = hipGetLastError();
