@@ -43,12 +43,18 @@ HOT = {
     "k_gtao_main<false, false>": ("gtao.hip", 1024, 64, 0, 2048, 8),
     "k_gtao_filter": ("gtao.hip", 256, 64, 0, 4096, 8),
     "k_gtao_accumulate": ("gtao.hip", 256, 64, 0, 0, 8),
+    # the dormant members of the GTAO family, which share the slice frame, the horizon walk and the arc (gtao_slice.hpp)
+    "k_gtao_v2<FmtD24>": ("variants.hip", 256, 48, 0, 0, 8),
+    "k_gtao_v2<FmtR32F>": ("variants.hip", 256, 48, 0, 0, 8),
+    "k_screen_trace": ("variants.hip", 256, 80, 0, 6144, 6),
+    "k_screen_trace_filter": ("variants.hip", 256, 64, 0, 9380, 8),
     "k_taa_resolve<true, true>": ("taa.hip", 256, 64, 0, 6 * 1024, 8),
     "k_taa_resolve<true, false>": ("taa.hip", 256, 64, 0, 2048, 8),
     "k_taa_resolve<false, false>": ("taa.hip", 256, 64, 0, 2048, 8),
 }
 
-NO_SPILLS = {"k_sssr_validate", "k_sssr_trace_indirect", "k_ssr_simple"}  # neither VGPRs to scratch nor SGPRs to VGPRs
+NO_SPILLS = {"k_sssr_validate", "k_sssr_trace_indirect", "k_ssr_simple",
+             "k_gtao_v2<FmtD24>", "k_gtao_v2<FmtR32F>", "k_screen_trace", "k_screen_trace_filter"}  # neither VGPRs to scratch nor SGPRs to VGPRs
 
 
 def resident_waves_per_simd(threads, vgprs, lds_bytes):

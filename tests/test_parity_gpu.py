@@ -313,10 +313,10 @@ def test_empty_tile_skip_against_no_skip(pathological, oracle_lib):
             assert not (differ & ~near).any(), f"{name}: skip and no-skip differ away from every planted non-finite weight"
 
 
-@pytest.mark.parametrize("size", [(640, 360), (1920, 1080)])
+@pytest.mark.parametrize("size", [(640, 360), (1920, 1080), (206, 226)])  # 206x226: the ragged size, k_gtao_main<false, false>
 def test_gtao_only_config1(size, oracle_lib):
     """BASELINE config 1: GTAO main pass only, non-MIS (use_mis = 0), single and two directions — also at the
-    configuration's own 1920x1080."""
+    configuration's own 1920x1080 and at a size whose floor-dispatch extent is not the image's (depth from global memory)."""
     from vk_renderer_amd.camera import FrameSetup
 
     for two in (0, 255):

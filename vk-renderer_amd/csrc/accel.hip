@@ -17,6 +17,7 @@
 // between them).  A node box that contains a hit point therefore always overlaps the segment box: no cull can discard a
 // triangle the test would hit, and the result is that of a brute-force loop over all triangles (tests/test_accel_gpu.py).
 #include "vkr_host.hpp"
+#include "gtao_slice.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -123,13 +124,6 @@ struct GtaoRtArgs {
   const float4* directions;
 };
 
-// rt_main.frag:50-61
-VKR_DEV f3 rt_tangent(f3 n) {
-  const float max_xy = vmax(fabsf(n.x), fabsf(n.y));
-  const f3 t = max_xy < 0.00001f ? mk3(1.0f, 0.0f, 0.0f) : mk3(n.y, -n.x, 0.0f);
-  return normalize(t);
-}
-
 // rt_main.frag:67-108; one wave per pixel of the window, lane i = direction i
 __global__ __launch_bounds__(256) void k_gtao_rt(GtaoRtArgs a) {
   __shared__ uint32_t stacks[4][ACCEL_STACK];
@@ -149,13 +143,11 @@ __global__ __launch_bounds__(256) void k_gtao_rt(GtaoRtArgs a) {
   f3 world = xyz(mul(a.camera_to_world, mk4(view_vec.x, view_vec.y, view_vec.z, 1.0f)));
   const f3 normal = decode_normal(sample<FmtRG16U>(a.normal, uv));
   world = madd(world, 1e-6f, normal);
-  f3 tangent = rt_tangent(normal);
-  f3 bitangent = normalize(cross(normal, tangent));
-  tangent = normalize(cross(bitangent, normal));
-  const int slot = (((gx + gy) & 3) << 2) + (gx & 3);
+  f3 tangent, bitangent;
+  tangent_frame(normal, &tangent, &bitangent);  // rt_main.frag:50-61,84-86
+  const int slot = gtao_dir_slot(gx, gy);
   tangent = normalize(madd(tangent * a.rot_cs[slot][0], a.rot_cs[slot][1], bitangent));
-  bitangent = normalize(cross(normal, tangent));
-  tangent = normalize(cross(bitangent, normal));
+  orthonormalise(normal, &tangent, &bitangent);
 
   const float4 r = a.directions[lane];
   f3 dir = normalize(mk3(r.x, r.y, r.z));
@@ -386,12 +378,7 @@ extern "C" int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img*
   if (((uintptr_t)directions & 15u) != 0) { set_error("gtao_rt_main: directions must be 16-byte aligned"); return VKR_ERR_LAYOUT; }
   load_mat(a.camera_to_world, params->camera_to_world);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  const float PI = 3.1415926535897932384626433832795f;
-  for (int k = 0; k < 16; k++) {  // rt_main.frag:89: angle = 2 PI (rotation + gtao_direction(pixel))
-    const float angle = (2.0f * PI) * (push->rotation + (1.0f / 16.0f) * (float)k);
-    a.rot_cs[k][0] = cosf(angle);
-    a.rot_cs[k][1] = sinf(angle);
-  }
+  fill_slice_table(a.rot_cs, push->rotation, 0.0f);  // rt_main.frag:89: angle = 2 PI (rotation + gtao_direction(pixel))
   a.accel = AccelView{accel->nodes, accel->tris, accel->node_count};
   a.directions = (const float4*)directions;
   const uint32_t pixels = (uint32_t)a.out.w * (uint32_t)a.out.h;

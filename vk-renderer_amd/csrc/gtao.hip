@@ -7,6 +7,7 @@
 // 7 B (non-MIS) and is latency/ALU-bound.
 #include <cstdlib>
 #include "vkr_host.hpp"
+#include "gtao_slice.hpp"
 
 namespace vkr {
 
@@ -58,26 +59,17 @@ template <bool TILED> VKR_DEV float depth_sample(const DepthTile& t, const Tex& 
   return sample<FmtD24>(depth, uv);
 }
 
-// main.comp:84-108
+// main.comp:84-108: 16 samples at start + (i / 16) dir
 template <bool TILED>
 VKR_DEV float find_horizon(const DepthTile& depth, const Tex& depth_tex, const Proj& pr, f2 start, f3 camera_start, f2 dir, f3 v) {
-  float h_cos = -1.0f;
-  float previous_z = camera_start.z;
   float s = 0.0f;  // i / 16: multiples of 2^-4 add exactly
-#pragma unroll 1
-  for (int i = 1; i <= 16; i++) {
-    s += 0.0625f;
-    f2 tc = madd(start, s, dir);
-    float sample_depth = depth_sample<TILED>(depth, depth_tex, tc);
-    f3 sample_pos = reconstruct_view_vec(tc, sample_depth, pr);
-    if (sample_pos.z > previous_z + 0.1f) break;  // MAX_THIKNESS, main.comp:82
-    previous_z = sample_pos.z;
-    f3 sample_offset = sample_pos - camera_start;
-    // max()-reduced cosine: the hardware rsq is accurate enough (the break test above stays exact)
-    float sample_cos = dot(v, sample_offset) * fast_rsq(dot(sample_offset, sample_offset));
-    asm("v_max_f32 %0, %1, %2" : "=v"(h_cos) : "v"(h_cos), "v"(sample_cos));  // fmaxf without the canonicalising self-max (a NaN cosine is dropped either way)
-  }
-  return h_cos;
+  return horizon_walk<16>(pr, camera_start, v,
+      [&](int) { s += 0.0625f; return madd(start, s, dir); },
+      [&](f2 tc) { return depth_sample<TILED>(depth, depth_tex, tc); },
+      [](float h_cos, float sample_cos) {  // fmaxf without the canonicalising self-max (a NaN cosine is dropped either way)
+        asm("v_max_f32 %0, %1, %2" : "=v"(h_cos) : "v"(h_cos), "v"(sample_cos));
+        return h_cos;
+      });
 }
 
 // One thread per half-res pixel.  The slice-direction pattern repeats every 4x4 pixels
@@ -137,11 +129,10 @@ __global__ __launch_bounds__(GT_BX * GT_BY, 8) void k_gtao_main(GtaoArgs a) {
     // Smooth (hardware rsq): the slice frame and its angles.
     const f3 camera_pos = reconstruct_view_vec(screen_uv, frag_depth, a.pr);
     const f3 w0 = -normalize(camera_pos);
-    const f3 n_world = decode_normal(sample<FmtRG16U>(a.normal, screen_uv));
-    const f3 camera_normal = normalize(xyz(mul(a.normal_mat, mk4(n_world.x, n_world.y, n_world.z, 0.0f))));
+    const f3 camera_normal = sample_view_normal(a.normal, a.normal_mat, screen_uv);
     const float rad = vmin(100.0f / length(camera_pos), 16.0f);
     const f2 dir_radius = mk2(rad / (float)a.depth.fw, rad / (float)a.depth.fh);
-    const int dir_slot = (((gx + gy) & 3) << 2) + (gx & 3);  // 16 * gtao_direction(pos)
+    const int dir_slot = gtao_dir_slot(gx, gy);
     const int dirs = MIS ? 1 : (a.two_directions ? 2 : 1);
     float sum = 0.0f, occlusion = 0.0f;
     f3 L = mk3(0, 0, 0);
@@ -149,31 +140,27 @@ __global__ __launch_bounds__(GT_BX * GT_BY, 8) void k_gtao_main(GtaoArgs a) {
       const f2 cs = mk2(a.slice_cs[di][dir_slot][0], a.slice_cs[di][dir_slot][1]);
       const f2 sample_direction = dir_radius * cs;
       const f3 sample_end_pos = reconstruct_view_vec(screen_uv + sample_direction, frag_depth, a.pr);
-      f3 slice_normal = normalize_fast(cross(w0, -sample_end_pos));
-      f3 normal_projected = madd(camera_normal, -dot(camera_normal, slice_normal), slice_normal);
-      f3 X = -normalize_fast(cross(slice_normal, w0));
+      const f3 slice_normal = normalize_fast(cross(w0, -sample_end_pos));
+      const f3 normal_projected = madd(camera_normal, -dot(camera_normal, slice_normal), slice_normal);
+      const f3 X = -normalize_fast(cross(slice_normal, w0));
       const float np_len2 = dot(normal_projected, normal_projected);
       float np_len = fast_sqrt(np_len2);
       float n_cos = dot(normal_projected, X) * fast_rsq(np_len2);
       if (!(fabsf(n_cos) <= 0.9999f)) {
         // acos cliff (surface seen edge-on in this slice): whether the argument rounds past +-1 — NaN in the shader,
         // which zeroes the slice's arc — is decided by its last bit, so this rare case takes the exact sequence
-        slice_normal = normalize(cross(w0, -sample_end_pos));
-        normal_projected = madd(camera_normal, -dot(camera_normal, slice_normal), slice_normal);
-        X = -normalize(cross(slice_normal, w0));
-        n_cos = dot(normalize(normal_projected), X);
-        np_len = length(normal_projected);
+        const SliceFrame exact = slice_frame<true>(w0, -sample_end_pos, camera_normal);
+        n_cos = dot(normalize(exact.normal_projected), -exact.X);
+        np_len = length(exact.normal_projected);
       }
       const float n = VKR_PI / 2.0f - acosf(n_cos);
       const float h_cos = find_horizon<TILED>(tile, a.depth, a.pr, screen_uv, camera_pos, sample_direction, w0);
-      float h = acosf(h_cos);
-      h = vmin(n + vmin(h - n, VKR_PI / 2.0f), h);
-      const float arc = vmax((-cosf(2.0f * h - n) + cosf(n)) + (2.0f * h) * sinf(n), 0.0f);
+      const float h = clamp_horizon(acosf(h_cos), n);
       if (MIS) {
-        occlusion = (((1.0f / VKR_PI) * np_len) * 0.25f) * arc;
+        occlusion = arc_occlusion(h, n, np_len);
         L = normalize(sample_end_pos - camera_pos);
       } else {
-        sum += (np_len * 0.25f) * arc;
+        sum += (np_len * 0.25f) * horizon_arc(h, n);
       }
     }
     if (!MIS) {
@@ -199,10 +186,7 @@ __global__ __launch_bounds__(GT_BX * GT_BY, 8) void k_gtao_main(GtaoArgs a) {
       }
     }
   }
-  uint2 o;
-  o.x = float_to_half_bits(occ_x) | (float_to_half_bits(occ_y) << 16);
-  o.y = 0u;
-  *(uint2*)(const_cast<uint8_t*>(a.out.p) + dst_off) = o;
+  *(uint2*)(const_cast<uint8_t*>(a.out.p) + dst_off) = make_uint2(pack_half2(occ_x, occ_y), 0u);
 }
 
 // filter.comp:17-51: 4x4 taps at offsets -2..+1, depth-weighted mean of raw.r.  The block stages
@@ -294,8 +278,7 @@ __global__ __launch_bounds__(256) void k_gtao_accumulate(AccumArgs a) {
     samples_count += 1.0f;
     if (samples_count > 255.0f) samples_count = 100.0f;
   }
-  *texel_ptr<uint32_t>(a.out, lx, ly) =
-      float_to_half_bits(vclamp(computed_ao, 0.0f, 1.0f)) | (float_to_half_bits(samples_count / 255.0f) << 16);
+  *texel_ptr<uint32_t>(a.out, lx, ly) = pack_half2(vclamp(computed_ao, 0.0f, 1.0f), samples_count / 255.0f);
 }
 
 }  // namespace vkr
@@ -314,23 +297,15 @@ extern "C" int vkr_gtao_main(const vkr_img* depth, const vkr_gtao_params* params
   VKR_TRY(make_tex(gtao_inout, 0, VKR_FMT_RGBA16_SFLOAT, "gtao_main.gtao_out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  a.tex_w = (a.out.fw / 8) * 8;
-  a.tex_h = (a.out.fh / 4) * 4;
+  a.tex_w = floor_dispatch_w(a.out);
+  a.tex_h = floor_dispatch_h(a.out);
   a.weight_ratio = push->weight_ratio;
   a.use_mis = push->use_mis > 0 ? 1u : 0u;
   a.two_directions = push->two_directions;
   a.reflections_only = push->reflections_only;
-  const float PI = 3.1415926535897932384626433832795f;
+  // main.comp:198,233: angle = 2*PI*(gtao_direction + angle_offset [+ dir_index/dirs_count]); MIS has the one slice of di = 0
   const uint32_t dirs = a.use_mis ? 1u : (push->two_directions != 0 ? 2u : 1u);
-  for (uint32_t di = 0; di < 2; di++) {
-    for (int k = 0; k < 16; k++) {
-      // main.comp:198,233: angle = 2*PI*(gtao_direction + angle_offset [+ dir_index/dirs_count])
-      float base_angle = (1.0f / 16.0f) * (float)k + push->angle_offset;
-      float angle = a.use_mis ? (2.0f * PI) * base_angle : (2.0f * PI) * (base_angle + (float)di / (float)dirs);
-      a.slice_cs[di][k][0] = cosf(angle);
-      a.slice_cs[di][k][1] = sinf(angle);
-    }
-  }
+  for (uint32_t di = 0; di < 2; di++) fill_slice_table(a.slice_cs[di], push->angle_offset, a.use_mis ? 0.0f : (float)di / (float)dirs);
   dim3 block(GT_BX, GT_BY);
   // (the LDS tile is staged from frame coordinates clamped to the depth window, as sample<>() clamps: the output window may be
   // any part of the frame — a strip's own rows of a window image, host/frame.cpp — as long as both describe the same frame)
@@ -350,7 +325,7 @@ extern "C" int vkr_gtao_filter(const vkr_img* depth, const vkr_img* raw_gtao, co
   VKR_TRY(make_tex(out_filtered, 0, VKR_FMT_R16_SFLOAT, "gtao_filter.out", &out));
   dim3 block(GF_BX, GF_BY);
   hipLaunchKernelGGL(k_gtao_filter, grid2d(out.w, out.h, block), block, 0, (hipStream_t)stream, d, raw, out,
-                     (out.fw / 8) * 8, (out.fh / 4) * 4, push->znear, push->zfar);
+                     floor_dispatch_w(out), floor_dispatch_h(out), push->znear, push->zfar);
   return launch_status("gtao_filter");
 }
 

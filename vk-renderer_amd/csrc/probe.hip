@@ -430,8 +430,8 @@ extern "C" int vkr_cube2oct(const vkr_img* cube_color, const vkr_img* cube_dista
   VKR_TRY(make_tex(oct_depth, 0, VKR_FMT_R16_UNORM, "cube2oct.oct_depth", &a.oct_depth));
   VKR_TRY(check_single(a.oct_color, "cube2oct.oct_color"));
   if (!same_window(a.oct_color, a.oct_depth)) { set_error("cube2oct: oct_color and oct_depth differ in extent"); return VKR_ERR_EXTENT; }
-  a.tex_w = (a.oct_color.w / 8) * 8;
-  a.tex_h = (a.oct_color.h / 4) * 4;
+  a.tex_w = floor_dispatch_w(a.oct_color);  // (check_single: the window is the whole image)
+  a.tex_h = floor_dispatch_h(a.oct_color);
   if (a.tex_w == 0 || a.tex_h == 0) return VKR_OK;
   hipLaunchKernelGGL(k_cube2oct, dim3((a.tex_w + 7) / 8, (a.tex_h + 7) / 8), dim3(64), 0, (hipStream_t)stream, a);
   return launch_status("cube2oct");
@@ -487,8 +487,8 @@ extern "C" int vkr_trace_probe(const vkr_img* depth, const vkr_img* normal, cons
   a.probe_step.y = (consts->probe_max[1] - consts->probe_min[1]) / gm1;
   a.probe_step.z = (consts->probe_max[2] - consts->probe_min[2]) / gm1;
   load_proj(a.pr, consts->fovy, consts->aspect, consts->znear, consts->zfar);
-  a.tex_w = (a.out.w / 8) * 8;
-  a.tex_h = (a.out.h / 4) * 4;
+  a.tex_w = floor_dispatch_w(a.out);
+  a.tex_h = floor_dispatch_h(a.out);
   if (a.tex_w == 0 || a.tex_h == 0) return VKR_OK;
   hipLaunchKernelGGL(k_trace_probe, dim3((a.tex_w + 7) / 8, (a.tex_h + 7) / 8), dim3(64), 0, (hipStream_t)stream, a);
   return launch_status("trace_probe");

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void k_raster_resolve(ResolveArgs a) {
     o_albedo = float_to_srgb8_lds(out_albedo.x, s_thresh) | (float_to_srgb8_lds(out_albedo.y, s_thresh) << 8) | (float_to_srgb8_lds(out_albedo.z, s_thresh) << 16) | (float_to_unorm8(out_albedo.w) << 24);
     o_material = float_to_srgb8_lds(out_material.x, s_thresh) | (float_to_srgb8_lds(out_material.y, s_thresh) << 8) | (float_to_srgb8_lds(out_material.z, s_thresh) << 16) | (float_to_unorm8(out_material.w) << 24);
     o_normal = float_to_unorm16(en.x) | (float_to_unorm16(en.y) << 16);
-    o_velocity = float_to_half_bits(vel.x) | (float_to_half_bits(vel.y) << 16);
+    o_velocity = pack_half2(vel.x, vel.y);
     o_depth = (uint32_t)(key >> 32);
   }
   *texel_ptr<uint32_t>(a.albedo, lx, ly) = o_albedo;

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_brdf_preintegrate(const float4* __restr
   }
   A *= 1.0f / (float)VKR_HALTON_SEQ_SIZE;
   B *= 1.0f / (float)VKR_HALTON_SEQ_SIZE;
-  *texel_ptr<uint32_t>(out, x, y) = float_to_half_bits(A) | (float_to_half_bits(B) << 16);
+  *texel_ptr<uint32_t>(out, x, y) = pack_half2(A, B);
 }
 
 struct ShadingArgs {

@@ -8,6 +8,7 @@
 // so trace is latency-bound and blur ALU/LDS-bound.
 #include <cstdlib>
 #include "ssr_sampling.hpp"
+#include "gtao_slice.hpp"
 
 namespace vkr {
 
@@ -234,19 +235,13 @@ VKR_DEV void trace_epilogue(const TraceArgs& a, const Tex& depth0, const RayCons
     // its coordinates must match the reference sequence bit for bit (a 1e-7 perturbation there
     // moves raw.y by far more than 1e-3).
     const f3 w0 = -normalize(view_vec);
-    const f3 slice_normal = normalize(cross(w0, R));
-    const f3 normal_projected = pixel_normal - dot(pixel_normal, slice_normal) * slice_normal;
-    const f3 X = normalize(cross(slice_normal, w0));
-    const float n = VKR_PI / 2.0f - acosf(dot(normalize(normal_projected), X));
-    float hh = acosf(h);
-    hh = vmin(n + vmin(hh - n, VKR_PI / 2.0f), hh);
+    const SliceFrame fr = slice_frame<false>(w0, R, pixel_normal);
+    const float n = slice_normal_angle(fr.normal_projected, fr.X);
+    const float hh = clamp_horizon(acosf(h), n);
     const float pdf = sampleGGXdirPDF(a.pdf, w0, pixel_normal, R, roughness);
-    const float occlusion = arc_occlusion(hh, n, length(normal_projected));
+    const float occlusion = arc_occlusion(hh, n, length(fr.normal_projected));
     const float result = is_nan(occlusion) ? 0.0f : occlusion;
-    uint2 o;
-    o.x = float_to_half_bits(result) | (float_to_half_bits(pdf) << 16);
-    o.y = 0u;
-    *texel_ptr<uint2>(a.out_occ, lx, ly) = o;
+    *texel_ptr<uint2>(a.out_occ, lx, ly) = make_uint2(pack_half2(result, pdf), 0u);
   }
 }
 
@@ -327,8 +322,7 @@ __global__ __launch_bounds__(TRACE_THREADS) void k_sssr_trace(TraceArgs a) {
     const float mg = mixf(0.0f, a.max_roughness, roughness);
     roughness = mg * mg;
     pixel_depth = taps_resolve<FmtD24>(taps_depth);
-    const f3 pixel_normal_world = decode_normal(taps_resolve<FmtRG16U>(taps_normal));
-    rc.normal = normalize(xyz(mul(a.normal_mat, mk4(pixel_normal_world.x, pixel_normal_world.y, pixel_normal_world.z, 0.0f))));
+    rc.normal = normalize(decode_view_normal(a.normal_mat, taps_resolve<FmtRG16U>(taps_normal)));
     rc.view_vec = reconstruct_view_vec(screen_uv, pixel_depth, pr);
 
     R = setup_ray(rc, screen_uv, roughness, a.halton, a.frame_random, pr, a.f_over_fn);  // trace.comp:61-84

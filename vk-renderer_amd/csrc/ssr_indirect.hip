@@ -85,8 +85,7 @@ __global__ __launch_bounds__(64) void k_sssr_trace_indirect(TraceIndirectArgs a)
   roughness *= roughness;
   const float pixel_depth = sample<FmtD24>(depth0, screen_uv);
   RayConst rc;
-  const f3 pnw = decode_normal(sample<FmtRG16U>(a.normal, screen_uv));
-  rc.normal = normalize(xyz(mul(a.normal_mat, mk4(pnw.x, pnw.y, pnw.z, 0.0f))));
+  rc.normal = sample_view_normal(a.normal, a.normal_mat, screen_uv);
   rc.view_vec = reconstruct_view_vec(screen_uv, pixel_depth, pr);
   const f3 R = setup_ray(rc, screen_uv, roughness, a.halton, a.frame_random, pr, a.f_over_fn);
 

@@ -5,13 +5,6 @@
 
 namespace vkr {
 
-// trace.comp:143-154
-VKR_DEV f3 get_tangent(f3 n) {
-  float max_xy = vmax(fabsf(n.x), fabsf(n.y));
-  f3 t = (max_xy < 0.00001f) ? mk3(1, 0, 0) : mk3(n.y, -n.x, 0);
-  return normalize(t);
-}
-
 // brdf.glsl:135-155; cos/sin(phi), phi = 2*PI*U2, come with the Halton entry (vkr_halton23_fill:
 // evaluated in double on the host and rounded once — they steer the march)
 VKR_DEV f3 sampleGGXVNDF(f3 Ve, float alpha_x, float alpha_y, float U1, float cos_phi, float sin_phi) {
@@ -38,9 +31,8 @@ VKR_DEV f3 setup_ray(RayConst& rc, f2 screen_uv, float roughness, const float4* 
   const float4 hv = halton[index];
 
   // trace.comp:65-77
-  f3 tangent = get_tangent(rc.normal);
-  const f3 bitangent = normalize(cross(rc.normal, tangent));
-  tangent = normalize(cross(bitangent, rc.normal));
+  f3 tangent, bitangent;
+  tangent_frame(rc.normal, &tangent, &bitangent);
   f3 view_dir = -normalize(rc.view_vec);
   view_dir = mk3(dot(view_dir, tangent), dot(view_dir, bitangent), dot(view_dir, rc.normal));
   const f3 brdf_norm = sampleGGXVNDF(view_dir, roughness, roughness, hv.x, hv.z, hv.w);
@@ -66,9 +58,7 @@ VKR_DEV bool ray_moved(f3 out_ray, f3 ray_start, f2 tex_size) {
 }
 // :101-109: the surface at the hit faces away from the ray (texture(normal, hit uv), not normalised)
 VKR_DEV bool hit_faces_away(const Tex& normal, const Mat4& normal_mat, f2 hit_uv, f3 R) {
-  const f3 hnw = decode_normal(sample<FmtRG16U>(normal, hit_uv));
-  const f3 hit_normal = xyz(mul(normal_mat, mk4(hnw.x, hnw.y, hnw.z, 0.0f)));
-  return dot(hit_normal, R) > 0.0f;
+  return dot(sample_view_normal_raw(normal, normal_mat, hit_uv), R) > 0.0f;
 }
 // :111-118: the ray ends at most 0.3 behind and 0.1 in front of the surface at the hit (linear depth)
 VKR_DEV bool hit_depth_in_window(const Tex& depth0, f3 out_ray, const Proj& pr) {

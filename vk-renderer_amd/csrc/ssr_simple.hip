@@ -69,8 +69,7 @@ __global__ __launch_bounds__(256) void k_ssr_simple(SsrArgs a) {
                                      floorf(screen_uv.y * tex_size.y) / tex_size.y + 0.5f / tex_size.y);
     const float roughness = sample_srgb_channel(a.material, screen_uv, 1, s_lut);
     const float pixel_depth = sample_depth_nearest(depth0, aligned_screen_uv);
-    const f3 pnw = decode_normal(sample<FmtRG16U>(a.normal, aligned_screen_uv));
-    const f3 pixel_normal = normalize(xyz(mul(a.camera_normal, mk4(pnw.x, pnw.y, pnw.z, 0.0f))));
+    const f3 pixel_normal = sample_view_normal(a.normal, a.camera_normal, aligned_screen_uv);
     // depth may be the border value 0 here -> general linearize, not the [0,1]-only fast path? 0 is in range.
     const f3 view_vec = reconstruct_view_vec(aligned_screen_uv, pixel_depth, pr);
     const f3 R = reflect(view_vec, pixel_normal);
@@ -101,9 +100,7 @@ __global__ __launch_bounds__(256) void k_ssr_simple(SsrArgs a) {
 
     const f2 dist0 = mk2(fabsf(out_ray.x - start.x), fabsf(out_ray.y - start.y));
     if (dist0.x < 2.0f / tex_size.x && dist0.y < 2.0f / tex_size.y) break;
-    const f3 hnw = decode_normal(sample<FmtRG16U>(a.normal, xy(out_ray)));
-    const f3 hit_normal = xyz(mul(a.camera_normal, mk4(hnw.x, hnw.y, hnw.z, 0.0f)));
-    if (dot(hit_normal, R) > 0.0f) break;
+    if (dot(sample_view_normal_raw(a.normal, a.camera_normal, xy(out_ray)), R) > 0.0f) break;
     const float hit_depth = sample_depth_nearest(depth0, xy(out_ray));
     if (out_ray.z > hit_depth + 0.0001f) break;
     const f2 fov = mk2(0.05f * (tex_size.y / tex_size.x), 0.05f * 1.0f);

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_synth_gbuffer(SynthArgs a) {
       mt = float_to_srgb8(0.5f) | (float_to_srgb8(roughness) << 8) | (float_to_srgb8(metallic) << 16) | (float_to_unorm8(0.5f) << 24);
       const f4 cp = mul(a.prev_mvp, mk4(P.x, P.y, P.z, 1.0f)), cc = mul(a.mvp, mk4(P.x, P.y, P.z, 1.0f));
       const float vx = 0.5f * (cp.x / cp.w - cc.x / cc.w), vy = 0.5f * (cp.y / cp.w - cc.y / cc.w);
-      vt = float_to_half_bits(vx) | (float_to_half_bits(vy) << 16);
+      vt = pack_half2(vx, vy);
     }
   }
   *texel_ptr<uint32_t>(a.depth, lx, ly) = d24;

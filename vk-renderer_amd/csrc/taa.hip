@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaArgs a) {
     }
   }
   uint2 o;
-  o.x = float_to_half_bits(out_color.x) | (float_to_half_bits(out_color.y) << 16);
+  o.x = pack_half2(out_color.x, out_color.y);
   o.y = float_to_half_bits(out_color.z);  // alpha 0 (resolve.comp:69)
   *texel_ptr<uint2>(a.out, lx, ly) = o;
 }

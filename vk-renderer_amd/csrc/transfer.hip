@@ -50,7 +50,7 @@ VKR_DEV Word4 encode_rgba(uint32_t fmt, f4 c, const float* thresh) {
   Word4 o; o.x = o.y = o.z = o.w = 0u;
   switch (fmt) {
     case VKR_FMT_RG16_UNORM: o.x = float_to_unorm16(c.x) | (float_to_unorm16(c.y) << 16); break;
-    case VKR_FMT_RG16_SFLOAT: o.x = float_to_half_bits(c.x) | (float_to_half_bits(c.y) << 16); break;
+    case VKR_FMT_RG16_SFLOAT: o.x = pack_half2(c.x, c.y); break;
     case VKR_FMT_RGBA8_SRGB:
       o.x = float_to_srgb8_lds(c.x, thresh) | (float_to_srgb8_lds(c.y, thresh) << 8) | (float_to_srgb8_lds(c.z, thresh) << 16) | (float_to_unorm8(c.w) << 24);
       break;
@@ -58,9 +58,7 @@ VKR_DEV Word4 encode_rgba(uint32_t fmt, f4 c, const float* thresh) {
     case VKR_FMT_RGBA16_UNORM:
       o.x = float_to_unorm16(c.x) | (float_to_unorm16(c.y) << 16); o.y = float_to_unorm16(c.z) | (float_to_unorm16(c.w) << 16);
       break;
-    case VKR_FMT_RGBA16_SFLOAT:
-      o.x = float_to_half_bits(c.x) | (float_to_half_bits(c.y) << 16); o.y = float_to_half_bits(c.z) | (float_to_half_bits(c.w) << 16);
-      break;
+    case VKR_FMT_RGBA16_SFLOAT: o.x = pack_half2(c.x, c.y); o.y = pack_half2(c.z, c.w); break;
     case VKR_FMT_R16_SFLOAT: o.x = float_to_half_bits(c.x); break;
     case VKR_FMT_R16_UNORM: o.x = float_to_unorm16(c.x); break;
     case VKR_FMT_R32_SFLOAT: o.x = __float_as_uint(c.x); break;
@@ -226,13 +224,13 @@ template <int FMT> VKR_DEV typename MipRaw<FMT>::T mip_reduce(typename MipRaw<FM
     auto lo = [](uint32_t v) { return half_bits_to_float(v & 0xFFFFu); };
     auto hi = [](uint32_t v) { return half_bits_to_float(v >> 16); };
     uint2 o;
-    o.x = float_to_half_bits(avg4(lo(a.x), lo(b.x), lo(c.x), lo(d.x))) | (float_to_half_bits(avg4(hi(a.x), hi(b.x), hi(c.x), hi(d.x))) << 16);
-    o.y = float_to_half_bits(avg4(lo(a.y), lo(b.y), lo(c.y), lo(d.y))) | (float_to_half_bits(avg4(hi(a.y), hi(b.y), hi(c.y), hi(d.y))) << 16);
+    o.x = pack_half2(avg4(lo(a.x), lo(b.x), lo(c.x), lo(d.x)), avg4(hi(a.x), hi(b.x), hi(c.x), hi(d.x)));
+    o.y = pack_half2(avg4(lo(a.y), lo(b.y), lo(c.y), lo(d.y)), avg4(hi(a.y), hi(b.y), hi(c.y), hi(d.y)));
     return o;
   } else if constexpr (FMT == VKR_FMT_RG16_SFLOAT) {
     auto lo = [](uint32_t v) { return half_bits_to_float(v & 0xFFFFu); };
     auto hi = [](uint32_t v) { return half_bits_to_float(v >> 16); };
-    return float_to_half_bits(avg4(lo(a), lo(b), lo(c), lo(d))) | (float_to_half_bits(avg4(hi(a), hi(b), hi(c), hi(d))) << 16);
+    return pack_half2(avg4(lo(a), lo(b), lo(c), lo(d)), avg4(hi(a), hi(b), hi(c), hi(d)));
   } else if constexpr (FMT == VKR_FMT_R16_SFLOAT) {
     return float_to_half_bits(avg4(half_bits_to_float(a), half_bits_to_float(b), half_bits_to_float(c), half_bits_to_float(d)));
   } else if constexpr (FMT == VKR_FMT_R32_SFLOAT) {

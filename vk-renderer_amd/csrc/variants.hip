@@ -8,6 +8,7 @@
 // (exact IEEE sequence for everything that places a sample or decides a branch, libm for the smooth
 // angles) and sample straight from global memory — L1/L2 serve the 20-tap horizon walks.
 #include "vkr_host.hpp"
+#include "gtao_slice.hpp"
 
 namespace vkr {
 
@@ -22,23 +23,6 @@ struct Gtao2Args {
   int tex_w, tex_h;       // divisor of screen_uv
   int half_texel;         // 1: uv = (pos + 0.5) / tex (fragment), 0: uv = pos / tex (compute)
 };
-
-template <class F> VKR_DEV float find_horizon20(const Tex& depth, const Proj& pr, f2 start, f3 camera_start, f2 dir, f3 v) {
-  float h_cos = -1.0f;
-  float previous_z = camera_start.z;
-#pragma unroll 1
-  for (int i = 1; i <= 20; i++) {
-    const f2 tc = start + ((float)i / 20.0f) * dir;
-    const float sample_depth = sample<F>(depth, tc);
-    const f3 sample_pos = reconstruct_view_vec(tc, sample_depth, pr);
-    if (sample_pos.z > previous_z + 0.1f) break;  // MAX_THIKNESS, main.frag:64
-    previous_z = sample_pos.z;
-    const f3 sample_offset = sample_pos - camera_start;
-    // max()-reduced cosine: hardware rsq (the break test above stays exact)
-    h_cos = vmax(h_cos, dot(v, sample_offset) * fast_rsq(dot(sample_offset, sample_offset)));
-  }
-  return h_cos;
-}
 
 // main.frag:164-186 == main_deinterleaved.comp:86-116, dirs_count = 1
 template <class F> __global__ __launch_bounds__(256) void k_gtao_v2(Gtao2Args a) {
@@ -56,29 +40,36 @@ template <class F> __global__ __launch_bounds__(256) void k_gtao_v2(Gtao2Args a)
   if (frag_depth < 1.0f) {
     const f3 camera_pos = reconstruct_view_vec(screen_uv, frag_depth, a.pr);
     const f3 w0 = -normalize(camera_pos);
-    const f3 n_world = decode_normal(sample<FmtRG16U>(a.normal, screen_uv));
-    const f3 camera_normal = normalize(xyz(mul(a.normal_mat, mk4(n_world.x, n_world.y, n_world.z, 0.0f))));
+    const f3 camera_normal = sample_view_normal(a.normal, a.normal_mat, screen_uv);
     const float rad = vmin(200.0f / length(camera_pos), 32.0f);
     const f2 dir_radius = mk2(rad / (float)a.depth.fw, rad / (float)a.depth.fh);
-    const int dir_slot = (((gx + gy) & 3) << 2) + (gx & 3);
+    const int dir_slot = gtao_dir_slot(gx, gy);
     const f2 sample_direction = dir_radius * mk2(a.slice_cs[dir_slot][0], a.slice_cs[dir_slot][1]);
     const f3 sample_end_pos = reconstruct_view_vec(screen_uv + sample_direction, frag_depth, a.pr);
     // The argument of this acos reaches +-1 when the projected normal lines up with the slice
     // direction (main.frag:181 normalises both and takes acos of their dot): whether it lands on
     // 1.0000001 (NaN) or 0.99999994 is decided by the last bit, so the whole chain stays exact.
-    const f3 slice_normal = normalize(cross(w0, -sample_end_pos));
-    const f3 normal_projected = camera_normal - dot(camera_normal, slice_normal) * slice_normal;
-    const float n = VKR_PI / 2.0f - acosf(dot(normalize(normal_projected), normalize(sample_end_pos - camera_pos)));
-    const float h_cos = find_horizon20<F>(a.depth, a.pr, screen_uv, camera_pos, sample_direction, w0);
-    float h = acosf(h_cos);
-    h = vmin(n + vmin(h - n, VKR_PI / 2.0f), h);
-    const float sum = (length(normal_projected) * 0.25f) * vmax((-cosf(2.0f * h - n) + cosf(n)) + (2.0f * h) * sinf(n), 0.0f);
+    const f3 normal_projected = slice_frame<false>(w0, -sample_end_pos, camera_normal).normal_projected;
+    const float n = slice_normal_angle(normal_projected, normalize(sample_end_pos - camera_pos));
+    // main.frag:66-90: 20 samples at start + (i / 20) dir, straight from global memory
+    const float h_cos = horizon_walk<20>(a.pr, camera_pos, w0,
+        [&](int i) { return screen_uv + ((float)i / 20.0f) * sample_direction; },
+        [&](f2 tc) { return sample<F>(a.depth, tc); },
+        [](float h_cos, float sample_cos) { return vmax(h_cos, sample_cos); });
+    const float h = clamp_horizon(acosf(h_cos), n);
+    const float sum = (length(normal_projected) * 0.25f) * horizon_arc(h, n);
     occlusion = 2.0f * sum;
   }
-  uint2 o;
-  o.x = float_to_half_bits(occlusion);  // (occlusion, 0, 0, 0)
-  o.y = 0u;
-  *texel_ptr<uint2>(a.out, lx, ly) = o;
+  *texel_ptr<uint2>(a.out, lx, ly) = make_uint2(float_to_half_bits(occlusion), 0u);  // (occlusion, 0, 0, 0)
+}
+
+// The static reprojection test of reproject.comp:52 (STATIC_REPROJECT) and screen_trace/accumulate.comp:31: the texel's view
+// depth is what it was a frame ago (cur_view.z == linearize_depth2(current_depth), gbuffer_encode.glsl:58-69) and it is not sky
+VKR_DEV bool depth_is_static(const Tex& depth, const Tex& prev_depth, int gx, int gy, float znear, float zfar) {
+  const float cur_z = linearize_depth2_unorm(fetch<FmtD24>(depth, gx, gy), znear, zfar);
+  const float sampled_depth = fetch<FmtD24>(prev_depth, gx, gy);
+  const float sampled_z = linearize_depth2_unorm(sampled_depth, znear, zfar);
+  return fabsf(sampled_z - cur_z) < 1e-6f && sampled_depth < 1.0f;
 }
 
 // reproject.comp:27-66 (STATIC_REPROJECT)
@@ -89,12 +80,8 @@ __global__ __launch_bounds__(256) void k_gtao_reproject(Tex depth, Tex prev_dept
   const int gx = out.ox + lx, gy = out.oy + ly;
   if (gx >= tex_w || gy >= tex_h) return;
   const float new_ao = fetch<FmtR16F>(cur_ao, gx, gy);
-  // cur_view.z == linearize_depth2(current_depth) (gbuffer_encode.glsl:58-69): only z is used
-  const float cur_z = linearize_depth2_unorm(fetch<FmtD24>(depth, gx, gy), pr.znear, pr.zfar);
-  const float sampled_depth = fetch<FmtD24>(prev_depth, gx, gy);
-  const float sampled_z = linearize_depth2_unorm(sampled_depth, pr.znear, pr.zfar);
   float ao = new_ao;
-  if (fabsf(sampled_z - cur_z) < 1e-6f && sampled_depth < 1.0f) ao = mixf(fetch<FmtR16F>(prev_ao, gx, gy), new_ao, 0.05f);
+  if (depth_is_static(depth, prev_depth, gx, gy, pr.znear, pr.zfar)) ao = mixf(fetch<FmtR16F>(prev_ao, gx, gy), new_ao, 0.05f);
   *texel_ptr<uint16_t>(out, lx, ly) = (uint16_t)float_to_half_bits(ao);
 }
 
@@ -125,10 +112,6 @@ struct ScreenTraceArgs {
   int tex_w, tex_h;
 };
 
-VKR_DEV f3 st_sample_normal(const ScreenTraceArgs& a, f2 uv) {
-  const f3 n = decode_normal(sample<FmtRG16U>(a.normal, uv));
-  return normalize(xyz(mul(a.normal_mat, mk4(n.x, n.y, n.z, 0.0f))));
-}
 // brdf.glsl:31-38 with hardware rcp (a smooth weight)
 VKR_DEV float ggx_d_fast(f3 N, f3 H, float alpha) {
   const float NoH = dot(N, H), alpha2 = alpha * alpha, NoH2 = NoH * NoH;
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(ST_TILE * ST_TILE * ST_TILES_X) void k_screen_trace
     if (screen_pos.z < 1.0f) {
       alive = true;
       camera_pos = reconstruct_view_vec(screen_uv, screen_pos.z, a.pr);
-      camera_normal = st_sample_normal(a, screen_uv);
+      camera_normal = sample_view_normal(a.normal, a.normal_mat, screen_uv);
       camera_pos = camera_pos + 1e-6f * camera_normal;
       // calc_tangent_space, trace.comp:213-226
       f3 tangent;
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(ST_TILE * ST_TILE * ST_TILES_X) void k_screen_trace
       const float sin_na = (float)sin((double)normal_angle);
       const float rad = vmin(200.0f / length(camera_pos), 32.0f);
       const f2 ao_dir_radius = mk2(rad / (float)a.depth.fw, rad / (float)a.depth.fh);
-      const int dir_slot = (((gx + gy) & 3) << 2) + (gx & 3);
+      const int dir_slot = gtao_dir_slot(gx, gy);
       const float cs_x = a.slice_cs[dir_slot][0], cs_y = a.slice_cs[dir_slot][1];
       const f3 camera_sample_dir = normalize((cs_x * tangent + cs_y * bitangent) + camera_normal * sin_na);
       f3 screen_dir = project_view_vec(camera_pos + camera_sample_dir, a.pr) - screen_pos;
@@ -218,7 +201,7 @@ __global__ __launch_bounds__(ST_TILE * ST_TILE * ST_TILES_X) void k_screen_trace
         previous_z = camera_z;
       }
       if (ray_hit) {
-        const f3 hit_normal = st_sample_normal(a, mk2(hp.x, hp.y));
+        const f3 hit_normal = sample_view_normal(a.normal, a.normal_mat, mk2(hp.x, hp.y));
         ray_hit = dot(camera_normal, hit_normal) < 0.0f;
       }
       if (ray_hit) {
@@ -261,10 +244,7 @@ __global__ __launch_bounds__(ST_TILE * ST_TILE * ST_TILES_X) void k_screen_trace
       result.x = accum.x * inv; result.y = accum.y * inv; result.z = accum.z * inv;
     }
   }
-  uint2 o;
-  o.x = float_to_half_bits(result.x) | (float_to_half_bits(result.y) << 16);
-  o.y = float_to_half_bits(result.z) | (float_to_half_bits(result.w) << 16);
-  *texel_ptr<uint2>(a.out, lx, ly) = o;
+  *texel_ptr<uint2>(a.out, lx, ly) = pack_half4(result);
 }
 
 // screen_trace/filter.comp:13-39: {linear depth, raw rgba} tile with the (-2..+1) apron in LDS
@@ -304,11 +284,7 @@ __global__ __launch_bounds__(SF_BX * SF_BY) void k_screen_trace_filter(Tex raw, 
       sum = mk4(sum.x + weight * r.x, sum.y + weight * r.y, sum.z + weight * r.z, sum.w + weight * r.w);
     }
   }
-  sum = sum / weight_sum;
-  uint2 o;
-  o.x = float_to_half_bits(sum.x) | (float_to_half_bits(sum.y) << 16);
-  o.y = float_to_half_bits(sum.z) | (float_to_half_bits(sum.w) << 16);
-  *texel_ptr<uint2>(out, lx, ly) = o;
+  *texel_ptr<uint2>(out, lx, ly) = pack_half4(sum / weight_sum);
 }
 
 // screen_trace/accumulate.comp:21-40 (in place)
@@ -319,31 +295,16 @@ __global__ __launch_bounds__(256) void k_screen_trace_accumulate(Tex depth, Tex 
   const int gx = acc.ox + lx, gy = acc.oy + ly;
   if (gx >= tex_w || gy >= tex_h) return;
   const f4 new_sum = fetch<FmtRGBA16F>(cur, gx, gy);
-  const float cur_z = linearize_depth2_unorm(fetch<FmtD24>(depth, gx, gy), znear, zfar);
-  const float sampled_depth = fetch<FmtD24>(prev_depth, gx, gy);
-  const float sampled_z = linearize_depth2_unorm(sampled_depth, znear, zfar);
   f4 out_sum = new_sum;
   uint2* dst = texel_ptr<uint2>(acc, lx, ly);
-  if (fabsf(sampled_z - cur_z) < 1e-6f && sampled_depth < 1.0f) {
+  if (depth_is_static(depth, prev_depth, gx, gy, znear, zfar)) {
     const uint2 p = *dst;
     const f4 sampled_sum = mk4(half_bits_to_float(p.x & 0xFFFFu), half_bits_to_float(p.x >> 16), half_bits_to_float(p.y & 0xFFFFu), half_bits_to_float(p.y >> 16));
     out_sum = mix4(sampled_sum, new_sum, 0.05f);
   }
-  uint2 o;
-  o.x = float_to_half_bits(out_sum.x) | (float_to_half_bits(out_sum.y) << 16);
-  o.y = float_to_half_bits(out_sum.z) | (float_to_half_bits(out_sum.w) << 16);
-  *dst = o;
+  *dst = pack_half4(out_sum);
 }
 
-static void fill_slice_table(float (*cs)[2], float angle_offset) {
-  const float PI = 3.1415926535897932384626433832795f;
-  for (int k = 0; k < 16; k++) {
-    const float base_angle = (1.0f / 16.0f) * (float)k + angle_offset;
-    const float angle = (2.0f * PI) * (base_angle + 0.0f / 1.0f);
-    cs[k][0] = cosf(angle);
-    cs[k][1] = sinf(angle);
-  }
-}
 static int make_layers(const vkr_img* layers, uint32_t count, const char* what, Tex* first, LayerSet* set) {
   if (!layers || count == 0 || count > 64) { set_error("%s: needs 1..64 array layers", what); return VKR_ERR_NULL; }
   VKR_TRY(make_tex(&layers[0], 0, VKR_FMT_R32_SFLOAT, what, first));
@@ -373,7 +334,7 @@ extern "C" int vkr_gtao_main_graphics(const vkr_img* depth, const vkr_gtao_param
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "gtao_main.out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  fill_slice_table(a.slice_cs, push->angle_offset);
+  fill_slice_table(a.slice_cs, push->angle_offset, 0.0f);
   a.inv_w = a.out.fw; a.inv_h = a.out.fh;
   a.scale = 1; a.off_x = 0; a.off_y = 0;
   a.tex_w = a.out.fw; a.tex_h = a.out.fh;
@@ -396,7 +357,7 @@ extern "C" int vkr_gtao_reproject(const vkr_gtao_reprojection* params, const vkr
   load_proj(pr, params->fovy, params->aspect, params->znear, params->zfar);
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_gtao_reproject, grid2d(out.w, out.h, block), block, 0, (hipStream_t)stream, d, pd, cur, prev, out, pr,
-                     (out.fw / 8) * 8, (out.fh / 4) * 4);
+                     floor_dispatch_w(out), floor_dispatch_h(out));
   return launch_status("gtao_reproject");
 }
 
@@ -408,7 +369,7 @@ extern "C" int vkr_deinterleave_depth(const vkr_img* depth, const vkr_img* layer
   LayerSet set;
   VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "deinterleave_depth.depth", &d));
   VKR_TRY(make_layers(layers, layer_count, "deinterleave_depth.out", &first, &set));
-  const int tw = (first.fw / 8) * 8, th = (first.fh / 4) * 4;
+  const int tw = floor_dispatch_w(first), th = floor_dispatch_h(first);
   if (tw == 0 || th == 0) return VKR_OK;
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_deinterleave, grid2d(tw, th, block), block, 0, (hipStream_t)stream, d, set, push->pattern_step, tw, th);
@@ -430,9 +391,9 @@ extern "C" int vkr_gtao_main_deinterleaved(const vkr_img* layers, uint32_t layer
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "main_deinterleaved.out", &a.out));
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  fill_slice_table(a.slice_cs, push->angle_offset);
+  fill_slice_table(a.slice_cs, push->angle_offset, 0.0f);
   const int scale = 1 << push->pattern_n;
-  a.inv_w = (a.out.fw / 8) * 8; a.inv_h = (a.out.fh / 4) * 4;
+  a.inv_w = floor_dispatch_w(a.out); a.inv_h = floor_dispatch_h(a.out);
   a.scale = scale;
   a.off_x = (int)(push->layer & (uint32_t)(scale - 1));
   a.off_y = (int)((push->layer >> push->pattern_n) & (uint32_t)(scale - 1));
@@ -463,7 +424,7 @@ extern "C" int vkr_screen_trace_main(const vkr_img* depth, const vkr_img* normal
   }
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  fill_slice_table(a.slice_cs, params->angle_offset);
+  fill_slice_table(a.slice_cs, params->angle_offset, 0.0f);
   a.random_offset = params->random_offset;
   const int groups_x = a.out.fw / ST_TILE, groups_y = a.out.fh / ST_TILE;
   a.tex_w = groups_x * ST_TILE; a.tex_h = groups_y * ST_TILE;
@@ -482,7 +443,7 @@ extern "C" int vkr_screen_trace_filter(const vkr_img* raw, const vkr_img* depth,
   VKR_TRY(make_tex(out_filtered, 0, VKR_FMT_RGBA16_SFLOAT, "screen_trace_filter.out", &out));
   dim3 block(SF_BX, SF_BY);
   hipLaunchKernelGGL(k_screen_trace_filter, grid2d(out.w, out.h, block), block, 0, (hipStream_t)stream, r, d, out,
-                     (out.fw / 8) * 8, (out.fh / 4) * 4, push->znear, push->zfar);
+                     floor_dispatch_w(out), floor_dispatch_h(out), push->znear, push->zfar);
   return launch_status("screen_trace_filter");
 }
 
@@ -496,6 +457,6 @@ extern "C" int vkr_screen_trace_accumulate(const vkr_img* depth, const vkr_img* 
   VKR_TRY(make_tex(accum_inout, 0, VKR_FMT_RGBA16_SFLOAT, "screen_trace_accumulate.accum", &acc));
   dim3 block(64, 4);
   hipLaunchKernelGGL(k_screen_trace_accumulate, grid2d(acc.w, acc.h, block), block, 0, (hipStream_t)stream, d, pd, cur, acc,
-                     (acc.fw / 8) * 8, (acc.fh / 4) * 4, push->znear, push->zfar);
+                     floor_dispatch_w(acc), floor_dispatch_h(acc), push->znear, push->zfar);
   return launch_status("screen_trace_accumulate");
 }

@@ -228,6 +228,9 @@ VKR_DEV uint32_t float_to_unorm16(float f) { return (uint32_t)rintf(vclamp(f, 0.
 VKR_DEV uint32_t float_to_unorm8(float f) { return (uint32_t)rintf(vclamp(f, 0.0f, 1.0f) * 255.0f); }
 VKR_DEV float half_bits_to_float(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 VKR_DEV uint32_t float_to_half_bits(float f) { return (uint32_t)__half_as_ushort(__float2half_rn(f)); }
+// two / four fp16 values as the dwords of an RG16F / RGBA16F texel
+VKR_DEV uint32_t pack_half2(float a, float b) { return float_to_half_bits(a) | (float_to_half_bits(b) << 16); }
+VKR_DEV uint2 pack_half4(f4 v) { return make_uint2(pack_half2(v.x, v.y), pack_half2(v.z, v.w)); }
 
 // ---- image windows ----------------------------------------------------------------------
 // One mip level of an image window.  (w,h): extent held in memory; (fw,fh): extent of the
@@ -446,6 +449,25 @@ VKR_DEV f3 decode_normal_fast(f2 uv) {
   }
   return normalize_fast(v);
 }
+// A G-buffer normal taken to view space by the camera's normal matrix: from its RG16_UNORM code, and as texture(normal, uv).
+// The hit-normal tests only take the sign of a dot product and leave it un-normalised (trace.comp:101-109, ssr/shader.frag).
+VKR_DEV f3 decode_view_normal(const Mat4& normal_mat, f2 code) {
+  const f3 n = decode_normal(code);
+  return xyz(mul(normal_mat, mk4(n.x, n.y, n.z, 0.0f)));
+}
+VKR_DEV f3 sample_view_normal_raw(const Tex& normal_tex, const Mat4& normal_mat, f2 uv) { return decode_view_normal(normal_mat, sample<FmtRG16U>(normal_tex, uv)); }
+VKR_DEV f3 sample_view_normal(const Tex& normal_tex, const Mat4& normal_mat, f2 uv) { return normalize(sample_view_normal_raw(normal_tex, normal_mat, uv)); }
+// trace.comp:65-67 == rt_main.frag:84-86: bitangent and tangent made perpendicular to n and to each other, from any tangent
+VKR_DEV void orthonormalise(f3 n, f3* tangent, f3* bitangent) {
+  *bitangent = normalize(cross(n, *tangent));
+  *tangent = normalize(cross(*bitangent, n));
+}
+// trace.comp:143-154,65-67 == rt_main.frag:50-61,84-86: a tangent frame around the normal n
+VKR_DEV void tangent_frame(f3 n, f3* tangent, f3* bitangent) {
+  const float max_xy = vmax(fabsf(n.x), fabsf(n.y));
+  *tangent = normalize(max_xy < 0.00001f ? mk3(1.0f, 0.0f, 0.0f) : mk3(n.y, -n.x, 0.0f));
+  orthonormalise(n, tangent, bitangent);
+}
 // gbuffer_encode.glsl:53-56
 VKR_DEV float linearize_depth2(float d, float n, float f) { return (n * f) / cfma(d, f - n, -f); }
 // the same for a stored depth d in [0,1]: the denominator lies in [-f, -n], far inside the normal range
@@ -541,11 +563,6 @@ VKR_DEV float sin_hash_arg(float x) {
   const double cs = __builtin_fma(z * z, pc, __builtin_fma(z, -0.5, 1.0));
   const double v = (k & 1) ? cs : sn;
   return (float)((k & 2) ? -v : v);
-}
-
-// the cosine-weighted horizon arc shared by main.comp:246-248 and trace.comp:127-134
-VKR_DEV float arc_occlusion(float h, float n, float len_np) {
-  return (((1.0f / VKR_PI) * len_np) * 0.25f) * vmax((-cosf(2.0f * h - n) + cosf(n)) + (2.0f * h) * sinf(n), 0.0f);
 }
 
 }  // namespace vkr

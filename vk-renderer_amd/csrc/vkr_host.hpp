@@ -99,6 +99,22 @@ inline void load_proj(Proj& pr, const float fovy_aspect_znear_zfar[4]) {
   load_proj(pr, fovy_aspect_znear_zfar[0], fovy_aspect_znear_zfar[1], fovy_aspect_znear_zfar[2], fovy_aspect_znear_zfar[3]);
 }
 
+// The extent a pass of 8 x 4 workgroups covers when the reference floors its group counts (gtao.cpp:145, w / 8 x h / 4
+// groups): the ragged edge of the frame is not dispatched, and main.comp:54 derives its texture size from this extent.
+inline int floor_dispatch_w(const Tex& t) { return (t.fw / 8) * 8; }
+inline int floor_dispatch_h(const Tex& t) { return (t.fh / 4) * 4; }
+
+// (cos, sin) of the 16 slice angles 2 PI (k / 16 + offset + turn), k = 16 * gtao_direction(pixel) (gtao_slice.hpp), host libm:
+// main.comp:198,233 (turn = dir_index / dirs_count), main.frag:170 and rt_main.frag:89 (turn = 0)
+inline void fill_slice_table(float (*cs)[2], float offset, float turn) {
+  const float PI = 3.1415926535897932384626433832795f;
+  for (int k = 0; k < 16; k++) {
+    const float angle = (2.0f * PI) * (((1.0f / 16.0f) * (float)k + offset) + turn);
+    cs[k][0] = cosf(angle);
+    cs[k][1] = sinf(angle);
+  }
+}
+
 inline int launch_status(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("%s: launch failed: %s", what, hipGetErrorString(e)); return (int)e; }
