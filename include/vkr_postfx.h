@@ -459,6 +459,25 @@ uint64_t vkr_default_shadow_scratch_bytes(uint32_t size, uint32_t layer_count, u
 int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4* mvps /* [layer_count] */, const vkr_img* layers /* [layer_count] */,
                        uint32_t layer_count, void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* program "ssao": SSAOPass::draw (ssao.cpp:54-97) + ssao/shader.{vert,frag}, the reference's first ambient-occlusion pass.
+ * The uniform block as the SHADER reads it (std140: a vec3 array has a 16-byte stride), 336 bytes; .w of a sample is not read. */
+typedef struct vkr_ssao_params {
+  vkr_mat4 projection;
+  float fovy, aspect, znear, zfar;
+  float samples[16][4];
+} vkr_ssao_params;
+/* Bindings in shader order: 0 depth (D24_UNORM_S8; mip 0 of the view, ssao.cpp:62), 1 the block, colour attachment
+ * out_occlusion (R8_UNORM, any extent: the shader works in uv).  Per output pixel g, shader.frag:21-41 in this order:
+ * screen_uv = (g + 0.5) / extent; frag_depth = texture(depth, screen_uv); camera_pos = reconstruct_view_vec(screen_uv,
+ * frag_depth, ...); for each of the 16 samples pos = camera_pos + 0.05 * sample (one fused multiply-add per component under
+ * numeric contract 2), ndc = projection * (pos, 1), ndc.xyz / ndc.w (IEEE division: w = 0, infinities and NaN as they fall),
+ * sample_uv = 0.5 * ndc.xy + 0.5, counted when ndc.z < texture(depth, sample_uv) + 0.0000001 (the sum rounded to float, then
+ * compared; a NaN on either side does not count); stored: count / 16 as UNORM8 = rint(x * 255), ties to even (8 / 16 -> 128).
+ * texture(): bilinear, clamp-to-edge, float -> int saturating with NaN -> 0.  Every texel of out_occlusion is written.
+ * Refused before any launch: a NULL argument, a descriptor without memory, other formats, a zero extent, an output wider or
+ * higher than 65535, and a windowed descriptor on either side (the taps reach anywhere: a single-GPU pass). */
+int vkr_ssao(const vkr_img* depth, const vkr_ssao_params* params, const vkr_img* out_occlusion, void* stream);
+
 /* synthetic G-buffer generator (no reference program).  Any of the
  * colour outputs may be NULL when VKR_SYNTH_DEPTH_ONLY is set.                          */
 int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, const vkr_img* albedo,

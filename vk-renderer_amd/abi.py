@@ -232,6 +232,13 @@ class ClearValue(C.Structure):  # vkr_clear_value
 
 FILTER_NEAREST, FILTER_LINEAR = 0, 1
 
+
+# ---- program ssao ----
+class SsaoParams(C.Structure):  # vkr_ssao_params: the block as ssao/shader.frag reads it (std140), 336 bytes, samples at offset 80
+    _fields_ = [("projection", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float),
+                ("samples", (C.c_float * 4) * 16)]
+
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -378,6 +385,9 @@ def product():
         lib.vkr_gen_mipmaps.argtypes = [_IMG, C.c_void_p]
         for name in ("clear_image", "blit_image", "gen_mipmaps"):
             getattr(lib, "vkr_" + name).restype = C.c_int
+        # the SSAO pass (checked against the numpy restatement tests/ssao_reference.py)
+        lib.vkr_ssao.argtypes = [_IMG, P(SsaoParams), _IMG, C.c_void_p]
+        lib.vkr_ssao.restype = C.c_int
         _product = lib
     return _product
 
@@ -444,6 +454,28 @@ def default_shadow(scene, mvps, layers, scratch, scratch_bytes, stream=None):
     mats = (Mat4 * max(1, n))(*[Mat4.from_np(m) for m in mvps])
     descs = (VkrImg * max(1, n))(*list(layers))
     check(lib.vkr_default_shadow(C.byref(scene), mats, descs, n, scratch, int(scratch_bytes), stream), lib)
+
+
+def ssao_params(projection, fovy, aspect, znear, zfar, samples):
+    """SsaoParams from a 4x4 projection (maths convention), the camera's four floats and 16 samples: an array of [16, 3] (w = 0)
+    or [16, 4] (the block's 16-byte slots as they are)."""
+    import numpy as np
+
+    s = np.asarray(samples, dtype=np.float32)
+    if s.shape not in ((16, 3), (16, 4)):
+        raise RuntimeError(f"ssao_params: samples of shape {s.shape}, expected (16, 3) or (16, 4)")
+    p = SsaoParams(Mat4.from_np(projection), float(fovy), float(aspect), float(znear), float(zfar))
+    for i in range(16):
+        for c in range(s.shape[1]):
+            p.samples[i][c] = float(s[i, c])
+    return p
+
+
+def ssao(depth, params, out_occlusion, stream=None):
+    """vkr_ssao: out_occlusion (R8_UNORM VkrImg, any extent) := the 16-sample SSAO of `depth` (D24_UNORM_S8 VkrImg, mip 0 of the
+    view) under `params` (SsaoParams, e.g. ssao_params(...)).  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    check(lib.vkr_ssao(C.byref(depth), C.byref(params), C.byref(out_occlusion), stream), lib)
 
 
 COMM_ID_BYTES = 128

@@ -20,6 +20,7 @@ STAGE_PROBE_TRACE = 1 << 22  # ProbeTracePass::run through the grid of bake_prob
 STAGE_SHADOW = 1 << 23  # SceneRenderer::render_shadow per configured light -> layers of image "shadows"; needs load_scene(); not tiled
 STAGE_CLEAR_PREV_DEPTH = 1 << 24  # clear_depth(graph, gbuffer.prev_depth) (main.cpp:306), before every other stage; not tiled
 TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the host, the frame builds the others (vkr_gen_mipmaps)
+STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); after the G-buffer / raster / shadow stages, before the downsample; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -137,7 +138,10 @@ def lib():
                            ("vkrh_transfer", [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_float)]),
                            # deferred shading in the tiled frame (same rule)
                            ("vkrh_tiled_set_shading", [C.c_void_p, C.c_uint32]),
-                           ("vkrh_tiled_shading", [C.c_void_p])):
+                           ("vkrh_tiled_shading", [C.c_void_p]),
+                           # the SSAO pass (same rule)
+                           ("vkrh_set_ssao_samples", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
+                           ("vkrh_selftest_ssao", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -347,6 +351,14 @@ class HostFrame:
         for i, m in enumerate(mvps):
             flat[16 * i: 16 * i + 16] = list(_mat16(m))
         self._check(lib().vkrh_set_shadow_lights(self.h, flat, len(mvps), int(size)))
+
+    def set_ssao_samples(self, samples, std140=0):
+        """vkrh_set_ssao_samples: pins the 16 samples ([16, 3]) of STAGE_SSAO and their packing in the uniform block: std140 = 0
+        the reference's (the shader sees samples 12..15 as zero and the others shifted), 1 one 16-byte slot per sample."""
+        s = np.ascontiguousarray(np.asarray(samples, dtype=np.float32)[:, :3]).reshape(-1)
+        if s.size != 48:
+            raise RuntimeError(f"set_ssao_samples: {s.size} floats, expected 16 x 3")
+        self._check(lib().vkrh_set_ssao_samples(self.h, (C.c_float * 48)(*[float(v) for v in s]), int(std140)))
 
     def shadow_lights(self):
         """vkrh_shadow_lights: the light matrices in use as 4x4 float32 arrays (maths convention)"""

@@ -108,6 +108,25 @@ struct PostFxFrame {
   uint32_t shadow_size = 1024;
   std::vector<glm::mat4> shadow_lights{default_shadow_mvp()};
 
+  // VKRH_STAGE_SSAO: the pass and its target, created on first use (the constructor draws from rand(): a frame that never runs
+  // the stage leaves the sequence of the other passes' draws alone)
+  std::unique_ptr<SSAOPass> ssao_pass;
+  rendergraph::ImageResourceId ssao_tex;
+  SSAOPass& ensure_ssao() {
+    if (!ssao_pass) {
+      ssao_tex = create_ssao_texture(graph, cfg.width, cfg.height);
+      ssao_pass.reset(new SSAOPass(graph, ssao_tex));
+    }
+    return *ssao_pass;
+  }
+  void set_ssao_samples(const float* xyz, uint32_t std140) {
+    if (!xyz) throw std::runtime_error{"vkrh_set_ssao_samples: NULL argument"};
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_ssao_samples: on a tiled frame (VKRH_STAGE_SSAO runs on one GPU)"};
+    SSAOPass& pass = ensure_ssao();
+    for (uint32_t i = 0; i < 16; i++) pass.sphere_samples[i] = glm::vec3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    pass.std140_samples = std140 != 0;
+  }
+
   // main.cpp:392-396: the RGBA8_SRGB image the final frame is blitted into before it is read back (capture kind 3)
   rendergraph::ImageResourceId readback_image;
   bool has_readback_image = false;
@@ -207,6 +226,8 @@ struct PostFxFrame {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
     if ((mask & VKRH_STAGE_CLEAR_PREV_DEPTH) && cfg.tiled)  // refused before anything is recorded
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_CLEAR_PREV_DEPTH on a tiled frame (transfers take whole images)"};
+    if ((mask & VKRH_STAGE_SSAO) && cfg.tiled)  // refused before anything is recorded
+      throw std::runtime_error{"vkrh_run: VKRH_STAGE_SSAO on a tiled frame (a sample's reach is unbounded near the eye: SSAO runs on one GPU)"};
     if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
@@ -241,6 +262,10 @@ struct PostFxFrame {
       ensure_shadows();
       for (uint32_t l = 0; l < shadow_lights.size(); l++) scene_renderer->render_shadow(graph, shadow_lights[l], shadows, l);
       shadows_rendered = true;
+    }
+    if (mask & VKRH_STAGE_SSAO) {  // reads depth mip 0 only: before the downsample writes the other mips
+      SSAOPass& pass = ensure_ssao();
+      pass.draw(graph, gbuffer.depth, ssao_tex, SSAOInParams{projection, fazz.x, fazz.y, fazz.z, fazz.w});
     }
     if (mask & VKRH_STAGE_DOWNSAMPLE)  // main.cpp:347
       downsample_pass.run(graph, gbuffer.normal, gbuffer.velocity_vectors, gbuffer.depth, gbuffer.downsampled_normals,
@@ -413,7 +438,7 @@ struct PostFxFrame {
         {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
-        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}};
+        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -434,6 +459,7 @@ struct PostFxFrame {
                : it->second == 34 ? probe_renderer->get_cubemap_color() : probe_renderer->get_cubemap_distance();
       case 36: if (!has_shadows) throw std::runtime_error{"vkrh_image: 'shadows' only exists after VKRH_STAGE_SHADOW"}; return shadows;
       case 37: if (!has_readback_image) throw std::runtime_error{"vkrh_image: 'readback' only exists after a final-frame capture (vkrh_capture kind 3)"}; return readback_image;
+      case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1234,6 +1260,9 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
     std::memcpy(out, f->shadow_lights.data(), 64 * f->shadow_lights.size());
   });
 }
+int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) {
+  return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); });
+}
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {
     auto* f = &frame_ref(frame);
@@ -1485,6 +1514,38 @@ int vkrh_selftest_transfers(char* buf, uint32_t buf_size) {
     for (const auto& t : g.pending_tasks()) {
       out += t.name + ":";
       for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+      out += "\n";
+    }
+  });
+  if (rc != 0) return rc;
+  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
+  return 0;
+}
+
+int vkrh_selftest_ssao(char* buf, uint32_t buf_size) {
+  std::string out;
+  const int rc = guarded([&] {
+    rendergraph::RenderGraph g;
+    auto depth = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT | VK_IMAGE_ASPECT_STENCIL_BIT, 64, 36, 1, 7, 1},
+                                VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_DEPTH_STENCIL_ATTACHMENT_BIT | VK_IMAGE_USAGE_SAMPLED_BIT);
+    auto target = create_ssao_texture(g, 64, 36);
+    SSAOPass pass{g, target};
+    for (uint32_t k = 0; k < 16; k++) pass.sphere_samples[k] = glm::vec3{float(3 * k), float(3 * k + 1), float(3 * k + 2)};
+    const SSAOInParams params{glm::mat4{1.f}, 1.0f, 1.5f, 0.05f, 80.f};
+    pass.draw(g, depth, target, params);
+    for (const auto& t : g.pending_tasks()) {
+      out += t.name + ":";
+      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+      out += "\n";
+    }
+    for (const bool std140 : {false, true}) {
+      pass.std140_samples = std140;
+      const std::vector<uint8_t> block = pass.uniform_block(params);
+      const vkr_ssao_params p = gpu::ssao_params_from_block(block.data(), block.size());
+      out += "packing " + std::to_string(block.size()) + ":";
+      float words[sizeof(p) / 4];
+      std::memcpy(words, &p, sizeof(p));
+      for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
       out += "\n";
     }
   });

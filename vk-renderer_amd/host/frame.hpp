@@ -67,6 +67,13 @@ enum {
   /* main.cpp:306: clear_depth(graph, gbuffer.prev_depth) — every mip of prev_depth to depth 1, stencil 0 (the word 0x00FFFFFF) —
    * recorded before every other stage of the run.  One GPU only (not on a tiled frame: transfers take whole images).           */
   VKRH_STAGE_CLEAR_PREV_DEPTH   = 1u << 24,
+  /* SSAOPass::draw (ssao.cpp:54-97; the reference ships the pass, its frame loop never records it): gbuffer.depth (mip 0 only)
+   * -> image "ssao" (R8_UNORM at the frame's extent, created on first use; vkrh_image) with the frame camera's projection and
+   * fovy, aspect, znear, zfar.  Recorded after the G-buffer, raster and shadow stages and before the downsample.  The samples
+   * are the constructor's rand() draws in the reference's packing until vkrh_set_ssao_samples pins them.  Nothing reads
+   * "ssao": the shading pass keeps GTAO's accumulated image at its occlusion binding.  One GPU only (not on a tiled frame: a
+   * sample's reach is unbounded near the eye).                                                                             */
+  VKRH_STAGE_SSAO               = 1u << 25,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -114,6 +121,15 @@ int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32
  * reallocates the image at the next VKRH_STAGE_SHADOW.  vkrh_shadow_lights returns the matrices in use (room for 4 x 16 floats). */
 int vkrh_set_shadow_lights(void* frame, const float* mvps, uint32_t count, uint32_t size);
 int vkrh_shadow_lights(void* frame, float* out, uint32_t* count);
+/* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
+ * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
+ * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */
+int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140);
+/* SSAOPass::draw recorded for pinned samples s[k] = (3k, 3k + 1, 3k + 2) and NOT submitted (no kernel is launched; images come
+ * from the installed allocator): depth is image 0 (64 x 36, 7 mips), the target image 1.  Writes the task line in the format of
+ * vkrh_selftest_transfers ("SSAO: R0.0 W1.0"), then for the reference's packing and for std140 one line "packing <bytes>:"
+ * followed by the 84 floats (%.9g) of the vkr_ssao_params the program "ssao" would hand to vkr_ssao for the recorded block. */
+int vkrh_selftest_ssao(char* buf, uint32_t buf_size);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */

@@ -5,7 +5,9 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 
 #include <map>
 #include <mutex>
@@ -288,6 +290,12 @@ template <typename T> const T* push(const LaunchState& st, const char* prog) {
   return (const T*)st.push;
 }
 }  // namespace
+
+vkr_ssao_params ssao_params_from_block(const void* block, uint64_t bytes) {
+  vkr_ssao_params p{};
+  if (block) std::memcpy(&p, block, (size_t)std::min<uint64_t>(bytes, sizeof(p)));
+  return p;
+}
 
 void create_program(const std::string& name, ProgramFn fn) { programs()[name] = std::move(fn); }
 bool has_program(const std::string& name) { return programs().count(name) != 0; }
@@ -660,6 +668,22 @@ void register_hot_path_programs() {
       for (uint32_t l = 0; l < layers; l++) { cl[l] = pc.image->describe_layer(l, 0, 1); dl[l] = pd.image->describe_layer(l, 0, pd.image->get_mip_levels()); }
       static_assert(sizeof(vkr_probe_trace_consts) == 116, "Constants of trace_probe/shader.comp");
       return vkr_trace_probe(&depth, &normal, cl.data(), dl.data(), layers, ubo<vkr_probe_trace_consts>(st, 4, P), &out, st.stream);
+    });
+    // ---- SSAO (ssao.cpp) ----
+    // ssao/shader.frag: set {0 depth, 1 SSAOParams}; colour attachment occlusion.  The block is taken as the shader would read
+    // it, whatever size the host struct has (ssao_params_from_block).
+    create_program("ssao", [=](LaunchState& st) {
+      const char* P = "ssao";
+      if (st.attachments.size() != 1) throw std::runtime_error{"ssao: expects one colour attachment"};
+      vkr_img depth = tex(st, 0, T, P);
+      const SetSlot& b = st.set->slots[1];
+      const void* data = b.host_data ? b.host_data : (b.buffer ? b.buffer->host_data() : nullptr);
+      const uint64_t size = b.host_data ? b.host_size : (b.buffer ? b.buffer->get_size() : 0);
+      if (b.kind != SetSlot::Ubo || !data || size < 80) throw std::runtime_error{"ssao: uniform block 1 is not bound"};
+      static_assert(sizeof(vkr_ssao_params) == 336 && offsetof(vkr_ssao_params, samples) == 80, "SSAOParams of ssao/shader.frag (std140)");
+      const vkr_ssao_params params = ssao_params_from_block(data, size);
+      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      return vkr_ssao(&depth, &params, &out, st.stream);
     });
     // ---- dormant GTAO variants ----
     // gtao/main.frag: set {0 depth, 1 GTAOParams, 2 normal}; colour attachment raw

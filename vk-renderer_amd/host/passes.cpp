@@ -1166,6 +1166,81 @@ void SceneRenderer::render_shadow(RenderGraph &graph, const glm::mat4 &shadow_mv
     });
 }
 
+// ==== SSAOPass (ssao.cpp) ================================================================================
+ImageResourceId create_ssao_texture(RenderGraph &graph, uint32_t width, uint32_t height) {  // :8-11
+  return make_image(graph, VK_FORMAT_R8_UNORM, width, height, VK_IMAGE_USAGE_COLOR_ATTACHMENT_BIT|VK_IMAGE_USAGE_SAMPLED_BIT);
+}
+
+namespace {
+constexpr uint32_t SSAO_SAMPLES_COUNT = 16;  // :13
+struct SSAOParams {  // :15-22, the host's view of the block: 272 bytes
+  glm::mat4 projection;
+  float fovy;
+  float aspect;
+  float znear;
+  float zfar;
+  glm::vec3 samples[SSAO_SAMPLES_COUNT];
+};
+static_assert(sizeof(SSAOParams) == 272 && sizeof(vkr_ssao_params) == 336, "SSAOParams: host packing and std140");
+}  // namespace
+
+// :24-52: 16 points drawn by rejection inside the unit ball, normalised; nothing is printed
+SSAOPass::SSAOPass(RenderGraph &graph, ImageResourceId target) {
+  pipeline = fullscreen_pipeline("ssao");
+  pipeline.set_rendersubpass({false, {graph.get_descriptor(target).format}});
+  sampler = default_sampler();
+  for (uint32_t i = 0; i < SSAO_SAMPLES_COUNT; i++) {
+    while (true) {
+      const float x = 2.f * rand()/float(RAND_MAX) - 1.f;
+      const float y = 2.f * rand()/float(RAND_MAX) - 1.f;
+      const float z = 2.f * rand()/float(RAND_MAX) - 1.f;
+      const float l2 = x*x + y*y + z*z;
+      if (l2 < 1.0) {
+        const auto len = std::sqrt(l2);
+        sphere_samples.push_back(glm::vec3 {x/len, y/len, z/len});
+        break;
+      }
+    }
+  }
+}
+
+std::vector<uint8_t> SSAOPass::uniform_block(const SSAOInParams &params) const {
+  if (sphere_samples.size() != SSAO_SAMPLES_COUNT)
+    throw std::runtime_error {"SSAOPass: sphere_samples holds " + std::to_string(sphere_samples.size()) + " samples, the shader reads 16"};
+  std::vector<uint8_t> bytes(std140_samples? sizeof(vkr_ssao_params) : sizeof(SSAOParams), 0);
+  if (std140_samples) {
+    vkr_ssao_params block {};
+    copy_mat(block.projection, params.projection);
+    block.fovy = params.fovy; block.aspect = params.aspect; block.znear = params.znear; block.zfar = params.zfar;
+    for (uint32_t i = 0; i < SSAO_SAMPLES_COUNT; i++)
+      for (int c = 0; c < 3; c++) block.samples[i][c] = sphere_samples[i][c];
+    std::memcpy(bytes.data(), &block, sizeof(block));
+  } else {  // :69-77
+    SSAOParams block {};
+    block.projection = params.projection;
+    block.fovy = params.fovy;
+    block.aspect = params.aspect;
+    block.znear = params.znear;
+    block.zfar = params.zfar;
+    for (uint32_t i = 0; i < SSAO_SAMPLES_COUNT; i++) block.samples[i] = sphere_samples[i];
+    std::memcpy(bytes.data(), &block, sizeof(block));
+  }
+  return bytes;
+}
+
+// :54-97: task "SSAO"; depth sampled (depth aspect, mip 0, one level), colour attachment `target`, the block from the frame's
+// uniform ring, one full-screen triangle at the target's extent
+void SSAOPass::draw(RenderGraph &graph, ImageResourceId depth, ImageResourceId target, const SSAOInParams &params) {
+  rec::Binding block;
+  block.kind = rec::Binding::UniformBlock;
+  block.slot = 1;
+  block.bytes = uniform_block(params);
+  const auto ext = graph.get_descriptor(target);
+  rec::fullscreen(graph, "SSAO", pipeline,
+    {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), block, rec::color_target(target)},
+    rec::no_push(), ext.width, ext.height);
+}
+
 // ==== probe renderer (probe_renderer.hpp; reference: src/probe_renderer.cpp, whose render_side is a commented-out body: here it draws)
 // Every task executes through the programs cubemap_probe, cube2oct, probe_downsample and trace_probe registered in gpu/gpu.cpp.
 using rendergraph::ImageViewId;

@@ -656,6 +656,45 @@ private:
 
 
 // ======================================================================================================
+// ssao.hpp — the reference's first ambient-occlusion pass, public interface of src/ssao.hpp:7-26 over the C-ABI program
+// "ssao" (DESIGN.md 7.4).  Two host behaviours of the reference are kept as they are (DESIGN_NUMERICS.md, SSAO):
+// the constructor draws its 16 unit samples with rand(), and draw() packs them at a 12-byte stride into a 272-byte block
+// under a shader that reads a 16-byte stride over 336 bytes.
+
+
+rendergraph::ImageResourceId create_ssao_texture(rendergraph::RenderGraph &graph, uint32_t width, uint32_t height);
+
+struct SSAOInParams {
+  glm::mat4 projection;
+  float fovy;
+  float aspect;
+  float znear;
+  float zfar;
+};
+
+struct SSAOPass {
+  SSAOPass(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId target);
+
+  void draw(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId target, const SSAOInParams &params);
+
+  // the bytes draw() uploads as the uniform block for `params`: 272 in the reference's packing, 336 with std140_samples
+  std::vector<uint8_t> uniform_block(const SSAOInParams &params) const;
+
+  // Private in the reference; public here so that a caller can pin the 16 samples (as GTAO::pin_angle_jitter pins its
+  // jitter): overwrite the entries, keep the count.
+  std::vector<glm::vec3> sphere_samples;
+  // false: the reference's packing (ssao.cpp:15-22,75-77): the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat
+  // 48-float array for i <= 11 and zero for i = 12..15.  true: every sample in its own 16-byte slot of a 336-byte block,
+  // the SSAO the shader's declaration means.
+  bool std140_samples = false;
+
+private:
+  gpu::GraphicsPipeline pipeline;
+  VkSampler sampler;
+};
+
+
+// ======================================================================================================
 // synthetic_gbuffer.hpp — headless replacement of the G-buffer raster stage
 // (SceneRenderer::draw_taa, src/scene_renderer.cpp:140-220 + shaders/gbuf/opaque_taa.*).
 // Writes the same attachments of `Gbuffer` from an analytic scene so the post-process chain runs
