@@ -47,8 +47,7 @@ typedef enum vkr_format {
   VKR_FMT_R16_SFLOAT     = 8,  /* 1 x fp16                                         */
   VKR_FMT_R32_SFLOAT     = 9,  /* 1 x fp32                                         */
   VKR_FMT_R8_UNORM       = 10, /* 1 x uint8 (create_gtao_texture, gtao.cpp:10)     */
-  VKR_FMT_RGBA32_SFLOAT  = 11, /* 4 x fp32: AdvancedSSR::tile_planes (advanced_ssr.cpp:85), allocated by the reference's
-                                  constructor, bound by no program of this path       */
+  VKR_FMT_RGBA32_SFLOAT  = 11, /* 4 x fp32: AdvancedSSR::tile_planes (advanced_ssr.cpp:85), written by vkr_tile_regression */
   VKR_FMT_R16_UNORM      = 12  /* 1 x uint16: the octahedral probe depth (probe_renderer.cpp:284,302) */
 } vkr_format;
 
@@ -477,6 +476,25 @@ typedef struct vkr_ssao_params {
  * Refused before any launch: a NULL argument, a descriptor without memory, other formats, a zero extent, an output wider or
  * higher than 65535, and a windowed descriptor on either side (the taps reach anywhere: a single-GPU pass). */
 int vkr_ssao(const vkr_img* depth, const vkr_ssao_params* params, const vkr_img* out_occlusion, void* stream);
+
+/* program "tile_regression": AdvancedSSR::run_tile_regression_pass (advanced_ssr.cpp:497-538) + advanced_ssr/regression.comp, the
+ * per-tile plane fit of the tile-classified SSR experiment.  The push constants as the shader declares them, 80 bytes. */
+typedef struct vkr_tile_regression_push { vkr_mat4 camera_to_world; float fovy, aspect, znear, zfar; } vkr_tile_regression_push;
+/* Bindings in shader order: 0 depth (D24_UNORM_S8; mip 0 of the view is read: the caller passes a view of mip 1 of the G-buffer
+ * depth, advanced_ssr.cpp:523), 1 out_planes (RGBA32_SFLOAT, one texel per 8 x 8 tile of the depth view; any extent up to
+ * ceil(w / 8) x ceil(h / 8); the reference allocates (W / 16, H / 16) of the full-resolution frame, rounded down).  Per tile,
+ * regression.comp:22-101 in the order DESIGN_NUMERICS.md (Tile regression) freezes: lane i = ly * 8 + lx takes pixel
+ * p = 8 * tile + (lx, ly); screen_uv = vec2(p) / vec2(size) (no half-texel offset, IEEE division, pixel 0 gives 0);
+ * r = (camera_to_world * (reconstruct_view_vec(screen_uv, texelFetch(depth, p), ...), 1) - camera_to_world * (0, 0, 0, 1)).xyz;
+ * a lane whose pixel lies outside the view contributes r = 0 and is still one of the 64; depth 1 (sky) has no special case.
+ * The sums of r, r * r and (r.x r.y, r.x r.z, r.y r.z) follow the shader's tree s[i] += s[i + off], off = 32 .. 1;
+ * plane = inverse(mat3 of the sums) * sum r with the inverse as the adjugate over the determinant (GLM's layout, nothing fused,
+ * 1 / det an IEEE division: det = 0 gives infinities, and plane is stored as it falls); each lane's squared residual
+ * (dot(plane, r) - 1)^2, 1e10 where that is NaN, so an outside lane adds 1; .w = their tree sum / 64.
+ * Every texel of out_planes is written and nothing outside its rows.  Refused before any launch: a NULL argument, a descriptor
+ * without memory, other formats, a zero extent, an out_planes wider or higher than ceil(w / 8) x ceil(h / 8) (such a tile has no
+ * pixel and the reference never dispatches it) or higher than 65535, and a windowed descriptor on either side. */
+int vkr_tile_regression(const vkr_img* depth, const vkr_img* out_planes, const vkr_tile_regression_push* push, void* stream);
 
 /* synthetic G-buffer generator (no reference program).  Any of the
  * colour outputs may be NULL when VKR_SYNTH_DEPTH_ONLY is set.                          */

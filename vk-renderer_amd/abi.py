@@ -239,6 +239,11 @@ class SsaoParams(C.Structure):  # vkr_ssao_params: the block as ssao/shader.frag
                 ("samples", (C.c_float * 4) * 16)]
 
 
+# ---- program tile_regression ----
+class TileRegressionPush(C.Structure):  # vkr_tile_regression_push: the push constants of advanced_ssr/regression.comp, 80 bytes
+    _fields_ = [("camera_to_world", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
+
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -388,6 +393,9 @@ def product():
         # the SSAO pass (checked against the numpy restatement tests/ssao_reference.py)
         lib.vkr_ssao.argtypes = [_IMG, P(SsaoParams), _IMG, C.c_void_p]
         lib.vkr_ssao.restype = C.c_int
+        # the tile plane regression (checked against the numpy restatement tests/tile_regression_reference.py)
+        lib.vkr_tile_regression.argtypes = [_IMG, _IMG, P(TileRegressionPush), C.c_void_p]
+        lib.vkr_tile_regression.restype = C.c_int
         _product = lib
     return _product
 
@@ -476,6 +484,20 @@ def ssao(depth, params, out_occlusion, stream=None):
     view) under `params` (SsaoParams, e.g. ssao_params(...)).  Raises RuntimeError with the library's message on a refusal."""
     lib = product()
     check(lib.vkr_ssao(C.byref(depth), C.byref(params), C.byref(out_occlusion), stream), lib)
+
+
+def tile_regression_push(camera_to_world, fovy, aspect, znear, zfar):
+    """TileRegressionPush from a 4x4 camera-to-world matrix (maths convention) and the camera's four floats"""
+    return TileRegressionPush(Mat4.from_np(camera_to_world), float(fovy), float(aspect), float(znear), float(zfar))
+
+
+def tile_regression(depth, out_planes, push, stream=None):
+    """vkr_tile_regression: out_planes (RGBA32_SFLOAT VkrImg, at most ceil(w / 8) x ceil(h / 8)) := per 8 x 8 tile of `depth`
+    (D24_UNORM_S8 VkrImg, mip 0 of the view: pass a view of the G-buffer depth's mip 1) the fitted plane and its mean squared
+    residual under `push` (TileRegressionPush, e.g. tile_regression_push(...)).  Raises RuntimeError with the library's message
+    on a refusal."""
+    lib = product()
+    check(lib.vkr_tile_regression(C.byref(depth), C.byref(out_planes), C.byref(push), stream), lib)
 
 
 COMM_ID_BYTES = 128

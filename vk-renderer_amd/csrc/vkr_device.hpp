@@ -196,6 +196,32 @@ VKR_DEV f4 mul(const Mat4& M, f4 v) {
   return r;
 }
 
+// inverse(mat3) laid out as GLM's (GLSL leaves its arithmetic open; DESIGN_NUMERICS.md, Tile regression): the adjugate times
+// 1 / det.  Column-major, m[3 * c + r].  Nothing is fused under either contract: every cofactor is round(p * q) - round(r * s),
+// det = (m00 * c00 - m10 * c01) + m20 * c02 along the first row, 1.0f / det is the IEEE division (det = 0 gives an infinity
+// and the entries fall as IEEE makes them), every entry is its signed cofactor times that quotient.
+struct Mat3 { float m[9]; };
+VKR_DEV Mat3 inverse_adjugate(const Mat3& a) {
+  const float m00 = a.m[0], m01 = a.m[1], m02 = a.m[2], m10 = a.m[3], m11 = a.m[4], m12 = a.m[5], m20 = a.m[6], m21 = a.m[7], m22 = a.m[8];
+  const float c00 = m11 * m22 - m21 * m12, c01 = m01 * m22 - m21 * m02, c02 = m01 * m12 - m11 * m02;
+  const float inv_det = 1.0f / ((m00 * c00 - m10 * c01) + m20 * c02);
+  Mat3 r;
+  r.m[0] = c00 * inv_det;
+  r.m[1] = -c01 * inv_det;
+  r.m[2] = c02 * inv_det;
+  r.m[3] = -(m10 * m22 - m20 * m12) * inv_det;
+  r.m[4] = (m00 * m22 - m20 * m02) * inv_det;
+  r.m[5] = -(m00 * m12 - m10 * m02) * inv_det;
+  r.m[6] = (m10 * m21 - m20 * m11) * inv_det;
+  r.m[7] = -(m00 * m21 - m20 * m01) * inv_det;
+  r.m[8] = (m00 * m11 - m10 * m01) * inv_det;
+  return r;
+}
+// M * v, rows accumulated left to right without fusing: (m_r0 * v.x + m_r1 * v.y) + m_r2 * v.z
+VKR_DEV f3 mul_unfused(const Mat3& a, f3 v) {
+  return mk3((a.m[0] * v.x + a.m[3] * v.y) + a.m[6] * v.z, (a.m[1] * v.x + a.m[4] * v.y) + a.m[7] * v.z, (a.m[2] * v.x + a.m[5] * v.y) + a.m[8] * v.z);
+}
+
 // ---- storage codecs -------------------------------------------------------------------
 #include "srgb_tables.inc"
 VKR_DEV float srgb8_to_float(uint32_t c) { return __uint_as_float(k_srgb_decode_bits[c]); }

@@ -21,6 +21,7 @@ STAGE_SHADOW = 1 << 23  # SceneRenderer::render_shadow per configured light -> l
 STAGE_CLEAR_PREV_DEPTH = 1 << 24  # clear_depth(graph, gbuffer.prev_depth) (main.cpp:306), before every other stage; not tiled
 TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the host, the frame builds the others (vkr_gen_mipmaps)
 STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); after the G-buffer / raster / shadow stages, before the downsample; not tiled
+STAGE_TILE_REGRESSION = 1 << 26  # AdvancedSSR::run_tile_regression_pass: depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W/16, H/16)); after the downsample; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -141,7 +142,9 @@ def lib():
                            ("vkrh_tiled_shading", [C.c_void_p]),
                            # the SSAO pass (same rule)
                            ("vkrh_set_ssao_samples", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
-                           ("vkrh_selftest_ssao", [C.c_char_p, C.c_uint32])):
+                           ("vkrh_selftest_ssao", [C.c_char_p, C.c_uint32]),
+                           # the tile plane regression (same rule)
+                           ("vkrh_selftest_tile_regression", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l

@@ -127,6 +127,9 @@ struct PostFxFrame {
     pass.std140_samples = std140 != 0;
   }
 
+  // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
+  bool has_tile_planes = false;
+
   // main.cpp:392-396: the RGBA8_SRGB image the final frame is blitted into before it is read back (capture kind 3)
   rendergraph::ImageResourceId readback_image;
   bool has_readback_image = false;
@@ -228,6 +231,8 @@ struct PostFxFrame {
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_CLEAR_PREV_DEPTH on a tiled frame (transfers take whole images)"};
     if ((mask & VKRH_STAGE_SSAO) && cfg.tiled)  // refused before anything is recorded
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_SSAO on a tiled frame (a sample's reach is unbounded near the eye: SSAO runs on one GPU)"};
+    if ((mask & VKRH_STAGE_TILE_REGRESSION) && cfg.tiled)  // refused before anything is recorded
+      throw std::runtime_error{"vkrh_run: VKRH_STAGE_TILE_REGRESSION on a tiled frame (halved strip bounds are no multiples of 8: tiles would straddle owners)"};
     if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
@@ -283,6 +288,10 @@ struct PostFxFrame {
     const glm::mat4 normal_mat = glm::transpose(glm::inverse(view));
     const GTAOParams gtao_params{normal_mat, fazz.x, fazz.y, fazz.z, fazz.w};
     const AdvancedSSRParams assr_params{normal_mat, fazz.x, fazz.y, fazz.z, fazz.w};
+    if (mask & VKRH_STAGE_TILE_REGRESSION) {  // reads depth mip 1: after the downsample of this run; independent of the SSR stages
+      ssr.run_tile_regression_pass(graph, assr_params, gbuffer);
+      has_tile_planes = true;
+    }
     if (mask & (VKRH_STAGE_SSR | VKRH_STAGE_SSR_CLASSIFIED)) {                               // main.cpp:375
       ssr.get_settings().use_tile_classification = (mask & VKRH_STAGE_SSR_CLASSIFIED) != 0;
       ssr.run(graph, assr_params, draw_params, gbuffer, gtao.raw);
@@ -438,7 +447,8 @@ struct PostFxFrame {
         {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
-        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38}};
+        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38},
+        {"tile_planes", 39}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -460,6 +470,7 @@ struct PostFxFrame {
       case 36: if (!has_shadows) throw std::runtime_error{"vkrh_image: 'shadows' only exists after VKRH_STAGE_SHADOW"}; return shadows;
       case 37: if (!has_readback_image) throw std::runtime_error{"vkrh_image: 'readback' only exists after a final-frame capture (vkrh_capture kind 3)"}; return readback_image;
       case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
+      case 39: if (!has_tile_planes) throw std::runtime_error{"vkrh_image: 'tile_planes' only exists after VKRH_STAGE_TILE_REGRESSION"}; return ssr.get_tile_planes();
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1548,6 +1559,38 @@ int vkrh_selftest_ssao(char* buf, uint32_t buf_size) {
       for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
       out += "\n";
     }
+  });
+  if (rc != 0) return rc;
+  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
+  return 0;
+}
+
+int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size) {
+  std::string out;
+  const int rc = guarded([&] {
+    rendergraph::RenderGraph g;
+    Gbuffer gbuffer{g, 64, 48};
+    AdvancedSSR pass{g, 64, 48};
+    glm::mat4 normal_mat{0.f};
+    for (int c = 0; c < 4; c++)
+      for (int r = 0; r < 4; r++) normal_mat[c][r] = float(4 * c + r + 1);
+    const AdvancedSSRParams params{normal_mat, 1.0f, 1.5f, 0.05f, 80.f};
+    pass.run_tile_regression_pass(g, params, gbuffer);
+    const uint32_t depth = gbuffer.depth.get_index(), planes = pass.get_tile_planes().get_index();
+    out += "images: depth " + std::to_string(depth) + " tile_planes " + std::to_string(planes) + "\n";
+    const auto ext = g.get_descriptor(pass.get_tile_planes());
+    out += "tile_planes: " + std::to_string(ext.width) + "x" + std::to_string(ext.height) + " format " + std::to_string(int(ext.format)) + "\n";
+    for (const auto& t : g.pending_tasks()) {
+      out += t.name + ":";
+      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+      out += "\n";
+    }
+    const vkr_tile_regression_push pc = AdvancedSSR::tile_regression_push(params);
+    float words[sizeof(pc) / 4];
+    std::memcpy(words, &pc, sizeof(pc));
+    out += "push " + std::to_string(sizeof(pc)) + ":";
+    for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
+    out += "\n";
   });
   if (rc != 0) return rc;
   if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }

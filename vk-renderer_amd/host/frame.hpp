@@ -74,6 +74,13 @@ enum {
    * "ssao": the shading pass keeps GTAO's accumulated image at its occlusion binding.  One GPU only (not on a tiled frame: a
    * sample's reach is unbounded near the eye).                                                                             */
   VKRH_STAGE_SSAO               = 1u << 25,
+  /* AdvancedSSR::run_tile_regression_pass (advanced_ssr.cpp:497-538; the reference ships the pass, its run() has it commented
+   * out): gbuffer.depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W / 16, H / 16), created on first use; vkrh_image): per
+   * 8 x 8 tile of the half-resolution depth the fitted plane and its mean squared residual, with camera_to_world =
+   * transpose(normal matrix) of the frame's camera.  Recorded after the downsample of the same run (it reads mip 1) and before
+   * the SSR stages, which do not read it.  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame: halved strip
+   * bounds are no multiples of 8, tiles would straddle owners).                                                              */
+  VKRH_STAGE_TILE_REGRESSION    = 1u << 26,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -130,6 +137,12 @@ int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140);
  * vkrh_selftest_transfers ("SSAO: R0.0 W1.0"), then for the reference's packing and for std140 one line "packing <bytes>:"
  * followed by the 84 floats (%.9g) of the vkr_ssao_params the program "ssao" would hand to vkr_ssao for the recorded block. */
 int vkrh_selftest_ssao(char* buf, uint32_t buf_size);
+/* AdvancedSSR::run_tile_regression_pass recorded on a 64 x 48 G-buffer for the normal matrix m[c][r] = 4c + r + 1 (column-major
+ * 1..16, not symmetric) and fovy, aspect, znear, zfar = 1, 1.5, 0.05, 80, and NOT submitted (no kernel is launched; images come
+ * from the installed allocator).  Writes "images: depth <i> tile_planes <j>" (graph indices), "tile_planes: <w>x<h> format <VkFormat>",
+ * the task line in the format of vkrh_selftest_transfers ("SSSR_Tile_Regression: R<i>.1 W<j>.0") and "push 80:" followed by the
+ * 20 floats (%.9g) of the push constants the task records for the program "tile_regression". */
+int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */

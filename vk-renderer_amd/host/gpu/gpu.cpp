@@ -333,10 +333,14 @@ void register_hot_path_programs() {
       vkr_img depth = ds.view.image->describe(ds.view.range.base_mip, 1 + (uint32_t)st.attachments.size());
       return vkr_depth_mips(&depth, 0, st.stream);
     });
-    // Programs the reference's constructors name but this path does not implement (out of scope):
-    // known to the table, so that constructing the pass works as it does in the reference; launching one throws.
-    for (const char* name : {"tile_regression"})
-      create_program(name, [name](LaunchState&) -> int { throw std::runtime_error{std::string{name} + ": program is not implemented on the post-process path"}; });
+    // advanced_ssr/regression.comp: set {0 depth (a view of mip 1), 1 planes}; push constants camera_to_world + fovy, aspect,
+    // znear, zfar.  The kernel covers the storage image's extent: the groups the reference dispatches beyond it store nothing.
+    create_program("tile_regression", [=](LaunchState& st) {
+      const char* P = "tile_regression";
+      vkr_img depth = tex(st, 0, T, P), planes = tex(st, 1, S, P);
+      static_assert(sizeof(vkr_tile_regression_push) == 80, "PushConstants of advanced_ssr/regression.comp");
+      return vkr_tile_regression(&depth, &planes, push<vkr_tile_regression_push>(st, P), st.stream);
+    });
     // gtao/rt_main.frag: set {0 GTAORTParams, 1 depth, 2 normal, 3 acceleration structure, 4 RandomVectors}; colour attachment raw
     create_program("gtao_rt_main", [=](LaunchState& st) {
       const char* P = "gtao_rt_main";

@@ -730,10 +730,30 @@ void ScreenSpaceTrace::add_accumulate_pass(RenderGraph &graph, const ScreenTrace
 }
 
 // ==== DeferedShadingPass (defered_shading.cpp) ======================================================================
-// advanced_ssr.cpp:497-545: the program "tile_regression" is not in the table (out of scope)
+// advanced_ssr.cpp:508-519: the push constants of "tile_regression"
+vkr_tile_regression_push AdvancedSSR::tile_regression_push(const AdvancedSSRParams &params) {
+  vkr_tile_regression_push pc;
+  copy_mat(pc.camera_to_world, glm::transpose(params.normal_mat));
+  pc.fovy = params.fovy; pc.aspect = params.aspect; pc.znear = params.znear; pc.zfar = params.zfar;
+  return pc;
+}
+
+// advanced_ssr.cpp:497-538: task "SSSR_Tile_Regression"; depth mip 1 sampled, tile_planes stored, ceil((w/2)/8) x ceil((h/2)/8)
+// groups (rays has the half-resolution extent the reference divides out of the depth's).  tile_planes is (w/16, h/16) RGBA32F
+// (:85-86), allocated here on first use instead of in the constructor: frames that never run the pass keep their allocations.
 #ifndef VKR_REFERENCE_PASSES  // defined by the reference's own source in the drop-in build (Makefile: refpasses)
-void AdvancedSSR::run_tile_regression_pass(RenderGraph &, const AdvancedSSRParams &, const Gbuffer &) {
-  throw std::runtime_error {"AdvancedSSR::run_tile_regression_pass: tile_regression is not implemented on the post-process path"};
+void AdvancedSSR::run_tile_regression_pass(RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff) {
+  if (tile_planes == ImageResourceId {}) {
+    const auto full = graph.get_descriptor(gbuff.depth).extent2D();
+    if (full.width < 16 || full.height < 16)
+      throw std::runtime_error {"AdvancedSSR::run_tile_regression_pass: a " + std::to_string(full.width) + "x" + std::to_string(full.height) +
+                                " frame has no (w/16, h/16) tile image"};
+    tile_planes = make_image(graph, VK_FORMAT_R32G32B32A32_SFLOAT, full.width/16, full.height/16, VK_IMAGE_USAGE_SAMPLED_BIT|VK_IMAGE_USAGE_STORAGE_BIT);
+  }
+  if (!tile_regression.has_program()) tile_regression = gpu::create_compute_pipeline("tile_regression");
+  rec::compute(graph, "SSSR_Tile_Regression", tile_regression,
+    {rec::sampled_mips(0, gbuff.depth, sampler, DEPTH, 1, 1), rec::storage(1, tile_planes)},
+    rec::push(tile_regression_push(params)), rec::Grid {rays, 8, 8, rec::Ceil});
 }
 #endif
 

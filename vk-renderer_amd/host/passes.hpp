@@ -393,8 +393,8 @@ private:
 // preintegrate_pdf / preintegrate_brdf, remap_images, the getters, and the tile-classified trace the
 // reference leaves commented out of run() (advanced_ssr.cpp:547-550):
 // clear_indirect_params -> run_classification_pass -> run_trace_indirect_pass, selected with
-// Settings::use_tile_classification (default off = the reference's behaviour).  The tile-regression
-// experiment (advanced_ssr.cpp:497-538) stays out of scope.
+// Settings::use_tile_classification (default off = the reference's behaviour).  The third member of that experiment, the
+// tile regression (advanced_ssr.cpp:497-538), is recorded by run_tile_regression_pass and stays out of run(), as in the reference.
 
 
 
@@ -464,15 +464,18 @@ struct AdvancedSSR {
   rendergraph::BufferResourceId get_glossy_tiles() const { return glossy_tiles; }
   rendergraph::BufferResourceId get_reflective_indirect() const { return reflective_indirect; }
   rendergraph::BufferResourceId get_glossy_indirect() const { return glossy_indirect; }
-  // advanced_ssr.cpp:497-545 "tile_regression" (per-tile plane fit; commented out of run() in the reference and out of
-  // scope here).  Declared for source compatibility; throws "Program not found" like any program
-  // the table does not hold.
+  // advanced_ssr.cpp:497-538 "tile_regression" (per-tile plane fit; commented out of run() in the reference, and not part of
+  // run() here): task "SSSR_Tile_Regression", depth mip 1 -> tile_planes, camera_to_world = transpose(params.normal_mat).
+  // tile_planes ((w/16, h/16) RGBA32F, advanced_ssr.cpp:85-86) is allocated by the first call; get_tile_planes() is only
+  // meaningful after it.  tile_regression_push: the 80 bytes of push constants the task records for `params`.
   void run_tile_regression_pass(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff);
+  rendergraph::ImageResourceId get_tile_planes() const { return tile_planes; }
+  static vkr_tile_regression_push tile_regression_push(const AdvancedSSRParams &params);
 
 private:
   gpu::BufferPtr halton_buffer;
-  gpu::ComputePipeline tile_regression;        // never bound (see run_tile_regression_pass)
-  rendergraph::ImageResourceId tile_planes;    // advanced_ssr.cpp:85-86: output of the regression pass (RGBA32F; never allocated here)
+  gpu::ComputePipeline tile_regression;        // bound by run_tile_regression_pass
+  rendergraph::ImageResourceId tile_planes;    // advanced_ssr.cpp:85-86: output of the regression pass (RGBA32F; allocated on first use)
 
   gpu::ComputePipeline trace_pass;
   gpu::ComputePipeline trace_windowed_pass;  // multi-GPU: hit normals by request (not in the reference)

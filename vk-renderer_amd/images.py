@@ -114,6 +114,8 @@ class ImageBuf:
             return np.ascontiguousarray(rows).view(np.float32).reshape(h, w, 1)
         if f == abi.FMT_R8_UNORM:
             return np.ascontiguousarray(rows).reshape(h, w, 1)
+        if f == abi.FMT_RGBA32_SFLOAT:
+            return np.ascontiguousarray(rows).view(np.float32).reshape(h, w, 4)
         raise ValueError(f)
 
     def set_raw(self, arr, mip=0):
