@@ -496,6 +496,25 @@ typedef struct vkr_tile_regression_push { vkr_mat4 camera_to_world; float fovy, 
  * pixel and the reference never dispatches it) or higher than 65535, and a windowed descriptor on either side. */
 int vkr_tile_regression(const vkr_img* depth, const vkr_img* out_planes, const vkr_tile_regression_push* push, void* stream);
 
+/* program "texdraw": add_backbuffer_subpass (backbuffer_subpass2.cpp:15-52) + texdraw/shader.{vert,frag}, the last pass of the
+ * reference's frame and its debug view: any colour image, all channels or one, onto an 8-bit surface of the window's extent.
+ * The push constants as the shader declares them, 4 bytes. */
+typedef struct vkr_texdraw_push { uint32_t flags; } vkr_texdraw_push;   /* texdraw/shader.frag:15-17 */
+enum { VKR_TEXDRAW_SHOW_ALL = 0, VKR_TEXDRAW_SHOW_R = 1, VKR_TEXDRAW_SHOW_G = 2, VKR_TEXDRAW_SHOW_B = 4, VKR_TEXDRAW_SHOW_A = 8 };
+/* Binding 0 target_tex (any colour format vkr_blit_image takes as a source; mip 0 of the view is sampled), colour attachment
+ * backbuffer (RGBA8_SRGB or RGBA8_UNORM, any extent: the shader works in uv).  Per destination pixel g (DESIGN_NUMERICS.md,
+ * Texdraw): uv = (g + 0.5) / extent per axis (IEEE division); c = texture(target_tex, uv): texel coordinate uv * size - 0.5 (one
+ * fused multiply-add under numeric contract 2), floor, fraction by subtraction, float -> int saturating with NaN -> 0,
+ * clamp-to-edge, the decoded RGBA (absent channels 0, 0, 0, 1; RGBA8_SRGB rgb through the EOTF table, alpha linear) mixed rows
+ * first, then columns, all four channels; then the shader's four ifs in order, so the LAST set bit of R, G, B, A wins
+ * (flags = 3 shows G, 15 shows A, bits above 8 are ignored) and a shown channel goes to all four outputs; stored as the
+ * backbuffer stores: RGBA8_SRGB rgb by the threshold rule and alpha as UNORM8, RGBA8_UNORM rint(clamp(x, 0, 1) * 255); NaN -> 0.
+ * The reference's clear of the attachment to 0 is never visible (the triangle covers every pixel) and is not executed.
+ * Every texel of the backbuffer is written.  Refused before any launch: a NULL argument, a descriptor without memory,
+ * D24_UNORM_S8 or an unknown format as source, any other destination format, a zero extent, a destination wider or higher than
+ * 65535, a windowed descriptor on either side, and target_tex == backbuffer (the same memory). */
+int vkr_texdraw(const vkr_img* target_tex, const vkr_img* backbuffer, const vkr_texdraw_push* push, void* stream);
+
 /* synthetic G-buffer generator (no reference program).  Any of the
  * colour outputs may be NULL when VKR_SYNTH_DEPTH_ONLY is set.                          */
 int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, const vkr_img* albedo,
@@ -764,6 +783,11 @@ int vkr_selftest_pixel_uv(uint32_t* device_counter, uint32_t max_size, void* str
  * sqrt_ieee) differs from sqrtf(x); [1] the floats s in [2^-48, 2^64] whose cheap exact reciprocal differs from 1.0f / s
  * (two device uint32, zeroed by the caller)                                                                       */
 int vkr_selftest_sqrt(uint32_t* device_counters2, void* stream);
+/* Test hook: counts (into one device uint32, zeroed by the caller) the fp32 bit patterns — all 2^32 of them: NaNs, +-0,
+ * negatives, denormals, values >= 1 and infinities included — for which the texdraw pass's sRGB encode (vkr_device.hpp
+ * float_to_srgb8_fast: an arithmetic estimate of the code corrected by one threshold compare) differs from the binary search
+ * of the blit and the mips (float_to_srgb8_lds).                                                                   */
+int vkr_selftest_srgb_encode(uint32_t* device_counter, void* stream);
 
 #ifdef __cplusplus
 }

@@ -244,6 +244,14 @@ class TileRegressionPush(C.Structure):  # vkr_tile_regression_push: the push con
     _fields_ = [("camera_to_world", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
 
 
+# ---- program texdraw ----
+class TexdrawPush(C.Structure):  # vkr_texdraw_push: the push constants of texdraw/shader.frag, 4 bytes
+    _fields_ = [("flags", C.c_uint32)]
+
+
+TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
+
+
 HIT_BOTH_ROWS, HIT_NORMAL, HIT_REPLY_BYTES = 0x10000000, 0x20000000, 16
 HIT_WORKSPACE_WORDS = 4096  # include/vkr_postfx.h VKR_HIT_WORKSPACE_WORDS
 
@@ -396,6 +404,11 @@ def product():
         # the tile plane regression (checked against the numpy restatement tests/tile_regression_reference.py)
         lib.vkr_tile_regression.argtypes = [_IMG, _IMG, P(TileRegressionPush), C.c_void_p]
         lib.vkr_tile_regression.restype = C.c_int
+        # the backbuffer texdraw pass (checked against the numpy restatement tests/texdraw_reference.py) and its encode's self-test
+        lib.vkr_texdraw.argtypes = [_IMG, _IMG, P(TexdrawPush), C.c_void_p]
+        lib.vkr_texdraw.restype = C.c_int
+        lib.vkr_selftest_srgb_encode.argtypes = [C.c_void_p, C.c_void_p]
+        lib.vkr_selftest_srgb_encode.restype = C.c_int
         _product = lib
     return _product
 
@@ -498,6 +511,20 @@ def tile_regression(depth, out_planes, push, stream=None):
     on a refusal."""
     lib = product()
     check(lib.vkr_tile_regression(C.byref(depth), C.byref(out_planes), C.byref(push), stream), lib)
+
+
+def texdraw_push(flags=TEXDRAW_SHOW_ALL):
+    """TexdrawPush from the DrawTex flags (TEXDRAW_SHOW_*; the last set bit of R, G, B, A wins)"""
+    return TexdrawPush(int(flags) & 0xFFFFFFFF)
+
+
+def texdraw(target_tex, backbuffer, push=None, stream=None):
+    """vkr_texdraw: backbuffer (RGBA8_SRGB or RGBA8_UNORM VkrImg of any extent) := texture(target_tex, pixel-centre uv) of
+    `target_tex` (a VkrImg of any colour format, mip 0 of the view), all channels or the one `push` (TexdrawPush, e.g.
+    texdraw_push(TEXDRAW_SHOW_R); default: all) selects.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    push = push if push is not None else TexdrawPush(TEXDRAW_SHOW_ALL)
+    check(lib.vkr_texdraw(C.byref(target_tex), C.byref(backbuffer), C.byref(push), stream), lib)
 
 
 COMM_ID_BYTES = 128

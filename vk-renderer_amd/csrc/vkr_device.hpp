@@ -359,6 +359,21 @@ VKR_DEV uint32_t float_to_srgb8_lds(float x, const float* thresh) {
   }
   return (uint32_t)lo;
 }
+// float_to_srgb8_lds without the search (program "texdraw", which encodes three channels of every pixel of every frame).
+// The thresholds are the points where 255 * OETF(x) = i - 0.5 (gen_tables.py), so for thresh[i] <= x < thresh[i + 1] the
+// real 255 * OETF(x) lies in [i - 0.5, i + 0.5) and its floor is i - 1 or i.  est is that quantity within 0.01
+// (v_log_f32 / v_exp_f32 are good to 1 ulp: ~1e-4 of a code; the rounding of a threshold to fp32 moves it by < 1e-5 of a code;
+// tests/test_texdraw.py bounds the formula), far inside the 0.5 the argument needs; e = floor(clamp(est, 0, 254)) is therefore
+// the code or one less, and ONE compare against the next threshold decides.  x < thresh[1], negatives, -inf: est <= 0.5, e = 0,
+// the compare fails: 0.  x >= thresh[255], +inf: e = 254, the compare holds: 255.  NaN: est is NaN, fmaxf gives 0, the compare
+// fails: 0.  vkr_selftest_srgb_encode compares the two encodes on all 2^32 bit patterns.
+VKR_DEV uint32_t float_to_srgb8_fast(float x, const float* thresh) {
+  // 255 * (1.055 * x^(1 / 2.4) - 0.055) = exp2(log2(x) / 2.4 + log2(269.025)) - 14.025
+  const float curve = __builtin_amdgcn_exp2f(__builtin_fmaf(__builtin_amdgcn_logf(x), 0x1.aaaaaap-2f, 0x1.024a84p+3f)) - 14.025f;
+  const float est = x < 0.0031308f ? x * 3294.6f : curve;  // 255 * 12.92 x on the linear toe (also every x <= 0)
+  const uint32_t e = (uint32_t)fminf(fmaxf(est, 0.0f), 254.0f);
+  return e + (thresh[e + 1u] <= x ? 1u : 0u);
+}
 VKR_DEV uint32_t load_u32_clamped(const Tex& t, int gx, int gy) {
   int lx = iclamp(gx - t.ox, 0, t.w - 1), ly = iclamp(gy - t.oy, 0, t.h - 1);
   return *(const uint32_t*)(t.p + toff(t, lx, ly, 4));

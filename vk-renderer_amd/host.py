@@ -22,6 +22,7 @@ STAGE_CLEAR_PREV_DEPTH = 1 << 24  # clear_depth(graph, gbuffer.prev_depth) (main
 TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the host, the frame builds the others (vkr_gen_mipmaps)
 STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); after the G-buffer / raster / shadow stages, before the downsample; not tiled
 STAGE_TILE_REGRESSION = 1 << 26  # AdvancedSSR::run_tile_regression_pass: depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W/16, H/16)); after the downsample; not tiled
+STAGE_BACKBUFFER = 1 << 27  # add_backbuffer_subpass + add_present_subpass: the TAA output (or set_backbuffer's image) -> image "backbuffer" (RGBA8_SRGB); last; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -144,7 +145,10 @@ def lib():
                            ("vkrh_set_ssao_samples", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
                            ("vkrh_selftest_ssao", [C.c_char_p, C.c_uint32]),
                            # the tile plane regression (same rule)
-                           ("vkrh_selftest_tile_regression", [C.c_char_p, C.c_uint32])):
+                           ("vkrh_selftest_tile_regression", [C.c_char_p, C.c_uint32]),
+                           # the backbuffer texdraw pass (same rule)
+                           ("vkrh_set_backbuffer", [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+                           ("vkrh_selftest_texdraw", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -362,6 +366,12 @@ class HostFrame:
         if s.size != 48:
             raise RuntimeError(f"set_ssao_samples: {s.size} floats, expected 16 x 3")
         self._check(lib().vkrh_set_ssao_samples(self.h, (C.c_float * 48)(*[float(v) for v in s]), int(std140)))
+
+    def set_backbuffer(self, source=None, flags=0, width=0, height=0):
+        """vkrh_set_backbuffer: what STAGE_BACKBUFFER draws: `source` an image name (None: the TAA output), `flags` the DrawTex
+        bits (abi.TEXDRAW_SHOW_*), width x height the backbuffer's extent (0, 0: the frame's)."""
+        name = source.encode() if source else None
+        self._check(lib().vkrh_set_backbuffer(self.h, name, int(flags), int(width), int(height)))
 
     def shadow_lights(self):
         """vkrh_shadow_lights: the light matrices in use as 4x4 float32 arrays (maths convention)"""

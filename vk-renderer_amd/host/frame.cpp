@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "advanced_ssr.hpp"
+#include "backbuffer_subpass2.hpp"
 #include "defered_shading.hpp"
 #include "downsample_pass.hpp"
 #include "gtao.hpp"
@@ -130,6 +131,25 @@ struct PostFxFrame {
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
   bool has_tile_planes = false;
 
+  // VKRH_STAGE_BACKBUFFER (main.cpp:398-401): what is drawn, how and at which extent (vkrh_set_backbuffer)
+  std::string backbuffer_source;  // empty: the TAA output
+  uint32_t backbuffer_flags = 0, backbuffer_w = 0, backbuffer_h = 0;  // extent 0: the frame's
+  bool backbuffer_drawn = false;
+  VkSampler backbuffer_sampler = gpu::create_sampler(gpu::DEFAULT_SAMPLER);
+  rendergraph::ImageResourceId backbuffer_source_id() { return backbuffer_source.empty() ? taa_pass.get_output() : lookup(backbuffer_source); }
+  void set_backbuffer(const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_backbuffer: on a tiled frame (VKRH_STAGE_BACKBUFFER runs on one GPU)"};
+    if ((width == 0) != (height == 0) || width > 65535 || height > 65535)
+      throw std::runtime_error{"vkrh_set_backbuffer: extent " + std::to_string(width) + "x" + std::to_string(height) + " (0 x 0: the frame's; at most 65535 a side)"};
+    const std::string name = source_image ? source_image : "";
+    if (name == "backbuffer") throw std::runtime_error{"vkrh_set_backbuffer: the backbuffer cannot be its own source"};
+    if (!name.empty()) {  // an unknown name throws here; the image is looked up again when the stage is recorded
+      const auto info = graph.get_descriptor(lookup(name));
+      if (info.format == VK_FORMAT_D24_UNORM_S8_UINT) throw std::runtime_error{"vkrh_set_backbuffer: '" + name + "' is a depth image (texdraw samples colour formats)"};
+    }
+    backbuffer_source = name; backbuffer_flags = flags; backbuffer_w = width; backbuffer_h = height;
+  }
+
   // main.cpp:392-396: the RGBA8_SRGB image the final frame is blitted into before it is read back (capture kind 3)
   rendergraph::ImageResourceId readback_image;
   bool has_readback_image = false;
@@ -233,6 +253,9 @@ struct PostFxFrame {
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_SSAO on a tiled frame (a sample's reach is unbounded near the eye: SSAO runs on one GPU)"};
     if ((mask & VKRH_STAGE_TILE_REGRESSION) && cfg.tiled)  // refused before anything is recorded
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_TILE_REGRESSION on a tiled frame (halved strip bounds are no multiples of 8: tiles would straddle owners)"};
+    if ((mask & VKRH_STAGE_BACKBUFFER) && cfg.tiled)  // refused before anything is recorded
+      throw std::runtime_error{"vkrh_run: VKRH_STAGE_BACKBUFFER on a tiled frame (the uv of a pixel spans the whole source: the backbuffer is drawn on one GPU)"};
+    if (mask & VKRH_STAGE_BACKBUFFER) (void)backbuffer_source_id();  // a source that does not exist (yet) is refused before anything is recorded
     if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
@@ -348,6 +371,12 @@ struct PostFxFrame {
       shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
     }
     if (mask & VKRH_STAGE_TAA) taa_pass.run(graph, gbuffer, (mask & VKRH_STAGE_SHADING) ? color_out_tex : gbuffer.albedo, draw_params);
+    if (mask & VKRH_STAGE_BACKBUFFER) {  // main.cpp:398-401
+      graph.set_backbuffer_extent(backbuffer_w ? backbuffer_w : cfg.width, backbuffer_h ? backbuffer_h : cfg.height);
+      add_backbuffer_subpass(graph, backbuffer_source_id(), backbuffer_sampler, DrawTex(backbuffer_flags));
+      add_present_subpass(graph);
+      backbuffer_drawn = true;
+    }
     graph.submit();
     if ((mask & (VKRH_STAGE_GBUFFER | VKRH_STAGE_RASTER)) && gbuffer.pipelined) copy_depth_to_next_set();
     task_names.clear();
@@ -448,7 +477,7 @@ struct PostFxFrame {
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
         {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38},
-        {"tile_planes", 39}};
+        {"tile_planes", 39}, {"backbuffer", 40}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -471,6 +500,7 @@ struct PostFxFrame {
       case 37: if (!has_readback_image) throw std::runtime_error{"vkrh_image: 'readback' only exists after a final-frame capture (vkrh_capture kind 3)"}; return readback_image;
       case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
       case 39: if (!has_tile_planes) throw std::runtime_error{"vkrh_image: 'tile_planes' only exists after VKRH_STAGE_TILE_REGRESSION"}; return ssr.get_tile_planes();
+      case 40: if (!backbuffer_drawn) throw std::runtime_error{"vkrh_image: 'backbuffer' only exists after VKRH_STAGE_BACKBUFFER"}; return graph.get_backbuffer();
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1274,6 +1304,9 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
 int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) {
   return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); });
 }
+int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
+  return guarded([&] { frame_ref(frame).set_backbuffer(source_image, flags, width, height); });
+}
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {
     auto* f = &frame_ref(frame);
@@ -1591,6 +1624,33 @@ int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size) {
     out += "push " + std::to_string(sizeof(pc)) + ":";
     for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
     out += "\n";
+  });
+  if (rc != 0) return rc;
+  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
+  return 0;
+}
+
+int vkrh_selftest_texdraw(char* buf, uint32_t buf_size) {
+  std::string out;
+  const int rc = guarded([&] {
+    rendergraph::RenderGraph g;
+    g.set_backbuffer_extent(64, 36);
+    auto source = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16B16A16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 128, 72, 1, 3, 1},
+                                 VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT | VK_IMAGE_USAGE_SAMPLED_BIT);
+    add_backbuffer_subpass(g, source, gpu::create_sampler(gpu::DEFAULT_SAMPLER), DrawTex::ShowR);
+    add_present_subpass(g);
+    const auto backbuffer = g.get_backbuffer();
+    out += "images: source " + std::to_string(source.get_index()) + " backbuffer " + std::to_string(backbuffer.get_index()) + "\n";
+    const auto ext = g.get_descriptor(backbuffer);
+    out += "backbuffer: " + std::to_string(ext.width) + "x" + std::to_string(ext.height) + " format " + std::to_string(int(ext.format)) + "\n";
+    for (const auto& t : g.pending_tasks()) {
+      out += t.name + ":";
+      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+      out += "\n";
+    }
+    out += std::string{"program: texdraw "} + (gpu::has_program("texdraw") ? "1" : "0") + "\n";
+    const vkr_texdraw_push pc = texdraw_push(DrawTex::ShowR);
+    out += "push " + std::to_string(sizeof(pc)) + ": " + std::to_string(pc.flags) + "\n";
   });
   if (rc != 0) return rc;
   if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }

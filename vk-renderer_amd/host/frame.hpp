@@ -81,6 +81,12 @@ enum {
    * the SSR stages, which do not read it.  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame: halved strip
    * bounds are no multiples of 8, tiles would straddle owners).                                                              */
   VKRH_STAGE_TILE_REGRESSION    = 1u << 26,
+  /* add_backbuffer_subpass + add_present_subpass (main.cpp:398-401; backbuffer_subpass2.cpp): the source image (default: the
+   * TAA output of this run) drawn by program "texdraw" onto image "backbuffer" (RGBA8_SRGB; default: the frame's extent;
+   * vkrh_image, vkrh_capture and the read-backs address it), all channels or the one vkrh_set_backbuffer selected.  Recorded
+   * last, after TAA.  Nothing reads "backbuffer".  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame: the uv
+   * of a pixel spans the whole source).                                                                                    */
+  VKRH_STAGE_BACKBUFFER         = 1u << 27,
   VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -143,6 +149,17 @@ int vkrh_selftest_ssao(char* buf, uint32_t buf_size);
  * the task line in the format of vkrh_selftest_transfers ("SSSR_Tile_Regression: R<i>.1 W<j>.0") and "push 80:" followed by the
  * 20 floats (%.9g) of the push constants the task records for the program "tile_regression". */
 int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size);
+/* What VKRH_STAGE_BACKBUFFER draws: `source_image` a name vkrh_image knows (NULL or "": the TAA output, "taa_target"), looked
+ * up when the stage is recorded; `flags` the DrawTex bits (VKR_TEXDRAW_SHOW_*: 0 all channels, else the last set bit of R, G,
+ * B, A wins); width / height the backbuffer's extent, 0 and 0 the frame's.  An unknown image name, a depth image (D24_UNORM_S8),
+ * "backbuffer" itself, one extent 0 and the other not, or an extent above 65535 is an error.  Not on a tiled frame.        */
+int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height);
+/* add_backbuffer_subpass(graph, image, sampler, DrawTex::ShowR) + add_present_subpass(graph) recorded on a graph whose
+ * backbuffer is 64 x 36 for a 128 x 72 RGBA16_SFLOAT source with 3 mips, and NOT submitted (no kernel is launched; images come
+ * from the installed allocator).  Writes "images: source <i> backbuffer <j>" (graph indices), "backbuffer: <w>x<h> format
+ * <VkFormat>", the task lines in the format of vkrh_selftest_transfers ("BackbufSubpass: W<j>.0 R<i>.0", "presentPrepare:
+ * R<j>.0"), "program: texdraw <0|1>" (registered?) and "push 4: <flags>", the push constants the task records. */
+int vkrh_selftest_texdraw(char* buf, uint32_t buf_size);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */

@@ -689,6 +689,17 @@ void register_hot_path_programs() {
       vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
       return vkr_ssao(&depth, &params, &out, st.stream);
     });
+    // ---- backbuffer (backbuffer_subpass2.cpp) ----
+    // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the
+    // reference records first is covered by the triangle and not executed.
+    create_program("texdraw", [=](LaunchState& st) {
+      const char* P = "texdraw";
+      if (st.attachments.size() != 1) throw std::runtime_error{"texdraw: expects one colour attachment"};
+      vkr_img target_tex = tex(st, 0, T, P);
+      static_assert(sizeof(vkr_texdraw_push) == 4, "Constants of texdraw/shader.frag");
+      vkr_img backbuffer = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      return vkr_texdraw(&target_tex, &backbuffer, push<vkr_texdraw_push>(st, P), st.stream);
+    });
     // ---- dormant GTAO variants ----
     // gtao/main.frag: set {0 depth, 1 GTAOParams, 2 normal}; colour attachment raw
     create_program("gtao_main", [=](LaunchState& st) {

@@ -15,6 +15,7 @@
 #include "probe_renderer.hpp"
 #include "scene/scene_as.hpp"
 #include "util_passes.hpp"
+#include "backbuffer_subpass2.hpp"
 
 using rendergraph::ImageResourceId;
 using rendergraph::RenderGraph;
@@ -1508,4 +1509,69 @@ void ProbeTracePass::run(RenderGraph &graph, OctahedralProbeGrid &probe, ImageRe
       cmd.bind_descriptors_compute(0, {set}, {blk.offset});
       cmd.dispatch(desc.width/8, desc.height/4, 1);
     });
+}
+
+// ==== backbuffer subpass (backbuffer_subpass2.cpp) =======================================================
+vkr_texdraw_push texdraw_push(DrawTex flags) { return vkr_texdraw_push {uint32_t(flags)}; }
+
+namespace {
+// :17-20,27-28,38-50: what both overloads share once the texture view exists.  `texture`: the view of a graph image
+// (declared by the builder), or none, in which case `image` is bound directly (:74-77).
+struct BackbufData {
+  rendergraph::ImageViewId backbuff_view;
+  rendergraph::ImageViewId texture_view;
+  std::shared_ptr<gpu::ImageViewObject> direct_view;  // lives as long as the task: the set only holds a pointer to it
+};
+
+void record_backbuffer_subpass(RenderGraph &graph, const ImageResourceId *draw_img, gpu::ImagePtr image, VkSampler sampler, DrawTex flags) {
+  gpu::GraphicsPipeline pipeline = fullscreen_pipeline("texdraw");
+  pipeline.set_rendersubpass({false, {graph.get_descriptor(graph.get_backbuffer()).format}});
+  const vkr_texdraw_push pc = texdraw_push(flags);
+  graph.add_task<BackbufData>("BackbufSubpass",
+    [&](BackbufData &data, rendergraph::RenderGraphBuilder &builder) {
+      data.backbuff_view = builder.use_backbuffer_attachment();
+      if (draw_img) data.texture_view = builder.sample_image(*draw_img, VK_SHADER_STAGE_FRAGMENT_BIT, 0, 0, 1, 0, 1);
+    },
+    [=](BackbufData &data, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      const auto ext = resources.get_image(data.backbuff_view)->get_extent();
+      VkImageView texture;
+      if (image) {  // :74: a view of every mip of the image; the program samples its base level
+        gpu::ImageViewRange range;
+        range.aspect = image->get_info().aspect; range.base_mip = 0; range.mips_count = image->get_mip_levels();
+        data.direct_view = std::make_shared<gpu::ImageViewObject>(gpu::ImageViewObject {image.get(), range});
+        texture = (VkImageView)data.direct_view.get();
+      } else {
+        texture = resources.get_view(data.texture_view);
+      }
+      VkDescriptorSet set = resources.allocate_set(pipeline, 0);
+      gpu::write_set(set, gpu::TextureBinding {0, texture, sampler});
+      cmd.set_framebuffer(ext.width, ext.height, {resources.get_image_range(data.backbuff_view)});
+      cmd.bind_pipeline(pipeline);
+      cmd.clear_color_attachments(0.f, 0.f, 0.f, 0.f);
+      cmd.bind_descriptors_graphics(0, {set}, {});
+      cmd.push_constants_graphics(VK_SHADER_STAGE_FRAGMENT_BIT, 0, sizeof(pc), &pc);
+      cmd.bind_viewport(0.f, 0.f, float(ext.width), float(ext.height), 0.f, 1.f);
+      cmd.bind_scissors(0, 0, ext.width, ext.height);
+      cmd.draw(3, 1, 0, 0);
+      imgui_draw(nullptr);
+      cmd.end_renderpass();
+    });
+}
+}  // namespace
+
+void add_backbuffer_subpass(RenderGraph &graph, ImageResourceId draw_img, VkSampler sampler, DrawTex flags) {
+  record_backbuffer_subpass(graph, &draw_img, nullptr, sampler, flags);
+}
+
+void add_backbuffer_subpass(RenderGraph &graph, gpu::ImagePtr &image, VkSampler sampler, DrawTex flags) {
+  if (!image) throw std::runtime_error {"add_backbuffer_subpass: null image"};
+  record_backbuffer_subpass(graph, nullptr, image, sampler, flags);
+}
+
+// :95-104: task "presentPrepare" hands the backbuffer over; nothing executes
+void add_present_subpass(RenderGraph &graph) {
+  struct Nil {};
+  graph.add_task<Nil>("presentPrepare",
+    [&](Nil &, rendergraph::RenderGraphBuilder &builder) { builder.prepare_backbuffer(); },
+    [=](Nil &, rendergraph::RenderResources &, gpu::CmdContext &) {});
 }

@@ -93,6 +93,12 @@ void RenderGraphBuilder::transfer_write(ImageResourceId id, uint32_t base_mip, u
   resources.declare(id, base_mip, mip_count, Usage::TransferWrite, task_index, log);
 }
 gpu::ImageInfo RenderGraphBuilder::get_image_info(ImageResourceId id) { return resources.get_image(id)->get_info(); }
+ImageResourceId RenderGraphBuilder::get_backbuffer() {
+  if (!graph) throw std::runtime_error{"RenderGraphBuilder: no graph, no backbuffer"};
+  return graph->get_backbuffer();
+}
+ImageViewId RenderGraphBuilder::use_backbuffer_attachment() { return use_color_attachment(get_backbuffer(), 0, 0); }
+void RenderGraphBuilder::prepare_backbuffer() { resources.declare(get_backbuffer(), 0, 1, Usage::TransferRead, task_index, log); }
 
 VkImageView RenderResources::get_view(const ImageViewId& ref) {
   views.emplace_back(new gpu::ImageViewObject{resources.get_image(ref.get_id()).get(), ref.get_range()});
@@ -104,11 +110,23 @@ RenderGraph::RenderGraph(void* stream) : cmd{stream}, main_stream{stream} { gpu:
 RenderGraph::RenderGraph(void* stream, const gpu::DeviceConfig& device) : RenderGraph{stream} { device_config = device; }
 ImageResourceId RenderGraph::get_backbuffer() {
   if (!has_backbuffer) {
-    backbuffer = create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, win_w ? win_w : 1u, win_h ? win_h : 1u},
-                              VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_COLOR_ATTACHMENT_BIT | VK_IMAGE_USAGE_TRANSFER_SRC_BIT);
+    const uint32_t w = backbuffer_w ? backbuffer_w : win_w ? win_w : 1u, h = backbuffer_h ? backbuffer_h : win_h ? win_h : 1u;
+    // never a window of the frame, whatever its extent: the surface is whole (create_frame_image)
+    backbuffer = backbuffer_w ? create_frame_image(gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, w, h})
+                              : create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, w, h},
+                                             VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_COLOR_ATTACHMENT_BIT | VK_IMAGE_USAGE_TRANSFER_SRC_BIT);
     has_backbuffer = true;
   }
   return backbuffer;
+}
+void RenderGraph::set_backbuffer_extent(uint32_t width, uint32_t height) {
+  if (!width || !height) throw std::runtime_error{"set_backbuffer_extent: zero extent"};
+  backbuffer_w = width; backbuffer_h = height;
+  if (!has_backbuffer) return;
+  const auto info = resources.get_image(backbuffer)->get_info();
+  if (info.width == width && info.height == height) return;
+  if (hipStreamSynchronize((hipStream_t)main_stream) != hipSuccess) throw std::runtime_error{"set_backbuffer_extent: stream synchronisation failed"};
+  resources.get_image(backbuffer) = std::make_shared<gpu::Image>(gpu::ImageInfo{VK_FORMAT_R8G8B8A8_SRGB, VK_IMAGE_ASPECT_COLOR_BIT, width, height}, gpu::FrameWindow{});
 }
 RenderGraph::~RenderGraph() {
   for (auto& t : timed) { event_pool.push_back(t.start); event_pool.push_back(t.stop); }

@@ -96,8 +96,8 @@ struct GraphResources {
 struct RenderGraph;
 
 struct RenderGraphBuilder {  // rendergraph.hpp:17-55
-  RenderGraphBuilder(GraphResources& res, uint32_t task, std::vector<GraphResources::Access>* access_log = nullptr)
-      : resources{res}, task_index{task}, log{access_log} {}
+  RenderGraphBuilder(GraphResources& res, uint32_t task, std::vector<GraphResources::Access>* access_log = nullptr, RenderGraph* owner = nullptr)
+      : resources{res}, task_index{task}, log{access_log}, graph{owner} {}
   ImageViewId use_color_attachment(ImageResourceId id, uint32_t mip, uint32_t layer);
   ImageViewId use_depth_attachment(ImageResourceId id, uint32_t mip, uint32_t layer);
   ImageViewId use_storage_image(ImageResourceId id, VkShaderStageFlags stages, uint32_t mip, uint32_t layer);
@@ -119,6 +119,11 @@ struct RenderGraphBuilder {  // rendergraph.hpp:17-55
   void transfer_read(ImageResourceId id, uint32_t base_mip, uint32_t mip_count, uint32_t base_layer, uint32_t layer_count);
   void transfer_write(ImageResourceId id, uint32_t base_mip, uint32_t mip_count, uint32_t base_layer, uint32_t layer_count);
   gpu::ImageInfo get_image_info(ImageResourceId id);
+  // rendergraph.hpp:26,52 (backbuffer_subpass2.cpp:24,66,99): the backbuffer as the task's colour attachment (mip 0, layer 0),
+  // and the hand-over to the presentation engine.  Headless nothing presents: prepare_backbuffer declares the read a present
+  // would be, so the task is ordered after the draw, and records nothing.
+  ImageViewId use_backbuffer_attachment();
+  void prepare_backbuffer();
   // rendergraph.hpp:139: the swapchain image of the current frame.  Headless: an RGBA8_SRGB image of the window's
   // extent, created the first time somebody asks (only DeferedShadingPass's constructor does, for its format).
   ImageResourceId get_backbuffer();
@@ -128,6 +133,7 @@ struct RenderGraphBuilder {  // rendergraph.hpp:17-55
   GraphResources& resources;
   uint32_t task_index;
   std::vector<GraphResources::Access>* log;
+  RenderGraph* graph;  // the backbuffer belongs to the graph (null: a builder made outside add_task has none)
 };
 
 struct RenderResources {  // rendergraph.hpp:57-83
@@ -180,7 +186,7 @@ struct RenderGraph {  // rendergraph.hpp:112-158
   template <typename TaskData>
   void add_task(const std::string& name, TaskCreateCB<TaskData> create_cb, TaskRunCB<TaskData> run_cb) {
     std::unique_ptr<Task<TaskData>> ptr{new Task<TaskData>{name}};
-    RenderGraphBuilder builder{resources, (uint32_t)tasks.size() + task_base, &ptr->accesses};
+    RenderGraphBuilder builder{resources, (uint32_t)tasks.size() + task_base, &ptr->accesses, this};
     create_cb(ptr->data, builder);
     ptr->callback = run_cb;
     tasks.push_back(std::move(ptr));
@@ -205,6 +211,10 @@ struct RenderGraph {  // rendergraph.hpp:112-158
   uint32_t get_frame_index() const { return 0; }
 
   // ---- additions for headless / tiled use (not in the reference) ----------------------------------
+  // The extent of the backbuffer: the reference's is the window's.  Headless the caller says (the frame: its own extent unless
+  // vkrh_set_backbuffer names another); until then it is the frame window's, or 1 x 1 without one.  The id stays what
+  // get_backbuffer() returned: an image of another extent takes the old one's place in the table (the stream is drained first).
+  void set_backbuffer_extent(uint32_t width, uint32_t height);
   void set_stream(void* stream) { main_stream = stream; cmd.set_stream(stream); }
   void* get_stream() const { return main_stream; }
   // false (default): every task on the graph's stream (one in-order stream).  true: independent tasks of one
@@ -259,6 +269,7 @@ struct RenderGraph {  // rendergraph.hpp:112-158
   uint32_t full_w = 0, full_h = 0, win_w = 0, win_h = 0;
   ImageResourceId backbuffer;
   bool has_backbuffer = false;
+  uint32_t backbuffer_w = 0, backbuffer_h = 0;  // set_backbuffer_extent; 0: the frame window's
   int32_t org_x = 0, org_y = 0;
 };
 
