@@ -59,11 +59,11 @@ template <bool TILED> VKR_DEV float depth_sample(const DepthTile& t, const Tex& 
   return sample<FmtD24>(depth, uv);
 }
 
-// main.comp:84-108: 16 samples at start + (i / 16) dir
-template <bool TILED>
+// main.comp:84-108: 16 samples at start + (i / 16) dir.  EXACT_COS: see horizon_walk (the non-MIS pass stores the bare arc)
+template <bool TILED, bool EXACT_COS>
 VKR_DEV float find_horizon(const DepthTile& depth, const Tex& depth_tex, const Proj& pr, f2 start, f3 camera_start, f2 dir, f3 v) {
   float s = 0.0f;  // i / 16: multiples of 2^-4 add exactly
-  return horizon_walk<16>(pr, camera_start, v,
+  return horizon_walk<16, EXACT_COS>(pr, camera_start, v,
       [&](int) { s += 0.0625f; return madd(start, s, dir); },
       [&](f2 tc) { return depth_sample<TILED>(depth, depth_tex, tc); },
       [](float h_cos, float sample_cos) {  // fmaxf without the canonicalising self-max (a NaN cosine is dropped either way)
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(GT_BX * GT_BY, 8) void k_gtao_main(GtaoArgs a) {
         np_len = length(exact.normal_projected);
       }
       const float n = VKR_PI / 2.0f - acosf(n_cos);
-      const float h_cos = find_horizon<TILED>(tile, a.depth, a.pr, screen_uv, camera_pos, sample_direction, w0);
+      const float h_cos = find_horizon<TILED, !MIS>(tile, a.depth, a.pr, screen_uv, camera_pos, sample_direction, w0);
       const float h = clamp_horizon(acosf(h_cos), n);
       if (MIS) {
         occlusion = arc_occlusion(h, n, np_len);

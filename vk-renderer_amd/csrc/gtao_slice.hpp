@@ -38,8 +38,14 @@ VKR_DEV float arc_occlusion(float h, float n, float len_np) { return (((1.0f / V
 // main.comp:84-108 == main.frag:66-90: the largest cosine, against the view direction v, of the directions from camera_start
 // to the surface under STEPS samples of a screen-space segment; the walk ends where the surface recedes by more than 0.1
 // (MAX_THIKNESS).  sample_uv(i): texture coordinate of sample i = 1 .. STEPS; depth_at(uv): texture(depth, uv);
-// max_of(a, b): the running maximum.  The break test is exact; the cosine is max()-reduced, so the hardware rsq serves it.
-template <int STEPS, class SampleUv, class DepthAt, class MaxOf>
+// max_of(a, b): the running maximum.  The break test is exact.  The cosine is max()-reduced and then goes through acos,
+// whose slope is unbounded at +-1: where the depth has no coherence the offset to a sample is all but parallel to the view
+// direction, the cosine sits one or two ulps from 1 and the last bit moves the horizon by 3e-4 rad — an arc of the order of
+// 1e-4, which is the whole value where the arc is small.  EXACT_COS: dot(v, normalize(offset)) in the shader's operation order
+// (bit for bit the contract's cosine: main.frag, main_deinterleaved.comp and main.comp without MIS store the bare arc);
+// otherwise the dot product scaled by the hardware rsq (1 ulp, another order: main.comp under MIS, on the frame's chain,
+// where the blend with the trace's term swamps that arc).
+template <int STEPS, bool EXACT_COS = false, class SampleUv, class DepthAt, class MaxOf>
 VKR_DEV float horizon_walk(const Proj& pr, f3 camera_start, f3 v, SampleUv sample_uv, DepthAt depth_at, MaxOf max_of) {
   float h_cos = -1.0f;
   float previous_z = camera_start.z;
@@ -51,7 +57,7 @@ VKR_DEV float horizon_walk(const Proj& pr, f3 camera_start, f3 v, SampleUv sampl
     if (sample_pos.z > previous_z + 0.1f) break;
     previous_z = sample_pos.z;
     const f3 sample_offset = sample_pos - camera_start;
-    h_cos = max_of(h_cos, dot(v, sample_offset) * fast_rsq(dot(sample_offset, sample_offset)));
+    h_cos = max_of(h_cos, EXACT_COS ? dot(v, normalize(sample_offset)) : dot(v, sample_offset) * fast_rsq(dot(sample_offset, sample_offset)));
   }
   return h_cos;
 }

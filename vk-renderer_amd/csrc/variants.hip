@@ -51,8 +51,9 @@ template <class F> __global__ __launch_bounds__(256) void k_gtao_v2(Gtao2Args a)
     // 1.0000001 (NaN) or 0.99999994 is decided by the last bit, so the whole chain stays exact.
     const f3 normal_projected = slice_frame<false>(w0, -sample_end_pos, camera_normal).normal_projected;
     const float n = slice_normal_angle(normal_projected, normalize(sample_end_pos - camera_pos));
-    // main.frag:66-90: 20 samples at start + (i / 20) dir, straight from global memory
-    const float h_cos = horizon_walk<20>(a.pr, camera_pos, w0,
+    // main.frag:66-90: 20 samples at start + (i / 20) dir, straight from global memory; the cosine in the shader's own
+    // operation order (the arc below is the stored value: see horizon_walk)
+    const float h_cos = horizon_walk<20, true>(a.pr, camera_pos, w0,
         [&](int i) { return screen_uv + ((float)i / 20.0f) * sample_direction; },
         [&](f2 tc) { return sample<F>(a.depth, tc); },
         [](float h_cos, float sample_cos) { return vmax(h_cos, sample_cos); });
