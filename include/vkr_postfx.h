@@ -515,6 +515,46 @@ enum { VKR_TEXDRAW_SHOW_ALL = 0, VKR_TEXDRAW_SHOW_R = 1, VKR_TEXDRAW_SHOW_G = 2,
  * 65535, a windowed descriptor on either side, and target_tex == backbuffer (the same memory). */
 int vkr_texdraw(const vkr_img* target_tex, const vkr_img* backbuffer, const vkr_texdraw_push* push, void* stream);
 
+/* program "shadow_mask" (no reference program: the reference renders its shadow maps and never samples them).  The lookup half of
+ * the shadow pipeline: for every full-resolution pixel the visibility of up to four lights through the D24 layers that
+ * vkr_default_shadow rendered, one RGBA8_UNORM texel per pixel, channel l = light l, channels at or beyond layer_count = 255. */
+typedef struct vkr_shadow_mask_params {
+  vkr_mat4 inverse_camera;          /* view -> world, as in vkr_shading_params      */
+  vkr_mat4 mvps[4];                 /* the matrices the layers were rendered with   */
+  float    fovy, aspect, znear, zfar;
+  uint32_t layer_count;             /* 1..4                                         */
+  uint32_t radius;                  /* 0, 1, 2: 1, 9 or 25 taps                     */
+  uint32_t bias;                    /* in D24 codes, added to the map's side        */
+  uint32_t reserved;                /* 0                                            */
+} vkr_shadow_mask_params;
+/* depth: the G-buffer depth (D24_UNORM_S8, mip 0 of the view) at out_mask's extent; layers: layer_count square D24_UNORM_S8
+ * descriptors of one extent `size`; out_mask: RGBA8_UNORM.  Per pixel g and light l (DESIGN_NUMERICS.md, Shadow mask):
+ * uv = (g + 0.5) / extent; d = the exact decode of depth texel g (by index, unfiltered); d >= 1 stores 255 in every channel;
+ * view = reconstruct_view_vec(uv, d, ...); clip = M_l * (view, 1) with M_l = mvps[l] * inverse_camera taken on the host in
+ * double and rounded once to float (16 multiply-adds per light in the order of every mat4 * vec4 here); ndc = clip.xyz / clip.w
+ * (IEEE division).  Lit without taps when clip.w <= 0, ndc.x or ndc.y outside [-1, 1], ndc.z > 1, or any of them NaN; nowhere
+ * else.  Otherwise code = rint(clamp(ndc.z, 0, 1) * 16777215) (the rasteriser's depth quantisation), the centre texel
+ * t = floor((0.5 * ndc.xy + 0.5) * size) (float -> int: truncate, saturating) clamped to [0, size - 1], and each of the
+ * (2 radius + 1)^2 taps t + (dx, dy) passes when it lies outside the map or code <= (word & 0xFFFFFF) + bias (an integer
+ * compare without wrap-around: the top byte of a word is ignored, bias >= 2^24 passes everything); the channel is
+ * passes / taps as UNORM8 = rint(x * 255), ties to even.  Every texel of out_mask is written, nothing outside its rows.
+ * Refused before any launch: a NULL argument, a descriptor without memory, other formats, depth and out_mask of different
+ * extents, an extent above 65535, a windowed descriptor anywhere (the taps reach anywhere: a single-GPU pass), layers that are
+ * not square or not of one extent, layer_count outside 1..4, radius > 2, reserved != 0. */
+int vkr_shadow_mask(const vkr_img* depth, const vkr_img* layers /* [layer_count] */, const vkr_shadow_mask_params* params,
+                    const vkr_img* out_mask, void* stream);
+
+/* program "defered_shading_shadowed": vkr_defered_shading with one more binding, shadow_mask (RGBA8_UNORM at the extent and
+ * window of `out`, as vkr_shadow_mask writes it).  Channel .x of the pixel's own texel, read by index as code / 255, multiplies
+ * the direct term of shader.frag:91 (Lo before the reflection is added) and nothing else: the ambient term, the reflection term
+ * and the show_ao branch are those of vkr_defered_shading.  The shading light is the shader's hard-coded LIGHT_POS, the eye of
+ * the default shadow light (main.cpp:295), so the channel used is light 0 of the mask; the other channels are not read.  A
+ * mask of 255 everywhere gives the bytes of vkr_defered_shading. */
+int vkr_defered_shading_shadowed(const vkr_img* albedo, const vkr_img* normal, const vkr_img* material, const vkr_img* depth,
+                                 const vkr_shading_params* consts, const vkr_img* occlusion, const vkr_img* brdf,
+                                 const vkr_img* reflections, const vkr_img* shadow_mask, const vkr_img* out,
+                                 const vkr_shading_push* push, void* stream);
+
 /* synthetic G-buffer generator (no reference program).  Any of the
  * colour outputs may be NULL when VKR_SYNTH_DEPTH_ONLY is set.                          */
 int vkr_synth_gbuffer(const vkr_img* depth, const vkr_img* normal, const vkr_img* albedo,

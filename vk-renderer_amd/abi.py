@@ -249,6 +249,12 @@ class TexdrawPush(C.Structure):  # vkr_texdraw_push: the push constants of texdr
     _fields_ = [("flags", C.c_uint32)]
 
 
+# ---- program shadow_mask ----
+class ShadowMaskParams(C.Structure):  # vkr_shadow_mask_params, 352 bytes
+    _fields_ = [("inverse_camera", Mat4), ("mvps", Mat4 * 4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float),
+                ("zfar", C.c_float), ("layer_count", C.c_uint32), ("radius", C.c_uint32), ("bias", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
 
 
@@ -409,6 +415,11 @@ def product():
         lib.vkr_texdraw.restype = C.c_int
         lib.vkr_selftest_srgb_encode.argtypes = [C.c_void_p, C.c_void_p]
         lib.vkr_selftest_srgb_encode.restype = C.c_int
+        # the shadow mask (checked against the numpy restatement tests/shadow_mask_reference.py) and the shading that applies it
+        lib.vkr_shadow_mask.argtypes = [_IMG, _IMG, P(ShadowMaskParams), _IMG, C.c_void_p]
+        lib.vkr_shadow_mask.restype = C.c_int
+        lib.vkr_defered_shading_shadowed.argtypes = [_IMG, _IMG, _IMG, _IMG, P(ShadingParams), _IMG, _IMG, _IMG, _IMG, _IMG, P(ShadingPush), C.c_void_p]
+        lib.vkr_defered_shading_shadowed.restype = C.c_int
         _product = lib
     return _product
 
@@ -525,6 +536,41 @@ def texdraw(target_tex, backbuffer, push=None, stream=None):
     lib = product()
     push = push if push is not None else TexdrawPush(TEXDRAW_SHOW_ALL)
     check(lib.vkr_texdraw(C.byref(target_tex), C.byref(backbuffer), C.byref(push), stream), lib)
+
+
+def shadow_mask_params(inverse_camera, mvps, fovy, aspect, znear, zfar, radius=1, bias=0):
+    """ShadowMaskParams from the camera's view -> world matrix and 1..4 light matrices (4x4, maths convention, the ones the
+    layers were rendered with, e.g. camera.shadow_mvp(...)), the camera's four floats, the box radius (0, 1, 2) and the bias in
+    D24 codes.  layer_count = len(mvps); radius and bias are passed on as given (the entry refuses what it does not take)."""
+    p = ShadowMaskParams()
+    p.inverse_camera = Mat4.from_np(inverse_camera)
+    if len(mvps) > 4:
+        raise RuntimeError(f"shadow_mask_params: {len(mvps)} light matrices, at most 4")
+    for l, m in enumerate(mvps):
+        p.mvps[l] = Mat4.from_np(m)
+    p.fovy, p.aspect, p.znear, p.zfar = float(fovy), float(aspect), float(znear), float(zfar)
+    p.layer_count, p.radius, p.bias, p.reserved = len(mvps), int(radius), int(bias), 0
+    return p
+
+
+def shadow_mask(depth, layers, params, out_mask, stream=None):
+    """vkr_shadow_mask: out_mask (RGBA8_UNORM VkrImg) := per pixel of `depth` (D24_UNORM_S8 VkrImg of the same extent, mip 0 of
+    the view) the visibility of light l in channel l, through `layers` (a (VkrImg * n) array or a sequence of square
+    D24_UNORM_S8 VkrImg of one extent, n >= params.layer_count) under `params` (ShadowMaskParams, e.g. shadow_mask_params(...)).
+    Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    descs = (VkrImg * max(1, len(layers)))(*list(layers))
+    check(lib.vkr_shadow_mask(C.byref(depth), descs, C.byref(params), C.byref(out_mask), stream), lib)
+
+
+def defered_shading_shadowed(albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, out, push, stream=None):
+    """vkr_defered_shading_shadowed: vkr_defered_shading (same VkrImg bindings, ShadingParams and ShadingPush) with channel .x of
+    `shadow_mask` (RGBA8_UNORM VkrImg at out's extent) on the direct term.  Raises RuntimeError with the library's message on a
+    refusal."""
+    lib = product()
+    check(lib.vkr_defered_shading_shadowed(C.byref(albedo), C.byref(normal), C.byref(material), C.byref(depth), C.byref(consts),
+                                           C.byref(occlusion), C.byref(brdf), C.byref(reflections), C.byref(shadow_mask), C.byref(out),
+                                           C.byref(push), stream), lib)
 
 
 COMM_ID_BYTES = 128

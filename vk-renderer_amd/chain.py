@@ -463,6 +463,19 @@ class PostFxChain:
                   C.byref(self.depth.desc()), C.byref(p), C.byref(self.acc_ao.desc()), C.byref(self.brdf.desc()),
                   C.byref(self.blurred.desc()), C.byref(self.color_out.desc()), C.byref(push))
 
+    def shadow_mask(self, layers, mvps, radius=1, bias=0):
+        """vkr_shadow_mask on this chain's depth -> shadow_mask_out (RGBA8_UNORM, channel l = light l): `layers` the square
+        D24_UNORM_S8 descriptors (VkrImg) that vkr_default_shadow rendered with the matrices `mvps` (4x4, maths convention).
+        Product backend only: the expectation is the numpy restatement tests/shadow_mask_reference.py, not a checker library."""
+        if self.backend != "product":
+            raise RuntimeError("PostFxChain.shadow_mask: only the product backend has the program shadow_mask")
+        if self.tiled:
+            raise RuntimeError("PostFxChain.shadow_mask: not on a window of the frame (the taps reach anywhere: a single-GPU pass)")
+        if not hasattr(self, "shadow_mask_out"):
+            self.shadow_mask_out = ImageBuf(abi.FMT_RGBA8_UNORM, self.depth.width, self.depth.height, device=self.device)
+        p = abi.shadow_mask_params(self.setup.inv_view, mvps, *self.setup.fazz, radius=radius, bias=bias)
+        abi.shadow_mask(self.depth.desc(0, 1), layers, p, self.shadow_mask_out.desc(), self.stream)
+
     # ---- tile-classified trace (advanced_ssr.cpp:216-302,440-495; commented out of AdvancedSSR::run) ----
     def _i32_buffer(self, n):
         if self.device is None:

@@ -60,6 +60,7 @@ struct ShadingArgs {
   Proj pr;
   float min_roughness, max_roughness;
   uint32_t show_ao;
+  Tex mask;  // SHADOWED only: the RGBA8_UNORM shadow mask at out's window (program "shadow_mask")
 };
 
 // brdf.glsl:31-38
@@ -77,7 +78,11 @@ VKR_DEV float distribution_ggx(f3 N, f3 H, float alpha) {
 // image is at least two texels wide — the four full-resolution samples then share one footprint record, the material
 // texels are fetched once for both channels, and every bilinear row is one 8-byte load: 19 loads per pixel instead of
 // 41 (the pass is bound by the texture-address unit, which spends the same 16 cycles on a wave's load whatever its width).
-template <bool FAST>
+// SHADOWED (program "defered_shading_shadowed"): channel .x of the pixel's own texel of a.mask, code / 255, multiplies the direct
+// term of shader.frag:91 and nothing else: one 4-byte load and three multiplies.  The shading light is the hard-coded LIGHT_POS,
+// the eye of the default shadow light (main.cpp:295), so the channel is light 0 of the mask.  The false instantiations are the
+// kernels of program "defered_shading", unchanged.
+template <bool FAST, bool SHADOWED>
 __global__ __launch_bounds__(256) void k_defered_shading(ShadingArgs a) {
   __shared__ float s_lut[VKR_SRGB_LUT_SIZE];
   __shared__ float s_thresh[VKR_SRGB_LUT_SIZE];
@@ -177,6 +182,7 @@ __global__ __launch_bounds__(256) void k_defered_shading(ShadingArgs a) {
   const f2 ssr_brdf = FAST ? taps_resolve<FmtRG16F>(pair_taps(a.brdf, pair_footprint(a.brdf, mk2(biased_rougness, NdotV))))
                            : sample<FmtRG16F>(a.brdf, mk2(biased_rougness, NdotV));
   f3 Lo = (((kD * albedo) * (1.0f / VKR_PI) + specular) * rad) * NdotL;
+  if (SHADOWED) Lo = Lo * unorm8_to_float(*(const uint32_t*)(a.mask.p + toff(a.mask, lx, ly, 4)) & 0xFFu);
   Lo = Lo + reflection * (F0 * ssr_brdf.x + mk3(ssr_brdf.y, ssr_brdf.y, ssr_brdf.y));
   const f3 color = occlusion * (mk3(0.6f, 0.6f, 0.6f) * albedo + Lo);
   const f3 o = a.show_ao ? mk3(occlusion, occlusion, occlusion) : color;
@@ -197,20 +203,33 @@ extern "C" int vkr_brdf_preintegrate(const float* halton_vec4, const vkr_img* ou
   return launch_status("brdf_preintegrate");
 }
 
-extern "C" int vkr_defered_shading(const vkr_img* albedo, const vkr_img* normal, const vkr_img* material, const vkr_img* depth,
-                                   const vkr_shading_params* consts, const vkr_img* occlusion, const vkr_img* brdf,
-                                   const vkr_img* reflections, const vkr_img* out, const vkr_shading_push* push, void* stream) {
-  if (!consts || !push) { set_error("defered_shading: NULL params"); return VKR_ERR_NULL; }
+// the validation, set-up and launch of both shading programs; shadow_mask == NULL: program "defered_shading"
+static int shading_launch(const char* prog, const vkr_img* albedo, const vkr_img* normal, const vkr_img* material, const vkr_img* depth,
+                          const vkr_shading_params* consts, const vkr_img* occlusion, const vkr_img* brdf, const vkr_img* reflections,
+                          const vkr_img* shadow_mask, bool shadowed, const vkr_img* out, const vkr_shading_push* push, void* stream) {
+  if (!consts || !push) { set_error("%s: NULL params", prog); return VKR_ERR_NULL; }
+  char what[96];
+  auto name = [&](const char* binding) { std::snprintf(what, sizeof what, "%s.%s", prog, binding); return (const char*)what; };
   ShadingArgs a;
-  VKR_TRY(make_tex(albedo, 0, VKR_FMT_RGBA8_SRGB, "defered_shading.albedo", &a.albedo));
-  VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "defered_shading.normal", &a.normal));
-  VKR_TRY(make_tex(material, 0, VKR_FMT_RGBA8_SRGB, "defered_shading.material", &a.material));
-  VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "defered_shading.depth", &a.depth0));
-  VKR_TRY(make_tex(depth, 1, VKR_FMT_D24_UNORM_S8, "defered_shading.depth (lod 1)", &a.depth1));
-  VKR_TRY(make_tex(occlusion, 0, VKR_FMT_RG16_SFLOAT, "defered_shading.occlusion", &a.occlusion));
-  VKR_TRY(make_tex(brdf, 0, VKR_FMT_RG16_SFLOAT, "defered_shading.brdf", &a.brdf));
-  VKR_TRY(make_tex(reflections, 0, VKR_FMT_RGBA8_UNORM, "defered_shading.reflections", &a.reflections));
-  VKR_TRY(make_tex(out, 0, VKR_FMT_RGBA8_SRGB, "defered_shading.out", &a.out));
+  VKR_TRY(make_tex(albedo, 0, VKR_FMT_RGBA8_SRGB, name("albedo"), &a.albedo));
+  VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, name("normal"), &a.normal));
+  VKR_TRY(make_tex(material, 0, VKR_FMT_RGBA8_SRGB, name("material"), &a.material));
+  VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, name("depth"), &a.depth0));
+  VKR_TRY(make_tex(depth, 1, VKR_FMT_D24_UNORM_S8, name("depth (lod 1)"), &a.depth1));
+  VKR_TRY(make_tex(occlusion, 0, VKR_FMT_RG16_SFLOAT, name("occlusion"), &a.occlusion));
+  VKR_TRY(make_tex(brdf, 0, VKR_FMT_RG16_SFLOAT, name("brdf"), &a.brdf));
+  VKR_TRY(make_tex(reflections, 0, VKR_FMT_RGBA8_UNORM, name("reflections"), &a.reflections));
+  VKR_TRY(make_tex(out, 0, VKR_FMT_RGBA8_SRGB, name("out"), &a.out));
+  if (shadowed) {
+    VKR_TRY(make_tex(shadow_mask, 0, VKR_FMT_RGBA8_UNORM, name("shadow_mask"), &a.mask));
+    if (!same_window(a.mask, a.out)) {
+      set_error("%s: shadow_mask is %dx%d at (%d,%d), out %dx%d at (%d,%d): one window expected", prog, a.mask.w, a.mask.h, a.mask.ox, a.mask.oy,
+                a.out.w, a.out.h, a.out.ox, a.out.oy);
+      return VKR_ERR_EXTENT;
+    }
+  } else {
+    a.mask = a.out;  // never read
+  }
   load_mat(a.inverse_camera, consts->inverse_camera);
   load_proj(a.pr, consts->fovy, consts->aspect, consts->znear, consts->zfar);
   a.min_roughness = push->min_max_roughness[0];
@@ -219,7 +238,22 @@ extern "C" int vkr_defered_shading(const vkr_img* albedo, const vkr_img* normal,
   const bool fast = same_layout(a.normal, a.albedo) && same_layout(a.normal, a.material) && same_layout(a.normal, a.depth0) && a.normal.w >= 2 &&
                     a.depth1.w >= 2 && a.occlusion.w >= 2 && a.reflections.w >= 2 && a.brdf.w >= 2 && !(switches() & VKR_SWITCH_SHADING_GENERIC);
   dim3 block(64, 4);
-  if (fast) hipLaunchKernelGGL(k_defered_shading<true>, grid2d(a.out.w, a.out.h, block), block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_defered_shading<false>, grid2d(a.out.w, a.out.h, block), block, 0, (hipStream_t)stream, a);
-  return launch_status("defered_shading");
+  void (*kernel)(ShadingArgs) = shadowed ? (fast ? k_defered_shading<true, true> : k_defered_shading<false, true>)
+                                         : (fast ? k_defered_shading<true, false> : k_defered_shading<false, false>);
+  hipLaunchKernelGGL(kernel, grid2d(a.out.w, a.out.h, block), block, 0, (hipStream_t)stream, a);
+  return launch_status(prog);
+}
+
+extern "C" int vkr_defered_shading(const vkr_img* albedo, const vkr_img* normal, const vkr_img* material, const vkr_img* depth,
+                                   const vkr_shading_params* consts, const vkr_img* occlusion, const vkr_img* brdf,
+                                   const vkr_img* reflections, const vkr_img* out, const vkr_shading_push* push, void* stream) {
+  return shading_launch("defered_shading", albedo, normal, material, depth, consts, occlusion, brdf, reflections, nullptr, false, out, push, stream);
+}
+
+extern "C" int vkr_defered_shading_shadowed(const vkr_img* albedo, const vkr_img* normal, const vkr_img* material, const vkr_img* depth,
+                                            const vkr_shading_params* consts, const vkr_img* occlusion, const vkr_img* brdf,
+                                            const vkr_img* reflections, const vkr_img* shadow_mask, const vkr_img* out,
+                                            const vkr_shading_push* push, void* stream) {
+  return shading_launch("defered_shading_shadowed", albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, true, out, push,
+                        stream);
 }

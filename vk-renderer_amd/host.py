@@ -23,6 +23,7 @@ TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the ho
 STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); after the G-buffer / raster / shadow stages, before the downsample; not tiled
 STAGE_TILE_REGRESSION = 1 << 26  # AdvancedSSR::run_tile_regression_pass: depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W/16, H/16)); after the downsample; not tiled
 STAGE_BACKBUFFER = 1 << 27  # add_backbuffer_subpass + add_present_subpass: the TAA output (or set_backbuffer's image) -> image "backbuffer" (RGBA8_SRGB); last; not tiled
+STAGE_SHADOW_MASK = 1 << 28  # ShadowMaskPass::run: depth mip 0 + the layers of "shadows" -> image "shadow_mask" (RGBA8_UNORM, channel l = light l); after the raster / shadow stages, before the shading; needs the maps of STAGE_SHADOW; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
 
@@ -148,7 +149,9 @@ def lib():
                            ("vkrh_selftest_tile_regression", [C.c_char_p, C.c_uint32]),
                            # the backbuffer texdraw pass (same rule)
                            ("vkrh_set_backbuffer", [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
-                           ("vkrh_selftest_texdraw", [C.c_char_p, C.c_uint32])):
+                           ("vkrh_selftest_texdraw", [C.c_char_p, C.c_uint32]),
+                           # the shadow mask (same rule)
+                           ("vkrh_set_shadow_mask", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -358,6 +361,12 @@ class HostFrame:
         for i, m in enumerate(mvps):
             flat[16 * i: 16 * i + 16] = list(_mat16(m))
         self._check(lib().vkrh_set_shadow_lights(self.h, flat, len(mvps), int(size)))
+
+    def set_shadow_mask(self, bias=0, radius=1, apply=0):
+        """vkrh_set_shadow_mask: the lookup of STAGE_SHADOW_MASK: bias in D24 codes, radius 0, 1, 2 (a box of 1, 9, 25 taps);
+        apply != 0: a STAGE_SHADING of a run that also has STAGE_SHADOW_MASK multiplies its direct term by light 0's channel
+        (program defered_shading_shadowed); 0 (the default): the shading is what it is without the mask."""
+        self._check(lib().vkrh_set_shadow_mask(self.h, int(bias), int(radius), 1 if apply else 0))
 
     def set_ssao_samples(self, samples, std140=0):
         """vkrh_set_ssao_samples: pins the 16 samples ([16, 3]) of STAGE_SSAO and their packing in the uniform block: std140 = 0

@@ -27,6 +27,7 @@
 #include "scene/scene_as.hpp"
 #include "scene_renderer.hpp"
 #include "screen_trace.hpp"
+#include "shadow_mask.hpp"
 #include "synthetic_gbuffer.hpp"
 #include "taa.hpp"
 #include "util_passes.hpp"
@@ -126,6 +127,25 @@ struct PostFxFrame {
     SSAOPass& pass = ensure_ssao();
     for (uint32_t i = 0; i < 16; i++) pass.sphere_samples[i] = glm::vec3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     pass.std140_samples = std140 != 0;
+  }
+
+  // VKRH_STAGE_SHADOW_MASK: the pass and its target, created on first use; the lookup's settings (vkrh_set_shadow_mask).
+  // shadow_maps_current: VKRH_STAGE_SHADOW has rendered a layer for every light configured now.
+  std::unique_ptr<ShadowMaskPass> shadow_mask_pass;
+  rendergraph::ImageResourceId shadow_mask_tex;
+  uint32_t shadow_mask_bias = 0, shadow_mask_radius = 1;
+  bool shadow_mask_apply = false, shadow_maps_current = false;
+  ShadowMaskPass& ensure_shadow_mask() {
+    if (!shadow_mask_pass) {
+      shadow_mask_tex = create_shadow_mask_texture(graph, cfg.width, cfg.height);
+      shadow_mask_pass.reset(new ShadowMaskPass());
+    }
+    return *shadow_mask_pass;
+  }
+  void set_shadow_mask(uint32_t bias, uint32_t radius, uint32_t apply) {
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_mask: on a tiled frame (VKRH_STAGE_SHADOW_MASK runs on one GPU)"};
+    if (radius > 2) throw std::runtime_error{"vkrh_set_shadow_mask: radius " + std::to_string(radius) + ", needs 0..2 (a box of 1, 9 or 25 taps)"};
+    shadow_mask_bias = bias; shadow_mask_radius = radius; shadow_mask_apply = apply != 0;
   }
 
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
@@ -228,6 +248,7 @@ struct PostFxFrame {
     shadow_lights.resize(count);
     for (uint32_t i = 0; i < count; i++) std::memcpy((void*)&shadow_lights[i], mvps + 16 * i, 64);
     shadow_size = size ? size : 1024;
+    shadow_maps_current = false;  // VKRH_STAGE_SHADOW_MASK waits for the next VKRH_STAGE_SHADOW
   }
 
   // the `shadows` image, created on first use (main.cpp:279-287) and again when the size changes
@@ -256,6 +277,11 @@ struct PostFxFrame {
     if ((mask & VKRH_STAGE_BACKBUFFER) && cfg.tiled)  // refused before anything is recorded
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_BACKBUFFER on a tiled frame (the uv of a pixel spans the whole source: the backbuffer is drawn on one GPU)"};
     if (mask & VKRH_STAGE_BACKBUFFER) (void)backbuffer_source_id();  // a source that does not exist (yet) is refused before anything is recorded
+    if (mask & VKRH_STAGE_SHADOW_MASK) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK on a tiled frame (the shadow maps are rendered on one GPU)"};
+      if (!(mask & VKRH_STAGE_SHADOW) && !shadow_maps_current)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK without rendered shadow maps (VKRH_STAGE_SHADOW for the lights in use)"};
+    }
     if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
@@ -290,6 +316,12 @@ struct PostFxFrame {
       ensure_shadows();
       for (uint32_t l = 0; l < shadow_lights.size(); l++) scene_renderer->render_shadow(graph, shadow_lights[l], shadows, l);
       shadows_rendered = true;
+      shadow_maps_current = true;
+    }
+    if (mask & VKRH_STAGE_SHADOW_MASK) {  // reads depth mip 0 and the layers just rendered
+      ShadowMaskPass& pass = ensure_shadow_mask();
+      pass.update_params(view, shadow_lights.data(), (uint32_t)shadow_lights.size(), fazz.x, fazz.y, fazz.z, fazz.w, shadow_mask_radius, shadow_mask_bias);
+      pass.run(graph, gbuffer.depth, shadows, (uint32_t)shadow_lights.size(), shadow_mask_tex);
     }
     if (mask & VKRH_STAGE_SSAO) {  // reads depth mip 0 only: before the downsample writes the other mips
       SSAOPass& pass = ensure_ssao();
@@ -368,7 +400,11 @@ struct PostFxFrame {
       // main.cpp:339,390: once VKRH_STAGE_SHADOW has filled it, layer 0 of `shadows` and its matrix; until then the dummy
       const bool lit = has_shadows && shadows_rendered;
       shading_pass.update_params(view, lit ? shadow_lights[0] : glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
-      shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
+      if (shadow_mask_apply && (mask & VKRH_STAGE_SHADOW_MASK))  // vkrh_set_shadow_mask(apply) and the mask of this run
+        shading_pass.draw_shadowed(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(),
+                                   shadow_mask_tex, color_out_tex);
+      else
+        shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
     }
     if (mask & VKRH_STAGE_TAA) taa_pass.run(graph, gbuffer, (mask & VKRH_STAGE_SHADING) ? color_out_tex : gbuffer.albedo, draw_params);
     if (mask & VKRH_STAGE_BACKBUFFER) {  // main.cpp:398-401
@@ -477,7 +513,7 @@ struct PostFxFrame {
         {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
         {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
         {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38},
-        {"tile_planes", 39}, {"backbuffer", 40}};
+        {"tile_planes", 39}, {"backbuffer", 40}, {"shadow_mask", 41}};
     auto it = ids.find(name);
     if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
     switch (it->second) {
@@ -501,6 +537,7 @@ struct PostFxFrame {
       case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
       case 39: if (!has_tile_planes) throw std::runtime_error{"vkrh_image: 'tile_planes' only exists after VKRH_STAGE_TILE_REGRESSION"}; return ssr.get_tile_planes();
       case 40: if (!backbuffer_drawn) throw std::runtime_error{"vkrh_image: 'backbuffer' only exists after VKRH_STAGE_BACKBUFFER"}; return graph.get_backbuffer();
+      case 41: if (!shadow_mask_pass) throw std::runtime_error{"vkrh_image: 'shadow_mask' only exists after VKRH_STAGE_SHADOW_MASK"}; return shadow_mask_tex;
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1300,6 +1337,9 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
     *count = (uint32_t)f->shadow_lights.size();
     std::memcpy(out, f->shadow_lights.data(), 64 * f->shadow_lights.size());
   });
+}
+int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply) {
+  return guarded([&] { frame_ref(frame).set_shadow_mask(bias, radius, apply); });
 }
 int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) {
   return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); });

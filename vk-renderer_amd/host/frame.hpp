@@ -87,7 +87,15 @@ enum {
    * last, after TAA.  Nothing reads "backbuffer".  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame: the uv
    * of a pixel spans the whole source).                                                                                    */
   VKRH_STAGE_BACKBUFFER         = 1u << 27,
-  VKRH_STAGE_CHAIN      = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
+  /* ShadowMaskPass::run (no reference counterpart: the reference renders its shadow maps and never samples them): gbuffer.depth
+   * (mip 0) and one layer of "shadows" per configured light -> image "shadow_mask" (RGBA8_UNORM at the frame's extent, created on
+   * first use; vkrh_image): channel l = the visibility of light l under the bias and radius of vkrh_set_shadow_mask, 255 in the
+   * channels of lights that are not configured.  Recorded after the G-buffer, raster and shadow stages and before
+   * VKRH_STAGE_SHADING, which reads it only when vkrh_set_shadow_mask asked for it.  Needs the maps: VKRH_STAGE_SHADOW in this
+   * run or an earlier one since the lights were last set.  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame:
+   * the shadow maps are rendered on one GPU).                                                                               */
+  VKRH_STAGE_SHADOW_MASK        = 1u << 28,
+  VKRH_STAGE_CHAIN     = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
 typedef void* (*vkrh_alloc_fn)(uint64_t bytes, void* user);
@@ -134,6 +142,12 @@ int vkrh_bake_probes(void* frame, const float min[3], const float max[3], uint32
  * reallocates the image at the next VKRH_STAGE_SHADOW.  vkrh_shadow_lights returns the matrices in use (room for 4 x 16 floats). */
 int vkrh_set_shadow_lights(void* frame, const float* mvps, uint32_t count, uint32_t size);
 int vkrh_shadow_lights(void* frame, float* out, uint32_t* count);
+/* The lookup of VKRH_STAGE_SHADOW_MASK: `bias` in D24 codes, added to the map's side of the compare; `radius` 0, 1 or 2 (a box of
+ * 1, 9 or 25 taps; anything else is an error); `apply` != 0: a VKRH_STAGE_SHADING of a vkrh_run that also produced the mask
+ * records DeferedShadingPass::draw_shadowed (program "defered_shading_shadowed": light 0's channel multiplies the direct term)
+ * instead of draw.  Defaults: bias 0, radius 1, apply 0, under which VKRH_STAGE_SHADING records what it always recorded.
+ * Not on a tiled frame. */
+int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply);
 /* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
  * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
  * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */

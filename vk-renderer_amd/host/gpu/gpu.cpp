@@ -474,8 +474,18 @@ void register_hot_path_programs() {
       return vkr_defered_shading(&albedo, &normal, &material, &depth, ubo<vkr_shading_params>(st, 4, P), &occlusion, &brdf, &refl, &out,
                                  push<vkr_shading_push>(st, P), st.stream);
     });
+    // the same set plus {9 shadow mask}: DeferedShadingPass::draw_shadowed
+    create_program("defered_shading_shadowed", [=](LaunchState& st) {
+      const char* P = "defered_shading_shadowed";
+      if (st.attachments.size() != 1) throw std::runtime_error{"defered_shading_shadowed: expects one colour attachment"};
+      vkr_img albedo = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P), depth = tex(st, 3, T, P);
+      vkr_img occlusion = tex(st, 6, T, P), brdf = tex(st, 7, T, P), refl = tex(st, 8, T, P), mask = tex(st, 9, T, P);
+      vkr_img out = st.attachments[0].image->describe_store(st.attachments[0].range.base_mip, 1);
+      return vkr_defered_shading_shadowed(&albedo, &normal, &material, &depth, ubo<vkr_shading_params>(st, 4, P), &occlusion, &brdf, &refl, &mask,
+                                          &out, push<vkr_shading_push>(st, P), st.stream);
+    });
     // ---- tile-classified trace ----
-    auto ssbo = [](const LaunchState& st, uint32_t slot, const char* prog) -> Buffer* {
+    auto ssbo =[](const LaunchState& st, uint32_t slot, const char* prog) -> Buffer* {
       const SetSlot& s = st.set ? st.set->slots[slot] : SetSlot{};
       if (!st.set || s.kind != SetSlot::Ssbo || !s.buffer) throw std::runtime_error{std::string{prog} + ": storage buffer " + std::to_string(slot) + " is not bound"};
       return s.buffer.get();
@@ -688,6 +698,21 @@ void register_hot_path_programs() {
       const vkr_ssao_params params = ssao_params_from_block(data, size);
       vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
       return vkr_ssao(&depth, &params, &out, st.stream);
+    });
+    // ---- shadow mask (ShadowMaskPass; no reference program) ----
+    // set {0 depth (mip 0), 1 the shadow array (every layer), 2 vkr_shadow_mask_params, 3 the mask (storage)}
+    create_program("shadow_mask", [=](LaunchState& st) {
+      const char* P = "shadow_mask";
+      vkr_img depth = tex(st, 0, T, P), out = tex(st, 3, S, P);
+      const ImageViewObject& maps = bound_view(st, 1, T, P);
+      static_assert(sizeof(vkr_shadow_mask_params) == 352, "vkr_shadow_mask_params: five matrices and eight words");
+      const vkr_shadow_mask_params* params = ubo<vkr_shadow_mask_params>(st, 2, P);
+      if (params->layer_count < 1 || params->layer_count > 4 || params->layer_count > maps.image->get_array_layers())
+        throw std::runtime_error{"shadow_mask: layer_count " + std::to_string(params->layer_count) + " of a shadow map with " +
+                                 std::to_string(maps.image->get_array_layers()) + " layers"};
+      vkr_img layers[4];
+      for (uint32_t l = 0; l < params->layer_count; l++) layers[l] = maps.image->describe_layer(l, 0, 1);
+      return vkr_shadow_mask(&depth, layers, params, &out, st.stream);
     });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the

@@ -825,6 +825,59 @@ void DeferedShadingPass::draw(RenderGraph &graph, const Gbuffer &gbuffer, ImageR
 }
 #endif
 
+// draw() with the shadow mask at binding 9, through program "defered_shading_shadowed" (no reference counterpart, so it is part
+// of both builds of the mirror)
+void DeferedShadingPass::draw_shadowed(RenderGraph &graph, const Gbuffer &gbuffer, ImageResourceId shadow, ImageResourceId ssao, ImageResourceId brdf_tex,
+  ImageResourceId reflections, ImageResourceId mask, ImageResourceId out_image)
+{
+  if (!shadowed_pipeline.has_program()) shadowed_pipeline = fullscreen_pipeline("defered_shading_shadowed");
+  vkr_shading_push pc {{min_max_roughness.x, min_max_roughness.y}, only_ao? 1u : 0u};
+  shadowed_pipeline.set_rendersubpass({false, {graph.get_descriptor(out_image).format}});
+  std::vector<rec::Binding> binds {
+    rec::sampled(0, gbuffer.albedo, sampler), rec::sampled(1, gbuffer.normal, sampler), rec::sampled(2, gbuffer.material, sampler),
+    rec::sampled(3, gbuffer.depth, sampler, DEPTH), rec::uniform_buffer(4, ubo_consts), rec::sampled(6, ssao, sampler),
+    rec::sampled(7, brdf_tex, sampler), rec::sampled(8, reflections, sampler), rec::sampled(9, mask, sampler), rec::color_target(out_image)};
+  if (shadow.get_index() != ~0u) binds.push_back(rec::sampled_mips(5, shadow, sampler, DEPTH, 0, 1));
+  const auto ext = graph.get_descriptor(out_image);
+  rec::fullscreen(graph, "DeferedShading", shadowed_pipeline, binds, rec::push(pc), ext.width, ext.height);
+}
+
+// ==== ShadowMaskPass (shadow_mask.hpp) ===============================================================================
+ImageResourceId create_shadow_mask_texture(RenderGraph &graph, uint32_t width, uint32_t height) {
+  return make_image(graph, VK_FORMAT_R8G8B8A8_UNORM, width, height, VK_IMAGE_USAGE_STORAGE_BIT|VK_IMAGE_USAGE_SAMPLED_BIT);
+}
+
+ShadowMaskPass::ShadowMaskPass() {
+  pipeline = gpu::create_compute_pipeline("shadow_mask");
+  sampler = default_sampler();
+}
+
+void ShadowMaskPass::update_params(const glm::mat4 &camera, const glm::mat4 *mvps, uint32_t count, float fovy, float aspect, float znear, float zfar,
+  uint32_t radius, uint32_t bias)
+{
+  if (!mvps || count < 1 || count > 4) throw std::runtime_error {"ShadowMaskPass::update_params: " + std::to_string(count) + " lights, needs 1..4"};
+  params = vkr_shadow_mask_params {};
+  copy_mat(params.inverse_camera, glm::inverse(camera));
+  for (uint32_t l = 0; l < count; l++) copy_mat(params.mvps[l], mvps[l]);
+  params.fovy = fovy; params.aspect = aspect; params.znear = znear; params.zfar = zfar;
+  params.layer_count = count; params.radius = radius; params.bias = bias;
+}
+
+// task "ShadowMask": set {0 depth (mip 0), 1 the shadow array (every layer), 2 the block, 3 the mask (storage)}, one 16 x 16 group
+// per 16 x 16 pixels
+void ShadowMaskPass::run(RenderGraph &graph, ImageResourceId depth, ImageResourceId shadows, uint32_t layer_count, ImageResourceId out) {
+  const auto maps = graph.get_descriptor(shadows);
+  if (layer_count < 1 || layer_count > 4 || layer_count > std::max(1u, maps.array_layers))
+    throw std::runtime_error {"ShadowMaskPass::run: " + std::to_string(layer_count) + " layers of a shadow map with " + std::to_string(std::max(1u, maps.array_layers))};
+  if (maps.width != maps.height)
+    throw std::runtime_error {"ShadowMaskPass::run: the shadow map is " + std::to_string(maps.width) + "x" + std::to_string(maps.height) + ", it must be square"};
+  vkr_shadow_mask_params block = params;
+  block.layer_count = layer_count;
+  rec::compute(graph, "ShadowMask", pipeline,
+    {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, shadows, sampler, DEPTH), rec::uniform(2, block), rec::storage(3, out)},
+    rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
+}
+
 // ==== SyntheticGbuffer ===============================================================================================
 SyntheticGbuffer::SyntheticGbuffer(uint32_t s) : seed {s} {
   pipeline = gpu::create_graphics_pipeline();

@@ -641,6 +641,18 @@ struct DeferedShadingPass {
     rendergraph::ImageResourceId reflections,
     rendergraph::ImageResourceId out_image);
 
+  // Beyond the reference: draw() with the shadow mask of ShadowMaskPass (RGBA8_UNORM at out_image's extent) at binding 9, through
+  // program "defered_shading_shadowed": channel .x of the mask (light 0: the shader's LIGHT_POS is the eye of the default shadow
+  // light) multiplies the direct term and nothing else.  Same task name, same constants and push constants as draw().
+  void draw_shadowed(rendergraph::RenderGraph &graph,
+    const Gbuffer &gbuffer,
+    rendergraph::ImageResourceId shadow,
+    rendergraph::ImageResourceId ssao,
+    rendergraph::ImageResourceId brdf_tex,
+    rendergraph::ImageResourceId reflections,
+    rendergraph::ImageResourceId mask,
+    rendergraph::ImageResourceId out_image);
+
   void draw_ui();  // defered_shading.cpp:120-126; headless: the ImGui names are inert (imgui_pass.hpp)
 
   // headless equivalents of the ImGui sliders (defered_shading.cpp:120-126)
@@ -655,6 +667,34 @@ private:
   glm::vec2 min_max_roughness {0.f, 1.f};
   bool only_ao = false;
   rendergraph::RenderGraph *graph_ref = nullptr;  // update_params writes the constant buffer the graph owns
+  gpu::GraphicsPipeline shadowed_pipeline;  // "defered_shading_shadowed", bound by the first draw_shadowed()
+};
+
+
+// ======================================================================================================
+// shadow_mask.hpp — the lookup half of the shadow pipeline (no reference counterpart: the reference renders its shadow maps,
+// SceneRenderer::render_shadow, and never samples them), over the C-ABI program "shadow_mask" (DESIGN.md 7.7).
+
+
+// RGBA8_UNORM, storage | sampled: channel l = visibility of light l
+rendergraph::ImageResourceId create_shadow_mask_texture(rendergraph::RenderGraph &graph, uint32_t width, uint32_t height);
+
+struct ShadowMaskPass {
+  ShadowMaskPass();
+
+  // camera: the view matrix (the block carries its inverse, as DeferedShadingPass::update_params makes it); mvps: the `count`
+  // (1..4) matrices the layers were rendered with; radius 0, 1, 2: a box of 1, 9, 25 taps; bias in D24 codes
+  void update_params(const glm::mat4 &camera, const glm::mat4 *mvps, uint32_t count, float fovy, float aspect, float znear, float zfar,
+    uint32_t radius, uint32_t bias);
+
+  // task "ShadowMask": depth (mip 0) and the first layer_count layers of the square D24S8 array `shadows` -> out
+  void run(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId shadows, uint32_t layer_count,
+    rendergraph::ImageResourceId out);
+
+private:
+  gpu::ComputePipeline pipeline;
+  VkSampler sampler;
+  vkr_shadow_mask_params params {};
 };
 
 
