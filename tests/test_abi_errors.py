@@ -198,11 +198,73 @@ def test_windowed_trace_and_validate_refuse_bad_windows(lib):
     assert call(WindowPush(1.0, 32, fh + 1)) == ERR_EXTENT
     windowed_normals = img(abi.FMT_RG16_UNORM, 128, 64, full=(128, fh), origin=(0, 32))
     assert call(WindowPush(1.0, 32, 96), n=windowed_normals) == ERR_EXTENT  # `normal` must be the whole-frame image
-    assert "whole-frame" in (lib.vkr_last_error() or b"").decode()
+    assert "sssr_trace_windowed: `normal` must be the whole-frame image" in (lib.vkr_last_error() or b"").decode()
     assert call(WindowPush(1.0, 32, 96), d=img(abi.FMT_RGBA32_SFLOAT, w2, h2)) == ERR_EXTENT
     assert call(WindowPush(1.0, 32, 96), m=img(abi.FMT_RG16_UNORM, w2, h2)) == ERR_FORMAT
     assert lib.vkr_sssr_validate(C.byref(rays), C.byref(mask), C.byref(data), C.byref(normal), None, None) == ERR_NULL
     assert lib.vkr_sssr_validate(C.byref(rays), C.byref(mask), C.byref(img(abi.FMT_RGBA32_SFLOAT, w2, h2)), C.byref(normal), C.byref(params), None) == ERR_EXTENT
+
+
+# ---- whole-frame bindings (require_whole_frame, csrc/vkr_host.hpp): one windowed descriptor among otherwise valid ones --------
+WINDOW = dict(full=(64, 128), origin=(0, 32))
+
+
+def _faces(fmt, windowed=None):
+    """the 6 layers of a 64 x 64 cube at a regular stride; face `windowed` is a window of a 64 x 128 frame"""
+    a = (abi.VkrImg * 6)()
+    for f in range(6):
+        a[f] = img(fmt, 64, 64, base=FAKE + f * 64 * 64 * 4, **(WINDOW if f == windowed else {}))
+    return a
+
+
+def _cubemap_probe(lib):
+    scene, pos = abi.RasterScene(), (C.c_float * 3)()
+    return lib.vkr_cubemap_probe(C.byref(scene), pos, _faces(abi.FMT_RGBA8_SRGB, windowed=2), _faces(abi.FMT_R16_SFLOAT), FAKE, 1 << 30, None)
+
+
+def _cube2oct(lib):
+    oc, od = img(abi.FMT_RGBA8_UNORM, 64, 64), img(abi.FMT_R16_UNORM, 64, 64)
+    return lib.vkr_cube2oct(_faces(abi.FMT_RGBA8_SRGB), _faces(abi.FMT_R16_SFLOAT, windowed=4), C.byref(oc), C.byref(od), None)
+
+
+def _trace_probe(lib):
+    depth, normal, out = img(abi.FMT_D24_UNORM_S8, 64, 64), img(abi.FMT_RG16_UNORM, 64, 64), img(abi.FMT_RGBA8_UNORM, 64, 64)
+    color, pdepth = (abi.VkrImg * 4)(), (abi.VkrImg * 4)()
+    for l in range(4):
+        color[l] = img(abi.FMT_RGBA8_UNORM, 64, 64, **WINDOW)
+        pdepth[l] = img(abi.FMT_R16_UNORM, 64, 64)
+    consts = abi.ProbeTraceConsts()
+    consts.grid_size = 2
+    return lib.vkr_trace_probe(C.byref(depth), C.byref(normal), color, pdepth, 4, C.byref(consts), C.byref(out), None)
+
+
+def _hit_scatter_normals(lib):
+    lib.vkr_hit_scatter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    albedo, normals = img(abi.FMT_RGBA8_SRGB, 64, 64), img(abi.FMT_RG16_UNORM, 64, 64, **WINDOW)
+    return lib.vkr_hit_scatter(C.byref(albedo), C.byref(normals), FAKE, FAKE, 4, None)
+
+
+def _screen_trace_main(lib):
+    d = [img(f, 64, 64, **WINDOW) for f in (abi.FMT_D24_UNORM_S8, abi.FMT_RG16_UNORM, abi.FMT_RGBA8_SRGB, abi.FMT_RGBA8_SRGB, abi.FMT_RGBA16_SFLOAT)]
+    params = abi.ScreenTraceParams()
+    return lib.vkr_screen_trace_main(*[C.byref(x) for x in d], C.byref(params), None)
+
+
+@pytest.mark.parametrize("call,names", [
+    (_cubemap_probe, ("cubemap_probe", "windows are not supported (single-GPU pass)")),
+    (_cube2oct, ("cube2oct.cube_distance", "windows are not supported (single-GPU pass)")),
+    (_trace_probe, ("trace_probe.probe_color", "array layers cannot be windows")),
+    (_hit_scatter_normals, ("hit_scatter", "whole-frame")),
+    (_screen_trace_main, ("screen_trace_main", "windows are not supported")),
+], ids=["cubemap_probe", "cube2oct", "trace_probe", "hit_scatter", "screen_trace_main"])
+def test_whole_frame_bindings_refuse_a_window(lib, call, names):
+    """Passes that cannot run on a tile of the frame refuse a windowed descriptor with VKR_ERR_EXTENT; the message names the
+    program (the binding where the pass has several) and says why."""
+    rc = call(lib)
+    msg = (lib.vkr_last_error() or b"").decode()
+    assert rc == ERR_EXTENT, (rc, msg)
+    for n in names:
+        assert n in msg, msg
 
 
 def test_comm_entries_refuse_null(lib):

@@ -1,5 +1,6 @@
 // common.hip — library-wide pieces of the C-ABI: version, last-error string, format table.
 #include "vkr_host.hpp"
+#include "image_codec.hpp"
 #include <atomic>
 #include <cstdarg>
 #include <cstdlib>
@@ -44,15 +45,7 @@ extern "C" uint32_t vkr_numeric_contract(void) { return VKR_CONTRACT; }
 extern "C" const char* vkr_last_error(void) { return vkr::g_error; }
 
 extern "C" uint32_t vkr_format_bytes(uint32_t format) {
-  switch (format) {
-    case VKR_FMT_D24_UNORM_S8: case VKR_FMT_RG16_UNORM: case VKR_FMT_RG16_SFLOAT:
-    case VKR_FMT_RGBA8_SRGB: case VKR_FMT_RGBA8_UNORM: case VKR_FMT_R32_SFLOAT: return 4;
-    case VKR_FMT_RGBA16_UNORM: case VKR_FMT_RGBA16_SFLOAT: return 8;
-    case VKR_FMT_RGBA32_SFLOAT: return 16;
-    case VKR_FMT_R16_SFLOAT: case VKR_FMT_R16_UNORM: return 2;
-    case VKR_FMT_R8_UNORM: return 1;
-    default: return 0;
-  }
+  return format == VKR_FMT_D24_UNORM_S8 ? 4u : vkr::colour_format_bytes(format);
 }
 
 // advanced_ssr.cpp:8-34 (float-floor division quirk kept) + host-evaluated cos/sin of 2*PI*y in zw

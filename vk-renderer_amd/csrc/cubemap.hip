@@ -184,8 +184,7 @@ __global__ __launch_bounds__(256) void k_cubemap_resolve(CubeResolveArgs a) {
                        (b[0] * t.vp[0].z + b[1] * t.vp[1].z) + b[2] * t.vp[2].z);
     // shader.frag:22-30
     const f4 out_albedo = sample_trilinear(a.r.tex[t.albedo], fu.uv, fu.ddx, fu.ddy, s_lut);
-    o_color = float_to_srgb8_lds(out_albedo.x, s_thresh) | (float_to_srgb8_lds(out_albedo.y, s_thresh) << 8) |
-              (float_to_srgb8_lds(out_albedo.z, s_thresh) << 16) | (float_to_unorm8(out_albedo.w) << 24);
+    o_color = pack_srgb8(out_albedo, s_thresh);
     o_distance = float_to_half_bits(length(pos));
   }
   Tex color = a.color, distance = a.distance;  // face is uniform over the block: scalar address arithmetic
@@ -250,7 +249,7 @@ extern "C" int vkr_cubemap_probe(const vkr_raster_scene* scene, const float pos[
     VKR_TRY(make_tex(&cube_color[f], 0, VKR_FMT_RGBA8_SRGB, "cubemap_probe.cube_color", &color[f]));
     VKR_TRY(make_tex(&cube_distance[f], 0, VKR_FMT_R16_SFLOAT, "cubemap_probe.cube_distance", &distance[f]));
     const Tex& c = color[f];
-    if (c.ox != 0 || c.oy != 0 || c.w != c.fw || c.h != c.fh) { set_error("cubemap_probe: windows are not supported (single-GPU pass)"); return VKR_ERR_EXTENT; }
+    VKR_TRY(require_whole_frame(c, "cubemap_probe", "windows are not supported (single-GPU pass)"));
     if (c.w != c.h || c.w != color[0].w || !same_window(distance[f], c)) {
       set_error("cubemap_probe: the 6 faces of both cubes must share one square extent");
       return VKR_ERR_EXTENT;

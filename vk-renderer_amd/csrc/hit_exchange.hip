@@ -325,11 +325,11 @@ extern "C" int vkr_hit_scatter(const vkr_img* frame_albedo, const vkr_img* frame
   if (!requests || !replies) { set_error("hit_scatter: NULL argument"); return VKR_ERR_NULL; }
   Tex t, n;
   VKR_TRY(make_tex(frame_albedo, 0, VKR_FMT_RGBA8_SRGB, "hit_scatter.frame_albedo", &t));
-  if (t.ox != 0 || t.oy != 0 || t.w != t.fw || t.h != t.fh) { set_error("hit_scatter: the destination must be the whole-frame image"); return VKR_ERR_EXTENT; }
+  VKR_TRY(require_whole_frame(t, "hit_scatter", "the destination must be the whole-frame image"));
   n = t;
   if (frame_normals) {
     VKR_TRY(make_tex(frame_normals, 0, VKR_FMT_RG16_UNORM, "hit_scatter.frame_normals", &n));
-    if (n.ox != 0 || n.oy != 0 || n.w != n.fw || n.h != n.fh) { set_error("hit_scatter: the destination must be the whole-frame image"); return VKR_ERR_EXTENT; }
+    VKR_TRY(require_whole_frame(n, "hit_scatter", "the destination must be the whole-frame image"));
   }
   hipLaunchKernelGGL(k_hit_scatter, dim3((count + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, t, n, requests, (const uint4*)replies, count);
   return launch_status("hit_scatter");

@@ -21,7 +21,7 @@ static int make_layer_array(const vkr_img* layers, uint32_t count, uint32_t form
   for (int m = 0; m < mips; m++) {
     VKR_TRY(make_tex(&layers[0], m, format, what, &out->mip[m]));
     const Tex& t0 = out->mip[m];
-    if (t0.ox != 0 || t0.oy != 0 || t0.w != t0.fw || t0.h != t0.fh) { set_error("%s: array layers cannot be windows", what); return VKR_ERR_EXTENT; }
+    VKR_TRY(require_whole_frame(t0, what, "array layers cannot be windows"));
     out->stride[m] = 0;
     for (uint32_t l = 1; l < count; l++) {
       Tex t;
@@ -407,10 +407,7 @@ __global__ __launch_bounds__(64) void k_trace_probe(TraceProbeArgs a) {
 
 using namespace vkr;
 
-static int check_single(const Tex& t, const char* what) {
-  if (t.ox != 0 || t.oy != 0 || t.w != t.fw || t.h != t.fh) { set_error("%s: windows are not supported (single-GPU pass)", what); return VKR_ERR_EXTENT; }
-  return VKR_OK;
-}
+static int check_single(const Tex& t, const char* what) { return require_whole_frame(t, what, "windows are not supported (single-GPU pass)"); }
 
 extern "C" int vkr_cube2oct(const vkr_img* cube_color, const vkr_img* cube_distance, const vkr_img* oct_color, const vkr_img* oct_depth,
                             void* stream) {

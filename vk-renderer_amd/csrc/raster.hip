@@ -240,8 +240,8 @@ __global__ __launch_bounds__(256) void k_raster_resolve(ResolveArgs a) {
     if (d.mr_index != 0xFFFFFFFFu) out_material = sample_trilinear(a.r.tex[d.mr_index], in_uv, ddx, ddy, s_lut);
     const f2 en = encode_normal(in_normal);
     const f2 vel = mk2(0.5f * (pb.x / pb.w - pa.x / pa.w), 0.5f * (pb.y / pb.w - pa.y / pa.w));
-    o_albedo = float_to_srgb8_lds(out_albedo.x, s_thresh) | (float_to_srgb8_lds(out_albedo.y, s_thresh) << 8) | (float_to_srgb8_lds(out_albedo.z, s_thresh) << 16) | (float_to_unorm8(out_albedo.w) << 24);
-    o_material = float_to_srgb8_lds(out_material.x, s_thresh) | (float_to_srgb8_lds(out_material.y, s_thresh) << 8) | (float_to_srgb8_lds(out_material.z, s_thresh) << 16) | (float_to_unorm8(out_material.w) << 24);
+    o_albedo = pack_srgb8(out_albedo, s_thresh);
+    o_material = pack_srgb8(out_material, s_thresh);
     o_normal = float_to_unorm16(en.x) | (float_to_unorm16(en.y) << 16);
     o_velocity = pack_half2(vel.x, vel.y);
     o_depth = (uint32_t)(key >> 32);

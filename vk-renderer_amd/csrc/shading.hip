@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_defered_shading(ShadingArgs a) {
     const PairFootprint fp = pair_footprint(a.normal, screen_uv);
     const BilinearTaps tn = pair_taps(a.normal, fp), ta = pair_taps(a.albedo, fp), tm = pair_taps(a.material, fp), td = pair_taps(a.depth0, fp);
     N = decode_normal_fast(taps_resolve<FmtRG16U>(tn));
-    albedo = mix3(mix3(srgb_rgb(ta.t00, s_lut), srgb_rgb(ta.t10, s_lut), ta.fx), mix3(srgb_rgb(ta.t01, s_lut), srgb_rgb(ta.t11, s_lut), ta.fx), ta.fy);
+    albedo = taps_srgb_rgb(ta, s_lut);
     roughness = taps_srgb_channel(tm, 1, s_lut);
     metallic = mixf(0.1f, 1.0f, taps_srgb_channel(tm, 2, s_lut));
     depth = taps_resolve<FmtD24>(td);
@@ -186,8 +186,7 @@ __global__ __launch_bounds__(256) void k_defered_shading(ShadingArgs a) {
   Lo = Lo + reflection * (F0 * ssr_brdf.x + mk3(ssr_brdf.y, ssr_brdf.y, ssr_brdf.y));
   const f3 color = occlusion * (mk3(0.6f, 0.6f, 0.6f) * albedo + Lo);
   const f3 o = a.show_ao ? mk3(occlusion, occlusion, occlusion) : color;
-  *texel_ptr<uint32_t>(a.out, lx, ly) =
-      float_to_srgb8_lds(o.x, s_thresh) | (float_to_srgb8_lds(o.y, s_thresh) << 8) | (float_to_srgb8_lds(o.z, s_thresh) << 16);  // alpha 0
+  *texel_ptr<uint32_t>(a.out, lx, ly) = pack_srgb8(mk4(o.x, o.y, o.z, 0.0f), s_thresh);  // alpha 0
 }
 
 }  // namespace vkr

@@ -190,7 +190,7 @@ extern "C" int vkr_default_shadow(const vkr_raster_scene* scene, const vkr_mat4*
   for (uint32_t l = 0; l < layer_count; l++) {
     Tex t;
     VKR_TRY(make_tex(&layers[l], 0, VKR_FMT_D24_UNORM_S8, "default_shadow.layers", &t));
-    if (t.ox != 0 || t.oy != 0 || t.w != t.fw || t.h != t.fh) { set_error("default_shadow: layers: windows are not supported (single-GPU pass)"); return VKR_ERR_EXTENT; }
+    VKR_TRY(require_whole_frame(t, "default_shadow: layers", "windows are not supported (single-GPU pass)"));
     if (l == 0) first = t;
     if (t.w != t.h || t.w != first.w) {
       set_error("default_shadow: layers: layer %u is %dx%d, every layer must be square and of one extent (layer 0: %dx%d)", l, t.w, t.h, first.w, first.h);

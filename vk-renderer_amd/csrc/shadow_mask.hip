@@ -111,23 +111,19 @@ extern "C" int vkr_shadow_mask(const vkr_img* depth, const vkr_img* layers, cons
   ShadowMaskArgs a;
   VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "shadow_mask.depth", &a.depth));
   VKR_TRY(make_tex(out_mask, 0, VKR_FMT_RGBA8_UNORM, "shadow_mask.out_mask", &a.out));
-  for (const Tex* t : {&a.depth, &a.out})
-    if (t->ox != 0 || t->oy != 0 || t->w != t->fw || t->h != t->fh) {
-      set_error("shadow_mask: %s: windows are not supported (the taps reach anywhere: a single-GPU pass)", t == &a.depth ? "depth" : "out_mask");
-      return VKR_ERR_EXTENT;
-    }
+  VKR_TRY(require_whole_frame(a.depth, "shadow_mask: depth", "windows are not supported (the taps reach anywhere: a single-GPU pass)"));
+  VKR_TRY(require_whole_frame(a.out, "shadow_mask: out_mask", "windows are not supported (the taps reach anywhere: a single-GPU pass)", 65535));
   if (a.depth.w != a.out.w || a.depth.h != a.out.h) {
     set_error("shadow_mask: depth is %dx%d, out_mask %dx%d: one extent expected", a.depth.w, a.depth.h, a.out.w, a.out.h);
     return VKR_ERR_EXTENT;
   }
-  if (a.out.w > 65535 || a.out.h > 65535) { set_error("shadow_mask: out_mask is %dx%d, at most 65535 texels a side", a.out.w, a.out.h); return VKR_ERR_EXTENT; }
   a.layer_count = params->layer_count;
   a.size = 0;
   for (uint32_t l = 0; l < SM_MAX_LAYERS; l++) {
     if (l >= a.layer_count) { a.layer[l] = a.layer[0]; continue; }
     Tex t;
     VKR_TRY(make_tex(&layers[l], 0, VKR_FMT_D24_UNORM_S8, "shadow_mask.layers", &t));
-    if (t.ox != 0 || t.oy != 0 || t.w != t.fw || t.h != t.fh) { set_error("shadow_mask: layers: windows are not supported (single-GPU pass)"); return VKR_ERR_EXTENT; }
+    VKR_TRY(require_whole_frame(t, "shadow_mask: layers", "windows are not supported (single-GPU pass)"));
     if (l == 0) a.size = t.w;
     if (t.w != t.h || t.w != a.size) {
       set_error("shadow_mask: layers: layer %u is %dx%d, every layer must be square and of one extent (layer 0: %dx%d)", l, t.w, t.h, a.size, a.size);

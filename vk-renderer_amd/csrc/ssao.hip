@@ -79,12 +79,8 @@ extern "C" int vkr_ssao(const vkr_img* depth, const vkr_ssao_params* params, con
   SsaoArgs a;
   VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "ssao.depth", &a.depth));
   VKR_TRY(make_tex(out_occlusion, 0, VKR_FMT_R8_UNORM, "ssao.out_occlusion", &a.out));
-  for (const Tex* t : {&a.depth, &a.out})
-    if (t->ox != 0 || t->oy != 0 || t->w != t->fw || t->h != t->fh) {
-      set_error("ssao: %s: windows are not supported (the taps reach anywhere: a single-GPU pass)", t == &a.depth ? "depth" : "out_occlusion");
-      return VKR_ERR_EXTENT;
-    }
-  if (a.out.w > 65535 || a.out.h > 65535) { set_error("ssao: out_occlusion is %dx%d, at most 65535 texels a side", a.out.w, a.out.h); return VKR_ERR_EXTENT; }
+  VKR_TRY(require_whole_frame(a.depth, "ssao: depth", "windows are not supported (the taps reach anywhere: a single-GPU pass)"));
+  VKR_TRY(require_whole_frame(a.out, "ssao: out_occlusion", "windows are not supported (the taps reach anywhere: a single-GPU pass)", 65535));
   load_mat(a.projection, params->projection);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   for (int i = 0; i < SSAO_SAMPLES; i++)

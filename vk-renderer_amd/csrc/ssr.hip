@@ -1201,10 +1201,7 @@ static int make_windowed_args(TraceArgs& a, const vkr_img* depth, const vkr_img*
   if (!push) { set_error("%s: NULL argument", what); return VKR_ERR_NULL; }
   const vkr_trace_push base {push->max_roughness};
   VKR_TRY(make_trace_args(a, depth, normal, material, params, halton_vec4, out_ray, out_occlusion, pdf_tex, &base));
-  if (a.normal.ox != 0 || a.normal.oy != 0 || a.normal.w != a.normal.fw || a.normal.h != a.normal.fh) {
-    set_error("%s: `normal` must be the whole-frame image (rows outside the window are filled later)", what);
-    return VKR_ERR_EXTENT;
-  }
+  VKR_TRY(require_whole_frame(a.normal, what, "`normal` must be the whole-frame image (rows outside the window are filled later)"));
   if (push->normal_row0 >= push->normal_row1 || push->normal_row1 > (uint32_t)a.normal.fh) {
     set_error("%s: normal rows [%u, %u) of %d", what, push->normal_row0, push->normal_row1, a.normal.fh);
     return VKR_ERR_EXTENT;

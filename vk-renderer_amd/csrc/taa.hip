@@ -26,20 +26,19 @@ inline float sqrt_threshold(float limit) {
 
 // Byte offsets (4-byte texels) and weights of the bilinear footprint of texture(t, uv): what sample<F>() computes
 // before it loads.  Images that share one window geometry and pitch share the whole record.
-struct Footprint { uint32_t o00, o10, o01, o11; float fx, fy; };
-VKR_DEV Footprint footprint4(const Tex& t, f2 uv) {
-  Footprint f;
-  const float x = cfma(uv.x, (float)t.fw, -0.5f), y = cfma(uv.y, (float)t.fh, -0.5f);
-  const float x0f = floorf(x), y0f = floorf(y);
-  f.fx = x - x0f; f.fy = y - y0f;
-  const int x0 = f2i(x0f) - t.ox, y0 = f2i(y0f) - t.oy;
+struct TapOffsets { uint32_t o00, o10, o01, o11; float fx, fy; };
+VKR_DEV TapOffsets footprint4(const Tex& t, f2 uv) {
+  TapOffsets f;
+  const Footprint w = bilinear_footprint<true>(t, uv);
+  f.fx = w.fx; f.fy = w.fy;
+  const int x0 = w.x0, y0 = w.y0;
   const uint32_t xa = (uint32_t)iclamp(x0, 0, t.w - 1) * 4u, xb = (uint32_t)iclamp(x0 + 1, 0, t.w - 1) * 4u;
   const uint32_t ra = __umul24((uint32_t)iclamp(y0, 0, t.h - 1), (uint32_t)t.pitch);
   const uint32_t rb = __umul24((uint32_t)iclamp(y0 + 1, 0, t.h - 1), (uint32_t)t.pitch);
   f.o00 = ra + xa; f.o10 = ra + xb; f.o01 = rb + xa; f.o11 = rb + xb;
   return f;
 }
-VKR_DEV BilinearTaps taps_at(const Tex& t, const Footprint& f) {
+VKR_DEV BilinearTaps taps_at(const Tex& t, const TapOffsets& f) {
   BilinearTaps b;
   b.t00 = *(const uint32_t*)(t.p + f.o00); b.t10 = *(const uint32_t*)(t.p + f.o10);
   b.t01 = *(const uint32_t*)(t.p + f.o01); b.t11 = *(const uint32_t*)(t.p + f.o11);
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaArgs a) {
   const int gx = a.out.ox + lx, gy = a.out.oy + ly;
   // (g + 0.5) / size: both operands and the quotient are far inside the normal range
   const f2 screen_uv = mk2(pixel_centre_uv(gx, (float)a.out.fw), pixel_centre_uv(gy, (float)a.out.fh));
-  Footprint fc, fv;
+  TapOffsets fc, fv;
   BilinearTaps tc, tv, td_tile;
   if (TILED) {
     // the sampler's arithmetic (footprint4) up to the texel indices, which are taken relative to the tile; they cannot leave
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaArgs a) {
     tc.t00 = s_col[i00]; tc.t10 = s_col[i00 + 1]; tc.t01 = s_col[i00 + TAA_TW]; tc.t11 = s_col[i00 + TAA_TW + 1];
     tv.t00 = s_vel[i00]; tv.t10 = s_vel[i00 + 1]; tv.t01 = s_vel[i00 + TAA_TW]; tv.t11 = s_vel[i00 + TAA_TW + 1];
     td_tile.t00 = s_dep[i00]; td_tile.t10 = s_dep[i00 + 1]; td_tile.t01 = s_dep[i00 + TAA_TW]; td_tile.t11 = s_dep[i00 + TAA_TW + 1];
-    fc = Footprint {}; fv = fc;
+    fc = TapOffsets {}; fv = fc;
   } else {
     fc = footprint4(a.color, screen_uv);
     fv = SHARED ? fc : footprint4(a.velocity, screen_uv);
@@ -156,8 +155,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaArgs a) {
       h[10] = ld(2, 0); h[11] = ld(2, 1);
     }
   }
-  const f3 current_color = mix3(mix3(srgb_rgb(tc.t00, s_lut), srgb_rgb(tc.t10, s_lut), tc.fx),
-                                mix3(srgb_rgb(tc.t01, s_lut), srgb_rgb(tc.t11, s_lut), tc.fx), tc.fy);
+  const f3 current_color = taps_srgb_rgb(tc, s_lut);
   f3 out_color = current_color;
   if (inside) {
     // delta_len < 0.005 decided on the squared length (correctly rounded sqrt is monotone); the length itself is only
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaArgs a) {
       float cur_depth;
       if (TILED) cur_depth = taps_resolve<FmtD24>(td_tile);
       else {
-        const Footprint fd = SHARED ? fc : footprint4(a.cur_depth, screen_uv);
+        const TapOffsets fd = SHARED ? fc : footprint4(a.cur_depth, screen_uv);
         cur_depth = taps_resolve<FmtD24>(taps_at(a.cur_depth, fd));
       }
       const f3 vc = reconstruct_view_vec(screen_uv, cur_depth, a.pr);

@@ -105,11 +105,8 @@ extern "C" int vkr_tile_regression(const vkr_img* depth, const vkr_img* out_plan
   TileRegressionArgs a;
   VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "tile_regression.depth", &a.depth));
   VKR_TRY(make_tex(out_planes, 0, VKR_FMT_RGBA32_SFLOAT, "tile_regression.out_planes", &a.out));
-  for (const Tex* t : {&a.depth, &a.out})
-    if (t->ox != 0 || t->oy != 0 || t->w != t->fw || t->h != t->fh) {
-      set_error("tile_regression: %s: windows are not supported (tiles would straddle owners: a single-GPU pass)", t == &a.depth ? "depth" : "out_planes");
-      return VKR_ERR_EXTENT;
-    }
+  VKR_TRY(require_whole_frame(a.depth, "tile_regression: depth", "windows are not supported (tiles would straddle owners: a single-GPU pass)"));
+  VKR_TRY(require_whole_frame(a.out, "tile_regression: out_planes", "windows are not supported (tiles would straddle owners: a single-GPU pass)"));
   const int tiles_w = (a.depth.w + TILE_REGRESSION_TILE - 1) / TILE_REGRESSION_TILE, tiles_h = (a.depth.h + TILE_REGRESSION_TILE - 1) / TILE_REGRESSION_TILE;
   if (a.out.w > tiles_w || a.out.h > tiles_h) {
     set_error("tile_regression: out_planes is %dx%d, a %dx%d depth view has %dx%d tiles (a tile further out has no pixel)", a.out.w, a.out.h,

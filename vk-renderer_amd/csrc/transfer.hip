@@ -10,72 +10,34 @@
 // project's one mip rule (scene.build_mips): ((a + b) + (c + d)) * 0.25 of the 2x2 block of the STORED previous level.
 // Roofline: HBM.  A blit moves src + dst bytes once, a clear the destination once, a mip chain 4/3 of level 0.
 #include "vkr_host.hpp"
+#include "image_codec.hpp"
 #include <algorithm>
 
 namespace vkr {
 
-// ---- stores without an alignment beyond 4 bytes (the counterparts of load_u32x2 / load_u32x4) ----------------------------
-VKR_DEV void store_u32x2(uint8_t* p, uint32_t x, uint32_t y) { U32x2 v; v.x = x; v.y = y; *(U32x2*)p = v; }
-VKR_DEV void store_u32x4(uint8_t* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { U32x4 v; v.x = x; v.y = y; v.z = z; v.w = w; *(U32x4*)p = v; }
 VKR_DEV uint8_t* wptr(const Tex& t, int x, int y, int bpp) { return const_cast<uint8_t*>(t.p) + toff(t, x, y, bpp); }
 
-// ---- any colour format <-> float RGBA (format is wave-uniform: a scalar branch) --------------------------------------------
-// lut / thresh: the sRGB tables staged in LDS (only read for RGBA8_SRGB)
+// ---- any colour format <-> float RGBA through image_codec.hpp (the format is wave-uniform: a scalar branch) ----------------
+// lut / thresh: the sRGB tables staged in LDS (only read for RGBA8_SRGB).  Anything but a colour format: (0, 0, 0, 1) / zeros.
 VKR_DEV f4 load_rgba(const Tex& t, uint32_t fmt, int x, int y, const float* lut) {
-  switch (fmt) {
-    case VKR_FMT_RG16_UNORM: { const uint32_t v = *(const uint32_t*)(t.p + toff(t, x, y, 4));
-      return mk4(unorm16_to_float(v & 0xFFFFu), unorm16_to_float(v >> 16), 0.0f, 1.0f); }
-    case VKR_FMT_RG16_SFLOAT: { const uint32_t v = *(const uint32_t*)(t.p + toff(t, x, y, 4));
-      return mk4(half_bits_to_float(v & 0xFFFFu), half_bits_to_float(v >> 16), 0.0f, 1.0f); }
-    case VKR_FMT_RGBA8_SRGB: { const uint32_t v = *(const uint32_t*)(t.p + toff(t, x, y, 4));
-      return mk4(lut[v & 0xFFu], lut[(v >> 8) & 0xFFu], lut[(v >> 16) & 0xFFu], unorm8_to_float(v >> 24)); }
-    case VKR_FMT_RGBA8_UNORM: { const uint32_t v = *(const uint32_t*)(t.p + toff(t, x, y, 4));
-      return mk4(unorm8_to_float(v & 0xFFu), unorm8_to_float((v >> 8) & 0xFFu), unorm8_to_float((v >> 16) & 0xFFu), unorm8_to_float(v >> 24)); }
-    case VKR_FMT_RGBA16_UNORM: { const U32x2 v = load_u32x2(t.p + toff(t, x, y, 8));
-      return mk4(unorm16_to_float(v.x & 0xFFFFu), unorm16_to_float(v.x >> 16), unorm16_to_float(v.y & 0xFFFFu), unorm16_to_float(v.y >> 16)); }
-    case VKR_FMT_RGBA16_SFLOAT: { const U32x2 v = load_u32x2(t.p + toff(t, x, y, 8));
-      return mk4(half_bits_to_float(v.x & 0xFFFFu), half_bits_to_float(v.x >> 16), half_bits_to_float(v.y & 0xFFFFu), half_bits_to_float(v.y >> 16)); }
-    case VKR_FMT_R16_SFLOAT: return mk4(half_bits_to_float(*(const uint16_t*)(t.p + toff(t, x, y, 2))), 0.0f, 0.0f, 1.0f);
-    case VKR_FMT_R16_UNORM: return mk4(unorm16_to_float(*(const uint16_t*)(t.p + toff(t, x, y, 2))), 0.0f, 0.0f, 1.0f);
-    case VKR_FMT_R32_SFLOAT: return mk4(*(const float*)(t.p + toff(t, x, y, 4)), 0.0f, 0.0f, 1.0f);
-    case VKR_FMT_R8_UNORM: return mk4(unorm8_to_float(*(t.p + toff(t, x, y, 1))), 0.0f, 0.0f, 1.0f);
-    case VKR_FMT_RGBA32_SFLOAT: { const U32x4 v = load_u32x4(t.p + toff(t, x, y, 16));
-      return mk4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); }
-    default: return mk4(0.0f, 0.0f, 0.0f, 1.0f);
-  }
+  f4 c = mk4(0.0f, 0.0f, 0.0f, 1.0f);
+  with_colour_format(fmt, [&](auto codec) { c = codec.decode(load_raw<codec.bpp>(t.p + toff(t, x, y, codec.bpp)), lut); });
+  return c;
 }
-// the stored word(s) of one texel: up to four dwords, `fmt`'s bytes per texel of them are meaningful
-struct Word4 { uint32_t x, y, z, w; };
-VKR_DEV Word4 encode_rgba(uint32_t fmt, f4 c, const float* thresh) {
-  Word4 o; o.x = o.y = o.z = o.w = 0u;
-  switch (fmt) {
-    case VKR_FMT_RG16_UNORM: o.x = float_to_unorm16(c.x) | (float_to_unorm16(c.y) << 16); break;
-    case VKR_FMT_RG16_SFLOAT: o.x = pack_half2(c.x, c.y); break;
-    case VKR_FMT_RGBA8_SRGB:
-      o.x = float_to_srgb8_lds(c.x, thresh) | (float_to_srgb8_lds(c.y, thresh) << 8) | (float_to_srgb8_lds(c.z, thresh) << 16) | (float_to_unorm8(c.w) << 24);
-      break;
-    case VKR_FMT_RGBA8_UNORM: o.x = float_to_unorm8(c.x) | (float_to_unorm8(c.y) << 8) | (float_to_unorm8(c.z) << 16) | (float_to_unorm8(c.w) << 24); break;
-    case VKR_FMT_RGBA16_UNORM:
-      o.x = float_to_unorm16(c.x) | (float_to_unorm16(c.y) << 16); o.y = float_to_unorm16(c.z) | (float_to_unorm16(c.w) << 16);
-      break;
-    case VKR_FMT_RGBA16_SFLOAT: o.x = pack_half2(c.x, c.y); o.y = pack_half2(c.z, c.w); break;
-    case VKR_FMT_R16_SFLOAT: o.x = float_to_half_bits(c.x); break;
-    case VKR_FMT_R16_UNORM: o.x = float_to_unorm16(c.x); break;
-    case VKR_FMT_R32_SFLOAT: o.x = __float_as_uint(c.x); break;
-    case VKR_FMT_R8_UNORM: o.x = float_to_unorm8(c.x); break;
-    case VKR_FMT_RGBA32_SFLOAT: o.x = __float_as_uint(c.x); o.y = __float_as_uint(c.y); o.z = __float_as_uint(c.z); o.w = __float_as_uint(c.w); break;
-    default: break;
-  }
+VKR_DEV Raw encode_rgba(uint32_t fmt, f4 c, const float* thresh) {
+  Raw o = raw_words(0u);
+  with_colour_format(fmt, [&](auto codec) { o = codec.encode(c, thresh); });
   return o;
 }
-VKR_DEV void store_word(const Tex& t, int bpp, int x, int y, const Word4& o) {
+// the texel (x, y) of an image of `bpp` bytes a texel
+VKR_DEV void store_texel(const Tex& t, int bpp, int x, int y, const Raw& o) {
   uint8_t* p = wptr(t, x, y, bpp);
   switch (bpp) {
-    case 1: *p = (uint8_t)o.x; break;
-    case 2: *(uint16_t*)p = (uint16_t)o.x; break;
-    case 4: *(uint32_t*)p = o.x; break;
-    case 8: store_u32x2(p, o.x, o.y); break;
-    default: store_u32x4(p, o.x, o.y, o.z, o.w); break;
+    case 1: store_raw<1>(p, o); break;
+    case 2: store_raw<2>(p, o); break;
+    case 4: store_raw<4>(p, o); break;
+    case 8: store_raw<8>(p, o); break;
+    default: store_raw<16>(p, o); break;
   }
 }
 VKR_DEV bool is_srgb(uint32_t fmt) { return fmt == VKR_FMT_RGBA8_SRGB; }
@@ -95,11 +57,11 @@ struct ClearArgs {
 };
 __global__ __launch_bounds__(256) void k_transfer_clear(ClearArgs a) {
   __shared__ float s_thr[VKR_SRGB_LUT_SIZE];
-  __shared__ Word4 s_word;
+  __shared__ Raw s_word;
   const int tid = threadIdx.y * 64 + threadIdx.x;
   if (is_srgb(a.format)) { srgb_thresh_stage(s_thr, tid, 256); __syncthreads(); }
   if (tid == 0) {
-    Word4 w;
+    Raw w;
     if (a.format == VKR_FMT_D24_UNORM_S8) {
       w.x = (uint32_t)rintf(vclamp(a.depth, 0.0f, 1.0f) * 16777215.0f) | ((a.stencil & 0xFFu) << 24);
       w.y = w.z = w.w = 0u;
@@ -114,7 +76,7 @@ __global__ __launch_bounds__(256) void k_transfer_clear(ClearArgs a) {
     s_word = w;
   }
   __syncthreads();
-  const Word4 w = s_word;
+  const Raw w = s_word;
   uint32_t m = 0;
   while (m + 1 < a.mips && blockIdx.x >= a.first[m + 1]) m++;
   const Tex& t = a.mip[m];
@@ -154,20 +116,17 @@ template <bool LINEAR> __global__ __launch_bounds__(256) void k_transfer_blit(Bl
   }
   f4 c;
   if (LINEAR) {
-    const float xf = u - 0.5f, yf = v - 0.5f;
-    const float x0f = floorf(xf), y0f = floorf(yf);
-    const float fx = xf - x0f, fy = yf - y0f;
-    const int x0 = f2i(x0f), y0 = f2i(y0f);
-    const int xa = iclamp(x0, 0, a.src.w - 1), xb = iclamp(x0 + 1, 0, a.src.w - 1);
-    const int ya = iclamp(y0, 0, a.src.h - 1), yb = iclamp(y0 + 1, 0, a.src.h - 1);
+    const Footprint f = footprint_at(u - 0.5f, v - 0.5f);
+    const int xa = iclamp(f.x0, 0, a.src.w - 1), xb = iclamp(f.x0 + 1, 0, a.src.w - 1);
+    const int ya = iclamp(f.y0, 0, a.src.h - 1), yb = iclamp(f.y0 + 1, 0, a.src.h - 1);
     const f4 t00 = load_rgba(a.src, a.src_format, xa, ya, s_lut), t10 = load_rgba(a.src, a.src_format, xb, ya, s_lut);
     const f4 t01 = load_rgba(a.src, a.src_format, xa, yb, s_lut), t11 = load_rgba(a.src, a.src_format, xb, yb, s_lut);
-    c = mix4(mix4(t00, t10, fx), mix4(t01, t11, fx), fy);
+    c = mix4(mix4(t00, t10, f.fx), mix4(t01, t11, f.fx), f.fy);
   } else {
     const int sx = iclamp(f2i(floorf(u)), 0, a.src.w - 1), sy = iclamp(f2i(floorf(v)), 0, a.src.h - 1);
     c = load_rgba(a.src, a.src_format, sx, sy, s_lut);
   }
-  store_word(a.dst, (int)a.dst_bpp, x, y, encode_rgba(a.dst_format, c, s_thr));
+  store_texel(a.dst, (int)a.dst_bpp, x, y, encode_rgba(a.dst_format, c, s_thr));
 }
 
 // ---- mip chain ---------------------------------------------------------------------------------------------------------------
@@ -178,27 +137,26 @@ template <bool LINEAR> __global__ __launch_bounds__(256) void k_transfer_blit(Bl
 // written: both schedules call it on the same stored texels and therefore leave the same bytes.
 template <int FMT> struct MipRaw { typedef uint32_t T; };
 template <> struct MipRaw<VKR_FMT_RGBA16_SFLOAT> { typedef uint2 T; };
-template <int FMT> constexpr int mip_bpp() {
-  return FMT == VKR_FMT_RGBA16_SFLOAT ? 8 : FMT == VKR_FMT_R16_SFLOAT ? 2 : FMT == VKR_FMT_R8_UNORM ? 1 : 4;
+template <int FMT> constexpr int mip_bpp() { return Codec<FMT>::bpp; }
+// MipRaw<FMT>::T is the used dwords of a Raw
+template <int FMT> VKR_DEV typename MipRaw<FMT>::T mip_raw(const Raw& r) {
+  if constexpr (mip_bpp<FMT>() == 8) return make_uint2(r.x, r.y); else return r.x;
 }
 template <int FMT> VKR_DEV typename MipRaw<FMT>::T mip_load(const Tex& t, int x, int y) {
-  if constexpr (FMT == VKR_FMT_RGBA16_SFLOAT) { const U32x2 v = load_u32x2(t.p + toff(t, x, y, 8)); return make_uint2(v.x, v.y); }
-  else if constexpr (FMT == VKR_FMT_R16_SFLOAT) return *(const uint16_t*)(t.p + toff(t, x, y, 2));
-  else if constexpr (FMT == VKR_FMT_R8_UNORM) return *(t.p + toff(t, x, y, 1));
-  else return *(const uint32_t*)(t.p + toff(t, x, y, 4));
+  return mip_raw<FMT>(load_raw<mip_bpp<FMT>()>(t.p + toff(t, x, y, mip_bpp<FMT>())));
 }
-// texels (x, y) and (x + 1, y) as one load where the texel size allows it
+// texels (x, y) and (x + 1, y) as one load where the texel size allows it (1- and 2-byte texels: two loads, as measured)
 template <int FMT> VKR_DEV void mip_load_pair(const Tex& t, int x, int y, typename MipRaw<FMT>::T& l, typename MipRaw<FMT>::T& r) {
-  if constexpr (FMT == VKR_FMT_RGBA16_SFLOAT) { const U32x4 v = load_u32x4(t.p + toff(t, x, y, 8)); l = make_uint2(v.x, v.y); r = make_uint2(v.z, v.w); }
-  else if constexpr (mip_bpp<FMT>() == 4) { const U32x2 v = load_u32x2(t.p + toff(t, x, y, 4)); l = v.x; r = v.y; }
-  else { l = mip_load<FMT>(t, x, y); r = mip_load<FMT>(t, x + 1, y); }
+  if constexpr (mip_bpp<FMT>() >= 4) {
+    Raw a, b;
+    load_raw_pair<mip_bpp<FMT>()>(t.p + toff(t, x, y, mip_bpp<FMT>()), a, b);
+    l = mip_raw<FMT>(a); r = mip_raw<FMT>(b);
+  } else { l = mip_load<FMT>(t, x, y); r = mip_load<FMT>(t, x + 1, y); }
 }
 template <int FMT> VKR_DEV void mip_store(const Tex& t, int x, int y, typename MipRaw<FMT>::T v) {
-  uint8_t* p = wptr(t, x, y, mip_bpp<FMT>());
-  if constexpr (FMT == VKR_FMT_RGBA16_SFLOAT) store_u32x2(p, v.x, v.y);
-  else if constexpr (FMT == VKR_FMT_R16_SFLOAT) *(uint16_t*)p = (uint16_t)v;
-  else if constexpr (FMT == VKR_FMT_R8_UNORM) *p = (uint8_t)v;
-  else *(uint32_t*)p = v;
+  Raw o;
+  if constexpr (mip_bpp<FMT>() == 8) o = raw_words(v.x, v.y); else o = raw_words(v);
+  store_raw<mip_bpp<FMT>()>(wptr(t, x, y, mip_bpp<FMT>()), o);
 }
 VKR_DEV float avg4(float a, float b, float c, float d) { return ((a + b) + (c + d)) * 0.25f; }
 template <int FMT> VKR_DEV typename MipRaw<FMT>::T mip_reduce(typename MipRaw<FMT>::T a, typename MipRaw<FMT>::T b, typename MipRaw<FMT>::T c,
@@ -338,7 +296,7 @@ using namespace vkr;
 static int whole_image(const vkr_img* d, const char* what) {
   if (!d || !d->base) { set_error("%s: NULL image", what); return VKR_ERR_NULL; }
   if (vkr_format_bytes(d->format) == 0) { set_error("%s: unknown format %u", what, d->format); return VKR_ERR_FORMAT; }
-  if (d->origin_x != 0 || d->origin_y != 0 || d->full_width != d->width || d->full_height != d->height) {
+  if (!whole_frame(d->origin_x, d->origin_y, d->width, d->height, d->full_width, d->full_height)) {
     set_error("%s: a window (%d,%d)+(%ux%u) of a %ux%u frame: transfers are whole-image operations", what, d->origin_x, d->origin_y, d->width,
               d->height, d->full_width, d->full_height);
     return VKR_ERR_EXTENT;
@@ -413,12 +371,10 @@ template <int FMT> static int gen_mipmaps_launch(const Tex* lv, uint32_t mips, b
 
 extern "C" int vkr_gen_mipmaps(const vkr_img* img, void* stream) {
   VKR_TRY(whole_image(img, "gen_mipmaps.img"));
-  switch (img->format) {
-    case VKR_FMT_RGBA8_SRGB: case VKR_FMT_RGBA8_UNORM: case VKR_FMT_RGBA16_SFLOAT: case VKR_FMT_RG16_SFLOAT: case VKR_FMT_R16_SFLOAT:
-    case VKR_FMT_R32_SFLOAT: case VKR_FMT_R8_UNORM: break;
-    case VKR_FMT_D24_UNORM_S8: set_error("gen_mipmaps.img: D24_UNORM_S8 has no averaged mips (vkr_depth_mips builds the depth pyramid)"); return VKR_ERR_FORMAT;
-    default: set_error("gen_mipmaps.img: format %u has no mip rule", img->format); return VKR_ERR_FORMAT;
-  }
+  if (img->format == VKR_FMT_D24_UNORM_S8) { set_error("gen_mipmaps.img: D24_UNORM_S8 has no averaged mips (vkr_depth_mips builds the depth pyramid)"); return VKR_ERR_FORMAT; }
+  bool has_rule = false;
+  with_colour_format(img->format, [&](auto codec) { has_rule = codec.mips; });
+  if (!has_rule) { set_error("gen_mipmaps.img: format %u has no mip rule", img->format); return VKR_ERR_FORMAT; }
   Tex lv[VKR_MAX_MIPS];
   for (uint32_t m = 0; m < img->mip_count; m++) {
     VKR_TRY(make_tex(img, (int)m, img->format, "gen_mipmaps.img", &lv[m]));
@@ -428,13 +384,9 @@ extern "C" int vkr_gen_mipmaps(const vkr_img* img, void* stream) {
   const uint32_t sw = switches();
   const bool fused = (sw & VKR_SWITCH_MIPS_PER_LEVEL) ? false : (sw & VKR_SWITCH_MIPS_FUSED) ? true : VKR_MIPS_DEFAULT_FUSED != 0;
   const hipStream_t s = (hipStream_t)stream;
-  switch (img->format) {
-    case VKR_FMT_RGBA8_SRGB: return gen_mipmaps_launch<VKR_FMT_RGBA8_SRGB>(lv, img->mip_count, fused, s);
-    case VKR_FMT_RGBA8_UNORM: return gen_mipmaps_launch<VKR_FMT_RGBA8_UNORM>(lv, img->mip_count, fused, s);
-    case VKR_FMT_RGBA16_SFLOAT: return gen_mipmaps_launch<VKR_FMT_RGBA16_SFLOAT>(lv, img->mip_count, fused, s);
-    case VKR_FMT_RG16_SFLOAT: return gen_mipmaps_launch<VKR_FMT_RG16_SFLOAT>(lv, img->mip_count, fused, s);
-    case VKR_FMT_R16_SFLOAT: return gen_mipmaps_launch<VKR_FMT_R16_SFLOAT>(lv, img->mip_count, fused, s);
-    case VKR_FMT_R32_SFLOAT: return gen_mipmaps_launch<VKR_FMT_R32_SFLOAT>(lv, img->mip_count, fused, s);
-    default: return gen_mipmaps_launch<VKR_FMT_R8_UNORM>(lv, img->mip_count, fused, s);
-  }
+  int rc = VKR_OK;
+  with_colour_format(img->format, [&](auto codec) {
+    if constexpr (codec.mips) rc = gen_mipmaps_launch<(int)codec.format>(lv, img->mip_count, fused, s);
+  });
+  return rc;
 }

@@ -419,10 +419,7 @@ extern "C" int vkr_screen_trace_main(const vkr_img* depth, const vkr_img* normal
   VKR_TRY(make_tex(color, 0, VKR_FMT_RGBA8_SRGB, "screen_trace_main.color", &a.color));
   VKR_TRY(make_tex(material, 0, VKR_FMT_RGBA8_SRGB, "screen_trace_main.material", &a.material));
   VKR_TRY(make_tex(out_raw, 0, VKR_FMT_RGBA16_SFLOAT, "screen_trace_main.out", &a.out));
-  if (a.out.ox != 0 || a.out.oy != 0 || a.out.w != a.out.fw || a.out.h != a.out.fh) {
-    set_error("screen_trace_main: tiled windows are not supported (8x8 tile exchange)");
-    return VKR_ERR_EXTENT;
-  }
+  VKR_TRY(require_whole_frame(a.out, "screen_trace_main", "tiled windows are not supported (8x8 tile exchange)"));
   load_mat(a.normal_mat, params->normal_mat);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   fill_slice_table(a.slice_cs, params->angle_offset, 0.0f);

@@ -326,15 +326,29 @@ template <class F> VKR_DEV typename F::T fetch_clamped(const Tex& t, int gx, int
   int lx = iclamp(gx - t.ox, 0, t.w - 1), ly = iclamp(gy - t.oy, 0, t.h - 1);
   return F::load(t, lx, ly);
 }
+// The bilinear footprint around the unnormalised texel coordinate (x, y): the upper-left tap (x0, y0) = floor + the
+// textureOffset (dx, dy) - the origin (ox, oy) of the coordinates wanted, the weights (fx, fy) = the fractions.  The taps
+// are (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each clamped to the edge.
+struct Footprint { int x0, y0; float fx, fy; };
+VKR_DEV Footprint footprint_at(float x, float y, int dx = 0, int dy = 0, int ox = 0, int oy = 0) {
+  Footprint f;
+  const float x0f = floorf(x), y0f = floorf(y);
+  f.fx = x - x0f; f.fy = y - y0f;
+  f.x0 = f2i(x0f) + dx - ox; f.y0 = f2i(y0f) + dy - oy;
+  return f;
+}
+// ... of texture(t, uv) / textureOffset(t, uv, off): the one place the clamp-to-edge sampler's texel coordinate
+// uv * size - 0.5 is written (frozen order: fused, then floor, fraction, truncation, offset).  In frame coordinates, or
+// (WINDOW) in those of the window held in memory.
+template <bool WINDOW = false> VKR_DEV Footprint bilinear_footprint(const Tex& t, f2 uv, int offx = 0, int offy = 0) {
+  return footprint_at(cfma(uv.x, (float)t.fw, -0.5f), cfma(uv.y, (float)t.fh, -0.5f), offx, offy, WINDOW ? t.ox : 0, WINDOW ? t.oy : 0);
+}
 // texture()/textureLod()/textureOffset(): bilinear, clamp-to-edge
 template <class F> VKR_DEV typename F::T sample(const Tex& t, f2 uv, int offx = 0, int offy = 0) {
-  float x = cfma(uv.x, (float)t.fw, -0.5f), y = cfma(uv.y, (float)t.fh, -0.5f);
-  float x0f = floorf(x), y0f = floorf(y);
-  float fx = x - x0f, fy = y - y0f;
-  int x0 = f2i(x0f) + offx, y0 = f2i(y0f) + offy;
-  typename F::T t00 = fetch_clamped<F>(t, x0, y0), t10 = fetch_clamped<F>(t, x0 + 1, y0);
-  typename F::T t01 = fetch_clamped<F>(t, x0, y0 + 1), t11 = fetch_clamped<F>(t, x0 + 1, y0 + 1);
-  return F::lerp(F::lerp(t00, t10, fx), F::lerp(t01, t11, fx), fy);
+  const Footprint f = bilinear_footprint(t, uv, offx, offy);
+  typename F::T t00 = fetch_clamped<F>(t, f.x0, f.y0), t10 = fetch_clamped<F>(t, f.x0 + 1, f.y0);
+  typename F::T t01 = fetch_clamped<F>(t, f.x0, f.y0 + 1), t11 = fetch_clamped<F>(t, f.x0 + 1, f.y0 + 1);
+  return F::lerp(F::lerp(t00, t10, f.fx), F::lerp(t01, t11, f.fx), f.fy);
 }
 
 // ---- sRGB images ------------------------------------------------------------------------------------
@@ -374,6 +388,12 @@ VKR_DEV uint32_t float_to_srgb8_fast(float x, const float* thresh) {
   const uint32_t e = (uint32_t)fminf(fmaxf(est, 0.0f), 254.0f);
   return e + (thresh[e + 1u] <= x ? 1u : 0u);
 }
+// The RGBA8_SRGB word of a linear colour: rgb through the channel encoder `enc` (float_to_srgb8_lds unless a pass brings its
+// own), alpha as UNORM8.  The one place the word is put together.
+template <class Enc> VKR_DEV uint32_t pack_srgb8(f4 c, const float* thresh, Enc enc) {
+  return enc(c.x, thresh) | (enc(c.y, thresh) << 8) | (enc(c.z, thresh) << 16) | (float_to_unorm8(c.w) << 24);
+}
+VKR_DEV uint32_t pack_srgb8(f4 c, const float* thresh) { return pack_srgb8(c, thresh, float_to_srgb8_lds); }
 VKR_DEV uint32_t load_u32_clamped(const Tex& t, int gx, int gy) {
   int lx = iclamp(gx - t.ox, 0, t.w - 1), ly = iclamp(gy - t.oy, 0, t.h - 1);
   return *(const uint32_t*)(t.p + toff(t, lx, ly, 4));
@@ -385,16 +405,44 @@ struct __attribute__((packed, aligned(4))) U32x2 { uint32_t x, y; };
 struct __attribute__((packed, aligned(4))) U32x4 { uint32_t x, y, z, w; };
 VKR_DEV U32x2 load_u32x2(const uint8_t* p) { return *(const U32x2*)p; }
 VKR_DEV U32x4 load_u32x4(const uint8_t* p) { return *(const U32x4*)p; }
+VKR_DEV void store_u32x2(uint8_t* p, uint32_t x, uint32_t y) { U32x2 v; v.x = x; v.y = y; *(U32x2*)p = v; }
+VKR_DEV void store_u32x4(uint8_t* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { U32x4 v; v.x = x; v.y = y; v.z = z; v.w = w; *(U32x4*)p = v; }
+// The stored bytes of one texel of any format: the texel's BPP bytes in the low end, the rest 0.
+struct Raw { uint32_t x, y, z, w; };
+struct __attribute__((packed, aligned(2))) U16x2 { uint16_t x, y; };
+struct __attribute__((packed, aligned(1))) U8x2 { uint8_t x, y; };
+template <int BPP> VKR_DEV Raw load_raw(const uint8_t* p) {
+  Raw r; r.x = r.y = r.z = r.w = 0u;
+  if constexpr (BPP == 16) { const U32x4 v = load_u32x4(p); r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; }
+  else if constexpr (BPP == 8) { const U32x2 v = load_u32x2(p); r.x = v.x; r.y = v.y; }
+  else if constexpr (BPP == 4) r.x = *(const uint32_t*)p;
+  else if constexpr (BPP == 2) r.x = *(const uint16_t*)p;
+  else r.x = *p;
+  return r;
+}
+// texels (x, y) and (x + 1, y) as ONE load; BPP <= 8
+template <int BPP> VKR_DEV void load_raw_pair(const uint8_t* p, Raw& l, Raw& r) {
+  l.x = l.y = l.z = l.w = 0u; r = l;
+  if constexpr (BPP == 8) { const U32x4 v = load_u32x4(p); l.x = v.x; l.y = v.y; r.x = v.z; r.y = v.w; }
+  else if constexpr (BPP == 4) { const U32x2 v = load_u32x2(p); l.x = v.x; r.x = v.y; }
+  else if constexpr (BPP == 2) { const U16x2 v = *(const U16x2*)p; l.x = v.x; r.x = v.y; }
+  else { const U8x2 v = *(const U8x2*)p; l.x = v.x; r.x = v.y; }
+}
+template <int BPP> VKR_DEV void store_raw(uint8_t* p, const Raw& o) {
+  if constexpr (BPP == 16) store_u32x4(p, o.x, o.y, o.z, o.w);
+  else if constexpr (BPP == 8) store_u32x2(p, o.x, o.y);
+  else if constexpr (BPP == 4) *(uint32_t*)p = o.x;
+  else if constexpr (BPP == 2) *(uint16_t*)p = (uint16_t)o.x;
+  else *p = (uint8_t)o.x;
+}
 struct BilinearTaps { uint32_t t00, t10, t01, t11; float fx, fy; };
 // the four raw texels + weights of texture(tex, uv) for any 4-byte format
 VKR_DEV BilinearTaps bilinear_taps_u32(const Tex& t, f2 uv) {
   BilinearTaps b;
-  float x = cfma(uv.x, (float)t.fw, -0.5f), y = cfma(uv.y, (float)t.fh, -0.5f);
-  float x0f = floorf(x), y0f = floorf(y);
-  b.fx = x - x0f; b.fy = y - y0f;
-  int x0 = f2i(x0f), y0 = f2i(y0f);
-  b.t00 = load_u32_clamped(t, x0, y0); b.t10 = load_u32_clamped(t, x0 + 1, y0);
-  b.t01 = load_u32_clamped(t, x0, y0 + 1); b.t11 = load_u32_clamped(t, x0 + 1, y0 + 1);
+  const Footprint f = bilinear_footprint(t, uv);
+  b.fx = f.fx; b.fy = f.fy;
+  b.t00 = load_u32_clamped(t, f.x0, f.y0); b.t10 = load_u32_clamped(t, f.x0 + 1, f.y0);
+  b.t01 = load_u32_clamped(t, f.x0, f.y0 + 1); b.t11 = load_u32_clamped(t, f.x0 + 1, f.y0 + 1);
   return b;
 }
 // The value sample<F>(tex, uv) returns, from taps issued earlier: lets a kernel put the loads of several
@@ -402,31 +450,40 @@ VKR_DEV BilinearTaps bilinear_taps_u32(const Tex& t, f2 uv) {
 template <class F> VKR_DEV typename F::T taps_resolve(const BilinearTaps& b) {
   return F::lerp(F::lerp(F::decode(b.t00), F::decode(b.t10), b.fx), F::lerp(F::decode(b.t01), F::decode(b.t11), b.fx), b.fy);
 }
-// The bilinear footprint of texture(t, uv [, offset]) on a 4-byte format, each ROW fetched as one 8-byte load of the texel
-// pair (xs, xs + 1), xs = clamp(x0, 0, w - 2): the texture-address unit spends the same time on a wave's load whatever
-// its width, so two loads instead of four.  left_is_y / right_is_x say which half of the pair the left / right tap is;
-// they differ from (x, y) only in the first and last column, where clamp-to-edge makes both taps the same texel.
-// Needs w >= 2.  Images with one window geometry and pitch share the record.
+// A bilinear footprint on a format of BPP <= 8 bytes, each ROW fetched as one load of the texel pair (xs, xs + 1),
+// xs = clamp(x0, 0, w - 2): the texture-address unit spends the same time on a wave's load whatever its width, so two
+// loads instead of four.  left_is_y / right_is_x say which half of the pair the left / right tap is; they differ from
+// (x, y) only in the first and last column, where clamp-to-edge makes both taps the same texel.  Needs w >= 2.  Images
+// with one window geometry, pitch and texel size share the record.  (x0, y0) of pair_rows are window coordinates.
 struct PairFootprint { uint32_t row0, row1; bool left_is_y, right_is_x; float fx, fy; };
-VKR_DEV PairFootprint pair_footprint(const Tex& t, f2 uv, int offx = 0, int offy = 0) {
+template <int BPP> VKR_DEV PairFootprint pair_rows(const Tex& t, const Footprint& w) {
   PairFootprint f;
-  const float x = cfma(uv.x, (float)t.fw, -0.5f), y = cfma(uv.y, (float)t.fh, -0.5f);
-  const float x0f = floorf(x), y0f = floorf(y);
-  f.fx = x - x0f; f.fy = y - y0f;
-  const int x0 = f2i(x0f) + offx - t.ox, y0 = f2i(y0f) + offy - t.oy;
-  const int xs = iclamp(x0, 0, t.w - 2);
-  f.left_is_y = x0 > xs;    // x0 >= w - 1: both taps are the pair's second texel
-  f.right_is_x = x0 < xs;   // x0 <= -1: both taps are the pair's first texel
-  const uint32_t xb = (uint32_t)xs * 4u;
-  f.row0 = __umul24((uint32_t)iclamp(y0, 0, t.h - 1), (uint32_t)t.pitch) + xb;
-  f.row1 = __umul24((uint32_t)iclamp(y0 + 1, 0, t.h - 1), (uint32_t)t.pitch) + xb;
+  f.fx = w.fx; f.fy = w.fy;
+  const int xs = iclamp(w.x0, 0, t.w - 2);
+  f.left_is_y = w.x0 > xs;    // x0 >= w - 1: both taps are the pair's second texel
+  f.right_is_x = w.x0 < xs;   // x0 <= -1: both taps are the pair's first texel
+  const uint32_t xb = (uint32_t)xs * (uint32_t)BPP;
+  f.row0 = __umul24((uint32_t)iclamp(w.y0, 0, t.h - 1), (uint32_t)t.pitch) + xb;
+  f.row1 = __umul24((uint32_t)iclamp(w.y0 + 1, 0, t.h - 1), (uint32_t)t.pitch) + xb;
   return f;
 }
+// ... of texture(t, uv [, offset]) on a 4-byte format
+VKR_DEV PairFootprint pair_footprint(const Tex& t, f2 uv, int offx = 0, int offy = 0) {
+  return pair_rows<4>(t, bilinear_footprint<true>(t, uv, offx, offy));
+}
+// the four stored texels t00, t10, t01, t11 of a pair footprint
+template <int BPP> VKR_DEV void pair_taps_raw(const Tex& t, const PairFootprint& f, Raw (&r)[4]) {
+  Raw a0, a1, b0, b1;
+  load_raw_pair<BPP>(t.p + f.row0, a0, a1);
+  load_raw_pair<BPP>(t.p + f.row1, b0, b1);
+  r[0] = f.left_is_y ? a1 : a0; r[1] = f.right_is_x ? a0 : a1;
+  r[2] = f.left_is_y ? b1 : b0; r[3] = f.right_is_x ? b0 : b1;
+}
 VKR_DEV BilinearTaps pair_taps(const Tex& t, const PairFootprint& f) {
+  Raw r[4];
+  pair_taps_raw<4>(t, f, r);
   BilinearTaps b;
-  const U32x2 r0 = load_u32x2(t.p + f.row0), r1 = load_u32x2(t.p + f.row1);
-  b.t00 = f.left_is_y ? r0.y : r0.x; b.t10 = f.right_is_x ? r0.x : r0.y;
-  b.t01 = f.left_is_y ? r1.y : r1.x; b.t11 = f.right_is_x ? r1.x : r1.y;
+  b.t00 = r[0].x; b.t10 = r[1].x; b.t01 = r[2].x; b.t11 = r[3].x;
   b.fx = f.fx; b.fy = f.fy;
   return b;
 }
@@ -437,18 +494,13 @@ VKR_DEV float taps_srgb_channel(const BilinearTaps& b, int channel, const float*
   const float a01 = lut[(b.t01 >> sh) & 0xFFu], a11 = lut[(b.t11 >> sh) & 0xFFu];
   return mixf(mixf(a00, a10, b.fx), mixf(a01, a11, b.fx), b.fy);
 }
-VKR_DEV float sample_srgb_channel(const Tex& t, f2 uv, int channel, const float* lut) {
-  const BilinearTaps b = bilinear_taps_u32(t, uv);
-  const int sh = channel * 8;
-  const float a00 = lut[(b.t00 >> sh) & 0xFFu], a10 = lut[(b.t10 >> sh) & 0xFFu];
-  const float a01 = lut[(b.t01 >> sh) & 0xFFu], a11 = lut[(b.t11 >> sh) & 0xFFu];
-  return mixf(mixf(a00, a10, b.fx), mixf(a01, a11, b.fx), b.fy);
-}
+VKR_DEV float sample_srgb_channel(const Tex& t, f2 uv, int channel, const float* lut) { return taps_srgb_channel(bilinear_taps_u32(t, uv), channel, lut); }
+// rgb of texture() on an RGBA8_SRGB image
 VKR_DEV f3 srgb_rgb(uint32_t v, const float* lut) { return mk3(lut[v & 0xFFu], lut[(v >> 8) & 0xFFu], lut[(v >> 16) & 0xFFu]); }
-VKR_DEV f3 sample_srgb_rgb(const Tex& t, f2 uv, const float* lut) {
-  const BilinearTaps b = bilinear_taps_u32(t, uv);
+VKR_DEV f3 taps_srgb_rgb(const BilinearTaps& b, const float* lut) {
   return mix3(mix3(srgb_rgb(b.t00, lut), srgb_rgb(b.t10, lut), b.fx), mix3(srgb_rgb(b.t01, lut), srgb_rgb(b.t11, lut), b.fx), b.fy);
 }
+VKR_DEV f3 sample_srgb_rgb(const Tex& t, f2 uv, const float* lut) { return taps_srgb_rgb(bilinear_taps_u32(t, uv), lut); }
 
 template <class T> VKR_DEV T* texel_ptr(const Tex& t, int lx, int ly) { return (T*)(const_cast<uint8_t*>(t.p) + toff(t, lx, ly, (int)sizeof(T))); }
 

@@ -68,6 +68,16 @@ inline bool same_window(const Tex& a, const Tex& b) {
 // same window AND row pitch: texel (x, y) has the same byte offset in both (4-byte formats share bilinear footprints)
 inline bool same_layout(const Tex& a, const Tex& b) { return same_window(a, b) && a.pitch == b.pitch; }
 
+// The window is the whole frame (the one statement of the test), and no side exceeds max_side texels.
+inline bool whole_frame(int ox, int oy, int64_t w, int64_t h, int64_t fw, int64_t fh) { return ox == 0 && oy == 0 && w == fw && h == fh; }
+inline bool whole_frame(const Tex& t, int max_side = INT32_MAX) { return whole_frame(t.ox, t.oy, t.w, t.h, t.fw, t.fh) && t.w <= max_side && t.h <= max_side; }
+// The gate of a binding that cannot be a tile of the frame: "<what>: <why>" for a window, then the bound on the sides.
+inline int require_whole_frame(const Tex& t, const char* what, const char* why, int max_side = INT32_MAX) {
+  if (!whole_frame(t)) { set_error("%s: %s", what, why); return VKR_ERR_EXTENT; }
+  if (!whole_frame(t, max_side)) { set_error("%s is %dx%d, at most %d texels a side", what, t.w, t.h, max_side); return VKR_ERR_EXTENT; }
+  return VKR_OK;
+}
+
 // A whole-frame D24 depth pyramid as the Hi-Z marches bind it: 1 .. VKR_MAX_MIPS levels, every one the whole frame (rays have
 // unbounded reach) and at most 65535 texels wide and high (the LDS level table keeps w | h << 16); padded to 16 entries.
 inline int bind_depth_pyramid(const vkr_img* d, const char* program, const char* binding, Pyramid* out) {
@@ -80,7 +90,7 @@ inline int bind_depth_pyramid(const vkr_img* d, const char* program, const char*
     Tex& m = out->mip[i];
     int rc = make_tex(d, i, VKR_FMT_D24_UNORM_S8, what, &m);
     if (rc != VKR_OK) return rc;
-    if (m.ox != 0 || m.oy != 0 || m.w != m.fw || m.h != m.fh || m.w > 65535 || m.h > 65535) {
+    if (!whole_frame(m, 65535)) {
       set_error("%s: level %d (%dx%d at (%d,%d) of %dx%d) must cover the whole frame, at most 65535 texels a side", what, i, m.w, m.h, m.ox, m.oy, m.fw, m.fh);
       return VKR_ERR_EXTENT;
     }
