@@ -609,6 +609,40 @@ typedef struct vkr_gtao_rt_push { float rotation; } vkr_gtao_rt_push;  /* rt_mai
  * 2 PI (rotation + k / 16) are evaluated on the host.  One wave per pixel, one lane per direction.                        */
 int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel,
                      const float* directions, const vkr_img* out_raw, const vkr_gtao_rt_push* push, void* stream);
+/* vkr_accel_query for long rays: the arguments, the gates and the answers of vkr_accel_query, bit for bit.  The walk culls
+ * a node per ray (the segment-box term of vkr_accel_query AND a slab test against the node box widened by a per-ray margin,
+ * rounded outward; DESIGN_NUMERICS.md, "Ray query, the per-ray cull"), which is what keeps a wave of metres-long rays from
+ * descending nearly everywhere.                                                                                               */
+int vkr_accel_occluded(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                       uint32_t* out_hit, void* stream);
+
+/* program "shadow_mask_rt" (no reference program): the shadow mask of vkr_shadow_mask traced through the scene's ray-query
+ * structure instead of looked up in a shadow map: exact hard shadows of up to four point or directional lights, no map, no
+ * frustum, no depth bias.  One RGBA8_UNORM texel per pixel, channel l = light l, 0 or 255.                                   */
+typedef struct vkr_shadow_rt_params {   /* 160 bytes */
+  vkr_mat4 inverse_camera;              /* view -> world */
+  float    fovy, aspect, znear, zfar;
+  float    lights[4][4];                /* xyz, w: w == 1 a point light at xyz; w == 0 directional: xyz is the vector from the
+                                           surface towards the light, its length is the reach of the ray */
+  uint32_t light_count;                 /* 1..4 */
+  float    normal_offset;               /* origin = world + normal_offset * normal */
+  float    tmin;                        /* the segment is origin + t * dvec, t in [tmin, 1] */
+  uint32_t reserved;                    /* 0 */
+} vkr_shadow_rt_params;
+/* depth: D24_UNORM_S8 (mip 0 of the view); normal: RG16_UNORM at full resolution; out_mask: RGBA8_UNORM; one extent.  Per pixel
+ * g (DESIGN_NUMERICS.md, Shadow mask, ray traced): d = the exact decode of depth texel g (by index, unfiltered); d >= 1 stores
+ * 255 in every channel.  uv = (g + 0.5) / extent; view = reconstruct_view_vec(uv, d, ...); world = (inverse_camera * (view, 1)).xyz
+ * in the order of every mat4 * vec4 here; n = decode_normal(the exact decode of normal texel g, by index);
+ * origin = world + normal_offset * n (one multiply-add per component under contract 2).  Per light l < light_count:
+ * dvec = lights[l].xyz - origin for a point light (three subtractions), lights[l].xyz for a directional one; facing = dot(n, dvec);
+ * unless facing > 0 the channel is 0 and no ray is cast (a surface facing away, a light at the surface point, any NaN); otherwise
+ * the channel is 0 when the frozen any-hit of (origin, dvec, tmin, 1) reports a hit (vkr_accel_query's answer for that ray) and
+ * 255 when not.  Channels at or beyond light_count are 255.  Every texel of out_mask is written, nothing outside its rows.
+ * An empty structure is legal: every ray misses.  Refused before any launch: a NULL argument, a descriptor without memory, other
+ * formats, different extents, an extent above 65535, a windowed descriptor anywhere (the rays reach anywhere: a single-GPU
+ * pass), light_count outside 1..4, a light whose w is neither 0 nor 1, reserved != 0, tmin NaN.                               */
+int vkr_shadow_mask_rt(const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel, const vkr_shadow_rt_params* params,
+                       const vkr_img* out_mask, void* stream);
 
 /* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,

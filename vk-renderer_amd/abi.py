@@ -255,6 +255,17 @@ class ShadowMaskParams(C.Structure):  # vkr_shadow_mask_params, 352 bytes
                 ("zfar", C.c_float), ("layer_count", C.c_uint32), ("radius", C.c_uint32), ("bias", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# ---- program shadow_mask_rt ----
+# the defaults of the ray's offsets: the host frame's (host/frame.cpp), measured on a plane-only scene
+SHADOW_RT_NORMAL_OFFSET, SHADOW_RT_TMIN = 1e-3, 0.0
+
+
+class ShadowRtParams(C.Structure):  # vkr_shadow_rt_params, 160 bytes
+    _fields_ = [("inverse_camera", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float),
+                ("lights", (C.c_float * 4) * 4), ("light_count", C.c_uint32), ("normal_offset", C.c_float), ("tmin", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
 
 
@@ -380,7 +391,10 @@ def product():
         lib.vkr_accel_info.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]
         lib.vkr_accel_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.vkr_gtao_rt_main.argtypes = [P(GtaoRtParams), _IMG, _IMG, C.c_void_p, C.c_void_p, _IMG, P(GtaoRtPush), C.c_void_p]
-        for name in ("accel_layout", "accel_create", "accel_destroy", "accel_info", "accel_query", "gtao_rt_main"):
+        lib.vkr_accel_occluded.argtypes = lib.vkr_accel_query.argtypes
+        # the ray-traced shadow mask (checked against the numpy restatement tests/shadow_mask_rt_reference.py)
+        lib.vkr_shadow_mask_rt.argtypes = [_IMG, _IMG, C.c_void_p, P(ShadowRtParams), _IMG, C.c_void_p]
+        for name in ("accel_layout", "accel_create", "accel_destroy", "accel_info", "accel_query", "gtao_rt_main", "accel_occluded", "shadow_mask_rt"):
             getattr(lib, "vkr_" + name).restype = C.c_int
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
@@ -563,6 +577,41 @@ def shadow_mask(depth, layers, params, out_mask, stream=None):
     check(lib.vkr_shadow_mask(C.byref(depth), descs, C.byref(params), C.byref(out_mask), stream), lib)
 
 
+def shadow_rt_params(inverse_camera, lights, fovy, aspect, znear, zfar, normal_offset=SHADOW_RT_NORMAL_OFFSET, tmin=SHADOW_RT_TMIN):
+    """ShadowRtParams from the camera's view -> world matrix (4x4, maths convention), 1..4 lights of (x, y, z, w) — w == 1 a point
+    light at xyz, w == 0 a directional light whose xyz is the vector from the surface towards the light — the camera's four floats
+    and the two offsets of the ray.  light_count = len(lights); everything is passed on as given (the entry refuses what it does
+    not take)."""
+    p = ShadowRtParams()
+    p.inverse_camera = Mat4.from_np(inverse_camera)
+    if len(lights) > 4:
+        raise RuntimeError(f"shadow_rt_params: {len(lights)} lights, at most 4")
+    for l, v in enumerate(lights):
+        for k in range(4):
+            p.lights[l][k] = float(v[k])
+    p.fovy, p.aspect, p.znear, p.zfar = float(fovy), float(aspect), float(znear), float(zfar)
+    p.light_count, p.normal_offset, p.tmin, p.reserved = len(lights), float(normal_offset), float(tmin), 0
+    return p
+
+
+def shadow_mask_rt(depth, normal, accel, params, out_mask, stream=None):
+    """vkr_shadow_mask_rt: out_mask (RGBA8_UNORM VkrImg) := per pixel of `depth` (D24_UNORM_S8 VkrImg, mip 0 of the view) and
+    `normal` (RG16_UNORM VkrImg), all of one extent, channel l = 255 where the ray from the surface towards light l meets no
+    triangle of `accel` (an Accel, or None to show the refusal) and 0 where it does or where the surface faces away, under
+    `params` (ShadowRtParams, e.g. shadow_rt_params(...)).  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_shadow_mask_rt(C.byref(depth) if depth is not None else None, C.byref(normal) if normal is not None else None, handle,
+                                 C.byref(params) if params is not None else None, C.byref(out_mask) if out_mask is not None else None,
+                                 stream), lib)
+
+
+def accel_occluded(accel, origins, dirs, tmin, tmax, out, stream=None):
+    """vkr_accel_occluded: Accel.query on the walk for long rays — the same arguments (device tensors (n, 3) float32, out (n,)
+    int32 / uint32) and the same answers."""
+    accel.occluded(origins, dirs, tmin, tmax, out, stream)
+
+
 def defered_shading_shadowed(albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, out, push, stream=None):
     """vkr_defered_shading_shadowed: vkr_defered_shading (same VkrImg bindings, ShadingParams and ShadingPush) with channel .x of
     `shadow_mask` (RGBA8_UNORM VkrImg at out's extent) on the direct term.  Raises RuntimeError with the library's message on a
@@ -707,6 +756,11 @@ class Accel:
         """origins, dirs: device tensors (n, 3) float32; out: device tensor (n,) int32 / uint32"""
         n = int(origins.shape[0])
         check(self.lib.vkr_accel_query(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
+
+    def occluded(self, origins, dirs, tmin, tmax, out, stream=None):
+        """vkr_accel_occluded: query() on the walk with the per-ray cull (long rays); the same answers"""
+        n = int(origins.shape[0])
+        check(self.lib.vkr_accel_occluded(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
 
     def close(self):
         if self.handle:

@@ -476,6 +476,19 @@ class PostFxChain:
         p = abi.shadow_mask_params(self.setup.inv_view, mvps, *self.setup.fazz, radius=radius, bias=bias)
         abi.shadow_mask(self.depth.desc(0, 1), layers, p, self.shadow_mask_out.desc(), self.stream)
 
+    def shadow_mask_rt(self, accel, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN):
+        """vkr_shadow_mask_rt on this chain's depth and normal -> shadow_mask_out (RGBA8_UNORM, channel l = light l): one any-hit
+        ray per pixel and light through `accel` (abi.Accel); `lights` 1..4 of (x, y, z, w), w == 1 point, w == 0 directional.
+        Product backend only: the expectation is the numpy restatement tests/shadow_mask_rt_reference.py, not a checker library."""
+        if self.backend != "product":
+            raise RuntimeError("PostFxChain.shadow_mask_rt: only the product backend has the program shadow_mask_rt")
+        if self.tiled:
+            raise RuntimeError("PostFxChain.shadow_mask_rt: not on a window of the frame (the rays reach anywhere: a single-GPU pass)")
+        if not hasattr(self, "shadow_mask_out"):
+            self.shadow_mask_out = ImageBuf(abi.FMT_RGBA8_UNORM, self.depth.width, self.depth.height, device=self.device)
+        p = abi.shadow_rt_params(self.setup.inv_view, lights, *self.setup.fazz, normal_offset=normal_offset, tmin=tmin)
+        abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
+
     # ---- tile-classified trace (advanced_ssr.cpp:216-302,440-495; commented out of AdvancedSSR::run) ----
     def _i32_buffer(self, n):
         if self.device is None:

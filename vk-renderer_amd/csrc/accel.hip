@@ -1,5 +1,7 @@
 // accel.hip — the scene's acceleration structure and the ray query: vkr_accel_layout / _create / _destroy / _info (host),
-// vkr_accel_query (any-hit of arbitrary rays) and program "gtao_rt_main" (gtao.cpp:150-196 + gtao/rt_main.frag).
+// vkr_accel_query and vkr_accel_occluded (any-hit of arbitrary rays, on the walk for short and for long rays) and program
+// "gtao_rt_main" (gtao.cpp:150-196 + gtao/rt_main.frag).  The device side of the query — AccelView, the frozen triangle test and
+// the two walks — is accel_traverse.hpp, shared with shadow_mask_rt.hip.
 //
 // MI355X has no ray-tracing hardware, so the traversal is software.  The hierarchy is one level over world-space triangles
 // (an any-hit query of a static scene gains nothing from instancing); it is built once per scene on the host (binned SAH,
@@ -17,88 +19,16 @@
 // between them).  A node box that contains a hit point therefore always overlaps the segment box: no cull can discard a
 // triangle the test would hit, and the result is that of a brute-force loop over all triangles (tests/test_accel_gpu.py).
 #include "vkr_host.hpp"
+#include "accel_traverse.hpp"
 #include "gtao_slice.hpp"
 
 #include <algorithm>
 #include <vector>
 
-struct vkr_accel {
-  vkr_accel_node* nodes;  // device
-  vkr_accel_tri* tris;    // device
-  uint32_t node_count, tri_count;
-};
-
 namespace vkr {
 
-// the traversal stack holds one entry per level below the root; the build makes a leaf at this depth whatever it holds
-constexpr int ACCEL_MAX_DEPTH = 48;
-constexpr int ACCEL_STACK = 64;
 constexpr int ACCEL_BINS = 16;
 constexpr uint32_t ACCEL_MAX_LEAF = 8;
-
-struct AccelView {
-  const vkr_accel_node* nodes;
-  const vkr_accel_tri* tris;
-  uint32_t node_count;
-};
-
-// ---- the frozen fp32 triangle test (DESIGN_NUMERICS.md) ----------------------------------------------------------------
-// Moller-Trumbore in this operation order, every product and sum rounded on its own (no fused multiply-add under either
-// numeric contract); det == 0 is a miss, the edges are inclusive, tmin <= t <= tmax, and the point o + t * d (mul, then add)
-// must lie in the triangle's widened box.  NaN anywhere makes a comparison false: a miss.
-VKR_DEV bool ray_hits_triangle(f3 o, f3 d, float tmin, float tmax, const vkr_accel_tri& tr) {
-  const float e1x = tr.e1[0], e1y = tr.e1[1], e1z = tr.e1[2];
-  const float e2x = tr.e2[0], e2y = tr.e2[1], e2z = tr.e2[2];
-  const float px = d.y * e2z - d.z * e2y, py = d.z * e2x - d.x * e2z, pz = d.x * e2y - d.y * e2x;
-  const float det = (e1x * px + e1y * py) + e1z * pz;
-  if (det == 0.0f) return false;
-  const float inv = 1.0f / det;
-  const float tx = o.x - tr.v0[0], ty = o.y - tr.v0[1], tz = o.z - tr.v0[2];
-  const float u = ((tx * px + ty * py) + tz * pz) * inv;
-  const float qx = ty * e1z - tz * e1y, qy = tz * e1x - tx * e1z, qz = tx * e1y - ty * e1x;
-  const float v = ((d.x * qx + d.y * qy) + d.z * qz) * inv;
-  const float t = ((e2x * qx + e2y * qy) + e2z * qz) * inv;
-  if (!(u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= tmin && t <= tmax)) return false;
-  const float hx = o.x + t * d.x, hy = o.y + t * d.y, hz = o.z + t * d.z;
-  return hx >= tr.lo[0] && hx <= tr.hi[0] && hy >= tr.lo[1] && hy <= tr.hi[1] && hz >= tr.lo[2] && hz <= tr.hi[2];
-}
-
-// Any-hit of this lane's segment o + t * d, t in [tmin, tmax].  Every lane of the wave calls it (the walk is wave-uniform);
-// `live` false: the lane has no ray and only follows.  `stack`: ACCEL_STACK words of LDS owned by this wave.
-VKR_DEV bool wave_any_hit(const AccelView& a, f3 o, f3 d, float tmin, float tmax, bool live, uint32_t* stack) {
-  const float ax = o.x + tmin * d.x, ay = o.y + tmin * d.y, az = o.z + tmin * d.z;
-  const float bx = o.x + tmax * d.x, by = o.y + tmax * d.y, bz = o.z + tmax * d.z;
-  const float lox = fminf(ax, bx), loy = fminf(ay, by), loz = fminf(az, bz);
-  const float hix = fmaxf(ax, bx), hiy = fmaxf(ay, by), hiz = fmaxf(az, bz);
-  bool pending = live, hit = false;
-  if (a.node_count == 0) return false;
-  uint32_t node = 0;
-  int sp = 0;
-  for (;;) {
-    const vkr_accel_node nd = a.nodes[node];
-    const bool overlap = pending && lox <= nd.hi[0] && hix >= nd.lo[0] && loy <= nd.hi[1] && hiy >= nd.lo[1] &&
-                         loz <= nd.hi[2] && hiz >= nd.lo[2];
-    if (__ballot(overlap) != 0ull) {
-      if (nd.count == 0u) {  // interior: the second child waits, the first is next
-        stack[sp] = nd.first + 1u;
-        sp++;
-        node = nd.first;
-        continue;
-      }
-      bool test = overlap;
-      for (uint32_t k = 0; k < nd.count; k++) {
-        const vkr_accel_tri tr = a.tris[nd.first + k];
-        if (test && ray_hits_triangle(o, d, tmin, tmax, tr)) { hit = true; pending = false; test = false; }
-        if (__ballot(test) == 0ull) break;
-      }
-      if (__ballot(pending) == 0ull) break;
-    }
-    if (sp == 0) break;
-    sp--;
-    node = __builtin_amdgcn_readfirstlane(stack[sp]);
-  }
-  return hit;
-}
 
 __global__ __launch_bounds__(256) void k_accel_query(AccelView a, const float* org, const float* dir, float tmin, float tmax,
                                                      uint32_t n, uint32_t* out) {
@@ -111,6 +41,21 @@ __global__ __launch_bounds__(256) void k_accel_query(AccelView a, const float* o
     d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
   }
   const bool hit = wave_any_hit(a, o, d, tmin, tmax, live, stacks[threadIdx.x >> 6]);
+  if (live) out[i] = hit ? 1u : 0u;
+}
+
+// vkr_accel_occluded: k_accel_query on the walk for long rays (accel_traverse.hpp), the ray-level entry of the per-ray cull
+__global__ __launch_bounds__(256) void k_accel_occluded(AccelView a, const float* org, const float* dir, float tmin, float tmax,
+                                                        uint32_t n, uint32_t* out) {
+  __shared__ uint32_t stacks[4][ACCEL_STACK];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool live = i < n;
+  f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);
+  if (live) {
+    o = mk3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
+    d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+  }
+  const bool hit = wave_any_hit_ray(a, o, d, tmin, tmax, live, stacks[threadIdx.x >> 6]);
   if (live) out[i] = hit ? 1u : 0u;
 }
 
@@ -364,6 +309,17 @@ extern "C" int vkr_accel_query(const vkr_accel* accel, const float* origins, con
   const AccelView a{accel->nodes, accel->tris, accel->node_count};
   hipLaunchKernelGGL(k_accel_query, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, origins, dirs, tmin, tmax, n, out_hit);
   return launch_status("accel_query");
+}
+
+extern "C" int vkr_accel_occluded(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                                  uint32_t* out_hit, void* stream) {
+  if (!accel) { set_error("accel_occluded: NULL acceleration structure"); return VKR_ERR_NULL; }
+  if (n == 0) return VKR_OK;
+  if (!origins || !dirs || !out_hit) { set_error("accel_occluded: NULL rays or output"); return VKR_ERR_NULL; }
+  if (n > (1u << 30)) { set_error("accel_occluded: %u rays, at most 2^30 per call", n); return VKR_ERR_EXTENT; }
+  const AccelView a{accel->nodes, accel->tris, accel->node_count};
+  hipLaunchKernelGGL(k_accel_occluded, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, origins, dirs, tmin, tmax, n, out_hit);
+  return launch_status("accel_occluded");
 }
 
 extern "C" int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel,

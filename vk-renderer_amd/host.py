@@ -23,6 +23,7 @@ TEXTURE_GEN_MIPS = 1  # vkrh_scene_texture.flags: only level 0 comes from the ho
 STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); after the G-buffer / raster / shadow stages, before the downsample; not tiled
 STAGE_TILE_REGRESSION = 1 << 26  # AdvancedSSR::run_tile_regression_pass: depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W/16, H/16)); after the downsample; not tiled
 STAGE_BACKBUFFER = 1 << 27  # add_backbuffer_subpass + add_present_subpass: the TAA output (or set_backbuffer's image) -> image "backbuffer" (RGBA8_SRGB); last; not tiled
+STAGE_SHADOW_MASK_RT = 1 << 29  # ShadowMaskPass::run_rt: depth mip 0 + normal + the loaded scene's acceleration structure -> image "shadow_mask" (the image and slot of STAGE_SHADOW_MASK), one ray per pixel and light of set_shadow_rays; needs load_scene(); not with STAGE_SHADOW_MASK, not tiled
 STAGE_SHADOW_MASK = 1 << 28  # ShadowMaskPass::run: depth mip 0 + the layers of "shadows" -> image "shadow_mask" (RGBA8_UNORM, channel l = light l); after the raster / shadow stages, before the shading; needs the maps of STAGE_SHADOW; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
@@ -151,7 +152,9 @@ def lib():
                            ("vkrh_set_backbuffer", [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
                            ("vkrh_selftest_texdraw", [C.c_char_p, C.c_uint32]),
                            # the shadow mask (same rule)
-                           ("vkrh_set_shadow_mask", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32])):
+                           ("vkrh_set_shadow_mask", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+                           # the ray-traced shadow mask (same rule)
+                           ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -367,6 +370,15 @@ class HostFrame:
         apply != 0: a STAGE_SHADING of a run that also has STAGE_SHADOW_MASK multiplies its direct term by light 0's channel
         (program defered_shading_shadowed); 0 (the default): the shading is what it is without the mask."""
         self._check(lib().vkrh_set_shadow_mask(self.h, int(bias), int(radius), 1 if apply else 0))
+
+    def set_shadow_rays(self, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN):
+        """vkrh_set_shadow_rays: the rays of STAGE_SHADOW_MASK_RT: 1..4 lights of (x, y, z, w), w == 1 a point light at xyz, w == 0
+        a directional light whose xyz is the vector from the surface towards the light (its length is the ray's reach); the origin
+        is the surface point moved by normal_offset along the normal, the segment is t in [tmin, 1]."""
+        flat = (C.c_float * max(4, 4 * len(lights)))()
+        for i, v in enumerate(lights):
+            flat[4 * i: 4 * i + 4] = [float(x) for x in v]
+        self._check(lib().vkrh_set_shadow_rays(self.h, flat, len(lights), float(normal_offset), float(tmin)))
 
     def set_ssao_samples(self, samples, std140=0):
         """vkrh_set_ssao_samples: pins the 16 samples ([16, 3]) of STAGE_SSAO and their packing in the uniform block: std140 = 0

@@ -148,6 +148,22 @@ struct PostFxFrame {
     shadow_mask_bias = bias; shadow_mask_radius = radius; shadow_mask_apply = apply != 0;
   }
 
+  // VKRH_STAGE_SHADOW_MASK_RT: the lights and offsets of the rays (vkrh_set_shadow_rays).  Default: one point light at the shading
+  // pass's LIGHT_POS; normal_offset and tmin as measured on the plane-only scene.
+  std::vector<float> shadow_rays{-1.85867f, 5.81832f, -0.247114f, 1.0f};
+  float shadow_rays_offset = 1e-3f, shadow_rays_tmin = 0.0f;
+  void set_shadow_rays(const float* lights, uint32_t count, float normal_offset, float tmin) {
+    if (!lights) throw std::runtime_error{"vkrh_set_shadow_rays: NULL argument"};
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_rays: on a tiled frame (VKRH_STAGE_SHADOW_MASK_RT runs on one GPU)"};
+    if (count < 1 || count > 4) throw std::runtime_error{"vkrh_set_shadow_rays: count " + std::to_string(count) + ", needs 1..4 (the channels of the mask)"};
+    for (uint32_t l = 0; l < count; l++)
+      if (!(lights[4 * l + 3] == 0.0f || lights[4 * l + 3] == 1.0f))
+        throw std::runtime_error{"vkrh_set_shadow_rays: light " + std::to_string(l) + ": w must be 1 (a point light) or 0 (a directional light)"};
+    if (std::isnan(tmin)) throw std::runtime_error{"vkrh_set_shadow_rays: tmin is NaN"};
+    shadow_rays.assign(lights, lights + 4 * count);
+    shadow_rays_offset = normal_offset; shadow_rays_tmin = tmin;
+  }
+
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
   bool has_tile_planes = false;
 
@@ -277,6 +293,13 @@ struct PostFxFrame {
     if ((mask & VKRH_STAGE_BACKBUFFER) && cfg.tiled)  // refused before anything is recorded
       throw std::runtime_error{"vkrh_run: VKRH_STAGE_BACKBUFFER on a tiled frame (the uv of a pixel spans the whole source: the backbuffer is drawn on one GPU)"};
     if (mask & VKRH_STAGE_BACKBUFFER) (void)backbuffer_source_id();  // a source that does not exist (yet) is refused before anything is recorded
+    if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT on a tiled frame (the rays reach anywhere: ray-traced shadows run on one GPU)"};
+      if (mask & VKRH_STAGE_SHADOW_MASK)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT together with VKRH_STAGE_SHADOW_MASK (both write the image shadow_mask)"};
+      if (!scene_as || !scene_as->tlas)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
+    }
     if (mask & VKRH_STAGE_SHADOW_MASK) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!(mask & VKRH_STAGE_SHADOW) && !shadow_maps_current)
@@ -322,6 +345,11 @@ struct PostFxFrame {
       ShadowMaskPass& pass = ensure_shadow_mask();
       pass.update_params(view, shadow_lights.data(), (uint32_t)shadow_lights.size(), fazz.x, fazz.y, fazz.z, fazz.w, shadow_mask_radius, shadow_mask_bias);
       pass.run(graph, gbuffer.depth, shadows, (uint32_t)shadow_lights.size(), shadow_mask_tex);
+    }
+    if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // reads depth mip 0 and the normal of this run's G-buffer; the slot of the looked-up mask
+      ShadowMaskPass& pass = ensure_shadow_mask();
+      pass.update_rt_params(view, shadow_rays.data(), (uint32_t)(shadow_rays.size() / 4), fazz.x, fazz.y, fazz.z, fazz.w, shadow_rays_offset, shadow_rays_tmin);
+      pass.run_rt(graph, gbuffer.depth, gbuffer.normal, scene_as->tlas, shadow_mask_tex);
     }
     if (mask & VKRH_STAGE_SSAO) {  // reads depth mip 0 only: before the downsample writes the other mips
       SSAOPass& pass = ensure_ssao();
@@ -400,7 +428,7 @@ struct PostFxFrame {
       // main.cpp:339,390: once VKRH_STAGE_SHADOW has filled it, layer 0 of `shadows` and its matrix; until then the dummy
       const bool lit = has_shadows && shadows_rendered;
       shading_pass.update_params(view, lit ? shadow_lights[0] : glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
-      if (shadow_mask_apply && (mask & VKRH_STAGE_SHADOW_MASK))  // vkrh_set_shadow_mask(apply) and the mask of this run
+      if (shadow_mask_apply && (mask & (VKRH_STAGE_SHADOW_MASK | VKRH_STAGE_SHADOW_MASK_RT)))  // vkrh_set_shadow_mask(apply) and the mask of this run
         shading_pass.draw_shadowed(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(),
                                    shadow_mask_tex, color_out_tex);
       else
@@ -537,7 +565,7 @@ struct PostFxFrame {
       case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
       case 39: if (!has_tile_planes) throw std::runtime_error{"vkrh_image: 'tile_planes' only exists after VKRH_STAGE_TILE_REGRESSION"}; return ssr.get_tile_planes();
       case 40: if (!backbuffer_drawn) throw std::runtime_error{"vkrh_image: 'backbuffer' only exists after VKRH_STAGE_BACKBUFFER"}; return graph.get_backbuffer();
-      case 41: if (!shadow_mask_pass) throw std::runtime_error{"vkrh_image: 'shadow_mask' only exists after VKRH_STAGE_SHADOW_MASK"}; return shadow_mask_tex;
+      case 41: if (!shadow_mask_pass) throw std::runtime_error{"vkrh_image: 'shadow_mask' only exists after VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT"}; return shadow_mask_tex;
       case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
       default: return screen_trace.accumulated;
     }
@@ -1347,6 +1375,10 @@ int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) {
 int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
   return guarded([&] { frame_ref(frame).set_backbuffer(source_image, flags, width, height); });
 }
+int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float normal_offset, float tmin) {
+  return guarded([&] { frame_ref(frame).set_shadow_rays(lights, count, normal_offset, tmin); });
+}
+
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {
     auto* f = &frame_ref(frame);

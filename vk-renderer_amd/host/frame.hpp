@@ -95,6 +95,14 @@ enum {
    * run or an earlier one since the lights were last set.  Not part of VKRH_STAGE_CHAIN.  One GPU only (not on a tiled frame:
    * the shadow maps are rendered on one GPU).                                                                               */
   VKRH_STAGE_SHADOW_MASK        = 1u << 28,
+  /* ShadowMaskPass::run_rt (no reference counterpart): gbuffer.depth (mip 0), gbuffer.normal and the loaded scene's acceleration
+   * structure (built by vkrh_load_scene, as for VKRH_STAGE_GTAO_RT) -> image "shadow_mask", the image and the place in the frame
+   * order of VKRH_STAGE_SHADOW_MASK: channel l = 255 where the ray from the surface to light l of vkrh_set_shadow_rays meets no
+   * triangle, 0 where it does or where the surface faces away; 255 in the channels of lights that are not configured.  With
+   * `apply` of vkrh_set_shadow_mask, VKRH_STAGE_SHADING of the same run consumes the mask as it consumes the looked-up one.
+   * An error, before anything is recorded: together with VKRH_STAGE_SHADOW_MASK (both write the image), without a loaded scene,
+   * on a tiled frame (the rays reach anywhere: one GPU only).  Not part of VKRH_STAGE_CHAIN.                                 */
+  VKRH_STAGE_SHADOW_MASK_RT     = 1u << 29,
   VKRH_STAGE_CHAIN     = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
@@ -148,6 +156,12 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count);
  * instead of draw.  Defaults: bias 0, radius 1, apply 0, under which VKRH_STAGE_SHADING records what it always recorded.
  * Not on a tiled frame. */
 int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply);
+/* The rays of VKRH_STAGE_SHADOW_MASK_RT: `count` (1..4) lights of 4 floats (xyz, w: w == 1 a point light at xyz, w == 0 a
+ * directional light whose xyz is the vector from the surface towards the light and whose length is the reach of the ray; any
+ * other w is an error), the ray's origin is the surface point moved by normal_offset along the normal, the segment is
+ * t in [tmin, 1] (tmin NaN is an error).  Defaults: one point light at the shading pass's LIGHT_POS, normal_offset 1e-3, tmin 0
+ * (measured: DESIGN.md 7.8).  Not on a tiled frame. */
+int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float normal_offset, float tmin);
 /* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
  * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
  * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */

@@ -714,6 +714,16 @@ void register_hot_path_programs() {
       for (uint32_t l = 0; l < params->layer_count; l++) layers[l] = maps.image->describe_layer(l, 0, 1);
       return vkr_shadow_mask(&depth, layers, params, &out, st.stream);
     });
+    // ---- ray-traced shadow mask (ShadowMaskPass::run_rt; no reference program) ----
+    // set {0 depth (mip 0), 1 normal, 2 acceleration structure, 3 vkr_shadow_rt_params, 4 the mask (storage)}: the C-ABI's order
+    create_program("shadow_mask_rt", [=](LaunchState& st) {
+      const char* P = "shadow_mask_rt";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
+      const SetSlot& as = st.set->slots[2];
+      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"shadow_mask_rt: acceleration structure (binding 2) is not bound"};
+      static_assert(sizeof(vkr_shadow_rt_params) == 160, "vkr_shadow_rt_params: a matrix, four floats, four lights and four words");
+      return vkr_shadow_mask_rt(&depth, &normal, (const vkr_accel*)as.tlas, ubo<vkr_shadow_rt_params>(st, 3, P), &out, st.stream);
+    });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the
     // reference records first is covered by the triangle and not executed.

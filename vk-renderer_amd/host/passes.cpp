@@ -878,6 +878,30 @@ void ShadowMaskPass::run(RenderGraph &graph, ImageResourceId depth, ImageResourc
     rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
 }
 
+void ShadowMaskPass::update_rt_params(const glm::mat4 &camera, const float *lights, uint32_t count, float fovy, float aspect, float znear,
+  float zfar, float normal_offset, float tmin)
+{
+  if (!lights || count < 1 || count > 4) throw std::runtime_error {"ShadowMaskPass::update_rt_params: " + std::to_string(count) + " lights, needs 1..4"};
+  rt_params = vkr_shadow_rt_params {};
+  copy_mat(rt_params.inverse_camera, glm::inverse(camera));
+  rt_params.fovy = fovy; rt_params.aspect = aspect; rt_params.znear = znear; rt_params.zfar = zfar;
+  for (uint32_t l = 0; l < count; l++)
+    for (int k = 0; k < 4; k++) rt_params.lights[l][k] = lights[4*l + k];
+  rt_params.light_count = count; rt_params.normal_offset = normal_offset; rt_params.tmin = tmin;
+}
+
+// task "ShadowMaskRT": set {0 depth (mip 0), 1 normal, 2 the acceleration structure, 3 the block, 4 the mask (storage)} in the
+// C-ABI's order, one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels
+void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, VkAccelerationStructureKHR tlas, ImageResourceId out) {
+  if (!tlas)
+    throw std::runtime_error {"ShadowMaskPass::run_rt: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
+  if (!rt_pipeline.has_program()) rt_pipeline = gpu::create_compute_pipeline("shadow_mask_rt");
+  rec::compute(graph, "ShadowMaskRT", rt_pipeline,
+    {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, tlas), rec::uniform(3, rt_params),
+     rec::storage(4, out)},
+    rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
+}
+
 // ==== SyntheticGbuffer ===============================================================================================
 SyntheticGbuffer::SyntheticGbuffer(uint32_t s) : seed {s} {
   pipeline = gpu::create_graphics_pipeline();

@@ -691,10 +691,22 @@ struct ShadowMaskPass {
   void run(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId shadows, uint32_t layer_count,
     rendergraph::ImageResourceId out);
 
+  // The same mask traced through the scene's ray-query structure (program "shadow_mask_rt"): no map.
+  // camera: the view matrix; lights: count (1..4) x (xyz, w), w == 1 a point light at xyz, w == 0 a directional light whose xyz is
+  // the vector from the surface towards the light; origin = world + normal_offset * normal, the segment is t in [tmin, 1]
+  void update_rt_params(const glm::mat4 &camera, const float *lights, uint32_t count, float fovy, float aspect, float znear, float zfar,
+    float normal_offset, float tmin);
+
+  // task "ShadowMaskRT": depth (mip 0), the full-resolution normal and the structure `tlas` (a vkr_accel*) -> out
+  void run_rt(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
+    VkAccelerationStructureKHR tlas, rendergraph::ImageResourceId out);
+
 private:
   gpu::ComputePipeline pipeline;
+  gpu::ComputePipeline rt_pipeline;  // "shadow_mask_rt", bound by the first run_rt()
   VkSampler sampler;
   vkr_shadow_mask_params params {};
+  vkr_shadow_rt_params rt_params {};
 };
 
 
