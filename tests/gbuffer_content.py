@@ -146,17 +146,22 @@ def apply(chain, name, size):
     CLASSES[name](chain, np.random.default_rng(seed_of(name, size)))
 
 
-def prepare(name, size, **setup_kw):
-    """An oracle-backed chain holding class `name` at `size`, ready for any stage of the chain."""
+def prepare(name, size, pdf=None, **setup_kw):
+    """An oracle-backed chain holding class `name` at `size`, ready for any stage of the chain.  pdf: the bytes of an
+    already preintegrated PDF LUT (it depends on nothing of the frame), uploaded instead of integrating the 1024^2 table again."""
     w, h = size
     ref = PostFxChain(w, h, backend="oracle", setup=FrameSetup(w, h, **setup_kw))
     ref.synth()
     ref.build_prev_hiz()
     ref.init_histories()
-    ref.preintegrate_pdf()
+    if pdf is None:
+        ref.preintegrate_pdf()
+    else:
+        ref.pdf.upload(pdf)
     ref.frame()
     ref.swap_histories()
-    apply(ref, name, size)
+    if name is not None:  # None: the synthetic scene as it is
+        apply(ref, name, size)
     ref.build_prev_hiz()
     return ref
 

@@ -149,6 +149,55 @@ def test_known_answer_closed_slot_is_black():
     torch.cuda.synchronize()
 
 
+def small_output_case(w, h):
+    """-> (depth ImageBuf of 2w x 2h with 2 mips, normal ImageBuf, params, triangles) for an output of w x h pixels, fewer than one
+    wave: a wall at stored depth 0.5 with noise in its low bits, normals around +z, and an open box (no lid towards the camera)
+    of half-size 0.05 around pixel 0's surface point, so that some of its 64 rays hit and some escape"""
+    rng = np.random.default_rng([0x6A0, w, h])
+    depth = ImageBuf(abi.FMT_D24_UNORM_S8, 2 * w, 2 * h, 2)
+    depth.set_raw(np.full((2 * h, 2 * w, 1), 0x800000, np.uint32), 0)
+    depth.set_raw((np.uint32(0x800000) + rng.integers(0, 1 << 8, size=(h, w, 1), dtype=np.uint32)).astype(np.uint32), 1)
+    normal = ImageBuf(abi.FMT_RG16_UNORM, 2 * w, 2 * h)
+    normal.set_raw((32768 + rng.integers(-2000, 2000, size=(2 * h, 2 * w, 2))).astype(np.uint16), 0)
+    params = abi.GtaoRtParams(abi.Mat4.from_np(np.eye(4)), 1.0471976, 1.0, 0.05, 80.0)
+    ar = ref.Arith(int(abi.product().vkr_numeric_contract()))
+    world = ref.pixel_setup(ar, depth.raw(1)[..., 0], normal.raw(0), np.eye(4, dtype=F32), params.fovy, params.aspect,
+                            params.znear, params.zfar, 0.0, w, h)[1]
+    c = world[0, 0].astype(F32)
+    s = F32(0.05)
+    corners = np.array([[x, y, z] for x in (-s, s) for y in (-s, s) for z in (-s, s)], F32) + c
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4)]  # the face z = +s is left open
+    tris = np.array([[corners[a], corners[b], corners[cc]] for q in quads for a, b, cc in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))], F32)
+    return depth, normal, params, tris
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 1), (3, 1)])
+def test_parity_on_an_output_smaller_than_a_wave(w, h):
+    """A block is 4 waves of one pixel each: with 3 pixels the fourth wave takes the whole-wave return, with 1 pixel three do.
+    Parity with the numpy restatement under the rule of tests/parity.py, no exception."""
+    depth, normal, params, tris = small_output_case(w, h)
+    ddev = ImageBuf(abi.FMT_D24_UNORM_S8, 2 * w, 2 * h, 2, device="cuda")
+    ddev.upload(depth.to_host())
+    ndev = ImageBuf(abi.FMT_RG16_UNORM, 2 * w, 2 * h, device="cuda")
+    ndev.upload(normal.to_host())
+    dirs, dirs_dev = _directions_device()
+    accel = abi.Accel(tris)
+    out = ImageBuf(abi.FMT_RGBA16_SFLOAT, w, h, device="cuda", fill=0x5A)
+    rotation = 0.3
+    got = _launch(params, ddev.desc(1, 1), ndev.desc(), accel, dirs_dev, out, rotation)
+    accel.close()
+    host_bytes = out.to_host()
+    assert (host_bytes[8 * w: out.pitch[0]] == 0x5A).all() and (host_bytes[out.pitch[0] * h:] == 0x5A).all(), "bytes outside the image were written"
+    ar = ref.Arith(int(abi.product().vkr_numeric_contract()))
+    want = ref.gtao_rt(ar, depth.raw(1)[..., 0], normal.raw(0), (np.eye(4, dtype=F32), params.fovy, params.aspect, params.znear, params.zfar),
+                       rotation, dirs, tris, w, h)
+    n, _ = report(f"gtao_rt {w}x{h}", abi.FMT_RGBA16_SFLOAT, got.astype(F32), want.astype(F32))
+    assert n == 0
+    open_sky = 2.0 / 64.0 * float(np.maximum(dirs[:, 2].astype(np.float64), 0.0).sum())
+    assert want[0, 0, 1] == 1 and 0.0 < float(want[0, 0, 0]) < 0.9 * open_sky, "pixel 0 is to be partly occluded by the open box"
+
+
 @pytest.mark.gpu
 def test_frame_stage():
     import torch

@@ -313,10 +313,13 @@ def test_empty_tile_skip_against_no_skip(pathological, oracle_lib):
             assert not (differ & ~near).any(), f"{name}: skip and no-skip differ away from every planted non-finite weight"
 
 
-@pytest.mark.parametrize("size", [(640, 360), (1920, 1080), (206, 226)])  # 206x226: the ragged size, k_gtao_main<false, false>
+# 206x226: the ragged size, k_gtao_main<false, false>; 16x8: half-res 8x4, one dispatch group, the smallest TILED image;
+# 18x10: the smallest ragged dispatch (8x4 of 9x5, the uv -> texel map stretched by 12.5 % and 25 %)
+@pytest.mark.parametrize("size", [(640, 360), (1920, 1080), (206, 226), (16, 8), (18, 10)])
 def test_gtao_only_config1(size, oracle_lib):
     """BASELINE config 1: GTAO main pass only, non-MIS (use_mis = 0), single and two directions — also at the
-    configuration's own 1920x1080 and at a size whose floor-dispatch extent is not the image's (depth from global memory)."""
+    configuration's own 1920x1080 and at a size whose floor-dispatch extent is not the image's (depth from global memory).
+    At the two smallest sizes an image is 32 or 45 texels: no texel may be outside tolerance."""
     from vk_renderer_amd.camera import FrameSetup
 
     for two in (0, 255):
@@ -326,10 +329,15 @@ def test_gtao_only_config1(size, oracle_lib):
         _sync_inputs(ref, gpu)
         ref.gtao_main(two_directions=two)
         gpu.gtao_main(two_directions=two)
-        _compare(ref, gpu, ("raw",), budget=8)
+        _compare(ref, gpu, ("raw",), budget=0 if size[0] < 64 else 8)
 
 
-@pytest.mark.parametrize("size", [(256, 144), (640, 360)])
+# 2x130 / 130x2: half-res one texel wide / high; 18x10: the smallest ragged floor dispatch.  At these three the budget of
+# 1e-4 of the image is less than one texel: none may be outside tolerance.
+DEGENERATE = [(2, 130), (130, 2), (18, 10)]
+
+
+@pytest.mark.parametrize("size", [(256, 144), (640, 360)] + DEGENERATE)
 def test_simple_ssr(size, oracle_lib):
     """src/ssr.cpp + ssr/shader.frag (generic hierarchical_raymarch, nearest depth sampler)."""
     ref, gpu = _pair(*size, oracle_lib)
@@ -341,7 +349,10 @@ def test_simple_ssr(size, oracle_lib):
     _compare(ref, gpu, ("ssr_out",), budget=1e-4)
     lit = int((ref.ssr_out.raw(0)[..., :3].max(axis=-1) > 0).sum())
     print(f"[parity] ssr_out lit texels {lit}")
-    assert lit > 0.01 * size[0] * size[1], "simple SSR produced (almost) no reflections: the test scene does not exercise it"
+    # (a property of the picture, not of the kernel: the oracle's own image at 2x130 and 130x2 holds no lit texel — two
+    # columns / rows of the synthetic camera see no mirror — so the floor is asked of the sizes that can meet it)
+    if min(size) > 2:
+        assert lit > 0.01 * size[0] * size[1], "simple SSR produced (almost) no reflections: the test scene does not exercise it"
 
 
 def test_brdf_lut(oracle_lib):
@@ -353,7 +364,7 @@ def test_brdf_lut(oracle_lib):
     assert n == 0
 
 
-@pytest.mark.parametrize("size", [(256, 144), (640, 360)])
+@pytest.mark.parametrize("size", [(256, 144), (640, 360)] + DEGENERATE)  # 2x130: depth1.w < 2, the instantiation without pair loads
 def test_defered_shading(size, oracle_lib):
     """SURVEY 8(f) #1: the composite between GTAO/SSR and TAA (defered_shading/shader.frag)."""
     ref, gpu = _pair(*size, oracle_lib)

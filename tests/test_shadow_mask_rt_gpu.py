@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 FILL = 0xA5
 SKY = 0xFFFFFF
-SIZES = [(8, 8), (17, 9), (64, 36)]
+SIZES = [(8, 8), (17, 9), (64, 36), (1, 1), (1, 9), (9, 1)]  # a wave is an 8 x 8 tile: the last three are one live lane, one live column, one live row
 POINT_A = tuple(LIGHT_POS) + (1.0,)
 POINT_B = (3.0, 4.0, 2.0, 1.0)
 SUN_A = (1.5, 4.5, -1.5, 0.0)    # long enough to leave the scene from anywhere in it

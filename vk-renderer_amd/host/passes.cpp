@@ -195,7 +195,10 @@ GTAO::GTAO(RenderGraph &graph, uint32_t width, uint32_t height, bool use_ray_que
   accumulated_ao = make_image(graph, VK_FORMAT_R16G16_SFLOAT, width, height, usage);
   accumulated_history = make_image(graph, VK_FORMAT_R16G16_SFLOAT, width, height, usage);
   const uint32_t pattern_step = 1u << uint32_t(pattern_n);
-  deinterleaved_depth = make_image(graph, VK_FORMAT_R32_SFLOAT, width/pattern_step, height/pattern_step, usage, COLOR, 1, pattern_step * pattern_step);
+  // (an image cannot be empty: below pattern_step texels a side — a 2 x 2 frame — a layer is one texel, and the variant's floored
+  // 8 x 4 dispatch over it is no group at all)
+  deinterleaved_depth = make_image(graph, VK_FORMAT_R32_SFLOAT, std::max(1u, width/pattern_step), std::max(1u, height/pattern_step), usage, COLOR, 1,
+                                   pattern_step * pattern_step);
 
   main_pipeline = gpu::create_compute_pipeline("gtao_compute_main");
   filter_pipeline = gpu::create_compute_pipeline("gtao_filter");
