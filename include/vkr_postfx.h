@@ -615,6 +615,58 @@ int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img* depth, con
  * descending nearly everywhere.                                                                                               */
 int vkr_accel_occluded(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
                        uint32_t* out_hit, void* stream);
+/* The CLOSEST hit of n arbitrary rays (DESIGN_NUMERICS.md, "Ray query, closest hit"): of all triangles the frozen test accepts
+ * for the ray (the test of vkr_accel_query: its operation order, inclusive edges, det == 0 a miss, the widened-box clause, NaN a
+ * miss) the one with the smallest fp32 t; of equal t (==, so -0 == +0) the one with the smallest index in the caller's input,
+ * never the one the hierarchy happens to meet first.  t, u, v are that triangle's values as the frozen sequence computed them
+ * (the hit point is v0 + u e1 + v e2 = (1 - u - v) v0 + u v1 + v v2), index its position in the input of vkr_accel_create.   */
+typedef struct vkr_accel_hit { float t, u, v; uint32_t index; } vkr_accel_hit;  /* 16 bytes; a miss: index 0xFFFFFFFF, t = u = v = 0 */
+/* The arguments and gates of vkr_accel_occluded; out_hits: device, n records, 16-byte aligned (one 16-byte store per ray);
+ * records past n are not written.  An empty structure is legal: every ray misses.  hit.index != 0xFFFFFFFF is
+ * vkr_accel_occluded's answer for the ray.                                                                                    */
+int vkr_accel_closest(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                      vkr_accel_hit* out_hits, void* stream);
+
+/* program "reflections_rt" (no reference program): the `reflections` image of AdvancedSSR (RGBA8_UNORM, half resolution in the
+ * frame) traced through the scene's ray-query structure: per pixel the mirror ray of the view direction, its closest hit, and the
+ * albedo of the hit triangle there ("radiance = albedo at the hit", as ssr/filter.comp; alpha 0 as the filter stores it).  Where
+ * the screen-space trace goes black (the ray leaves the screen or passes behind geometry) this one still has an answer.       */
+typedef struct vkr_hit_attrib {         /* 32 bytes, one per INPUT triangle of the structure, in input order (device memory) */
+  float    uv[3][2];                    /* the texture coordinates of the triangle's three vertices */
+  uint32_t albedo_index;                /* index into `textures`; 0xFFFFFFFF or >= texture_count: untextured, (0.5, 0.5, 0.5) */
+  uint32_t reserved;
+} vkr_hit_attrib;
+#define VKR_REFLECT_RT_FILL_MISSES 1u   /* flags: only pixels whose screen-space ray is invalid (.w code of `rays` == 65535) are traced */
+typedef struct vkr_reflect_rt_params {  /* 112 bytes */
+  vkr_mat4 inverse_camera;              /* view -> world; its translation column is the eye */
+  float    fovy, aspect, znear, zfar;
+  float    normal_offset;               /* origin = world + normal_offset * normal */
+  float    tmin, max_distance;          /* the ray is origin + t * dir, dir of unit length, t in [tmin, max_distance] */
+  uint32_t texture_lod;                 /* the mip level sampled at a hit, clamped to the texture's chain */
+  uint32_t flags;                       /* VKR_REFLECT_RT_* */
+  uint32_t reserved[3];                 /* 0 */
+} vkr_reflect_rt_params;
+uint64_t vkr_reflections_rt_scratch_bytes(uint32_t texture_count);
+/* depth: D24_UNORM_S8 (mip 0 of the view); normal: RG16_UNORM; rays: RGBA16_UNORM (NULL unless VKR_REFLECT_RT_FILL_MISSES);
+ * out_reflections: RGBA8_UNORM; one extent (the frame binds the half-resolution set).  Per pixel g (DESIGN_NUMERICS.md,
+ * Reflections, ray traced): d = the exact decode of depth texel g (by index); d >= 1 stores (0, 0, 0, 0).  With FILL_MISSES a
+ * pixel whose `rays` texel has a .w code other than 65535 (a valid screen-space hit, filter.comp:94) is LEFT UNTOUCHED and casts
+ * nothing: in-place use on the filter's output.  uv = (g + 0.5) / extent; world = (inverse_camera * (reconstruct_view_vec(uv, d),
+ * 1)).xyz; n = decode_normal(normal texel g); origin = world + normal_offset * n; eye = inverse_camera's translation column;
+ * V = world - eye; R = V - (2 dot(n, V)) n; dir = normalize(R); unless dot(n, dir) > 0 (a surface seen from behind, a grazing
+ * zero, any NaN) the texel is 0.  Otherwise the closest hit of (origin, dir, tmin, max_distance) (vkr_accel_closest's answer): a
+ * miss stores 0; a hit on triangle `index` at (u, v) shades a = attribs[index]: w = (1 - u) - v, uv_hit = (w uv0 + u uv1) + v uv2
+ * per component, every operation rounded on its own; colour (0.5, 0.5, 0.5) when a.albedo_index is 0xFFFFFFFF or >=
+ * texture_count, else the bilinear REPEAT sample of level min(texture_lod, levels - 1) of textures[a.albedo_index] (RGBA8_SRGB,
+ * as vkr_raster_scene's) at uv_hit; stored as rint(255 x) per channel, alpha 0.  textures: host array (NULL only with
+ * texture_count 0, at most 32); its table goes into `scratch` (device, vkr_reflections_rt_scratch_bytes(texture_count)): nothing
+ * is allocated.  Refused before any launch: a NULL argument (rays only without the flag), other formats, different extents, an
+ * extent above 65535, a windowed descriptor anywhere (the rays reach anywhere: a single-GPU pass), attrib_count != the structure's
+ * triangle count, unknown flag bits, reserved != 0, tmin or max_distance NaN, scratch_bytes too small.                        */
+int vkr_reflections_rt(const vkr_img* depth, const vkr_img* normal, const vkr_img* rays, const vkr_accel* accel,
+                       const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
+                       const vkr_reflect_rt_params* params, const vkr_img* out_reflections, void* scratch, uint64_t scratch_bytes,
+                       void* stream);
 
 /* program "shadow_mask_rt" (no reference program): the shadow mask of vkr_shadow_mask traced through the scene's ray-query
  * structure instead of looked up in a shadow map: exact hard shadows of up to four point or directional lights, no map, no

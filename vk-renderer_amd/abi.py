@@ -266,6 +266,27 @@ class ShadowRtParams(C.Structure):  # vkr_shadow_rt_params, 160 bytes
                 ("reserved", C.c_uint32)]
 
 
+# ---- the closest-hit ray query and program reflections_rt ----
+ACCEL_MISS = 0xFFFFFFFF  # vkr_accel_hit.index of a ray that hits nothing
+
+
+class AccelHit(C.Structure):  # vkr_accel_hit, 16 bytes; numpy twin: accel_hit_dtype()
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("index", C.c_uint32)]
+
+
+class HitAttrib(C.Structure):  # vkr_hit_attrib, 32 bytes, one per input triangle; numpy twin: hit_attrib_dtype()
+    _fields_ = [("uv", (C.c_float * 2) * 3), ("albedo_index", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+REFLECT_RT_FILL_MISSES = 1  # VKR_REFLECT_RT_FILL_MISSES
+
+
+class ReflectRtParams(C.Structure):  # vkr_reflect_rt_params, 112 bytes
+    _fields_ = [("inverse_camera", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float),
+                ("normal_offset", C.c_float), ("tmin", C.c_float), ("max_distance", C.c_float), ("texture_lod", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
 
 
@@ -396,6 +417,15 @@ def product():
         lib.vkr_shadow_mask_rt.argtypes = [_IMG, _IMG, C.c_void_p, P(ShadowRtParams), _IMG, C.c_void_p]
         for name in ("accel_layout", "accel_create", "accel_destroy", "accel_info", "accel_query", "gtao_rt_main", "accel_occluded", "shadow_mask_rt"):
             getattr(lib, "vkr_" + name).restype = C.c_int
+        # the closest-hit query and the ray-traced reflections (checked against the numpy restatements tests/closest_hit_reference.py
+        # and tests/reflections_rt_reference.py)
+        lib.vkr_accel_closest.argtypes = lib.vkr_accel_query.argtypes
+        lib.vkr_accel_closest.restype = C.c_int
+        lib.vkr_reflections_rt_scratch_bytes.argtypes = [C.c_uint32]
+        lib.vkr_reflections_rt_scratch_bytes.restype = C.c_uint64
+        lib.vkr_reflections_rt.argtypes = [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ReflectRtParams), _IMG,
+                                           C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.vkr_reflections_rt.restype = C.c_int
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
         lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
@@ -612,6 +642,53 @@ def accel_occluded(accel, origins, dirs, tmin, tmax, out, stream=None):
     accel.occluded(origins, dirs, tmin, tmax, out, stream)
 
 
+def accel_hit_dtype():
+    """the numpy dtype of vkr_accel_hit: view a (n, 16) uint8 / (n, 4) int32 download with it"""
+    import numpy as np
+
+    return np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("index", np.uint32)])
+
+
+def hit_attrib_dtype():
+    """the numpy dtype of vkr_hit_attrib (32 bytes)"""
+    import numpy as np
+
+    return np.dtype([("uv", np.float32, (3, 2)), ("albedo_index", np.uint32), ("reserved", np.uint32)])
+
+
+def reflect_rt_params(inverse_camera, fovy, aspect, znear, zfar, fill_misses=False, normal_offset=SHADOW_RT_NORMAL_OFFSET, tmin=SHADOW_RT_TMIN,
+                      max_distance=None, texture_lod=0):
+    """ReflectRtParams from the camera's view -> world matrix (4x4, maths convention), its four floats and the ray's settings:
+    origin = world + normal_offset * normal, t in [tmin, max_distance] along the unit mirror direction (max_distance None: zfar),
+    the mip level sampled at a hit, and the mode (fill_misses: only pixels whose screen-space ray is invalid are traced)."""
+    p = ReflectRtParams()
+    p.inverse_camera = Mat4.from_np(inverse_camera)
+    p.fovy, p.aspect, p.znear, p.zfar = float(fovy), float(aspect), float(znear), float(zfar)
+    p.normal_offset, p.tmin, p.max_distance = float(normal_offset), float(tmin), float(zfar if max_distance is None else max_distance)
+    p.texture_lod, p.flags = int(texture_lod), REFLECT_RT_FILL_MISSES if fill_misses else 0
+    return p
+
+
+def reflections_rt_scratch_bytes(texture_count):
+    """vkr_reflections_rt_scratch_bytes: the device scratch of one call (the texture table)"""
+    return int(product().vkr_reflections_rt_scratch_bytes(int(texture_count)))
+
+
+def reflections_rt(depth, normal, rays, accel, attribs, attrib_count, textures, texture_count, params, out_reflections, scratch, scratch_bytes,
+                   stream=None):
+    """vkr_reflections_rt: out_reflections (RGBA8_UNORM VkrImg) := per pixel of `depth` (D24_UNORM_S8 VkrImg, mip 0 of the view) and
+    `normal` (RG16_UNORM VkrImg), all of one extent, the albedo at the closest hit of the mirror ray through `accel` (an Accel, or
+    None to show the refusal); `rays` (RGBA16_UNORM VkrImg) only with REFLECT_RT_FILL_MISSES, else None.  attribs: device pointer
+    to attrib_count vkr_hit_attrib records (scene_triangle_attributes order); textures: a (VkrImg * n) host array of RGBA8_SRGB
+    mip chains or None; scratch: device pointer of reflections_rt_scratch_bytes(texture_count).  Raises RuntimeError with the
+    library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_reflections_rt(ref(depth), ref(normal), ref(rays), handle, attribs, int(attrib_count), textures, int(texture_count),
+                                 ref(params), ref(out_reflections), scratch, int(scratch_bytes), stream), lib)
+
+
 def defered_shading_shadowed(albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, out, push, stream=None):
     """vkr_defered_shading_shadowed: vkr_defered_shading (same VkrImg bindings, ShadingParams and ShadingPush) with channel .x of
     `shadow_mask` (RGBA8_UNORM VkrImg at out's extent) on the direct term.  Raises RuntimeError with the library's message on a
@@ -715,6 +792,23 @@ def scene_triangles(sc):
     return np.concatenate(out) if out else np.zeros((0, 3, 3), np.float32)
 
 
+def scene_triangle_attributes(sc):
+    """One vkr_hit_attrib per triangle of scene_triangles(sc), in its order, as a numpy array of hit_attrib_dtype(): the uv of the
+    triangle's three vertices and the draw's albedo texture index (0xFFFFFFFF: none).  A mesh drawn by several nodes yields one
+    record per instance (scene/scene_as.hpp)."""
+    import numpy as np
+
+    out = []
+    for d in sc.draws:
+        n = d["index_count"] // 3 * 3
+        idx = sc.indices[d["index_offset"]:d["index_offset"] + n].astype(np.int64) + d["vertex_offset"]
+        rec = np.zeros(n // 3, hit_attrib_dtype())
+        rec["uv"] = sc.vertices[idx, 6:8].astype(np.float32).reshape(-1, 3, 2)
+        rec["albedo_index"] = np.uint32(d["albedo"] & 0xFFFFFFFF)
+        out.append(rec)
+    return np.concatenate(out) if out else np.zeros(0, hit_attrib_dtype())
+
+
 def accel_layout(triangles):
     """vkr_accel_layout on the host (no GPU): -> (nodes, tris) as numpy structured copies of the records"""
     import numpy as np
@@ -761,6 +855,12 @@ class Accel:
         """vkr_accel_occluded: query() on the walk with the per-ray cull (long rays); the same answers"""
         n = int(origins.shape[0])
         check(self.lib.vkr_accel_occluded(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
+
+    def closest(self, origins, dirs, tmin, tmax, out, stream=None):
+        """vkr_accel_closest: origins, dirs as query(); out: device tensor of n 16-byte records (e.g. (n, 4) int32): t, u, v as
+        float32 bits and the index of the input triangle, 0xFFFFFFFF for a miss (numpy: accel_hit_dtype())"""
+        n = int(origins.shape[0])
+        check(self.lib.vkr_accel_closest(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
 
     def close(self):
         if self.handle:

@@ -489,6 +489,28 @@ class PostFxChain:
         p = abi.shadow_rt_params(self.setup.inv_view, lights, *self.setup.fazz, normal_offset=normal_offset, tmin=tmin)
         abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
 
+    def reflections_rt(self, accel, attribs, scene, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN,
+                       max_distance=None, texture_lod=0):
+        """vkr_reflections_rt on this chain's half-resolution set (depth mip 1, dn, rays) -> reflections (RGBA8_UNORM): the albedo at
+        the closest hit of the mirror ray through `accel` (abi.Accel); `attribs`: device tensor of abi.scene_triangle_attributes
+        records; `scene`: the abi.RasterScene of Scene.upload(device) whose textures the records index.  fill_misses: only texels
+        whose screen-space ray (rays.w) is invalid are written, in place on what the filter left.  Product backend only: the
+        expectation is the numpy restatement tests/reflections_rt_reference.py, not a checker library."""
+        if self.backend != "product":
+            raise RuntimeError("PostFxChain.reflections_rt: only the product backend has the program reflections_rt")
+        if self.tiled:
+            raise RuntimeError("PostFxChain.reflections_rt: not on a window of the frame (the rays reach anywhere: a single-GPU pass)")
+        import torch
+
+        nbytes = abi.reflections_rt_scratch_bytes(scene.texture_count)
+        if getattr(self, "_reflect_rt_scratch", None) is None or self._reflect_rt_scratch.numel() < nbytes:
+            self._reflect_rt_scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        p = abi.reflect_rt_params(self.setup.inv_view, *self.setup.fazz, fill_misses=fill_misses, normal_offset=normal_offset, tmin=tmin,
+                                  max_distance=max_distance, texture_lod=texture_lod)
+        abi.reflections_rt(self.depth.desc(1, 1), self.dn.desc(), self.rays.desc() if fill_misses else None, accel, attribs.data_ptr(),
+                           attribs.numel() * attribs.element_size() // 32, scene.textures, scene.texture_count, p, self.reflections.desc(),
+                           self._reflect_rt_scratch.data_ptr(), nbytes, self.stream)
+
     # ---- tile-classified trace (advanced_ssr.cpp:216-302,440-495; commented out of AdvancedSSR::run) ----
     def _i32_buffer(self, n):
         if self.device is None:

@@ -24,6 +24,7 @@ STAGE_SSAO = 1 << 25  # SSAOPass::draw: depth mip 0 -> image "ssao" (R8_UNORM); 
 STAGE_TILE_REGRESSION = 1 << 26  # AdvancedSSR::run_tile_regression_pass: depth mip 1 -> image "tile_planes" (RGBA32_SFLOAT, (W/16, H/16)); after the downsample; not tiled
 STAGE_BACKBUFFER = 1 << 27  # add_backbuffer_subpass + add_present_subpass: the TAA output (or set_backbuffer's image) -> image "backbuffer" (RGBA8_SRGB); last; not tiled
 STAGE_SHADOW_MASK_RT = 1 << 29  # ShadowMaskPass::run_rt: depth mip 0 + normal + the loaded scene's acceleration structure -> image "shadow_mask" (the image and slot of STAGE_SHADOW_MASK), one ray per pixel and light of set_shadow_rays; needs load_scene(); not with STAGE_SHADOW_MASK, not tiled
+STAGE_REFLECTIONS_RT = 1 << 30  # AdvancedSSR::run_rt: depth mip 1 + the half-resolution normals + the loaded scene's acceleration structure, attribute table and textures -> images "reflections" and "blurred": ReflectionsRT -> SSSR_blur, or with set_reflection_rays(fill_misses=True) SSSR_trace -> SSSR_filter -> ReflectionsRT -> SSSR_blur; needs load_scene(); not with any SSR stage, not tiled
 STAGE_SHADOW_MASK = 1 << 28  # ShadowMaskPass::run: depth mip 0 + the layers of "shadows" -> image "shadow_mask" (RGBA8_UNORM, channel l = light l); after the raster / shadow stages, before the shading; needs the maps of STAGE_SHADOW; not tiled
 STAGE_CHAIN = STAGE_DOWNSAMPLE | STAGE_SSR | STAGE_GTAO | STAGE_TAA
 
@@ -154,7 +155,9 @@ def lib():
                            # the shadow mask (same rule)
                            ("vkrh_set_shadow_mask", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
                            # the ray-traced shadow mask (same rule)
-                           ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float])):
+                           ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float]),
+                           # the ray-traced reflections (same rule)
+                           ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -379,6 +382,15 @@ class HostFrame:
         for i, v in enumerate(lights):
             flat[4 * i: 4 * i + 4] = [float(x) for x in v]
         self._check(lib().vkrh_set_shadow_rays(self.h, flat, len(lights), float(normal_offset), float(tmin)))
+
+    def set_reflection_rays(self, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, max_distance=None,
+                            texture_lod=0):
+        """vkrh_set_reflection_rays: the rays of STAGE_REFLECTIONS_RT: fill_misses False traces every pixel (ReflectionsRT -> blur),
+        True only those whose screen-space ray is invalid (trace -> filter -> ReflectionsRT -> blur); the origin is the surface point
+        moved by normal_offset along the normal, the ray runs t in [tmin, max_distance] along the unit mirror direction
+        (max_distance None: the camera's zfar), a hit samples level texture_lod of its albedo texture."""
+        self._check(lib().vkrh_set_reflection_rays(self.h, 1 if fill_misses else 0, float(normal_offset), float(tmin),
+                                                   0.0 if max_distance is None else float(max_distance), int(texture_lod)))
 
     def set_ssao_samples(self, samples, std140=0):
         """vkrh_set_ssao_samples: pins the 16 samples ([16, 3]) of STAGE_SSAO and their packing in the uniform block: std140 = 0

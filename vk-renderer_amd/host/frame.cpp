@@ -164,6 +164,17 @@ struct PostFxFrame {
     shadow_rays_offset = normal_offset; shadow_rays_tmin = tmin;
   }
 
+  // VKRH_STAGE_REFLECTIONS_RT: the mode and the rays (vkrh_set_reflection_rays).  Defaults: every pixel traced, the offsets of the
+  // shadow rays, max_distance 0 = the camera's zfar at the time of the run, level 0 of the hit's texture.
+  AdvancedSSR::RtSettings reflection_rays {};
+  void set_reflection_rays(uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod) {
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_reflection_rays: on a tiled frame (VKRH_STAGE_REFLECTIONS_RT runs on one GPU)"};
+    if (std::isnan(tmin)) throw std::runtime_error{"vkrh_set_reflection_rays: tmin is NaN"};
+    if (std::isnan(max_distance)) throw std::runtime_error{"vkrh_set_reflection_rays: max_distance is NaN"};
+    reflection_rays.fill_misses = fill_misses != 0; reflection_rays.normal_offset = normal_offset; reflection_rays.tmin = tmin;
+    reflection_rays.max_distance = max_distance > 0.f ? max_distance : 0.f; reflection_rays.texture_lod = texture_lod;
+  }
+
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
   bool has_tile_planes = false;
 
@@ -300,6 +311,13 @@ struct PostFxFrame {
       if (!scene_as || !scene_as->tlas)
         throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
     }
+    if (mask & VKRH_STAGE_REFLECTIONS_RT) {  // refused before anything is recorded
+      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT on a tiled frame (the rays reach anywhere: ray-traced reflections run on one GPU)"};
+      if (mask & (VKRH_STAGE_SSR | VKRH_STAGE_SSR_CLASSIFIED | VKRH_STAGE_SSR_RESOLVE | VKRH_STAGE_SSR_TRACE | VKRH_STAGE_SSR_TRACE_HEAD | VKRH_STAGE_SSR_TRACE_RESUME))
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT together with an SSR stage (VKRH_STAGE_SSR, _SSR_CLASSIFIED, _SSR_RESOLVE, _SSR_TRACE*: all write the images reflections / blurred)"};
+      if (!scene_as || !scene_as->tlas || !scene_renderer)
+        throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT without a loaded scene (vkrh_load_scene builds its acceleration structure and attribute table)"};
+    }
     if (mask & VKRH_STAGE_SHADOW_MASK) {  // refused before anything is recorded
       if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK on a tiled frame (the shadow maps are rendered on one GPU)"};
       if (!(mask & VKRH_STAGE_SHADOW) && !shadow_maps_current)
@@ -383,6 +401,15 @@ struct PostFxFrame {
     if (mask & VKRH_STAGE_SSR_TRACE_RESUME) ssr.run_trace_resume(graph, gbuffer, gtao.raw);
     if (mask & VKRH_STAGE_SSR_TRACE) ssr.run_trace(graph, assr_params, gbuffer, gtao.raw);
     if (mask & VKRH_STAGE_SSR_RESOLVE) ssr.run_resolve(graph, assr_params, draw_params, gbuffer);
+    if (mask & VKRH_STAGE_REFLECTIONS_RT) {  // the place of the SSR stages: reads depth mip 1 and the half-resolution normals of the downsample
+      AdvancedSSR::RtSettings rt = reflection_rays;
+      if (!(rt.max_distance > 0.f)) rt.max_distance = fazz.w;
+      const bool classified = ssr.get_settings().use_tile_classification;  // fill mode traces with the plain trace; the setting is the SSR stages'
+      ssr.get_settings().use_tile_classification = false;
+      ssr.run_rt(graph, assr_params, draw_params, gbuffer, gtao.raw,
+                 AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()}, rt);
+      ssr.get_settings().use_tile_classification = classified;
+    }
     if (mask & VKRH_STAGE_GTAO_MAIN_ONLY)
       gtao.add_main_pass(graph, gtao_params, gbuffer.depth, gbuffer.normal, gbuffer.material, ssr.get_preintegrated_pdf());
     if (mask & VKRH_STAGE_GTAO) {                                                           // main.cpp:384-388
@@ -1377,6 +1404,9 @@ int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, u
 }
 int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float normal_offset, float tmin) {
   return guarded([&] { frame_ref(frame).set_shadow_rays(lights, count, normal_offset, tmin); });
+}
+int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod) {
+  return guarded([&] { frame_ref(frame).set_reflection_rays(fill_misses, normal_offset, tmin, max_distance, texture_lod); });
 }
 
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {

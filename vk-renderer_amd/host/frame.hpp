@@ -103,7 +103,18 @@ enum {
    * An error, before anything is recorded: together with VKRH_STAGE_SHADOW_MASK (both write the image), without a loaded scene,
    * on a tiled frame (the rays reach anywhere: one GPU only).  Not part of VKRH_STAGE_CHAIN.                                 */
   VKRH_STAGE_SHADOW_MASK_RT     = 1u << 29,
-  VKRH_STAGE_CHAIN     = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
+  /* AdvancedSSR::run_rt (no reference counterpart): the images "reflections" and "blurred" of VKRH_STAGE_SSR from rays traced through
+   * the loaded scene's acceleration structure, in the place of the SSR stages in the frame order.  Default mode (all): task
+   * ReflectionsRT (depth mip 1, the half-resolution normals, the structure, its attribute table, the scene's textures ->
+   * reflections: the albedo at the closest hit of the mirror ray, 0 at a miss) -> SSSR_blur.  No screen-space trace runs, so
+   * gtao.raw ("raw") is NOT written: VKRH_STAGE_GTAO with MIS then reads what an earlier frame left there; the companions are
+   * VKRH_STAGE_GTAO_RT or use_mis = 0.  fill_misses of vkrh_set_reflection_rays: SSSR_trace -> SSSR_filter -> ReflectionsRT (in
+   * place on reflections: only texels whose screen-space ray is invalid are traced, the others keep the filter's value) ->
+   * SSSR_blur; everything the trace writes for GTAO is as under VKRH_STAGE_SSR.  An error, before anything is recorded: on a tiled
+   * frame (the rays reach anywhere: one GPU only), without a loaded scene, together with VKRH_STAGE_SSR, _SSR_CLASSIFIED,
+   * _SSR_RESOLVE or any _SSR_TRACE* (all of them write reflections / blurred).  Not part of VKRH_STAGE_CHAIN.                 */
+  VKRH_STAGE_REFLECTIONS_RT     = 1u << 30,
+  VKRH_STAGE_CHAIN    = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7)
 };
 
 typedef void* (*vkrh_alloc_fn)(uint64_t bytes, void* user);
@@ -162,6 +173,12 @@ int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t a
  * t in [tmin, 1] (tmin NaN is an error).  Defaults: one point light at the shading pass's LIGHT_POS, normal_offset 1e-3, tmin 0
  * (measured: DESIGN.md 7.8).  Not on a tiled frame. */
 int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float normal_offset, float tmin);
+/* The rays of VKRH_STAGE_REFLECTIONS_RT: fill_misses != 0 traces only the pixels whose screen-space ray is invalid, after the
+ * screen-space trace and filter; the ray's origin is the surface point moved by normal_offset along the normal, the ray runs
+ * t in [tmin, max_distance] along the unit mirror direction (tmin or max_distance NaN is an error), a hit samples mip level
+ * texture_lod of its albedo texture (clamped to the chain).  Defaults: fill_misses 0, normal_offset 1e-3 and tmin 0 (those of
+ * vkrh_set_shadow_rays), max_distance = the camera's zfar (also what max_distance <= 0 selects), texture_lod 0.  Not on a tiled frame. */
+int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod);
 /* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
  * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
  * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */

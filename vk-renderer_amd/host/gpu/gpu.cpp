@@ -724,6 +724,32 @@ void register_hot_path_programs() {
       static_assert(sizeof(vkr_shadow_rt_params) == 160, "vkr_shadow_rt_params: a matrix, four floats, four lights and four words");
       return vkr_shadow_mask_rt(&depth, &normal, (const vkr_accel*)as.tlas, ubo<vkr_shadow_rt_params>(st, 3, P), &out, st.stream);
     });
+    // ---- ray-traced reflections (AdvancedSSR::run_reflections_rt_pass; no reference program) ----
+    // set {0 depth (mip 0 of the view), 1 normal, 2 rays (bound only in fill mode), 3 acceleration structure, 4 the attribute table,
+    // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace
+    create_program("reflections_rt", [=](LaunchState& st) {
+      const char* P = "reflections_rt";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 6, S, P);
+      static_assert(sizeof(vkr_reflect_rt_params) == 112, "vkr_reflect_rt_params: a matrix, eight floats / words, the flags and three words");
+      const vkr_reflect_rt_params* params = ubo<vkr_reflect_rt_params>(st, 5, P);
+      vkr_img rays{};
+      const bool fill = (params->flags & VKR_REFLECT_RT_FILL_MISSES) != 0;
+      if (fill) rays = tex(st, 2, T, P);
+      const SetSlot& as = st.set->slots[3];
+      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"reflections_rt: acceleration structure (binding 3) is not bound"};
+      const SetSlot& at = st.set->slots[4];
+      if (at.kind != SetSlot::Ubo || !at.buffer) throw std::runtime_error{"reflections_rt: attribute table (binding 4) is not bound"};
+      std::vector<vkr_img> textures;
+      for (const auto& v : st.set->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
+      const uint64_t bytes = vkr_reflections_rt_scratch_bytes((uint32_t)textures.size());
+      // the table of an empty scene still holds one (unused) record: a buffer has no size 0
+      uint32_t triangles = 0;
+      if (vkr_accel_info((const vkr_accel*)as.tlas, nullptr, &triangles) != 0) throw std::runtime_error{std::string{"reflections_rt: "} + vkr_last_error()};
+      const uint64_t records = at.buffer->get_size() / sizeof(vkr_hit_attrib);
+      return vkr_reflections_rt(&depth, &normal, fill ? &rays : nullptr, (const vkr_accel*)as.tlas, (const vkr_hit_attrib*)at.buffer->device_ptr(st.stream),
+                                records >= triangles ? triangles : (uint32_t)records, textures.empty() ? nullptr : textures.data(),
+                                (uint32_t)textures.size(), params, &out, st.require_workspace(bytes), bytes, st.stream);
+    });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the
     // reference records first is covered by the triangle and not executed.

@@ -761,6 +761,61 @@ void AdvancedSSR::run_tile_regression_pass(RenderGraph &graph, const AdvancedSSR
 }
 #endif
 
+// ---- ray-traced reflections (no reference counterpart) ----
+vkr_reflect_rt_params AdvancedSSR::reflect_rt_params(const AdvancedSSRParams &params, const RtSettings &rt) {
+  vkr_reflect_rt_params p {};
+  copy_mat(p.inverse_camera, glm::transpose(params.normal_mat));  // normal_mat = transpose(inverse(view))
+  p.fovy = params.fovy; p.aspect = params.aspect; p.znear = params.znear; p.zfar = params.zfar;
+  p.normal_offset = rt.normal_offset; p.tmin = rt.tmin; p.max_distance = rt.max_distance; p.texture_lod = rt.texture_lod;
+  p.flags = rt.fill_misses? VKR_REFLECT_RT_FILL_MISSES : 0u;
+  return p;
+}
+
+// task "ReflectionsRT": set {0 depth (mip 1 of the image: mip 0 of the view), 1 the half-resolution normals, 2 rays (only with
+// fill_misses), 3 the acceleration structure, 4 its attribute table, 5 the block, 6 reflections (storage), 7 the scene's textures[]},
+// one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels of reflections.  Written out instead of rec::compute because of
+// the array of images, which is no graph resource (as in ProbeRenderer's cube pass)
+void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
+  const RtSettings &rt)
+{
+  if (!scene.tlas)
+    throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
+  if (!scene.hit_attributes)
+    throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: no attribute table: build scene::SceneAccelerationStructure first"};
+  if (gbuff.tiled)
+    throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: on a window of the frame (the rays reach anywhere: a single-GPU pass)"};
+  if (!reflections_rt_pass.has_program()) reflections_rt_pass = gpu::create_compute_pipeline("reflections_rt");
+  std::vector<rec::Binding> bindings {rec::sampled_mips(0, gbuff.depth, sampler, DEPTH, 1, 1), rec::sampled(1, gbuff.downsampled_normals, sampler)};
+  if (rt.fill_misses) bindings.push_back(rec::sampled(2, rays, sampler));
+  bindings.insert(bindings.end(), {rec::accel(3, scene.tlas), rec::uniform_buffer(4, scene.hit_attributes), rec::uniform(5, reflect_rt_params(params, rt)),
+                                   rec::storage(6, reflections)});
+  struct Data { std::vector<rec::Bound> bound; };
+  const auto pipeline = reflections_rt_pass;
+  const auto textures = scene.textures;
+  const auto sized_by = reflections;
+  graph.add_task<Data>("ReflectionsRT",
+    [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(bindings, builder, VK_SHADER_STAGE_COMPUTE_BIT); },
+    [=](Data &d, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      VkDescriptorSet set = rec::write(d.bound, resources, cmd);
+      gpu::write_set(set, gpu::ArrayOfImagesBinding {7, textures});
+      cmd.bind_pipeline(pipeline);
+      cmd.bind_descriptors_compute(0, {set});
+      const auto extent = resources.get_image(sized_by)->get_extent();
+      cmd.dispatch((extent.width + 15)/16, (extent.height + 15)/16, 1);
+    });
+}
+
+void AdvancedSSR::run_rt(RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
+  ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt)
+{
+  if (rt.fill_misses) {
+    run_trace(graph, params, gbuff, ssr_occlusion);
+    run_filter_pass(graph, params, gbuff);
+  }
+  run_reflections_rt_pass(graph, params, gbuff, scene, rt);
+  run_blur_pass(graph, params, taa_params, gbuff);
+}
+
 // advanced_ssr.cpp:556-567
 #ifndef VKR_REFERENCE_PASSES  // defined by the reference's own source in the drop-in build (Makefile: refpasses)
 void AdvancedSSR::render_ui() {
@@ -1057,6 +1112,7 @@ SceneAccelerationStructure::~SceneAccelerationStructure() {
 
 void SceneAccelerationStructure::build(gpu::TransferCmdPool &transfer_pool, const CompiledScene &source) {  // scene_as.cpp:19-24
   blas_triangles.clear();
+  blas_attributes.clear();
   for (const auto &mesh : source.root_meshes) build_blas(transfer_pool, mesh, source);
   build_tlas(transfer_pool, source);
 }
@@ -1067,17 +1123,25 @@ void SceneAccelerationStructure::build_blas(gpu::TransferCmdPool &, const BaseMe
   const uint64_t vertex_count = vertices ? source.vertex_buffer->get_size() / sizeof(Vertex) : 0;
   const uint64_t index_count = indices ? source.index_buffer->get_size() / sizeof(uint32_t) : 0;
   std::vector<float> tris;
+  std::vector<vkr_hit_attrib> attribs;
   for (const auto &prim : mesh.primitives) {  // scene_as.cpp:60-70: primitiveCount = index_count / 3, firstVertex = vertex_offset
     if (uint64_t(prim.index_offset) + prim.index_count > index_count)
       throw std::runtime_error {"SceneAccelerationStructure: a primitive's indices lie outside the index buffer"};
-    for (uint32_t j = 0; j + 3 <= prim.index_count; j += 3)
+    const uint32_t albedo = prim.material_index < source.materials.size()? source.materials[prim.material_index].albedo_tex_index : 0xFFFFFFFFu;
+    for (uint32_t j = 0; j + 3 <= prim.index_count; j += 3) {
+      vkr_hit_attrib a {};
+      a.albedo_index = albedo;
       for (uint32_t k = 0; k < 3; k++) {
         const uint64_t v = uint64_t(prim.vertex_offset) + indices[prim.index_offset + j + k];
         if (v >= vertex_count) throw std::runtime_error {"SceneAccelerationStructure: an index names a vertex outside the vertex buffer"};
         tris.insert(tris.end(), {vertices[v].pos.x, vertices[v].pos.y, vertices[v].pos.z});
+        a.uv[k][0] = vertices[v].uv.x; a.uv[k][1] = vertices[v].uv.y;
       }
+      attribs.push_back(a);
+    }
   }
   blas_triangles.push_back(std::move(tris));
+  blas_attributes.push_back(std::move(attribs));
 }
 
 namespace {
@@ -1093,10 +1157,13 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
   std::vector<FlatNode> nodes;
   for (const auto &node : source.base_nodes) flatten_nodes(nodes, node, glm::mat4 {1.f});
   world_triangles.clear();
+  world_attributes.clear();
   for (const auto &n : nodes) {
     if (size_t(n.mesh) >= blas_triangles.size()) throw std::runtime_error {"SceneAccelerationStructure: a node names a mesh without a structure (build_blas first)"};
     const glm::mat4 &m = n.transform;  // m[column][row]
     const auto &obj = blas_triangles[n.mesh];
+    if (size_t(n.mesh) < blas_attributes.size())  // one record per instance, in the order of the triangles
+      world_attributes.insert(world_attributes.end(), blas_attributes[n.mesh].begin(), blas_attributes[n.mesh].end());
     for (size_t i = 0; i + 3 <= obj.size(); i += 3) {
       const float x = obj[i], y = obj[i + 1], z = obj[i + 2];
       for (int row = 0; row < 3; row++) {
@@ -1112,6 +1179,14 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
   if (vkr_accel_create(world_triangles.data(), uint32_t(world_triangles.size() / 9), &accel) != 0)
     throw std::runtime_error {std::string {"SceneAccelerationStructure: "} + vkr_last_error()};
   tlas = (VkAccelerationStructureKHR)accel;
+  // the attribute table of the closest-hit consumers: uploaded once, when it is first bound
+  hit_attributes.reset();
+  if (world_attributes.size() != world_triangles.size() / 9)
+    throw std::runtime_error {"SceneAccelerationStructure: the attribute table does not match the triangles (build_blas before build_tlas)"};
+  const uint64_t bytes = sizeof(vkr_hit_attrib) * world_attributes.size();
+  hit_attributes = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, std::max<uint64_t>(bytes, sizeof(vkr_hit_attrib)), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+  std::memset(hit_attributes->get_mapped_ptr(), 0, hit_attributes->get_size());  // an empty scene: one unused record (a buffer has no size 0)
+  if (bytes) std::memcpy(hit_attributes->get_mapped_ptr(), world_attributes.data(), bytes);
 }
 
 }  // namespace scene

@@ -472,7 +472,33 @@ struct AdvancedSSR {
   rendergraph::ImageResourceId get_tile_planes() const { return tile_planes; }
   static vkr_tile_regression_push tile_regression_push(const AdvancedSSRParams &params);
 
+  // Ray-traced reflections (program "reflections_rt"; no reference counterpart): `reflections` from the closest hit of
+  // the mirror ray through the scene's ray-query structure instead of (or, fill_misses, where it fails, after) the screen-space trace.
+  struct RtScene {
+    VkAccelerationStructureKHR tlas {nullptr};  // scene::SceneAccelerationStructure::tlas
+    gpu::BufferPtr hit_attributes;              // ... ::hit_attributes: one vkr_hit_attrib per triangle of the structure
+    std::vector<std::pair<VkImageView, VkSampler>> textures;  // SceneRenderer::get_images(): what albedo_index indexes
+  };
+  struct RtSettings {
+    bool fill_misses {false};
+    float normal_offset {1e-3f}, tmin {0.f};  // the offsets of ShadowMaskPass::run_rt
+    float max_distance {0.f};                 // the caller's (the frame: zfar)
+    uint32_t texture_lod {0};
+  };
+  // all (default): ReflectionsRT -> SSSR_blur.  No screen-space trace runs, so ssr_occlusion (gtao.raw) is NOT written: a GTAO main
+  // pass with MIS then reads what an earlier frame left; its companions are the ray-traced AO or use_mis = 0.
+  // fill_misses: SSSR_trace -> SSSR_filter -> ReflectionsRT (in place on `reflections`, reading `rays`) -> SSSR_blur; everything the
+  // trace writes for GTAO is as in run().
+  void run_rt(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
+    rendergraph::ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt);
+  // task "ReflectionsRT": depth mip 1, the half-resolution normals, (fill_misses: rays,) the structure, its attributes, the scene's
+  // textures and the block -> reflections
+  void run_reflections_rt_pass(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
+    const RtSettings &rt);
+  static vkr_reflect_rt_params reflect_rt_params(const AdvancedSSRParams &params, const RtSettings &rt);
+
 private:
+  gpu::ComputePipeline reflections_rt_pass;  // "reflections_rt", bound by the first run_reflections_rt_pass()
   gpu::BufferPtr halton_buffer;
   gpu::ComputePipeline tile_regression;        // bound by run_tile_regression_pass
   rendergraph::ImageResourceId tile_planes;    // advanced_ssr.cpp:85-86: output of the regression pass (RGBA32F; allocated on first use)

@@ -35,6 +35,15 @@ struct SceneAccelerationStructure {
   // the world-space triangles build_tlas() put into the structure (9 floats per triangle)
   std::vector<float> world_triangles;
   VkAccelerationStructureKHR tlas {nullptr};
+
+  // What a closest-hit query needs to shade its hit (program "reflections_rt"): one vkr_hit_attrib per triangle, in the order of
+  // world_triangles — the uv of its three vertices and the albedo texture index of its primitive's material (0xFFFFFFFF: none).  A
+  // mesh drawn by several nodes yields one record per instance.  blas_attributes: per mesh, in build_blas() order; hit_attributes:
+  // the table on the device, uploaded once by build_tlas() (one unused record for a scene without triangles) — vk-renderer_amd/abi.py
+  // scene_triangle_attributes() restates it in numpy.
+  std::vector<std::vector<vkr_hit_attrib>> blas_attributes;
+  std::vector<vkr_hit_attrib> world_attributes;
+  gpu::BufferPtr hit_attributes;
 };
 
 }  // namespace scene
