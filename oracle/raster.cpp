@@ -159,8 +159,9 @@ extern "C" int vkr_ref_raster_gbuffer(const vkr_raster_scene* scene, const vkr_g
         }
         const i64 minx = std::min(X[0], std::min(X[1], X[2])), maxx = std::max(X[0], std::max(X[1], X[2]));
         const i64 miny = std::min(Y[0], std::min(Y[1], Y[2])), maxy = std::max(Y[0], std::max(Y[1], Y[2]));
-        const int x0 = (int)std::max<i64>((minx - 128) >> 8, 0), x1 = (int)std::min<i64>((maxx - 128) >> 8, W - 1);
-        const int y0 = (int)std::max<i64>((miny - 128) >> 8, 0), y1 = (int)std::min<i64>((maxy - 128) >> 8, H - 1);
+        // the first centre at or after the smallest coordinate, the last at or before the largest
+        const int x0 = (int)std::max<i64>((minx + 127) >> 8, 0), x1 = (int)std::min<i64>((maxx - 128) >> 8, W - 1);
+        const int y0 = (int)std::max<i64>((miny + 127) >> 8, 0), y1 = (int)std::min<i64>((maxy - 128) >> 8, H - 1);
         const double inv = 1.0 / (double)area2;
         auto lambdas = [&](int px, int py, float l[3], i64 e[3]) {
           const i64 PX = ((i64)px << 8) + 128, PY = ((i64)py << 8) + 128;
@@ -183,7 +184,9 @@ extern "C" int vkr_ref_raster_gbuffer(const vkr_raster_scene* scene, const vkr_g
             if (e[0] == 0 && !is_top_left(X[1], Y[1], X[2], Y[2])) continue;
             if (e[1] == 0 && !is_top_left(X[2], Y[2], X[0], Y[0])) continue;
             if (e[2] == 0 && !is_top_left(X[0], Y[0], X[1], Y[1])) continue;
-            const float zf = (l[0] * z[0] + l[1] * z[1]) + l[2] * z[2];
+            float zf = (l[0] * z[0] + l[1] * z[1]) + l[2] * z[2];
+            // corners all at or before the far plane: the fragment cannot lie beyond it, only fp32 rounding can say so
+            if (zf > 1.0f && std::max(z[0], std::max(z[1], z[2])) <= 1.0f) zf = 1.0f;
             if (!(zf >= 0.0f && zf <= 1.0f)) continue;
             const uint32_t d24 = (uint32_t)rintf(zf * 16777215.0f);
             uint32_t& stored = zbuf[(size_t)py * W + px];

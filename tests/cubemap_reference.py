@@ -215,8 +215,8 @@ def _draw_triangle(ar, face, tri, levels, alpha_test):
             arr[1], arr[2] = arr[2], arr[1]
         area2 = -area2
     inv = 1.0 / float(area2)
-    x0, x1 = max((min(X) - 128) >> 8, 0), min((max(X) - 128) >> 8, size - 1)
-    y0, y1 = max((min(Y) - 128) >> 8, 0), min((max(Y) - 128) >> 8, size - 1)
+    x0, x1 = max((min(X) + 127) >> 8, 0), min((max(X) - 128) >> 8, size - 1)  # first centre at or after, last at or before
+    y0, y1 = max((min(Y) + 127) >> 8, 0), min((max(Y) - 128) >> 8, size - 1)
     if x0 > x1 or y0 > y1:
         return
     py, px = np.mgrid[y0:y1 + 1, x0:x1 + 1]
@@ -239,6 +239,8 @@ def _draw_triangle(ar, face, tri, levels, alpha_test):
     px, py = px[inside], py[inside]
     lam = lambdas([ei[inside] for ei in e])
     depth = (lam[0] * Z[0] + lam[1] * Z[1]) + lam[2] * Z[2]
+    if max(Z) <= 1:  # corners all at or before the far plane: a fragment cannot lie beyond it, only fp32 rounding can say so
+        depth = np.minimum(depth, F32(1.0))
     ok = (depth >= 0) & (depth <= 1)  # depth clipping (far plane; near was clipped)
     px, py, lam, depth = px[ok], py[ok], [v[ok] for v in lam], depth[ok]
     if len(px) == 0:

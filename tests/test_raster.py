@@ -97,9 +97,20 @@ class _IdentitySetup(FrameSetup):
         self.prev_mvp = np.eye(4, dtype=np.float32)
 
 
-def test_oracle_fill_rule_and_clear(oracle_lib):
+# the known answers of the raster rules run on the oracle (CPU) and on the HIP rasteriser (GPU): one body, two backends
+BACKENDS = ["oracle", pytest.param("product", marks=pytest.mark.gpu)]
+
+
+def _kat_chain(backend, W, H):
+    if backend == "product":
+        return PostFxChain(W, H, backend="product", device="cuda", setup=_IdentitySetup(W, H))
+    return PostFxChain(W, H, backend="oracle", setup=_IdentitySetup(W, H))
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_fill_rule_and_clear(backend, oracle_lib):
     W, H = 16, 8
-    c = PostFxChain(W, H, backend="oracle", setup=_IdentitySetup(W, H))
+    c = _kat_chain(backend, W, H)
     # screen x = (ndc + 1) / 2 * 16: the square [4, 12) x [2, 6) as two triangles sharing the diagonal, z = 0.25
     def ndc(x, y):
         return [x / 8.0 - 1.0, y / 4.0 - 1.0, 0.25]
@@ -120,9 +131,10 @@ def test_oracle_fill_rule_and_clear(oracle_lib):
     assert np.all(out["material"][covered] == np.array([188, 243, 188, 128], np.uint8))  # (0.5, 0.9, 0.5, 0.5)
 
 
-def test_oracle_depth_test_is_less_or_equal_and_near_clip(oracle_lib):
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_depth_test_is_less_or_equal_and_near_clip(backend, oracle_lib):
     W, H = 16, 8
-    c = PostFxChain(W, H, backend="oracle", setup=_IdentitySetup(W, H))
+    c = _kat_chain(backend, W, H)
     sc = scn.Scene()
     full = np.array([[-1, -1, 0.5], [3, -1, 0.5], [-1, 3, 0.5]], np.float32)  # covers the whole viewport at z = 0.5
     n0 = np.array([[0, 0, 1]] * 3, np.float32)

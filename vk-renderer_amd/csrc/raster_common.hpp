@@ -80,7 +80,10 @@ template <class T> VKR_DEV bool cover(const T& t, int px, int py, float lambda[3
   lambda[0] = (float)((double)e0 * inv);
   lambda[1] = (float)((double)e1 * inv);
   lambda[2] = (float)((double)e2 * inv);
-  const float depth = (lambda[0] * t.z[0] + lambda[1] * t.z[1]) + lambda[2] * t.z[2];
+  float depth = (lambda[0] * t.z[0] + lambda[1] * t.z[1]) + lambda[2] * t.z[2];
+  // A weighted mean of corner depths that are all <= 1 is <= 1; only the fp32 rounding of the rounded weights can lift it an ulp
+  // above (pinholes in a triangle that lies on the far plane).  Such a fragment is on the far plane, not beyond it.
+  if (depth > 1.0f && fmaxf(t.z[0], fmaxf(t.z[1], t.z[2])) <= 1.0f) depth = 1.0f;
   if (!(depth >= 0.0f && depth <= 1.0f)) return false;  // depth clipping (far plane; near was clipped)
   *d24 = (uint32_t)rintf(depth * 16777215.0f);
   return true;
@@ -161,8 +164,9 @@ VKR_DEV f4 sample_trilinear(const Pyramid& p, f2 uv, f2 duvdx, f2 duvdy, const f
 template <class T> VKR_DEV bool tri_bbox(const T& t, int width, int height, int* x0, int* y0, int* x1, int* y1) {
   const int minx = min(t.x[0], min(t.x[1], t.x[2])), maxx = max(t.x[0], max(t.x[1], t.x[2]));
   const int miny = min(t.y[0], min(t.y[1], t.y[2])), maxy = max(t.y[0], max(t.y[1], t.y[2]));
-  *x0 = max((minx - 128) >> 8, 0); *x1 = min((maxx - 128) >> 8, width - 1);
-  *y0 = max((miny - 128) >> 8, 0); *y1 = min((maxy - 128) >> 8, height - 1);
+  // the first centre at or after the smallest coordinate (rounded up), the last at or before the largest (rounded down)
+  *x0 = max((minx + 127) >> 8, 0); *x1 = min((maxx - 128) >> 8, width - 1);
+  *y0 = max((miny + 127) >> 8, 0); *y1 = min((maxy - 128) >> 8, height - 1);
   return *x0 <= *x1 && *y0 <= *y1;
 }
 #define RASTER_SMALL_BLOCKS 64  // sub-triangles whose bounding box has more 8x8 blocks go to the shared-work kernel
