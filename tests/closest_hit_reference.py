@@ -3,37 +3,15 @@ DESIGN_NUMERICS.md, "Ray query, closest hit") — the checker of tests/test_acce
 and the ray query of tests/reflections_rt_reference.py.
 
 Test infrastructure, like the oracle: the product package never imports it.  No hierarchy here: the frozen triangle test of
-tests/gtao_rt_reference.py, extended to hand back the t, u, v it computes, against ALL triangles, then the smallest t and of
-equal t (==, so -0 == +0) the smallest input index.
+tests/gtao_rt_reference.py (frozen_hit_tuv: it hands back the t, u, v it computes) against ALL triangles, then the smallest t
+and of equal t (==, so -0 == +0) the smallest input index.
 """
 import numpy as np
 
-from gtao_rt_reference import F32, segment_boxes, triangle_records  # noqa: F401
+from gtao_rt_reference import F32, frozen_hit_tuv, segment_boxes, triangle_records  # noqa: F401
 
 MISS = 0xFFFFFFFF
 HIT_DTYPE = np.dtype([("t", F32), ("u", F32), ("v", F32), ("index", np.uint32)])  # vkr_accel_hit
-
-
-def frozen_hit_tuv(o, d, tmin, tmax, v0, e1, e2, lo, hi):
-    """gtao_rt_reference.frozen_hit (the operation order of ray_hits_triangle, no fused multiply-add), returning what it
-    computed: -> (ok, t, u, v), element-wise"""
-    tmin, tmax = F32(tmin), F32(tmax)
-    with np.errstate(all="ignore"):
-        dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
-        e1x, e1y, e1z = e1[..., 0], e1[..., 1], e1[..., 2]
-        e2x, e2y, e2z = e2[..., 0], e2[..., 1], e2[..., 2]
-        px, py, pz = dy * e2z - dz * e2y, dz * e2x - dx * e2z, dx * e2y - dy * e2x
-        det = (e1x * px + e1y * py) + e1z * pz
-        inv = F32(1.0) / det
-        tx, ty, tz = o[..., 0] - v0[..., 0], o[..., 1] - v0[..., 1], o[..., 2] - v0[..., 2]
-        u = ((tx * px + ty * py) + tz * pz) * inv
-        qx, qy, qz = ty * e1z - tz * e1y, tz * e1x - tx * e1z, tx * e1y - ty * e1x
-        v = ((dx * qx + dy * qy) + dz * qz) * inv
-        t = ((e2x * qx + e2y * qy) + e2z * qz) * inv
-        ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t >= tmin) & (t <= tmax)
-        hx, hy, hz = o[..., 0] + t * dx, o[..., 1] + t * dy, o[..., 2] + t * dz
-        ok &= (hx >= lo[..., 0]) & (hx <= hi[..., 0]) & (hy >= lo[..., 1]) & (hy <= hi[..., 1]) & (hz >= lo[..., 2]) & (hz <= hi[..., 2])
-    return ok, t.astype(F32), u.astype(F32), v.astype(F32)
 
 
 def brute_force_closest(o, d, tmin, tmax, rec, chunk=512):

@@ -119,9 +119,9 @@ def triangle_records(tris):
             "hi": np.maximum(np.maximum(t[:, 0], t[:, 1]), t[:, 2]) + margin[:, None]}
 
 
-def frozen_hit(o, d, tmin, tmax, v0, e1, e2, lo, hi):
+def frozen_hit_tuv(o, d, tmin, tmax, v0, e1, e2, lo, hi):
     """element-wise: ray (o, d) of [.., 3] against triangle records of [.., 3] (broadcast); the operation order of
-    csrc/accel.hip ray_hits_triangle, no fused multiply-add"""
+    csrc/accel_traverse.hpp ray_triangle_closest, no fused multiply-add: -> (ok, t, u, v)"""
     tmin, tmax = F32(tmin), F32(tmax)
     with np.errstate(all="ignore"):
         dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
@@ -138,7 +138,12 @@ def frozen_hit(o, d, tmin, tmax, v0, e1, e2, lo, hi):
         ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t >= tmin) & (t <= tmax)
         hx, hy, hz = o[..., 0] + t * dx, o[..., 1] + t * dy, o[..., 2] + t * dz
         ok &= (hx >= lo[..., 0]) & (hx <= hi[..., 0]) & (hy >= lo[..., 1]) & (hy <= hi[..., 1]) & (hz >= lo[..., 2]) & (hz <= hi[..., 2])
-    return ok
+    return ok, t.astype(F32), u.astype(F32), v.astype(F32)
+
+
+def frozen_hit(o, d, tmin, tmax, v0, e1, e2, lo, hi):
+    """the any-hit form (ray_hits_triangle): whether, not where"""
+    return frozen_hit_tuv(o, d, tmin, tmax, v0, e1, e2, lo, hi)[0]
 
 
 def segment_boxes(o, d, tmin, tmax):

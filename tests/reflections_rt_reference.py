@@ -4,15 +4,17 @@ checker of tests/test_reflections_rt_gpu.py.
 Test infrastructure, like the oracle: the product package never imports it.  The arithmetic (Arith, the storage decodes,
 decode_normal) is that of tests/gtao_rt_reference.py, the ray query the brute force of tests/closest_hit_reference.py, the
 texture sampler (REPEAT, bilinear, sRGB decode through the library's table) that of tests/cubemap_reference.py; what is restated
-here is the pass: depth and normal read by index, the view -> world transform, the offset origin, the mirror direction about the
-normal, the closest hit, the interpolated uv and the albedo there.
+here is the pass: the surface of a pixel (tests/shadow_mask_rt_reference.py pixel_surface: depth and normal read by index, the
+view -> world transform, the offset origin), the mirror direction about the normal, the closest hit, the interpolated uv and the
+albedo there.
 """
 import numpy as np
 
 from closest_hit_reference import MISS, brute_force_closest
 from cubemap_reference import _sample_level
-from gtao_rt_reference import _LIBM, Arith, F32, d24_to_float, decode_normal, triangle_records, unorm16_to_float  # noqa: F401
+from gtao_rt_reference import Arith, F32, triangle_records  # noqa: F401
 from probe_reference import float_to_unorm
+from shadow_mask_rt_reference import pixel_surface
 
 FILL_MISSES = 1
 
@@ -21,25 +23,9 @@ def pixel_rays(ar, depth_words, normal_codes, inverse_camera, fovy, aspect, znea
     """steps 1-12 for every pixel: -> (sky [h, w] bool, origin [h, w, 3], dir [h, w, 3], cast [h, w] bool: dot(n, dir) > 0).
     depth_words: raw D24S8 texels [h, w] (the top byte is ignored); normal_codes: raw RG16_UNORM texels [h, w, 2];
     inverse_camera: 4x4 maths convention."""
-    h, w = depth_words.shape
-    gy, gx = np.mgrid[0:h, 0:w]
-    uvx = ((gx.astype(F32) + F32(0.5)) / F32(w)).astype(F32)
-    uvy = ((gy.astype(F32) + F32(0.5)) / F32(h)).astype(F32)
-    d = d24_to_float(np.asarray(depth_words, np.uint32))
-    sky = d >= F32(1.0)
-    tg = F32(_LIBM.tanf(float(F32(fovy) / F32(2.0))))
-    n_, f_ = F32(znear), F32(zfar)
+    sky, world, normal, origin = pixel_surface(ar, depth_words, normal_codes, inverse_camera, fovy, aspect, znear, zfar, normal_offset)
     with np.errstate(all="ignore"):
-        z = (n_ * f_) / ar.cfma(d, f_ - n_, -f_)
-        xd = ar.cfma(F32(2.0), uvx, F32(-1.0))
-        yd = ar.cfma(F32(2.0), uvy, F32(-1.0))
-        vx = -xd * ((z * F32(aspect)) * tg)
-        vy = -yd * (z * tg)
-        M = np.asarray(inverse_camera, F32)
-        world = np.stack([ar.cfma(M[r, 3], F32(1.0), ar.cfma(M[r, 2], z, ar.cfma(M[r, 1], vy, M[r, 0] * vx))) for r in range(3)], axis=-1).astype(F32)
-        normal = decode_normal(ar, unorm16_to_float(np.asarray(normal_codes))).astype(F32)
-        origin = ar.madd(world, F32(normal_offset), normal).astype(F32)
-        eye = M[:3, 3]  # the translation column, read
+        eye = np.asarray(inverse_camera, F32)[:3, 3]  # the translation column, read
         view = (world - eye[None, None, :]).astype(F32)
         s = -(F32(2.0) * ar.dot(normal, view))
         refl = ar.cfma(np.broadcast_to(s[..., None], normal.shape), normal, view)  # reflect(): V + (-(2 n.V)) n, one multiply-add each

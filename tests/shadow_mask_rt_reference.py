@@ -11,9 +11,10 @@ from gtao_rt_reference import (_LIBM, Arith, F32, brute_force_any_hit, d24_to_fl
                                unorm16_to_float)
 
 
-def pixel_origins(ar, depth_words, normal_codes, inverse_camera, fovy, aspect, znear, zfar, normal_offset):
-    """steps 1-4 for every pixel: -> (sky [h, w] bool, origin [h, w, 3], normal [h, w, 3]).  depth_words: raw D24S8 texels
-    [h, w] (the top byte is ignored); normal_codes: raw RG16_UNORM texels [h, w, 2]; inverse_camera: 4x4 maths convention."""
+def pixel_surface(ar, depth_words, normal_codes, inverse_camera, fovy, aspect, znear, zfar, normal_offset):
+    """steps 1-4 for every pixel: -> (sky [h, w] bool, world [h, w, 3], normal [h, w, 3], origin [h, w, 3]).  depth_words: raw
+    D24S8 texels [h, w] (the top byte is ignored); normal_codes: raw RG16_UNORM texels [h, w, 2]; inverse_camera: 4x4 maths
+    convention.  Shared with tests/reflections_rt_reference.py (csrc/rt_surface.hpp is what the two kernels share)."""
     h, w = depth_words.shape
     gy, gx = np.mgrid[0:h, 0:w]
     uvx = ((gx.astype(F32) + F32(0.5)) / F32(w)).astype(F32)
@@ -29,10 +30,16 @@ def pixel_origins(ar, depth_words, normal_codes, inverse_camera, fovy, aspect, z
         vx = -xd * ((z * F32(aspect)) * tg)
         vy = -yd * (z * tg)
         M = np.asarray(inverse_camera, F32)
-        world = np.stack([ar.cfma(M[r, 3], F32(1.0), ar.cfma(M[r, 2], z, ar.cfma(M[r, 1], vy, M[r, 0] * vx))) for r in range(3)], axis=-1)
-        normal = decode_normal(ar, unorm16_to_float(np.asarray(normal_codes)))
-        origin = ar.madd(world.astype(F32), F32(normal_offset), normal)
-    return sky, origin.astype(F32), normal.astype(F32)
+        world = np.stack([ar.cfma(M[r, 3], F32(1.0), ar.cfma(M[r, 2], z, ar.cfma(M[r, 1], vy, M[r, 0] * vx))) for r in range(3)], axis=-1).astype(F32)
+        normal = decode_normal(ar, unorm16_to_float(np.asarray(normal_codes))).astype(F32)
+        origin = ar.madd(world, F32(normal_offset), normal).astype(F32)
+    return sky, world, normal, origin
+
+
+def pixel_origins(*args):
+    """pixel_surface as the shadow pass needs it: -> (sky, origin, normal)"""
+    sky, _, normal, origin = pixel_surface(*args)
+    return sky, origin, normal
 
 
 def light_rays(ar, origin, normal, light):

@@ -119,3 +119,30 @@ def test_query_of_an_empty_structure():
         assert int(out.sum()) == 0
     finally:
         accel.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_partial_waves_and_blocks(n):
+    """the first n rays of a shuffle of every ray class of the box scene of tests/test_accel_occluded_gpu.py: a partial wave, a
+    whole one, one lane more, and a partial second block; the entries past the rays stay untouched"""
+    import torch
+
+    from test_accel_occluded_gpu import GUARD, _case
+
+    tris, o, d, tag, rec = _case("box")
+    order = np.random.default_rng([23, n]).permutation(len(o))[:n]
+    o, d, tag = np.ascontiguousarray(o[order]), np.ascontiguousarray(d[order]), tag[order]
+    accel = abi.Accel(tris)
+    try:
+        out = torch.full((n + 64,), GUARD, dtype=torch.int32, device="cuda")
+        accel.query(torch.from_numpy(o).to("cuda"), torch.from_numpy(d).to("cuda"), 0.0, 1.0, out, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        h = out.cpu().numpy()
+        assert (h[n:] == GUARD).all(), "entries past the last ray were written"
+        assert set(np.unique(h[:n]).tolist()) <= {0, 1}
+        want = ref.brute_force_any_hit(o, d, 0.0, 1.0, rec)
+        bad = np.nonzero(h[:n].astype(bool) != want)[0]
+        assert len(bad) == 0, f"{n} rays: {len(bad)} differ, e.g. {[(int(i), str(tag[i]), int(h[i]), bool(want[i])) for i in bad[:8]]}"
+    finally:
+        accel.close()

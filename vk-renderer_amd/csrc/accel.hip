@@ -1,23 +1,17 @@
 // accel.hip — the scene's acceleration structure and the ray query: vkr_accel_layout / _create / _destroy / _info (host),
 // vkr_accel_query and vkr_accel_occluded (any-hit of arbitrary rays, on the walk for short and for long rays) and program
-// "gtao_rt_main" (gtao.cpp:150-196 + gtao/rt_main.frag).  The device side of the query — AccelView, the frozen triangle test and
-// the two walks — is accel_traverse.hpp, shared with shadow_mask_rt.hip.
+// "gtao_rt_main" (gtao.cpp:150-196 + gtao/rt_main.frag).  The query itself — AccelView, the frozen triangle test, the walks and
+// what the ray-level entries share — is accel_traverse.hpp.
 //
 // MI355X has no ray-tracing hardware, so the traversal is software.  The hierarchy is one level over world-space triangles
 // (an any-hit query of a static scene gains nothing from instancing); it is built once per scene on the host (binned SAH,
 // deterministic) and read-only on the device.
 //
-// Traversal: a wave of 64 rays walks the hierarchy TOGETHER.  Node and triangle addresses are wave-uniform (scalar loads),
-// the node order lives on a per-wave stack in LDS (no private array: nothing goes to scratch), each lane tests its own
-// segment against the node box and the wave descends when any live lane overlaps it (a ballot), lanes retire on their first
-// hit and the wave leaves when every lane has hit or the stack is empty.  gtao_rt_main runs one wave per pixel, one lane per
-// direction: the 64 rays of a pixel share their origin and are 0.2 long, so the wave visits few nodes.
-//
-// Exactness: the frozen triangle test (ray_hits_triangle) accepts a hit only if the point o + t * d it computes lies in the
-// triangle's widened box.  Node boxes are exact unions of those boxes, and a lane's segment box is spanned by o + tmin * d and
-// o + tmax * d computed the same way (mul, then add: rounding is monotonic, so every such point of t in [tmin, tmax] lies
-// between them).  A node box that contains a hit point therefore always overlaps the segment box: no cull can discard a
-// triangle the test would hit, and the result is that of a brute-force loop over all triangles (tests/test_accel_gpu.py).
+// Traversal: a wave of 64 rays walks the hierarchy TOGETHER, with scalar loads of nodes and triangles and the node order on a
+// per-wave stack in LDS (no private array: nothing goes to scratch).  gtao_rt_main runs one wave per pixel, one lane per
+// direction: the 64 rays of a pixel share their origin and are 0.2 long, so the wave visits few nodes.  No cull of a walk can
+// discard a triangle the frozen test would hit (the argument stands beside LaneRay in accel_traverse.hpp), so the result is
+// that of a brute-force loop over all triangles (tests/test_accel_gpu.py).
 #include "vkr_host.hpp"
 #include "accel_traverse.hpp"
 #include "gtao_slice.hpp"
@@ -30,33 +24,20 @@ namespace vkr {
 constexpr int ACCEL_BINS = 16;
 constexpr uint32_t ACCEL_MAX_LEAF = 8;
 
+// the two any-hit ray-level entries: ray i of the batch on the walk for short rays and on the walk for long rays
 __global__ __launch_bounds__(256) void k_accel_query(AccelView a, const float* org, const float* dir, float tmin, float tmax,
                                                      uint32_t n, uint32_t* out) {
   __shared__ uint32_t stacks[4][ACCEL_STACK];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool live = i < n;
-  f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);
-  if (live) {
-    o = mk3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
-    d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-  }
-  const bool hit = wave_any_hit(a, o, d, tmin, tmax, live, stacks[threadIdx.x >> 6]);
-  if (live) out[i] = hit ? 1u : 0u;
+  const RayLane r = load_ray_lane(org, dir, n, stacks);
+  const bool hit = wave_any_hit(a, r.o, r.d, tmin, tmax, r.live, r.stack);
+  if (r.live) out[r.i] = hit ? 1u : 0u;
 }
-
-// vkr_accel_occluded: k_accel_query on the walk for long rays (accel_traverse.hpp), the ray-level entry of the per-ray cull
 __global__ __launch_bounds__(256) void k_accel_occluded(AccelView a, const float* org, const float* dir, float tmin, float tmax,
                                                         uint32_t n, uint32_t* out) {
   __shared__ uint32_t stacks[4][ACCEL_STACK];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool live = i < n;
-  f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);
-  if (live) {
-    o = mk3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
-    d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-  }
-  const bool hit = wave_any_hit_ray(a, o, d, tmin, tmax, live, stacks[threadIdx.x >> 6]);
-  if (live) out[i] = hit ? 1u : 0u;
+  const RayLane r = load_ray_lane(org, dir, n, stacks);
+  const bool hit = wave_any_hit_ray(a, r.o, r.d, tmin, tmax, r.live, r.stack);
+  if (r.live) out[r.i] = hit ? 1u : 0u;
 }
 
 // ---- gtao_rt_main ---------------------------------------------------------------------------------------------------------
@@ -302,23 +283,17 @@ extern "C" int vkr_accel_info(const vkr_accel* accel, uint32_t* node_count, uint
 
 extern "C" int vkr_accel_query(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
                                uint32_t* out_hit, void* stream) {
-  if (!accel) { set_error("accel_query: NULL acceleration structure"); return VKR_ERR_NULL; }
+  VKR_TRY(check_ray_batch("accel_query", accel, origins, dirs, out_hit, n));
   if (n == 0) return VKR_OK;
-  if (!origins || !dirs || !out_hit) { set_error("accel_query: NULL rays or output"); return VKR_ERR_NULL; }
-  if (n > (1u << 30)) { set_error("accel_query: %u rays, at most 2^30 per call", n); return VKR_ERR_EXTENT; }
-  const AccelView a{accel->nodes, accel->tris, accel->node_count};
-  hipLaunchKernelGGL(k_accel_query, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, origins, dirs, tmin, tmax, n, out_hit);
+  hipLaunchKernelGGL(k_accel_query, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, view_of(accel), origins, dirs, tmin, tmax, n, out_hit);
   return launch_status("accel_query");
 }
 
 extern "C" int vkr_accel_occluded(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
                                   uint32_t* out_hit, void* stream) {
-  if (!accel) { set_error("accel_occluded: NULL acceleration structure"); return VKR_ERR_NULL; }
+  VKR_TRY(check_ray_batch("accel_occluded", accel, origins, dirs, out_hit, n));
   if (n == 0) return VKR_OK;
-  if (!origins || !dirs || !out_hit) { set_error("accel_occluded: NULL rays or output"); return VKR_ERR_NULL; }
-  if (n > (1u << 30)) { set_error("accel_occluded: %u rays, at most 2^30 per call", n); return VKR_ERR_EXTENT; }
-  const AccelView a{accel->nodes, accel->tris, accel->node_count};
-  hipLaunchKernelGGL(k_accel_occluded, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, origins, dirs, tmin, tmax, n, out_hit);
+  hipLaunchKernelGGL(k_accel_occluded, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, view_of(accel), origins, dirs, tmin, tmax, n, out_hit);
   return launch_status("accel_occluded");
 }
 
@@ -335,7 +310,7 @@ extern "C" int vkr_gtao_rt_main(const vkr_gtao_rt_params* params, const vkr_img*
   load_mat(a.camera_to_world, params->camera_to_world);
   load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
   fill_slice_table(a.rot_cs, push->rotation, 0.0f);  // rt_main.frag:89: angle = 2 PI (rotation + gtao_direction(pixel))
-  a.accel = AccelView{accel->nodes, accel->tris, accel->node_count};
+  a.accel = view_of(accel);
   a.directions = (const float4*)directions;
   const uint32_t pixels = (uint32_t)a.out.w * (uint32_t)a.out.h;
   hipLaunchKernelGGL(k_gtao_rt, dim3((pixels + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);

@@ -1,11 +1,8 @@
 // accel_closest.hip — vkr_accel_closest: the closest hit of arbitrary rays, the ray-level entry of wave_closest_hit
 // (accel_traverse.hpp; DESIGN_NUMERICS.md, "Ray query, closest hit").  Where vkr_accel_query / vkr_accel_occluded say whether
 // anything is hit, this says where (t), on which input triangle (index) and at which barycentrics (u, v), so that something can
-// be shaded there: program "reflections_rt" (reflections_rt.hip) is the first consumer.  The structure, its build and the two
-// any-hit walks are untouched (accel.hip).
-//
-// A wave holds 64 consecutive rays and a block four waves with one 64-word stack each in LDS, as k_accel_occluded; a ray's
-// answer is one 16-byte store.
+// be shaded there: program "reflections_rt" (reflections_rt.hip) is the first consumer.  The kernel is k_accel_occluded's with
+// another walk; a ray's answer is one 16-byte store.
 #include "vkr_host.hpp"
 #include "accel_traverse.hpp"
 
@@ -27,16 +24,10 @@ namespace vkr {
 __global__ __launch_bounds__(256) void VKR_CLOSEST_KERNEL(AccelView a, const float* org, const float* dir, float tmin, float tmax,
                                                        uint32_t n, vkr_accel_hit* out) {
   __shared__ uint32_t stacks[4][ACCEL_STACK];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool live = i < n;
-  f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);
-  if (live) {
-    o = mk3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
-    d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-  }
+  const RayLane r = load_ray_lane(org, dir, n, stacks);
   vkr_accel_hit h;
-  VKR_CLOSEST_WALK(a, o, d, tmin, tmax, live, stacks[threadIdx.x >> 6], &h);
-  if (live) store_u32x4((uint8_t*)(out + i), __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v), h.index);
+  VKR_CLOSEST_WALK(a, r.o, r.d, tmin, tmax, r.live, r.stack, &h);
+  if (r.live) store_u32x4((uint8_t*)(out + r.i), __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v), h.index);
 }
 
 }  // namespace vkr
@@ -46,12 +37,9 @@ using namespace vkr;
 extern "C" int VKR_CLOSEST_ENTRY(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
                                  vkr_accel_hit* out_hits, void* stream) {
   static_assert(sizeof(vkr_accel_hit) == 16, "vkr_accel_hit: three floats and an index, one 16-byte store");
-  if (!accel) { set_error("accel_closest: NULL acceleration structure"); return VKR_ERR_NULL; }
+  VKR_TRY(check_ray_batch("accel_closest", accel, origins, dirs, out_hits, n));
   if (n == 0) return VKR_OK;
-  if (!origins || !dirs || !out_hits) { set_error("accel_closest: NULL rays or output"); return VKR_ERR_NULL; }
-  if (n > (1u << 30)) { set_error("accel_closest: %u rays, at most 2^30 per call", n); return VKR_ERR_EXTENT; }
   if (((uintptr_t)out_hits & 15u) != 0) { set_error("accel_closest: out_hits must be 16-byte aligned"); return VKR_ERR_LAYOUT; }
-  const AccelView a{accel->nodes, accel->tris, accel->node_count};
-  hipLaunchKernelGGL(VKR_CLOSEST_KERNEL, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, origins, dirs, tmin, tmax, n, out_hits);
+  hipLaunchKernelGGL(VKR_CLOSEST_KERNEL, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, view_of(accel), origins, dirs, tmin, tmax, n, out_hits);
   return launch_status("accel_closest");
 }

@@ -13,18 +13,15 @@
 // walk with live = false.  The hit is shaded after the walk: the attribute record, the texture table and the four texels are
 // not alive while the wave descends.
 #include "raster_common.hpp"
-#include "accel_traverse.hpp"
+#include "rt_surface.hpp"
 
 #include <cmath>
 
 namespace vkr {
 
 // All of it wave-uniform: a kernel argument, read through scalar loads
-struct ReflectRtArgs {
-  Tex depth, normal, rays, out;
-  Mat4 inverse_camera;
-  Proj pr;
-  AccelView accel;
+struct ReflectRtArgs : RtSurfaceArgs {
+  Tex rays;                       // read in fill mode only
   const vkr_hit_attrib* attribs;  // one per input triangle
   const Pyramid* textures;        // [texture_count], in scratch
   uint32_t texture_count, texture_lod, fill_misses;
@@ -45,40 +42,28 @@ VKR_DEV uint32_t shade_hit(const ReflectRtArgs& a, const vkr_accel_hit& h, const
   return float_to_unorm8(c.x) | (float_to_unorm8(c.y) << 8) | (float_to_unorm8(c.z) << 16);
 }
 
-// one lane per pixel of out (== every other image's extent); wave w of the block is the 8 x 8 tile (w & 1, w >> 1) of its 16 x 16
 __global__ __launch_bounds__(256) void k_reflections_rt(ReflectRtArgs a) {
   __shared__ uint32_t stacks[4][ACCEL_STACK];
   __shared__ float s_lut[VKR_SRGB_LUT_SIZE];
   srgb_lut_stage(s_lut, threadIdx.x, 256);
   __syncthreads();
-  const i2 blk = xcd_block<8, 8>();  // chunks of 128 x 128 pixels
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int lx = blk.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int ly = blk.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const bool inside = lx < a.out.w && ly < a.out.h;
-  const int cx = inside ? lx : 0, cy = inside ? ly : 0;  // a lane outside the image reads texel (0, 0) and writes nothing
-  const float d = d24_to_float(*(const uint32_t*)(a.depth.p + toff(a.depth, cx, cy, 4)));
-  const bool geometry = inside && d < 1.0f;
+  const RtPixel p = rt_pixel(a);
   bool keep = false;  // fill mode: the screen-space ray of this pixel is a valid hit, the filter's texel stays
-  if (a.fill_misses) keep = geometry && (texel_ptr<const uint2>(a.rays, cx, cy)->y >> 16) != 65535u;
-  const bool trace = geometry && !keep;
+  if (a.fill_misses) keep = p.geometry && (texel_ptr<const uint2>(a.rays, p.cx, p.cy)->y >> 16) != 65535u;
+  const bool trace = p.geometry && !keep;
   uint32_t result = 0u;
   if (__ballot(trace) != 0ull) {  // the whole wave
-    const f2 uv = mk2(pixel_centre_uv(cx, (float)a.out.w), pixel_centre_uv(cy, (float)a.out.h));
-    const f3 view = reconstruct_view_vec(uv, d, a.pr);
-    const f3 world = xyz(mul(a.inverse_camera, mk4(view.x, view.y, view.z, 1.0f)));
-    const f3 n = decode_normal(FmtRG16U::load(a.normal, cx, cy));
-    const f3 origin = madd(world, a.normal_offset, n);
+    const RtSurface s = rt_surface(a, p, a.normal_offset);
     const f3 eye = mk3(a.inverse_camera.m[12], a.inverse_camera.m[13], a.inverse_camera.m[14]);
-    const f3 dir = normalize(reflect(world - eye, n));
-    const bool cast = trace && dot(n, dir) > 0.0f;  // false for a surface seen from behind, a grazing zero and any NaN
+    const f3 dir = normalize(reflect(s.world - eye, s.n));
+    const bool cast = trace && dot(s.n, dir) > 0.0f;  // false for a surface seen from behind, a grazing zero and any NaN
     if (__ballot(cast) != 0ull) {  // the whole wave: lanes without a ray follow the walk
       vkr_accel_hit h;
-      wave_closest_hit(a.accel, origin, dir, a.tmin, a.max_distance, cast, stacks[wave], &h);
+      wave_closest_hit(a.accel, s.origin, dir, a.tmin, a.max_distance, cast, stacks[p.wave], &h);
       if (cast && h.index != 0xFFFFFFFFu) result = shade_hit(a, h, s_lut);
     }
   }
-  if (inside && !keep) *texel_ptr<uint32_t>(a.out, lx, ly) = result;
+  if (p.inside && !keep) *texel_ptr<uint32_t>(a.out, p.lx, p.ly) = result;
 }
 
 // the scratch: the texture table
@@ -104,11 +89,7 @@ extern "C" int vkr_reflections_rt(const vkr_img* depth, const vkr_img* normal, c
   static_assert(sizeof(vkr_reflect_rt_params) == 112, "vkr_reflect_rt_params: a matrix, eight floats / words, the flags and three words");
   static_assert(sizeof(vkr_hit_attrib) == 32, "vkr_hit_attrib: three uv pairs and two words");
   hipStream_t stream = (hipStream_t)stream_;
-  if (!depth) { set_error("reflections_rt: depth is NULL"); return VKR_ERR_NULL; }
-  if (!normal) { set_error("reflections_rt: normal is NULL"); return VKR_ERR_NULL; }
-  if (!accel) { set_error("reflections_rt: NULL acceleration structure"); return VKR_ERR_NULL; }
-  if (!params) { set_error("reflections_rt: params is NULL"); return VKR_ERR_NULL; }
-  if (!out_reflections) { set_error("reflections_rt: out_reflections is NULL"); return VKR_ERR_NULL; }
+  VKR_TRY(rt_surface_require("reflections_rt", "out_reflections", depth, normal, accel, params, out_reflections));
   if (!scratch) { set_error("reflections_rt: scratch is NULL"); return VKR_ERR_NULL; }
   if (params->flags & ~VKR_REFLECT_RT_FILL_MISSES) { set_error("reflections_rt: unknown flag bits 0x%x", params->flags & ~VKR_REFLECT_RT_FILL_MISSES); return VKR_ERR_EXTENT; }
   const bool fill = (params->flags & VKR_REFLECT_RT_FILL_MISSES) != 0;
@@ -123,24 +104,14 @@ extern "C" int vkr_reflections_rt(const vkr_img* depth, const vkr_img* normal, c
   if (params->reserved[0] != 0 || params->reserved[1] != 0 || params->reserved[2] != 0) { set_error("reflections_rt: reserved must be 0"); return VKR_ERR_EXTENT; }
   if (std::isnan(params->tmin)) { set_error("reflections_rt: tmin is NaN"); return VKR_ERR_EXTENT; }
   if (std::isnan(params->max_distance)) { set_error("reflections_rt: max_distance is NaN"); return VKR_ERR_EXTENT; }
-  const char* why = "windows are not supported (the rays reach anywhere: a single-GPU pass)";
   ReflectRtArgs a;
-  VKR_TRY(make_tex(depth, 0, VKR_FMT_D24_UNORM_S8, "reflections_rt.depth", &a.depth));
-  VKR_TRY(make_tex(normal, 0, VKR_FMT_RG16_UNORM, "reflections_rt.normal", &a.normal));
-  VKR_TRY(make_tex(out_reflections, 0, VKR_FMT_RGBA8_UNORM, "reflections_rt.out_reflections", &a.out));
-  VKR_TRY(require_whole_frame(a.depth, "reflections_rt: depth", why));
-  VKR_TRY(require_whole_frame(a.normal, "reflections_rt: normal", why));
-  VKR_TRY(require_whole_frame(a.out, "reflections_rt: out_reflections", why, 65535));
+  VKR_TRY(rt_surface_bind("reflections_rt", "out_reflections", depth, normal, accel, params, out_reflections, &a));
   a.rays = a.out;  // not read without the flag
   if (fill) {
     VKR_TRY(make_tex(rays, 0, VKR_FMT_RGBA16_UNORM, "reflections_rt.rays", &a.rays));
-    VKR_TRY(require_whole_frame(a.rays, "reflections_rt: rays", why));
+    VKR_TRY(require_whole_frame(a.rays, "reflections_rt: rays", RT_WHOLE_FRAME));
   }
-  if (a.depth.w != a.out.w || a.depth.h != a.out.h || a.normal.w != a.out.w || a.normal.h != a.out.h || (fill && (a.rays.w != a.out.w || a.rays.h != a.out.h))) {
-    set_error("reflections_rt: depth is %dx%d, normal %dx%d, out_reflections %dx%d%s: one extent expected", a.depth.w, a.depth.h, a.normal.w,
-              a.normal.h, a.out.w, a.out.h, fill ? ", rays another" : "");
-    return VKR_ERR_EXTENT;
-  }
+  VKR_TRY(rt_surface_one_extent("reflections_rt", "out_reflections", a, fill && (a.rays.w != a.out.w || a.rays.h != a.out.h), fill ? ", rays another" : ""));
   vkr_raster_scene sc {};
   sc.textures = textures; sc.texture_count = texture_count;
   std::vector<Pyramid> pyramids;
@@ -152,9 +123,6 @@ extern "C" int vkr_reflections_rt(const vkr_img* depth, const vkr_img* normal, c
     set_error("reflections_rt: scratch too small (%llu bytes, %llu needed)", (unsigned long long)scratch_bytes, (unsigned long long)lay.total);
     return VKR_ERR_EXTENT;
   }
-  load_mat(a.inverse_camera, params->inverse_camera);
-  load_proj(a.pr, params->fovy, params->aspect, params->znear, params->zfar);
-  a.accel = AccelView{accel->nodes, accel->tris, accel->node_count};
   a.attribs = attribs;
   a.textures = (const Pyramid*)((uint8_t*)scratch + lay.textures);
   a.texture_count = texture_count; a.texture_lod = params->texture_lod; a.fill_misses = fill ? 1u : 0u;
