@@ -696,6 +696,44 @@ typedef struct vkr_shadow_rt_params {   /* 160 bytes */
 int vkr_shadow_mask_rt(const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel, const vkr_shadow_rt_params* params,
                        const vkr_img* out_mask, void* stream);
 
+/* ---- alpha cutouts in the ray query (DESIGN_NUMERICS.md, "Ray query, cutouts") ---------------------------------------------------
+ * The rasterisers discard a fragment whose albedo alpha is 0; these entries ask the same of a ray.  A CANDIDATE is a triangle
+ * `index` that the frozen test accepts for the ray at (t, u, v).  It is TRANSPARENT for that ray when a = attribs[index] has
+ * a.albedo_index < texture_count, bit a.albedo_index of opaque_texture_mask is clear, and the alpha of the bilinear REPEAT sample
+ * of level min(alpha_lod, levels - 1) of textures[a.albedo_index] at uv_hit is == 0.0f; uv_hit and the sample are those of
+ * vkr_reflections_rt (w = (1 - u) - v, (w uv0 + u uv1) + v uv2, every operation rounded on its own; alpha decoded as UNORM8 and
+ * mixed in the sampler's order).  A compare with a NaN is false: opaque.  An untextured triangle is opaque.  A set mask bit means
+ * "do not test this texture": the triangle is opaque whatever its texels hold (set it for textures without an alpha-0 texel and
+ * the fetch is skipped; a wrong hint is a defined answer, not an error).
+ *   any hit:     does a triangle exist that the frozen test accepts and that is not transparent at its own (u, v)?
+ *   closest hit: of those triangles the one with the smallest fp32 t, of equal t the smallest input index.
+ * Both are defined over ALL triangles: the answers do not depend on the hierarchy.                                            */
+typedef struct vkr_ray_cutout { uint32_t alpha_lod; uint32_t opaque_texture_mask; } vkr_ray_cutout;  /* 8 bytes */
+/* the device scratch of one call of any _cutout entry (the texture table; equal to vkr_reflections_rt_scratch_bytes) */
+uint64_t vkr_accel_cutout_scratch_bytes(uint32_t texture_count);
+/* vkr_accel_occluded / vkr_accel_closest with the queries above: their arguments and gates, plus those vkr_reflections_rt has
+ * for attribs (attrib_count == the structure's triangle count), textures (whole-frame RGBA8_SRGB chains, at most 32: the mask is
+ * one word) and scratch; a NULL cutout is VKR_ERR_NULL; n == 0 is VKR_OK whatever else is passed.  With texture_count 0 or a
+ * mask of all ones the outputs are those of the opaque entries, bit for bit.                                                  */
+int vkr_accel_occluded_cutout(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                              const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
+                              const vkr_ray_cutout* cutout, uint32_t* out_hit, void* scratch, uint64_t scratch_bytes, void* stream);
+int vkr_accel_closest_cutout(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
+                             const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
+                             const vkr_ray_cutout* cutout, vkr_accel_hit* out_hits, void* scratch, uint64_t scratch_bytes, void* stream);
+/* vkr_shadow_mask_rt with "the frozen any-hit" replaced by the any hit above: the light passes through holes.  Every channel is
+ * at least vkr_shadow_mask_rt's on the same input.  The gates of vkr_shadow_mask_rt, then those of the two entries above.     */
+int vkr_shadow_mask_rt_cutout(const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel, const vkr_hit_attrib* attribs,
+                              uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count, const vkr_shadow_rt_params* params,
+                              const vkr_ray_cutout* cutout, const vkr_img* out_mask, void* scratch, uint64_t scratch_bytes, void* stream);
+/* vkr_reflections_rt with "the closest hit" replaced by the closest hit above: the mirror ray goes on through holes and what it
+ * meets behind them is shaded as vkr_reflections_rt shades a hit (at params->texture_lod; alpha_lod only decides the holes).
+ * The gates of vkr_reflections_rt, and a NULL cutout is VKR_ERR_NULL.                                                          */
+int vkr_reflections_rt_cutout(const vkr_img* depth, const vkr_img* normal, const vkr_img* rays, const vkr_accel* accel,
+                              const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
+                              const vkr_reflect_rt_params* params, const vkr_ray_cutout* cutout, const vkr_img* out_reflections,
+                              void* scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
  * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one

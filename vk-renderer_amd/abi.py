@@ -287,6 +287,11 @@ class ReflectRtParams(C.Structure):  # vkr_reflect_rt_params, 112 bytes
                 ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+# ---- alpha cutouts in the ray query ----
+class RayCutout(C.Structure):  # vkr_ray_cutout, 8 bytes
+    _fields_ = [("alpha_lod", C.c_uint32), ("opaque_texture_mask", C.c_uint32)]
+
+
 TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
 
 
@@ -426,6 +431,18 @@ def product():
         lib.vkr_reflections_rt.argtypes = [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ReflectRtParams), _IMG,
                                            C.c_void_p, C.c_uint64, C.c_void_p]
         lib.vkr_reflections_rt.restype = C.c_int
+        # alpha cutouts in the ray query (checked against the numpy restatement tests/ray_cutout_reference.py)
+        cutout_tail = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(RayCutout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.vkr_accel_cutout_scratch_bytes.argtypes = [C.c_uint32]
+        lib.vkr_accel_cutout_scratch_bytes.restype = C.c_uint64
+        lib.vkr_accel_occluded_cutout.argtypes = lib.vkr_accel_query.argtypes[:6] + cutout_tail
+        lib.vkr_accel_closest_cutout.argtypes = lib.vkr_accel_query.argtypes[:6] + cutout_tail
+        lib.vkr_shadow_mask_rt_cutout.argtypes = [_IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ShadowRtParams), P(RayCutout),
+                                                  _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.vkr_reflections_rt_cutout.argtypes = [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ReflectRtParams),
+                                                  P(RayCutout), _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
+        for name in ("accel_occluded_cutout", "accel_closest_cutout", "shadow_mask_rt_cutout", "reflections_rt_cutout"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
         lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
@@ -687,6 +704,76 @@ def reflections_rt(depth, normal, rays, accel, attribs, attrib_count, textures, 
     handle = accel.handle if accel is not None else None
     check(lib.vkr_reflections_rt(ref(depth), ref(normal), ref(rays), handle, attribs, int(attrib_count), textures, int(texture_count),
                                  ref(params), ref(out_reflections), scratch, int(scratch_bytes), stream), lib)
+
+
+def ray_cutout(alpha_lod=0, opaque_texture_mask=0):
+    """RayCutout: the mip level whose alpha decides a hole (clamped to each texture's chain) and the textures that are not to be
+    tested (bit i set: textures[i] is opaque whatever its texels hold; scene_opaque_texture_mask(scene) for a Scene)"""
+    return RayCutout(int(alpha_lod), int(opaque_texture_mask) & 0xFFFFFFFF)
+
+
+def scene_opaque_texture_mask(sc):
+    """The opaque_texture_mask of a scene.Scene: bit i set when no texel of any level of textures[i] has alpha 0 (what makes a
+    draw carry VKR_RASTER_DRAW_OPAQUE_ALBEDO): such a texture can make no hole, so the ray query need not fetch from it."""
+    mask = 0
+    for i, levels in enumerate(sc.textures[:32]):
+        if all(int(lv[..., 3].min()) > 0 for lv in levels):
+            mask |= 1 << i
+    return mask
+
+
+def accel_cutout_scratch_bytes(texture_count):
+    """vkr_accel_cutout_scratch_bytes: the device scratch of one call of a _cutout entry (the texture table)"""
+    return int(product().vkr_accel_cutout_scratch_bytes(int(texture_count)))
+
+
+def _cutout_tail(attribs, attrib_count, textures, texture_count, cutout):
+    return attribs, int(attrib_count), textures, int(texture_count), (C.byref(cutout) if cutout is not None else None)
+
+
+def accel_occluded_cutout(accel, origins, dirs, tmin, tmax, attribs, attrib_count, textures, texture_count, cutout, out, scratch, scratch_bytes,
+                          stream=None):
+    """vkr_accel_occluded_cutout: accel_occluded where a triangle whose albedo alpha at the hit is 0 is not there.  attribs: device
+    pointer to attrib_count vkr_hit_attrib records (scene_triangle_attributes order); textures: a (VkrImg * n) host array of
+    RGBA8_SRGB mip chains or None; cutout: a RayCutout; scratch: device pointer of accel_cutout_scratch_bytes(texture_count)."""
+    lib = product()
+    n = int(origins.shape[0])
+    check(lib.vkr_accel_occluded_cutout(accel.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n,
+                                        *_cutout_tail(attribs, attrib_count, textures, texture_count, cutout), out.data_ptr(), scratch,
+                                        int(scratch_bytes), stream), lib)
+
+
+def accel_closest_cutout(accel, origins, dirs, tmin, tmax, attribs, attrib_count, textures, texture_count, cutout, out, scratch, scratch_bytes,
+                         stream=None):
+    """vkr_accel_closest_cutout: Accel.closest among the triangles that are not transparent at their own hit; the other arguments
+    as accel_occluded_cutout, out as Accel.closest (n 16-byte records)."""
+    lib = product()
+    n = int(origins.shape[0])
+    check(lib.vkr_accel_closest_cutout(accel.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n,
+                                       *_cutout_tail(attribs, attrib_count, textures, texture_count, cutout), out.data_ptr(), scratch,
+                                       int(scratch_bytes), stream), lib)
+
+
+def shadow_mask_rt_cutout(depth, normal, accel, attribs, attrib_count, textures, texture_count, params, cutout, out_mask, scratch, scratch_bytes,
+                          stream=None):
+    """vkr_shadow_mask_rt_cutout: shadow_mask_rt whose rays pass through the holes of alpha-tested triangles; attribs, textures,
+    cutout and scratch as accel_occluded_cutout.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_shadow_mask_rt_cutout(ref(depth), ref(normal), handle, attribs, int(attrib_count), textures, int(texture_count), ref(params),
+                                        ref(cutout), ref(out_mask), scratch, int(scratch_bytes), stream), lib)
+
+
+def reflections_rt_cutout(depth, normal, rays, accel, attribs, attrib_count, textures, texture_count, params, cutout, out_reflections, scratch,
+                          scratch_bytes, stream=None):
+    """vkr_reflections_rt_cutout: reflections_rt whose mirror rays pass through the holes of alpha-tested triangles (cutout: a
+    RayCutout); everything else as reflections_rt.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_reflections_rt_cutout(ref(depth), ref(normal), ref(rays), handle, attribs, int(attrib_count), textures, int(texture_count),
+                                        ref(params), ref(cutout), ref(out_reflections), scratch, int(scratch_bytes), stream), lib)
 
 
 def defered_shading_shadowed(albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, out, push, stream=None):

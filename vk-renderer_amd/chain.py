@@ -476,10 +476,13 @@ class PostFxChain:
         p = abi.shadow_mask_params(self.setup.inv_view, mvps, *self.setup.fazz, radius=radius, bias=bias)
         abi.shadow_mask(self.depth.desc(0, 1), layers, p, self.shadow_mask_out.desc(), self.stream)
 
-    def shadow_mask_rt(self, accel, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN):
+    def shadow_mask_rt(self, accel, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, cutouts=None):
         """vkr_shadow_mask_rt on this chain's depth and normal -> shadow_mask_out (RGBA8_UNORM, channel l = light l): one any-hit
         ray per pixel and light through `accel` (abi.Accel); `lights` 1..4 of (x, y, z, w), w == 1 point, w == 0 directional.
-        Product backend only: the expectation is the numpy restatement tests/shadow_mask_rt_reference.py, not a checker library."""
+        cutouts: None, or (attribs, scene, abi.RayCutout) — the device tensor of abi.scene_triangle_attributes records, the
+        abi.RasterScene of Scene.upload(device) and the setting — for vkr_shadow_mask_rt_cutout: the light passes through holes.
+        Product backend only: the expectation is the numpy restatement tests/shadow_mask_rt_reference.py (tests/
+        ray_cutout_reference.py with cutouts), not a checker library."""
         if self.backend != "product":
             raise RuntimeError("PostFxChain.shadow_mask_rt: only the product backend has the program shadow_mask_rt")
         if self.tiled:
@@ -487,14 +490,30 @@ class PostFxChain:
         if not hasattr(self, "shadow_mask_out"):
             self.shadow_mask_out = ImageBuf(abi.FMT_RGBA8_UNORM, self.depth.width, self.depth.height, device=self.device)
         p = abi.shadow_rt_params(self.setup.inv_view, lights, *self.setup.fazz, normal_offset=normal_offset, tmin=tmin)
-        abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
+        if cutouts is None:
+            abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
+            return
+        attribs, scene, setting = cutouts
+        nbytes, scratch = self._cutout_scratch(scene.texture_count)
+        abi.shadow_mask_rt_cutout(self.depth.desc(0, 1), self.normal.desc(), accel, attribs.data_ptr(), attribs.numel() * attribs.element_size() // 32,
+                                  scene.textures, scene.texture_count, p, setting, self.shadow_mask_out.desc(), scratch, nbytes, self.stream)
+
+    def _cutout_scratch(self, texture_count):
+        """-> (bytes, device pointer) of the texture table of a ray-traced pass (one size for the opaque and the cutout entries)"""
+        import torch
+
+        nbytes = abi.accel_cutout_scratch_bytes(texture_count)
+        if getattr(self, "_reflect_rt_scratch", None) is None or self._reflect_rt_scratch.numel() < nbytes:
+            self._reflect_rt_scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return nbytes, self._reflect_rt_scratch.data_ptr()
 
     def reflections_rt(self, accel, attribs, scene, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN,
-                       max_distance=None, texture_lod=0):
+                       max_distance=None, texture_lod=0, cutouts=None):
         """vkr_reflections_rt on this chain's half-resolution set (depth mip 1, dn, rays) -> reflections (RGBA8_UNORM): the albedo at
         the closest hit of the mirror ray through `accel` (abi.Accel); `attribs`: device tensor of abi.scene_triangle_attributes
         records; `scene`: the abi.RasterScene of Scene.upload(device) whose textures the records index.  fill_misses: only texels
-        whose screen-space ray (rays.w) is invalid are written, in place on what the filter left.  Product backend only: the
+        whose screen-space ray (rays.w) is invalid are written, in place on what the filter left.  cutouts: None, or an abi.RayCutout
+        for vkr_reflections_rt_cutout (the mirror ray passes through holes).  Product backend only: the
         expectation is the numpy restatement tests/reflections_rt_reference.py, not a checker library."""
         if self.backend != "product":
             raise RuntimeError("PostFxChain.reflections_rt: only the product backend has the program reflections_rt")
@@ -507,6 +526,11 @@ class PostFxChain:
             self._reflect_rt_scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         p = abi.reflect_rt_params(self.setup.inv_view, *self.setup.fazz, fill_misses=fill_misses, normal_offset=normal_offset, tmin=tmin,
                                   max_distance=max_distance, texture_lod=texture_lod)
+        if cutouts is not None:
+            abi.reflections_rt_cutout(self.depth.desc(1, 1), self.dn.desc(), self.rays.desc() if fill_misses else None, accel, attribs.data_ptr(),
+                                      attribs.numel() * attribs.element_size() // 32, scene.textures, scene.texture_count, p, cutouts,
+                                      self.reflections.desc(), self._reflect_rt_scratch.data_ptr(), nbytes, self.stream)
+            return
         abi.reflections_rt(self.depth.desc(1, 1), self.dn.desc(), self.rays.desc() if fill_misses else None, accel, attribs.data_ptr(),
                            attribs.numel() * attribs.element_size() // 32, scene.textures, scene.texture_count, p, self.reflections.desc(),
                            self._reflect_rt_scratch.data_ptr(), nbytes, self.stream)

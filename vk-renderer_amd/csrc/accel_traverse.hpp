@@ -1,7 +1,7 @@
 // accel_traverse.hpp — the ray query against the scene's structure: the view of the structure, the frozen triangle test, the
-// set-up and node test of a lane's ray, the any-hit descent, the closest-hit walk, and what the ray-level entries share (the
-// kernel's preamble and the host's refusals).  Every walk gives the answer of the frozen test looped over all triangles
-// (DESIGN_NUMERICS.md, "Ray query", "Ray query, the per-ray cull" and "Ray query, closest hit").
+// set-up and node test of a lane's ray, the candidate filter, the any-hit descent, the closest-hit walk, and what the ray-level
+// entries share (the kernel's preamble and the host's refusals).  Every walk gives the answer of the frozen test looped over all
+// triangles (DESIGN_NUMERICS.md, "Ray query", "Ray query, the per-ray cull", "Ray query, closest hit" and "Ray query, cutouts").
 #ifndef VKR_ACCEL_TRAVERSE_HPP
 #define VKR_ACCEL_TRAVERSE_HPP
 
@@ -122,13 +122,24 @@ struct LaneRay {
   }
 };
 
+// ---- the candidate filter ----------------------------------------------------------------------------------------------------
+// A walk asks its filter whether a candidate — a triangle the frozen test accepts for the lane's ray at (u, v) — is really
+// there.  keep(index, u, v, cand) is called by the whole wave with the wave-uniform input index of the leaf slot; cand: this lane
+// has the candidate; it returns cand, or false where the filter removes it.  The default accepts everything and is never called:
+// the walks without a filter are the code they were before there was one.  ray_cutout.hpp has the filter of alpha cutouts.
+struct AcceptAll {
+  static constexpr bool ALL = true;
+  VKR_DEV bool keep(uint32_t, float, float, bool cand) const { return cand; }
+};
+
 // ---- any hit ---------------------------------------------------------------------------------------------------------------
 // Any-hit of this lane's segment.  Every lane of the wave calls it: node and triangle addresses are wave-uniform, the wave
 // descends when any pending lane enters the node (a ballot), a lane retires on its first hit and the wave leaves when every
 // lane has hit or the stack is empty.  `live` false: the lane has no ray and only follows.  `stack`: ACCEL_STACK words of LDS
-// owned by this wave.
-template <bool SLAB>
-VKR_DEV bool wave_any_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, float tmax, bool live, uint32_t* stack) {
+// owned by this wave.  With a filter a lane retires only on a candidate the filter keeps, and goes on through the rest of the
+// leaf and of the tree otherwise.
+template <bool SLAB, class Filter = AcceptAll>
+VKR_DEV bool wave_any_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, float tmax, bool live, uint32_t* stack, const Filter& filter = Filter()) {
   const LaneRay<SLAB> ray(o, d, tmin, tmax);
   bool pending = live, hit = false;
   if (a.node_count == 0) return false;
@@ -147,7 +158,13 @@ VKR_DEV bool wave_any_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, float
       bool test = overlap;
       for (uint32_t k = 0; k < nd.count; k++) {
         const vkr_accel_tri tr = a.tris[nd.first + k];
-        if (test && ray_hits_triangle(o, d, tmin, tmax, tr)) { hit = true; pending = false; test = false; }
+        if constexpr (Filter::ALL) {
+          if (test && ray_hits_triangle(o, d, tmin, tmax, tr)) { hit = true; pending = false; test = false; }
+        } else {
+          float t = 0.0f, u = 0.0f, v = 0.0f;
+          const bool cand = test && ray_triangle_closest(o, d, tmin, tmax, tr, &t, &u, &v);
+          if (filter.keep(tr.index, u, v, cand)) { hit = true; pending = false; test = false; }
+        }
         if (__ballot(test) == 0ull) break;
       }
       if (__ballot(pending) == 0ull) break;
@@ -173,9 +190,11 @@ VKR_DEV bool wave_any_hit_ray(const AccelView& a, f3 o, f3 d, float tmin, float 
 // (inclusive, so that a triangle of equal t and lower index stays reachable) and enters a node with t_best as t_far.  The walk
 // ends when the stack is empty.  Since the winner is defined by (t, index) alone, the answer does not depend on the order in
 // which nodes are visited.  NEAR_FIRST: at an interior node the child that more lanes enter is visited first (t_best shrinks
-// earlier).
-template <bool NEAR_FIRST>
-VKR_DEV void wave_closest_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, float tmax, bool live, uint32_t* stack, vkr_accel_hit* hit) {
+// earlier).  With a filter only a candidate the filter keeps becomes the best one (a removed candidate never shrinks the far
+// bound); the filter is asked after the (t, index) compare, so a candidate that cannot win costs no fetch.
+template <bool NEAR_FIRST, class Filter = AcceptAll>
+VKR_DEV void wave_closest_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, float tmax, bool live, uint32_t* stack, vkr_accel_hit* hit,
+                                   const Filter& filter = Filter()) {
   const LaneRay<true> ray(o, d, tmin, tmax);
   float t_best = tmax, u_best = 0.0f, v_best = 0.0f;
   uint32_t index_best = 0xFFFFFFFFu;
@@ -199,9 +218,15 @@ VKR_DEV void wave_closest_hit_walk(const AccelView& a, f3 o, f3 d, float tmin, f
         }
         for (uint32_t k = 0; k < nd.count; k++) {
           const vkr_accel_tri tr = a.tris[nd.first + k];
-          float t, u, v;
-          if (overlap && ray_triangle_closest(o, d, tmin, t_best, tr, &t, &u, &v) && (t < t_best || (t == t_best && tr.index < index_best))) {
-            t_best = t; u_best = u; v_best = v; index_best = tr.index;
+          if constexpr (Filter::ALL) {
+            float t, u, v;
+            if (overlap && ray_triangle_closest(o, d, tmin, t_best, tr, &t, &u, &v) && (t < t_best || (t == t_best && tr.index < index_best))) {
+              t_best = t; u_best = u; v_best = v; index_best = tr.index;
+            }
+          } else {
+            float t = 0.0f, u = 0.0f, v = 0.0f;
+            const bool cand = overlap && ray_triangle_closest(o, d, tmin, t_best, tr, &t, &u, &v) && (t < t_best || (t == t_best && tr.index < index_best));
+            if (filter.keep(tr.index, u, v, cand)) { t_best = t; u_best = u; v_best = v; index_best = tr.index; }
           }
         }
       }

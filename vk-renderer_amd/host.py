@@ -157,7 +157,9 @@ def lib():
                            # the ray-traced shadow mask (same rule)
                            ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float]),
                            # the ray-traced reflections (same rule)
-                           ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32])):
+                           ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
+                           # alpha cutouts in the rays of the two ray-traced stages (same rule)
+                           ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l
@@ -391,6 +393,12 @@ class HostFrame:
         (max_distance None: the camera's zfar), a hit samples level texture_lod of its albedo texture."""
         self._check(lib().vkrh_set_reflection_rays(self.h, 1 if fill_misses else 0, float(normal_offset), float(tmin),
                                                    0.0 if max_distance is None else float(max_distance), int(texture_lod)))
+
+    def set_ray_cutouts(self, enable=True, alpha_lod=0):
+        """vkrh_set_ray_cutouts: whether the rays of STAGE_SHADOW_MASK_RT and STAGE_REFLECTIONS_RT pass through triangles whose albedo
+        alpha at the hit (level alpha_lod of the texture) is 0, as the rasteriser discards such fragments.  Default: off.
+        STAGE_GTAO_RT stays opaque.  Not on a tiled frame."""
+        self._check(lib().vkrh_set_ray_cutouts(self.h, 1 if enable else 0, int(alpha_lod)))
 
     def set_ssao_samples(self, samples, std140=0):
         """vkrh_set_ssao_samples: pins the 16 samples ([16, 3]) of STAGE_SSAO and their packing in the uniform block: std140 = 0

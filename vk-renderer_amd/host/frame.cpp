@@ -175,6 +175,14 @@ struct PostFxFrame {
     reflection_rays.max_distance = max_distance > 0.f ? max_distance : 0.f; reflection_rays.texture_lod = texture_lod;
   }
 
+  // VKRH_STAGE_SHADOW_MASK_RT and VKRH_STAGE_REFLECTIONS_RT: whether their rays see alpha cutouts (vkrh_set_ray_cutouts).  Default:
+  // off, the opaque query.  VKRH_STAGE_GTAO_RT stays opaque, as the reference's rt_main.frag is.
+  RtCutouts ray_cutouts {};
+  void set_ray_cutouts(uint32_t enable, uint32_t alpha_lod) {
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_ray_cutouts: on a tiled frame (the ray-traced stages run on one GPU)"};
+    ray_cutouts.enable = enable != 0; ray_cutouts.alpha_lod = alpha_lod;
+  }
+
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
   bool has_tile_planes = false;
 
@@ -367,7 +375,11 @@ struct PostFxFrame {
     if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // reads depth mip 0 and the normal of this run's G-buffer; the slot of the looked-up mask
       ShadowMaskPass& pass = ensure_shadow_mask();
       pass.update_rt_params(view, shadow_rays.data(), (uint32_t)(shadow_rays.size() / 4), fazz.x, fazz.y, fazz.z, fazz.w, shadow_rays_offset, shadow_rays_tmin);
-      pass.run_rt(graph, gbuffer.depth, gbuffer.normal, scene_as->tlas, shadow_mask_tex);
+      if (ray_cutouts.enable && scene_renderer)
+        pass.run_rt(graph, gbuffer.depth, gbuffer.normal, AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()},
+                    ray_cutouts, shadow_mask_tex);
+      else
+        pass.run_rt(graph, gbuffer.depth, gbuffer.normal, scene_as->tlas, shadow_mask_tex);
     }
     if (mask & VKRH_STAGE_SSAO) {  // reads depth mip 0 only: before the downsample writes the other mips
       SSAOPass& pass = ensure_ssao();
@@ -407,7 +419,7 @@ struct PostFxFrame {
       const bool classified = ssr.get_settings().use_tile_classification;  // fill mode traces with the plain trace; the setting is the SSR stages'
       ssr.get_settings().use_tile_classification = false;
       ssr.run_rt(graph, assr_params, draw_params, gbuffer, gtao.raw,
-                 AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()}, rt);
+                 AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()}, rt, ray_cutouts);
       ssr.get_settings().use_tile_classification = classified;
     }
     if (mask & VKRH_STAGE_GTAO_MAIN_ONLY)
@@ -1407,6 +1419,9 @@ int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float
 }
 int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod) {
   return guarded([&] { frame_ref(frame).set_reflection_rays(fill_misses, normal_offset, tmin, max_distance, texture_lod); });
+}
+int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) {
+  return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); });
 }
 
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {

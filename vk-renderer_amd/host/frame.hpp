@@ -179,6 +179,12 @@ int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float
  * texture_lod of its albedo texture (clamped to the chain).  Defaults: fill_misses 0, normal_offset 1e-3 and tmin 0 (those of
  * vkrh_set_shadow_rays), max_distance = the camera's zfar (also what max_distance <= 0 selects), texture_lod 0.  Not on a tiled frame. */
 int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod);
+/* Alpha cutouts in the rays of VKRH_STAGE_SHADOW_MASK_RT and VKRH_STAGE_REFLECTIONS_RT: with enable != 0 the two
+ * stages record vkr_shadow_mask_rt_cutout / vkr_reflections_rt_cutout, whose rays pass through a triangle where the alpha of its albedo
+ * texture at the hit (level alpha_lod, clamped to the chain) is exactly 0, as the rasteriser discards such a fragment; textures
+ * without an alpha-0 texel are masked opaque from the scene's images.  Default: off, and a frame that never calls this or calls it
+ * with enable == 0 records the opaque entries.  VKRH_STAGE_GTAO_RT stays opaque (rt_main.frag is).  Not on a tiled frame.          */
+int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod);
 /* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
  * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
  * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */

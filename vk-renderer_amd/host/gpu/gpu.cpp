@@ -726,29 +726,74 @@ void register_hot_path_programs() {
     });
     // ---- ray-traced reflections (AdvancedSSR::run_reflections_rt_pass; no reference program) ----
     // set {0 depth (mip 0 of the view), 1 normal, 2 rays (bound only in fill mode), 3 acceleration structure, 4 the attribute table,
-    // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace
-    create_program("reflections_rt", [=](LaunchState& st) {
-      const char* P = "reflections_rt";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 6, S, P);
-      static_assert(sizeof(vkr_reflect_rt_params) == 112, "vkr_reflect_rt_params: a matrix, eight floats / words, the flags and three words");
-      const vkr_reflect_rt_params* params = ubo<vkr_reflect_rt_params>(st, 5, P);
-      vkr_img rays{};
-      const bool fill = (params->flags & VKR_REFLECT_RT_FILL_MISSES) != 0;
-      if (fill) rays = tex(st, 2, T, P);
-      const SetSlot& as = st.set->slots[3];
-      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"reflections_rt: acceleration structure (binding 3) is not bound"};
-      const SetSlot& at = st.set->slots[4];
-      if (at.kind != SetSlot::Ubo || !at.buffer) throw std::runtime_error{"reflections_rt: attribute table (binding 4) is not bound"};
+    // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace.
+    // "reflections_rt_cutout": the same set and 8 vkr_ray_cutout
+    struct HitTable {  // what a program that looks at hits binds besides its images: the structure, its attribute table, the textures
+      const vkr_accel* accel;
+      const vkr_hit_attrib* attribs;
+      uint32_t attrib_count;
       std::vector<vkr_img> textures;
-      for (const auto& v : st.set->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
-      const uint64_t bytes = vkr_reflections_rt_scratch_bytes((uint32_t)textures.size());
+      uint32_t opaque_mask;  // bit i: no texel of textures[i] has alpha 0 (Image::alpha_never_zero, what VKR_RASTER_DRAW_OPAQUE_ALBEDO comes from)
+    };
+    auto hit_table = [](LaunchState& st, uint32_t accel_slot, uint32_t attrib_slot, const std::string& P) {
+      HitTable h {};
+      const SetSlot& as = st.set->slots[accel_slot];
+      if (as.kind != SetSlot::AccelStruct || !as.tlas)
+        throw std::runtime_error{P + ": acceleration structure (binding " + std::to_string(accel_slot) + ") is not bound"};
+      const SetSlot& at = st.set->slots[attrib_slot];
+      if (at.kind != SetSlot::Ubo || !at.buffer) throw std::runtime_error{P + ": attribute table (binding " + std::to_string(attrib_slot) + ") is not bound"};
+      for (const auto& v : st.set->image_array) {
+        if (v.image->alpha_never_zero && h.textures.size() < 32) h.opaque_mask |= 1u << h.textures.size();
+        h.textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
+      }
+      h.accel = (const vkr_accel*)as.tlas;
       // the table of an empty scene still holds one (unused) record: a buffer has no size 0
       uint32_t triangles = 0;
-      if (vkr_accel_info((const vkr_accel*)as.tlas, nullptr, &triangles) != 0) throw std::runtime_error{std::string{"reflections_rt: "} + vkr_last_error()};
+      if (vkr_accel_info(h.accel, nullptr, &triangles) != 0) throw std::runtime_error{P + ": " + vkr_last_error()};
       const uint64_t records = at.buffer->get_size() / sizeof(vkr_hit_attrib);
-      return vkr_reflections_rt(&depth, &normal, fill ? &rays : nullptr, (const vkr_accel*)as.tlas, (const vkr_hit_attrib*)at.buffer->device_ptr(st.stream),
-                                records >= triangles ? triangles : (uint32_t)records, textures.empty() ? nullptr : textures.data(),
-                                (uint32_t)textures.size(), params, &out, st.require_workspace(bytes), bytes, st.stream);
+      h.attribs = (const vkr_hit_attrib*)at.buffer->device_ptr(st.stream);
+      h.attrib_count = records >= triangles ? triangles : (uint32_t)records;
+      return h;
+    };
+    // the cutout block of a _cutout program, with the bits of the textures that cannot make a hole added to its mask
+    auto cutout_block = [=](LaunchState& st, uint32_t slot, const HitTable& h, const char* P) {
+      static_assert(sizeof(vkr_ray_cutout) == 8, "vkr_ray_cutout: two words");
+      vkr_ray_cutout c = *ubo<vkr_ray_cutout>(st, slot, P);
+      c.opaque_texture_mask |= h.opaque_mask;
+      return c;
+    };
+    for (const bool cutouts : {false, true})
+      create_program(cutouts ? "reflections_rt_cutout" : "reflections_rt", [=](LaunchState& st) {
+        const char* P = cutouts ? "reflections_rt_cutout" : "reflections_rt";
+        vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 6, S, P);
+        static_assert(sizeof(vkr_reflect_rt_params) == 112, "vkr_reflect_rt_params: a matrix, eight floats / words, the flags and three words");
+        const vkr_reflect_rt_params* params = ubo<vkr_reflect_rt_params>(st, 5, P);
+        vkr_img rays{};
+        const bool fill = (params->flags & VKR_REFLECT_RT_FILL_MISSES) != 0;
+        if (fill) rays = tex(st, 2, T, P);
+        const HitTable h = hit_table(st, 3, 4, P);
+        const uint32_t count = (uint32_t)h.textures.size();
+        const uint64_t bytes = vkr_reflections_rt_scratch_bytes(count);
+        const vkr_img* textures = h.textures.empty() ? nullptr : h.textures.data();
+        if (!cutouts)
+          return vkr_reflections_rt(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, textures, count, params, &out,
+                                    st.require_workspace(bytes), bytes, st.stream);
+        const vkr_ray_cutout c = cutout_block(st, 8, h, P);
+        return vkr_reflections_rt_cutout(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, textures, count, params, &c, &out,
+                                         st.require_workspace(bytes), bytes, st.stream);
+      });
+    // ---- the ray-traced shadow mask that sees alpha cutouts (ShadowMaskPass::run_rt with cutouts; no reference program) ----
+    // set {0 depth (mip 0), 1 normal, 2 acceleration structure, 3 vkr_shadow_rt_params, 4 the mask (storage), 5 the attribute table,
+    // 6 vkr_ray_cutout, 7 the scene's textures[]}
+    create_program("shadow_mask_rt_cutout", [=](LaunchState& st) {
+      const char* P = "shadow_mask_rt_cutout";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
+      const HitTable h = hit_table(st, 2, 5, P);
+      const vkr_ray_cutout c = cutout_block(st, 6, h, P);
+      const uint32_t count = (uint32_t)h.textures.size();
+      const uint64_t bytes = vkr_accel_cutout_scratch_bytes(count);
+      return vkr_shadow_mask_rt_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, h.textures.empty() ? nullptr : h.textures.data(), count,
+                                       ubo<vkr_shadow_rt_params>(st, 3, P), &c, &out, st.require_workspace(bytes), bytes, st.stream);
     });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the

@@ -776,7 +776,7 @@ vkr_reflect_rt_params AdvancedSSR::reflect_rt_params(const AdvancedSSRParams &pa
 // one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels of reflections.  Written out instead of rec::compute because of
 // the array of images, which is no graph resource (as in ProbeRenderer's cube pass)
 void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
-  const RtSettings &rt)
+  const RtSettings &rt, const RtCutouts &cutouts)
 {
   if (!scene.tlas)
     throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
@@ -789,8 +789,12 @@ void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRP
   if (rt.fill_misses) bindings.push_back(rec::sampled(2, rays, sampler));
   bindings.insert(bindings.end(), {rec::accel(3, scene.tlas), rec::uniform_buffer(4, scene.hit_attributes), rec::uniform(5, reflect_rt_params(params, rt)),
                                    rec::storage(6, reflections)});
+  if (cutouts.enable) {  // the same set and the cutout block; the program adds the mask of the textures that cannot make a hole
+    if (!reflections_rt_cutout_pass.has_program()) reflections_rt_cutout_pass = gpu::create_compute_pipeline("reflections_rt_cutout");
+    bindings.push_back(rec::uniform(8, vkr_ray_cutout {cutouts.alpha_lod, 0u}));
+  }
   struct Data { std::vector<rec::Bound> bound; };
-  const auto pipeline = reflections_rt_pass;
+  const auto pipeline = cutouts.enable ? reflections_rt_cutout_pass : reflections_rt_pass;
   const auto textures = scene.textures;
   const auto sized_by = reflections;
   graph.add_task<Data>("ReflectionsRT",
@@ -806,13 +810,13 @@ void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRP
 }
 
 void AdvancedSSR::run_rt(RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
-  ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt)
+  ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts)
 {
   if (rt.fill_misses) {
     run_trace(graph, params, gbuff, ssr_occlusion);
     run_filter_pass(graph, params, gbuff);
   }
-  run_reflections_rt_pass(graph, params, gbuff, scene, rt);
+  run_reflections_rt_pass(graph, params, gbuff, scene, rt, cutouts);
   run_blur_pass(graph, params, taa_params, gbuff);
 }
 
@@ -958,6 +962,35 @@ void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageReso
     {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, tlas), rec::uniform(3, rt_params),
      rec::storage(4, out)},
     rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
+}
+
+// the same task through program "shadow_mask_rt_cutout": set {0..4 as above, 5 the attribute table, 6 the cutout block, 7 the scene's
+// textures[]}.  Written out instead of rec::compute because of the array of images (as AdvancedSSR::run_reflections_rt_pass)
+void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, const AdvancedSSR::RtScene &scene,
+  const RtCutouts &cutouts, ImageResourceId out)
+{
+  if (!cutouts.enable) { run_rt(graph, depth, normal, scene.tlas, out); return; }
+  if (!scene.tlas)
+    throw std::runtime_error {"ShadowMaskPass::run_rt: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
+  if (!scene.hit_attributes)
+    throw std::runtime_error {"ShadowMaskPass::run_rt: no attribute table: build scene::SceneAccelerationStructure first"};
+  if (!rt_cutout_pipeline.has_program()) rt_cutout_pipeline = gpu::create_compute_pipeline("shadow_mask_rt_cutout");
+  const std::vector<rec::Binding> bindings {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, scene.tlas),
+    rec::uniform(3, rt_params), rec::storage(4, out), rec::uniform_buffer(5, scene.hit_attributes),
+    rec::uniform(6, vkr_ray_cutout {cutouts.alpha_lod, 0u})};
+  struct Data { std::vector<rec::Bound> bound; };
+  const auto program = rt_cutout_pipeline;
+  const auto textures = scene.textures;
+  graph.add_task<Data>("ShadowMaskRT",
+    [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(bindings, builder, VK_SHADER_STAGE_COMPUTE_BIT); },
+    [=](Data &d, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
+      VkDescriptorSet set = rec::write(d.bound, resources, cmd);
+      gpu::write_set(set, gpu::ArrayOfImagesBinding {7, textures});
+      cmd.bind_pipeline(program);
+      cmd.bind_descriptors_compute(0, {set});
+      const auto extent = resources.get_image(out)->get_extent();
+      cmd.dispatch((extent.width + 15)/16, (extent.height + 15)/16, 1);
+    });
 }
 
 // ==== SyntheticGbuffer ===============================================================================================

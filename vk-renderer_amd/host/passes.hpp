@@ -408,6 +408,14 @@ struct AdvancedSSRParams {
 
 std::vector<glm::vec4> halton23_seq(uint32_t count);
 
+// Alpha cutouts in the ray query, the setting of AdvancedSSR::run_rt and ShadowMaskPass::run_rt: with `enable` the
+// task records the program's _cutout entry, whose rays pass through triangles where the albedo alpha at the hit is 0 (level
+// alpha_lod).  The mask of textures that cannot make a hole comes from the scene's images (alpha_never_zero) when the program runs.
+struct RtCutouts {
+  bool enable {false};
+  uint32_t alpha_lod {0};
+};
+
 struct AdvancedSSR {
   void render_ui();  // advanced_ssr.cpp:556-567; headless: the ImGui names are inert (imgui_pass.hpp), use get_settings()
 
@@ -490,15 +498,16 @@ struct AdvancedSSR {
   // fill_misses: SSSR_trace -> SSSR_filter -> ReflectionsRT (in place on `reflections`, reading `rays`) -> SSSR_blur; everything the
   // trace writes for GTAO is as in run().
   void run_rt(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
-    rendergraph::ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt);
+    rendergraph::ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts = {});
   // task "ReflectionsRT": depth mip 1, the half-resolution normals, (fill_misses: rays,) the structure, its attributes, the scene's
   // textures and the block -> reflections
   void run_reflections_rt_pass(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
-    const RtSettings &rt);
+    const RtSettings &rt, const RtCutouts &cutouts = {});
   static vkr_reflect_rt_params reflect_rt_params(const AdvancedSSRParams &params, const RtSettings &rt);
 
 private:
   gpu::ComputePipeline reflections_rt_pass;  // "reflections_rt", bound by the first run_reflections_rt_pass()
+  gpu::ComputePipeline reflections_rt_cutout_pass;  // "reflections_rt_cutout", bound by the first one with cutouts
   gpu::BufferPtr halton_buffer;
   gpu::ComputePipeline tile_regression;        // bound by run_tile_regression_pass
   rendergraph::ImageResourceId tile_planes;    // advanced_ssr.cpp:85-86: output of the regression pass (RGBA32F; allocated on first use)
@@ -726,10 +735,15 @@ struct ShadowMaskPass {
   // task "ShadowMaskRT": depth (mip 0), the full-resolution normal and the structure `tlas` (a vkr_accel*) -> out
   void run_rt(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
     VkAccelerationStructureKHR tlas, rendergraph::ImageResourceId out);
+  // the same task; with cutouts.enable it records program "shadow_mask_rt_cutout" (DESIGN.md 7.11), which also binds the scene's
+  // attribute table and textures: the light passes through the holes of alpha-tested triangles
+  void run_rt(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
+    const AdvancedSSR::RtScene &scene, const RtCutouts &cutouts, rendergraph::ImageResourceId out);
 
 private:
   gpu::ComputePipeline pipeline;
   gpu::ComputePipeline rt_pipeline;  // "shadow_mask_rt", bound by the first run_rt()
+  gpu::ComputePipeline rt_cutout_pipeline;  // "shadow_mask_rt_cutout", bound by the first run_rt() with cutouts
   VkSampler sampler;
   vkr_shadow_mask_params params {};
   vkr_shadow_rt_params rt_params {};
