@@ -734,6 +734,38 @@ int vkr_reflections_rt_cutout(const vkr_img* depth, const vkr_img* normal, const
                               const vkr_reflect_rt_params* params, const vkr_ray_cutout* cutout, const vkr_img* out_reflections,
                               void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- area lights in the traced shadow mask (DESIGN_NUMERICS.md, "Shadow mask, ray traced, area lights") ---------------------------
+ * A light with a radius is a disk that faces the surface point; the channel is the share of S points of the disk that the surface
+ * point sees, in 255ths.  Everything but the per-light step is vkr_shadow_mask_rt's.  Light l with radius[l] == 0 is traced as
+ * vkr_shadow_mask_rt traces it (one ray, 0 or 255).  Otherwise, with dvec as there: wv = normalize(dvec); tangent_frame(wv, &T, &B);
+ * the pattern slot of pixel (x, y) is p = (y & (P - 1)) * P + (x & (P - 1)); for k < S with (u, v) = samples[(p * S + k) * 2 ..]:
+ * e = fma(v, B, u * T) per component, dvec_k = fma(radius[l], e, dvec) per component (multiply-adds as contract 2 fuses them),
+ * sample k is cast when dot(n, dvec_k) > 0 and visible when cast and the frozen any-hit of (origin, dvec_k, tmin, 1) reports none.
+ * With V visible samples the channel is (510 V + S) / (2 S) in unsigned integers: 255 V / S rounded half up.  A light at the
+ * pixel's origin makes the frame NaN: no sample casts, the channel is 0.  For a directional light the disk sits at the tip of xyz:
+ * radius / |xyz| is the tangent of its angular radius.  The table is data: any finite (u, v) is legal.                          */
+typedef struct vkr_shadow_rt_soft {   /* 40 bytes */
+  float        radius[4];      /* per light, world units; 0 = this light is traced as vkr_shadow_mask_rt traces it */
+  uint32_t     sample_count;   /* S, 1..64 */
+  uint32_t     pattern_side;   /* P: 1, 2 or 4 */
+  const float* samples;        /* device, P*P*S*2 floats: (u, v) of sample k of pattern p at [(p*S + k)*2] */
+  uint32_t     reserved[2];    /* 0 */
+} vkr_shadow_rt_soft;
+/* The gates of vkr_shadow_mask_rt, then: soft or soft->samples NULL, sample_count outside 1..64, pattern_side not 1, 2 or 4, a
+ * radius (of a light in use) that is negative, NaN or infinite, reserved != 0.                                                */
+int vkr_shadow_mask_rt_soft(const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel, const vkr_shadow_rt_params* params,
+                            const vkr_shadow_rt_soft* soft, const vkr_img* out_mask, void* stream);
+/* the same with the any hit of the cutout entries: the gates of vkr_shadow_mask_rt_cutout, then those above.  Every channel is at
+ * least vkr_shadow_mask_rt_soft's on the same input.                                                                          */
+int vkr_shadow_mask_rt_soft_cutout(const vkr_img* depth, const vkr_img* normal, const vkr_accel* accel, const vkr_hit_attrib* attribs,
+                                   uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
+                                   const vkr_shadow_rt_params* params, const vkr_ray_cutout* cutout, const vkr_shadow_rt_soft* soft,
+                                   const vkr_img* out_mask, void* scratch, uint64_t scratch_bytes, void* stream);
+/* Host only: the sample table the frame uses.  Pattern p, sample k: rho = sqrt((k + 0.5) / S), phi = k * 2.399963229728653 +
+ * 2 pi * ((7 p) mod P^2) / P^2, (u, v) = (rho cos phi, rho sin phi), computed in double and rounded to fp32; out: P*P*S*2 floats.
+ * Nothing is written for a NULL out, S outside 1..64 or P not 1, 2 or 4.                                                       */
+void vkr_shadow_disk_samples(uint32_t sample_count, uint32_t pattern_side, float* out);
+
 /* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
  * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one

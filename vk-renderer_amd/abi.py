@@ -266,6 +266,11 @@ class ShadowRtParams(C.Structure):  # vkr_shadow_rt_params, 160 bytes
                 ("reserved", C.c_uint32)]
 
 
+class ShadowRtSoft(C.Structure):  # vkr_shadow_rt_soft, 40 bytes
+    _fields_ = [("radius", C.c_float * 4), ("sample_count", C.c_uint32), ("pattern_side", C.c_uint32), ("samples", C.c_void_p),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # ---- the closest-hit ray query and program reflections_rt ----
 ACCEL_MISS = 0xFFFFFFFF  # vkr_accel_hit.index of a ray that hits nothing
 
@@ -443,6 +448,14 @@ def product():
                                                   P(RayCutout), _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
         for name in ("accel_occluded_cutout", "accel_closest_cutout", "shadow_mask_rt_cutout", "reflections_rt_cutout"):
             getattr(lib, "vkr_" + name).restype = C.c_int
+        # area lights in the traced shadow mask (checked against the numpy restatement tests/shadow_mask_rt_soft_reference.py)
+        lib.vkr_shadow_mask_rt_soft.argtypes = [_IMG, _IMG, C.c_void_p, P(ShadowRtParams), P(ShadowRtSoft), _IMG, C.c_void_p]
+        lib.vkr_shadow_mask_rt_soft_cutout.argtypes = [_IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ShadowRtParams),
+                                                       P(RayCutout), P(ShadowRtSoft), _IMG, C.c_void_p, C.c_uint64, C.c_void_p]
+        for name in ("shadow_mask_rt_soft", "shadow_mask_rt_soft_cutout"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
+        lib.vkr_shadow_disk_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.vkr_shadow_disk_samples.restype = None
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
         lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
@@ -763,6 +776,62 @@ def shadow_mask_rt_cutout(depth, normal, accel, attribs, attrib_count, textures,
     handle = accel.handle if accel is not None else None
     check(lib.vkr_shadow_mask_rt_cutout(ref(depth), ref(normal), handle, attribs, int(attrib_count), textures, int(texture_count), ref(params),
                                         ref(cutout), ref(out_mask), scratch, int(scratch_bytes), stream), lib)
+
+
+def shadow_disk_samples(sample_count, pattern_side):
+    """vkr_shadow_disk_samples: the sample table of the area lights, float32 [pattern_side^2, sample_count, 2] of (u, v) in the
+    unit disk — the table the host frame uses."""
+    import numpy as np
+
+    sample_count, pattern_side = int(sample_count), int(pattern_side)
+    if not (1 <= sample_count <= 64) or pattern_side not in (1, 2, 4):
+        raise RuntimeError(f"shadow_disk_samples: {sample_count} samples in a pattern tile of side {pattern_side}, needs 1..64 and 1, 2 or 4")
+    out = np.zeros((pattern_side * pattern_side, sample_count, 2), np.float32)
+    product().vkr_shadow_disk_samples(sample_count, pattern_side, out.ctypes.data)
+    return out
+
+
+def shadow_rt_soft(radii, sample_count, pattern_side, device=None, table=None):
+    """ShadowRtSoft for shadow_mask_rt_soft: `radii` (up to 4, one per light; 0 keeps a light hard), S rays per pixel and light
+    with a radius, a pattern tile of side P.  The table — `table` (anything numpy takes, P^2 * S * 2 values) or
+    shadow_disk_samples(S, P) — is copied to `device` and kept alive by the returned block (attribute `table`); device None
+    leaves samples NULL (to show the refusal).  Everything is passed on as given: the entry refuses what it does not take."""
+    s = ShadowRtSoft()
+    if len(radii) > 4:
+        raise RuntimeError(f"shadow_rt_soft: {len(radii)} radii, at most 4")
+    for l, r in enumerate(radii):
+        s.radius[l] = float(r)
+    s.sample_count, s.pattern_side = int(sample_count), int(pattern_side)
+    s.table = None
+    if device is not None:
+        import numpy as np
+        import torch
+
+        host = np.ascontiguousarray(shadow_disk_samples(sample_count, pattern_side) if table is None else table, dtype=np.float32)
+        s.table = torch.from_numpy(host.reshape(-1).copy()).to(device)
+        s.samples = s.table.data_ptr()
+    return s
+
+
+def shadow_mask_rt_soft(depth, normal, accel, params, soft, out_mask, stream=None):
+    """vkr_shadow_mask_rt_soft: shadow_mask_rt with area lights: channel l = 255 * (visible samples of light l's disk) / S, rounded
+    half up, under `soft` (a ShadowRtSoft, e.g. shadow_rt_soft(...)); a light with radius 0 is traced as shadow_mask_rt traces it.
+    Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_shadow_mask_rt_soft(ref(depth), ref(normal), handle, ref(params), ref(soft), ref(out_mask), stream), lib)
+
+
+def shadow_mask_rt_soft_cutout(depth, normal, accel, attribs, attrib_count, textures, texture_count, params, cutout, soft, out_mask, scratch,
+                               scratch_bytes, stream=None):
+    """vkr_shadow_mask_rt_soft_cutout: shadow_mask_rt_soft whose rays pass through the holes of alpha-tested triangles; attribs,
+    textures, cutout and scratch as accel_occluded_cutout.  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_shadow_mask_rt_soft_cutout(ref(depth), ref(normal), handle, attribs, int(attrib_count), textures, int(texture_count), ref(params),
+                                             ref(cutout), ref(soft), ref(out_mask), scratch, int(scratch_bytes), stream), lib)
 
 
 def reflections_rt_cutout(depth, normal, rays, accel, attribs, attrib_count, textures, texture_count, params, cutout, out_reflections, scratch,

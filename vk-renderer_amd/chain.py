@@ -476,13 +476,15 @@ class PostFxChain:
         p = abi.shadow_mask_params(self.setup.inv_view, mvps, *self.setup.fazz, radius=radius, bias=bias)
         abi.shadow_mask(self.depth.desc(0, 1), layers, p, self.shadow_mask_out.desc(), self.stream)
 
-    def shadow_mask_rt(self, accel, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, cutouts=None):
+    def shadow_mask_rt(self, accel, lights, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, cutouts=None, soft=None):
         """vkr_shadow_mask_rt on this chain's depth and normal -> shadow_mask_out (RGBA8_UNORM, channel l = light l): one any-hit
         ray per pixel and light through `accel` (abi.Accel); `lights` 1..4 of (x, y, z, w), w == 1 point, w == 0 directional.
         cutouts: None, or (attribs, scene, abi.RayCutout) — the device tensor of abi.scene_triangle_attributes records, the
         abi.RasterScene of Scene.upload(device) and the setting — for vkr_shadow_mask_rt_cutout: the light passes through holes.
+        soft: None, or an abi.ShadowRtSoft (abi.shadow_rt_soft(radii, S, P, device)) for vkr_shadow_mask_rt_soft / _soft_cutout:
+        lights with a radius, S rays each.
         Product backend only: the expectation is the numpy restatement tests/shadow_mask_rt_reference.py (tests/
-        ray_cutout_reference.py with cutouts), not a checker library."""
+        ray_cutout_reference.py with cutouts, tests/shadow_mask_rt_soft_reference.py with soft), not a checker library."""
         if self.backend != "product":
             raise RuntimeError("PostFxChain.shadow_mask_rt: only the product backend has the program shadow_mask_rt")
         if self.tiled:
@@ -491,10 +493,17 @@ class PostFxChain:
             self.shadow_mask_out = ImageBuf(abi.FMT_RGBA8_UNORM, self.depth.width, self.depth.height, device=self.device)
         p = abi.shadow_rt_params(self.setup.inv_view, lights, *self.setup.fazz, normal_offset=normal_offset, tmin=tmin)
         if cutouts is None:
-            abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
+            if soft is not None:
+                abi.shadow_mask_rt_soft(self.depth.desc(0, 1), self.normal.desc(), accel, p, soft, self.shadow_mask_out.desc(), self.stream)
+            else:
+                abi.shadow_mask_rt(self.depth.desc(0, 1), self.normal.desc(), accel, p, self.shadow_mask_out.desc(), self.stream)
             return
         attribs, scene, setting = cutouts
         nbytes, scratch = self._cutout_scratch(scene.texture_count)
+        if soft is not None:
+            abi.shadow_mask_rt_soft_cutout(self.depth.desc(0, 1), self.normal.desc(), accel, attribs.data_ptr(), attribs.numel() * attribs.element_size() // 32,
+                                           scene.textures, scene.texture_count, p, setting, soft, self.shadow_mask_out.desc(), scratch, nbytes, self.stream)
+            return
         abi.shadow_mask_rt_cutout(self.depth.desc(0, 1), self.normal.desc(), accel, attribs.data_ptr(), attribs.numel() * attribs.element_size() // 32,
                                   scene.textures, scene.texture_count, p, setting, self.shadow_mask_out.desc(), scratch, nbytes, self.stream)
 

@@ -156,6 +156,8 @@ def lib():
                            ("vkrh_set_shadow_mask", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
                            # the ray-traced shadow mask (same rule)
                            ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float]),
+                           # area lights in the ray-traced shadow mask (same rule)
+                           ("vkrh_set_shadow_area_lights", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]),
                            # the ray-traced reflections (same rule)
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
@@ -384,6 +386,15 @@ class HostFrame:
         for i, v in enumerate(lights):
             flat[4 * i: 4 * i + 4] = [float(x) for x in v]
         self._check(lib().vkrh_set_shadow_rays(self.h, flat, len(lights), float(normal_offset), float(tmin)))
+
+    def set_shadow_area_lights(self, radii, sample_count=16, pattern_side=4):
+        """vkrh_set_shadow_area_lights: the sizes of the lights of STAGE_SHADOW_MASK_RT: one radius (world units) per light of
+        set_shadow_rays, sample_count (1..64) rays per pixel and light with a radius, a tile of pattern_side^2 (1, 2 or 4) sample
+        patterns from abi.shadow_disk_samples.  With any radius above 0 the stage records vkr_shadow_mask_rt_soft (task
+        ShadowMaskRTSoft) and a channel holds 255 * visible / sample_count rounded half up; every radius 0 (the default) is the hard
+        stage.  Not on a tiled frame."""
+        flat = (C.c_float * max(4, len(radii)))(*[float(r) for r in radii])
+        self._check(lib().vkrh_set_shadow_area_lights(self.h, flat, len(radii), int(sample_count), int(pattern_side)))
 
     def set_reflection_rays(self, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, max_distance=None,
                             texture_lod=0):

@@ -160,8 +160,29 @@ struct PostFxFrame {
       if (!(lights[4 * l + 3] == 0.0f || lights[4 * l + 3] == 1.0f))
         throw std::runtime_error{"vkrh_set_shadow_rays: light " + std::to_string(l) + ": w must be 1 (a point light) or 0 (a directional light)"};
     if (std::isnan(tmin)) throw std::runtime_error{"vkrh_set_shadow_rays: tmin is NaN"};
+    if (4 * count != shadow_rays.size()) shadow_area_radii.assign(count, 0.0f);  // the radii belong to the lights they were set for
     shadow_rays.assign(lights, lights + 4 * count);
     shadow_rays_offset = normal_offset; shadow_rays_tmin = tmin;
+  }
+
+  // VKRH_STAGE_SHADOW_MASK_RT: the sizes of its lights (vkrh_set_shadow_area_lights).  Default: every radius 0, the hard pass.
+  std::vector<float> shadow_area_radii{0.0f};
+  uint32_t shadow_area_samples = 16, shadow_area_pattern = 4;
+  void set_shadow_area_lights(const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side) {
+    if (!radii) throw std::runtime_error{"vkrh_set_shadow_area_lights: NULL argument"};
+    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_area_lights: on a tiled frame (VKRH_STAGE_SHADOW_MASK_RT runs on one GPU)"};
+    if (4 * (size_t)count != shadow_rays.size())
+      throw std::runtime_error{"vkrh_set_shadow_area_lights: count " + std::to_string(count) + ", but " + std::to_string(shadow_rays.size() / 4) +
+                               " lights are set (vkrh_set_shadow_rays)"};
+    if (sample_count < 1 || sample_count > 64)
+      throw std::runtime_error{"vkrh_set_shadow_area_lights: sample_count " + std::to_string(sample_count) + ", needs 1..64"};
+    if (pattern_side != 1 && pattern_side != 2 && pattern_side != 4)
+      throw std::runtime_error{"vkrh_set_shadow_area_lights: pattern_side " + std::to_string(pattern_side) + ", needs 1, 2 or 4"};
+    for (uint32_t l = 0; l < count; l++)
+      if (!(radii[l] >= 0.0f) || std::isinf(radii[l]))
+        throw std::runtime_error{"vkrh_set_shadow_area_lights: light " + std::to_string(l) + ": the radius must be finite and >= 0"};
+    shadow_area_radii.assign(radii, radii + count);
+    shadow_area_samples = sample_count; shadow_area_pattern = pattern_side;
   }
 
   // VKRH_STAGE_REFLECTIONS_RT: the mode and the rays (vkrh_set_reflection_rays).  Defaults: every pixel traced, the offsets of the
@@ -375,6 +396,9 @@ struct PostFxFrame {
     if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // reads depth mip 0 and the normal of this run's G-buffer; the slot of the looked-up mask
       ShadowMaskPass& pass = ensure_shadow_mask();
       pass.update_rt_params(view, shadow_rays.data(), (uint32_t)(shadow_rays.size() / 4), fazz.x, fazz.y, fazz.z, fazz.w, shadow_rays_offset, shadow_rays_tmin);
+      float radii[4] = {0.f, 0.f, 0.f, 0.f};
+      std::copy(shadow_area_radii.begin(), shadow_area_radii.end(), radii);
+      pass.update_rt_soft(radii, shadow_area_samples, shadow_area_pattern);
       if (ray_cutouts.enable && scene_renderer)
         pass.run_rt(graph, gbuffer.depth, gbuffer.normal, AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()},
                     ray_cutouts, shadow_mask_tex);
@@ -1419,6 +1443,9 @@ int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float
 }
 int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod) {
   return guarded([&] { frame_ref(frame).set_reflection_rays(fill_misses, normal_offset, tmin, max_distance, texture_lod); });
+}
+int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side) {
+  return guarded([&] { frame_ref(frame).set_shadow_area_lights(radii, count, sample_count, pattern_side); });
 }
 int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) {
   return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); });

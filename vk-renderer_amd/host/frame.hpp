@@ -173,6 +173,15 @@ int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t a
  * t in [tmin, 1] (tmin NaN is an error).  Defaults: one point light at the shading pass's LIGHT_POS, normal_offset 1e-3, tmin 0
  * (measured: DESIGN.md 7.8).  Not on a tiled frame. */
 int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float normal_offset, float tmin);
+/* Area lights in VKRH_STAGE_SHADOW_MASK_RT: radii[l] is the radius in world units of the disk that light l of
+ * vkrh_set_shadow_rays becomes (for a directional light at the tip of its xyz), sample_count (1..64) the rays per pixel and such
+ * light, pattern_side (1, 2 or 4) the side of the tile of sample patterns from vkr_shadow_disk_samples.  With any radius above 0 the
+ * stage records vkr_shadow_mask_rt_soft (with vkrh_set_ray_cutouts: vkr_shadow_mask_rt_soft_cutout) under the task name
+ * ShadowMaskRTSoft, and a channel holds 255 * visible / sample_count rounded half up; a light with radius 0 stays hard.  An error:
+ * `count` different from the number of lights set, sample_count or pattern_side outside those values, a radius that is negative,
+ * NaN or infinite.  Default: every radius 0, under which the stage records what it always recorded.  A vkrh_set_shadow_rays with
+ * another number of lights sets every radius back to 0.  No new stage bit.  Not on a tiled frame. */
+int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side);
 /* The rays of VKRH_STAGE_REFLECTIONS_RT: fill_misses != 0 traces only the pixels whose screen-space ray is invalid, after the
  * screen-space trace and filter; the ray's origin is the surface point moved by normal_offset along the normal, the ray runs
  * t in [tmin, max_distance] along the unit mirror direction (tmin or max_distance NaN is an error), a hit samples mip level

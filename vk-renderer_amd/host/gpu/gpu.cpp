@@ -795,6 +795,38 @@ void register_hot_path_programs() {
       return vkr_shadow_mask_rt_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, h.textures.empty() ? nullptr : h.textures.data(), count,
                                        ubo<vkr_shadow_rt_params>(st, 3, P), &c, &out, st.require_workspace(bytes), bytes, st.stream);
     });
+    // ---- the traced shadow mask with area lights (ShadowMaskPass::run_rt after update_rt_soft; no reference program) ----
+    // "shadow_mask_rt_soft": the set of "shadow_mask_rt", 5 vkr_shadow_rt_soft (its samples pointer is not read), 6 the sample table;
+    // "shadow_mask_rt_soft_cutout": the set of "shadow_mask_rt_cutout", 8 vkr_shadow_rt_soft, 9 the sample table
+    auto soft_block = [=](LaunchState& st, uint32_t slot, uint32_t table_slot, const char* P) {
+      static_assert(sizeof(vkr_shadow_rt_soft) == 40, "vkr_shadow_rt_soft: four radii, two words, a pointer and two words");
+      vkr_shadow_rt_soft soft = *ubo<vkr_shadow_rt_soft>(st, slot, P);
+      const SetSlot& table = st.set->slots[table_slot];
+      if (table.kind != SetSlot::Ubo || !table.buffer) throw std::runtime_error{std::string{P} + ": sample table (binding " + std::to_string(table_slot) + ") is not bound"};
+      if (table.buffer->get_size() < sizeof(float) * 2 * (uint64_t)soft.sample_count * soft.pattern_side * soft.pattern_side)
+        throw std::runtime_error{std::string{P} + ": the sample table is smaller than sample_count x pattern_side^2 pairs"};
+      soft.samples = (const float*)table.buffer->device_ptr(st.stream);
+      return soft;
+    };
+    create_program("shadow_mask_rt_soft", [=](LaunchState& st) {
+      const char* P = "shadow_mask_rt_soft";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
+      const SetSlot& as = st.set->slots[2];
+      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"shadow_mask_rt_soft: acceleration structure (binding 2) is not bound"};
+      const vkr_shadow_rt_soft soft = soft_block(st, 5, 6, P);
+      return vkr_shadow_mask_rt_soft(&depth, &normal, (const vkr_accel*)as.tlas, ubo<vkr_shadow_rt_params>(st, 3, P), &soft, &out, st.stream);
+    });
+    create_program("shadow_mask_rt_soft_cutout", [=](LaunchState& st) {
+      const char* P = "shadow_mask_rt_soft_cutout";
+      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
+      const HitTable h = hit_table(st, 2, 5, P);
+      const vkr_ray_cutout c = cutout_block(st, 6, h, P);
+      const vkr_shadow_rt_soft soft = soft_block(st, 8, 9, P);
+      const uint32_t count = (uint32_t)h.textures.size();
+      const uint64_t bytes = vkr_accel_cutout_scratch_bytes(count);
+      return vkr_shadow_mask_rt_soft_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, h.textures.empty() ? nullptr : h.textures.data(), count,
+                                            ubo<vkr_shadow_rt_params>(st, 3, P), &c, &soft, &out, st.require_workspace(bytes), bytes, st.stream);
+    });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the
     // reference records first is covered by the triangle and not executed.

@@ -952,11 +952,34 @@ void ShadowMaskPass::update_rt_params(const glm::mat4 &camera, const float *ligh
   rt_params.light_count = count; rt_params.normal_offset = normal_offset; rt_params.tmin = tmin;
 }
 
+void ShadowMaskPass::update_rt_soft(const float radius[4], uint32_t sample_count, uint32_t pattern_side) {
+  if (!radius || sample_count < 1 || sample_count > 64 || (pattern_side != 1 && pattern_side != 2 && pattern_side != 4))
+    throw std::runtime_error {"ShadowMaskPass::update_rt_soft: " + std::to_string(sample_count) + " samples in a pattern tile of side " +
+                              std::to_string(pattern_side) + ", needs 1..64 and 1, 2 or 4"};
+  for (int l = 0; l < 4; l++) {
+    if (!(radius[l] >= 0.f) || std::isinf(radius[l])) throw std::runtime_error {"ShadowMaskPass::update_rt_soft: light " + std::to_string(l) + ": the radius must be finite and >= 0"};
+    rt_soft.radius[l] = radius[l];
+  }
+  if (rt_soft_on() && (!rt_soft_table || rt_soft.sample_count != sample_count || rt_soft.pattern_side != pattern_side)) {
+    rt_soft_table = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, sizeof(float) * 2 * sample_count * pattern_side * pattern_side, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+    vkr_shadow_disk_samples(sample_count, pattern_side, (float *)rt_soft_table->get_mapped_ptr());
+    rt_soft.sample_count = sample_count; rt_soft.pattern_side = pattern_side;
+  }
+}
+
 // task "ShadowMaskRT": set {0 depth (mip 0), 1 normal, 2 the acceleration structure, 3 the block, 4 the mask (storage)} in the
 // C-ABI's order, one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels
 void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, VkAccelerationStructureKHR tlas, ImageResourceId out) {
   if (!tlas)
     throw std::runtime_error {"ShadowMaskPass::run_rt: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
+  if (rt_soft_on()) {  // set {0..4 as below, 5 the soft block, 6 the sample table}
+    if (!rt_soft_pipeline.has_program()) rt_soft_pipeline = gpu::create_compute_pipeline("shadow_mask_rt_soft");
+    rec::compute(graph, "ShadowMaskRTSoft", rt_soft_pipeline,
+      {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, tlas), rec::uniform(3, rt_params),
+       rec::storage(4, out), rec::uniform(5, rt_soft), rec::uniform_buffer(6, rt_soft_table)},
+      rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
+    return;
+  }
   if (!rt_pipeline.has_program()) rt_pipeline = gpu::create_compute_pipeline("shadow_mask_rt");
   rec::compute(graph, "ShadowMaskRT", rt_pipeline,
     {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, tlas), rec::uniform(3, rt_params),
@@ -974,14 +997,17 @@ void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageReso
     throw std::runtime_error {"ShadowMaskPass::run_rt: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
   if (!scene.hit_attributes)
     throw std::runtime_error {"ShadowMaskPass::run_rt: no attribute table: build scene::SceneAccelerationStructure first"};
-  if (!rt_cutout_pipeline.has_program()) rt_cutout_pipeline = gpu::create_compute_pipeline("shadow_mask_rt_cutout");
-  const std::vector<rec::Binding> bindings {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, scene.tlas),
+  const bool soft = rt_soft_on();  // "shadow_mask_rt_soft_cutout": the same set, 8 the soft block, 9 the sample table
+  gpu::ComputePipeline &pipeline_used = soft ? rt_soft_cutout_pipeline : rt_cutout_pipeline;
+  if (!pipeline_used.has_program()) pipeline_used = gpu::create_compute_pipeline(soft ? "shadow_mask_rt_soft_cutout" : "shadow_mask_rt_cutout");
+  std::vector<rec::Binding> bindings {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, scene.tlas),
     rec::uniform(3, rt_params), rec::storage(4, out), rec::uniform_buffer(5, scene.hit_attributes),
     rec::uniform(6, vkr_ray_cutout {cutouts.alpha_lod, 0u})};
+  if (soft) bindings.insert(bindings.end(), {rec::uniform(8, rt_soft), rec::uniform_buffer(9, rt_soft_table)});
   struct Data { std::vector<rec::Bound> bound; };
-  const auto program = rt_cutout_pipeline;
+  const auto program = pipeline_used;
   const auto textures = scene.textures;
-  graph.add_task<Data>("ShadowMaskRT",
+  graph.add_task<Data>(soft ? "ShadowMaskRTSoft" : "ShadowMaskRT",
     [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(bindings, builder, VK_SHADER_STAGE_COMPUTE_BIT); },
     [=](Data &d, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
       VkDescriptorSet set = rec::write(d.bound, resources, cmd);

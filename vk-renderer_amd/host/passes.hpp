@@ -732,6 +732,12 @@ struct ShadowMaskPass {
   void update_rt_params(const glm::mat4 &camera, const float *lights, uint32_t count, float fovy, float aspect, float znear, float zfar,
     float normal_offset, float tmin);
 
+  // Area lights (programs "shadow_mask_rt_soft" and "shadow_mask_rt_soft_cutout"): radius[l] in world units of the
+  // disk light l becomes, sample_count (1..64) rays per pixel and such light, pattern_side (1, 2 or 4).  The pass owns the device
+  // table of vkr_shadow_disk_samples, remade when sample_count or pattern_side change.  With every radius 0 (the default) run_rt
+  // records what it records without this call; with any above 0 it records the soft programs under the task name "ShadowMaskRTSoft".
+  void update_rt_soft(const float radius[4], uint32_t sample_count, uint32_t pattern_side);
+
   // task "ShadowMaskRT": depth (mip 0), the full-resolution normal and the structure `tlas` (a vkr_accel*) -> out
   void run_rt(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
     VkAccelerationStructureKHR tlas, rendergraph::ImageResourceId out);
@@ -747,6 +753,11 @@ private:
   VkSampler sampler;
   vkr_shadow_mask_params params {};
   vkr_shadow_rt_params rt_params {};
+  gpu::ComputePipeline rt_soft_pipeline;  // "shadow_mask_rt_soft", bound by the first run_rt() with a radius above 0
+  gpu::ComputePipeline rt_soft_cutout_pipeline;  // "shadow_mask_rt_soft_cutout", likewise with cutouts
+  vkr_shadow_rt_soft rt_soft {};  // samples stays NULL here: the program takes the pointer from rt_soft_table
+  gpu::BufferPtr rt_soft_table;  // sample_count x pattern_side^2 x (u, v)
+  bool rt_soft_on() const { return rt_soft.radius[0] > 0.f || rt_soft.radius[1] > 0.f || rt_soft.radius[2] > 0.f || rt_soft.radius[3] > 0.f; }
 };
 
 
