@@ -161,7 +161,9 @@ def lib():
                            # the ray-traced reflections (same rule)
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
-                           ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32])):
+                           ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32]),
+                           # the first refusal of every program of the table (same rule)
+                           ("vkrh_selftest_programs", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):
                 getattr(l, name).argtypes = args
         _lib = l

@@ -76,6 +76,36 @@ glm::mat4 default_shadow_mvp() {
   return out;
 }
 
+// What vkrh_run refuses before it records anything.  One rule per stage, in the order the checks are made: a mask that breaks
+// several rules is refused with the message of the first.  Per rule, in this order: why the stage does not run on a tiled frame;
+// the stages it cannot share a run with (they write the same images); what it needs from earlier calls.
+enum class Needs { Nothing, Scene, Tlas, TlasAndScene, Probes };
+struct StageRule {
+  uint32_t stage; const char* name;
+  const char* tiled;                                               // "<name> on a tiled frame (<tiled>)", or nullptr: the stage runs on one
+  uint32_t rivals = 0; const char* rivals_tail = nullptr;          // "<name> together with <rivals_tail>"
+  Needs needs = Needs::Nothing; const char* needs_tail = nullptr;  // "<name> without <needs_tail>"
+};
+constexpr uint32_t SSR_STAGES = VKRH_STAGE_SSR | VKRH_STAGE_SSR_CLASSIFIED | VKRH_STAGE_SSR_RESOLVE | VKRH_STAGE_SSR_TRACE |
+                                VKRH_STAGE_SSR_TRACE_HEAD | VKRH_STAGE_SSR_TRACE_RESUME;
+constexpr StageRule STAGE_RULES[] = {
+    {VKRH_STAGE_CLEAR_PREV_DEPTH, "VKRH_STAGE_CLEAR_PREV_DEPTH", "transfers take whole images"},
+    {VKRH_STAGE_SSAO, "VKRH_STAGE_SSAO", "a sample's reach is unbounded near the eye: SSAO runs on one GPU"},
+    {VKRH_STAGE_TILE_REGRESSION, "VKRH_STAGE_TILE_REGRESSION", "halved strip bounds are no multiples of 8: tiles would straddle owners"},
+    {VKRH_STAGE_BACKBUFFER, "VKRH_STAGE_BACKBUFFER", "the uv of a pixel spans the whole source: the backbuffer is drawn on one GPU"},  // + its source
+    {VKRH_STAGE_SHADOW_MASK_RT, "VKRH_STAGE_SHADOW_MASK_RT", "the rays reach anywhere: ray-traced shadows run on one GPU",
+     VKRH_STAGE_SHADOW_MASK, "VKRH_STAGE_SHADOW_MASK (both write the image shadow_mask)",
+     Needs::Tlas, "a loaded scene (vkrh_load_scene builds its acceleration structure)"},
+    {VKRH_STAGE_REFLECTIONS_RT, "VKRH_STAGE_REFLECTIONS_RT", "the rays reach anywhere: ray-traced reflections run on one GPU",
+     SSR_STAGES, "an SSR stage (VKRH_STAGE_SSR, _SSR_CLASSIFIED, _SSR_RESOLVE, _SSR_TRACE*: all write the images reflections / blurred)",
+     Needs::TlasAndScene, "a loaded scene (vkrh_load_scene builds its acceleration structure and attribute table)"},
+    {VKRH_STAGE_SHADOW_MASK, "VKRH_STAGE_SHADOW_MASK", "the shadow maps are rendered on one GPU"},  // + shadow maps, of this run or an earlier one
+    {VKRH_STAGE_SHADOW, "VKRH_STAGE_SHADOW", "the shadow maps are rendered on one GPU", 0, nullptr, Needs::Scene, "a loaded scene (vkrh_load_scene)"},
+    {VKRH_STAGE_GTAO_RT, "VKRH_STAGE_GTAO_RT", "ray-traced AO runs on one GPU", VKRH_STAGE_GTAO,
+     "VKRH_STAGE_GTAO (both write GTAO's raw, filtered and accumulated images)", Needs::Tlas, "a loaded scene (vkrh_load_scene builds its acceleration structure)"},
+    {VKRH_STAGE_PROBE_TRACE, "VKRH_STAGE_PROBE_TRACE", "probes are traced on one GPU", 0, nullptr, Needs::Probes, "baked probes (vkrh_bake_probes)"},
+};
+
 struct PostFxFrame {
   vkrh_config cfg;
   rendergraph::RenderGraph graph;
@@ -110,6 +140,19 @@ struct PostFxFrame {
   uint32_t shadow_size = 1024;
   std::vector<glm::mat4> shadow_lights{default_shadow_mvp()};
 
+  // what runs on one GPU only: "<who>: on a tiled frame (<why>)"
+  void refuse_tiled(const char* who, const char* why) const {
+    if (cfg.tiled) throw std::runtime_error{std::string{who} + ": on a tiled frame (" + why + ")"};
+  }
+  // what vkrh_last_tasks (and, after a run, vkrh_last_lanes) report: the submission that just ended
+  void record_submitted(bool lanes) {
+    task_names.clear();
+    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
+    if (!lanes) return;
+    task_lanes.clear();
+    for (uint32_t l : graph.last_submitted_lanes()) { task_lanes += std::to_string(l); task_lanes += ' '; }
+  }
+
   // VKRH_STAGE_SSAO: the pass and its target, created on first use (the constructor draws from rand(): a frame that never runs
   // the stage leaves the sequence of the other passes' draws alone)
   std::unique_ptr<SSAOPass> ssao_pass;
@@ -123,7 +166,7 @@ struct PostFxFrame {
   }
   void set_ssao_samples(const float* xyz, uint32_t std140) {
     if (!xyz) throw std::runtime_error{"vkrh_set_ssao_samples: NULL argument"};
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_ssao_samples: on a tiled frame (VKRH_STAGE_SSAO runs on one GPU)"};
+    refuse_tiled("vkrh_set_ssao_samples", "VKRH_STAGE_SSAO runs on one GPU");
     SSAOPass& pass = ensure_ssao();
     for (uint32_t i = 0; i < 16; i++) pass.sphere_samples[i] = glm::vec3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     pass.std140_samples = std140 != 0;
@@ -143,7 +186,7 @@ struct PostFxFrame {
     return *shadow_mask_pass;
   }
   void set_shadow_mask(uint32_t bias, uint32_t radius, uint32_t apply) {
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_mask: on a tiled frame (VKRH_STAGE_SHADOW_MASK runs on one GPU)"};
+    refuse_tiled("vkrh_set_shadow_mask", "VKRH_STAGE_SHADOW_MASK runs on one GPU");
     if (radius > 2) throw std::runtime_error{"vkrh_set_shadow_mask: radius " + std::to_string(radius) + ", needs 0..2 (a box of 1, 9 or 25 taps)"};
     shadow_mask_bias = bias; shadow_mask_radius = radius; shadow_mask_apply = apply != 0;
   }
@@ -154,7 +197,7 @@ struct PostFxFrame {
   float shadow_rays_offset = 1e-3f, shadow_rays_tmin = 0.0f;
   void set_shadow_rays(const float* lights, uint32_t count, float normal_offset, float tmin) {
     if (!lights) throw std::runtime_error{"vkrh_set_shadow_rays: NULL argument"};
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_rays: on a tiled frame (VKRH_STAGE_SHADOW_MASK_RT runs on one GPU)"};
+    refuse_tiled("vkrh_set_shadow_rays", "VKRH_STAGE_SHADOW_MASK_RT runs on one GPU");
     if (count < 1 || count > 4) throw std::runtime_error{"vkrh_set_shadow_rays: count " + std::to_string(count) + ", needs 1..4 (the channels of the mask)"};
     for (uint32_t l = 0; l < count; l++)
       if (!(lights[4 * l + 3] == 0.0f || lights[4 * l + 3] == 1.0f))
@@ -170,7 +213,7 @@ struct PostFxFrame {
   uint32_t shadow_area_samples = 16, shadow_area_pattern = 4;
   void set_shadow_area_lights(const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side) {
     if (!radii) throw std::runtime_error{"vkrh_set_shadow_area_lights: NULL argument"};
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_shadow_area_lights: on a tiled frame (VKRH_STAGE_SHADOW_MASK_RT runs on one GPU)"};
+    refuse_tiled("vkrh_set_shadow_area_lights", "VKRH_STAGE_SHADOW_MASK_RT runs on one GPU");
     if (4 * (size_t)count != shadow_rays.size())
       throw std::runtime_error{"vkrh_set_shadow_area_lights: count " + std::to_string(count) + ", but " + std::to_string(shadow_rays.size() / 4) +
                                " lights are set (vkrh_set_shadow_rays)"};
@@ -189,7 +232,7 @@ struct PostFxFrame {
   // shadow rays, max_distance 0 = the camera's zfar at the time of the run, level 0 of the hit's texture.
   AdvancedSSR::RtSettings reflection_rays {};
   void set_reflection_rays(uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod) {
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_reflection_rays: on a tiled frame (VKRH_STAGE_REFLECTIONS_RT runs on one GPU)"};
+    refuse_tiled("vkrh_set_reflection_rays", "VKRH_STAGE_REFLECTIONS_RT runs on one GPU");
     if (std::isnan(tmin)) throw std::runtime_error{"vkrh_set_reflection_rays: tmin is NaN"};
     if (std::isnan(max_distance)) throw std::runtime_error{"vkrh_set_reflection_rays: max_distance is NaN"};
     reflection_rays.fill_misses = fill_misses != 0; reflection_rays.normal_offset = normal_offset; reflection_rays.tmin = tmin;
@@ -200,7 +243,7 @@ struct PostFxFrame {
   // off, the opaque query.  VKRH_STAGE_GTAO_RT stays opaque, as the reference's rt_main.frag is.
   RtCutouts ray_cutouts {};
   void set_ray_cutouts(uint32_t enable, uint32_t alpha_lod) {
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_ray_cutouts: on a tiled frame (the ray-traced stages run on one GPU)"};
+    refuse_tiled("vkrh_set_ray_cutouts", "the ray-traced stages run on one GPU");
     ray_cutouts.enable = enable != 0; ray_cutouts.alpha_lod = alpha_lod;
   }
 
@@ -214,7 +257,7 @@ struct PostFxFrame {
   VkSampler backbuffer_sampler = gpu::create_sampler(gpu::DEFAULT_SAMPLER);
   rendergraph::ImageResourceId backbuffer_source_id() { return backbuffer_source.empty() ? taa_pass.get_output() : lookup(backbuffer_source); }
   void set_backbuffer(const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
-    if (cfg.tiled) throw std::runtime_error{"vkrh_set_backbuffer: on a tiled frame (VKRH_STAGE_BACKBUFFER runs on one GPU)"};
+    refuse_tiled("vkrh_set_backbuffer", "VKRH_STAGE_BACKBUFFER runs on one GPU");
     if ((width == 0) != (height == 0) || width > 65535 || height > 65535)
       throw std::runtime_error{"vkrh_set_backbuffer: extent " + std::to_string(width) + "x" + std::to_string(height) + " (0 x 0: the frame's; at most 65535 a side)"};
     const std::string name = source_image ? source_image : "";
@@ -283,7 +326,7 @@ struct PostFxFrame {
   void bake_probes(const float* mn, const float* mx, uint32_t grid_size, uint32_t probe_size, uint32_t cube_size) {
     // refused before anything is recorded
     if (!mn || !mx) throw std::runtime_error{"vkrh_bake_probes: NULL argument"};
-    if (cfg.tiled) throw std::runtime_error{"vkrh_bake_probes: on a tiled frame (probes are baked on one GPU)"};
+    refuse_tiled("vkrh_bake_probes", "probes are baked on one GPU");
     if (grid_size < 2 || grid_size > 64) throw std::runtime_error{"vkrh_bake_probes: grid_size " + std::to_string(grid_size) + ", needs 2..64"};
     if (probe_size == 0 || probe_size % 8 || probe_size > 4096) throw std::runtime_error{"vkrh_bake_probes: probe_size must be a multiple of 8 in 8..4096"};
     if (cube_size == 0 || cube_size % 8 || cube_size > 4096) throw std::runtime_error{"vkrh_bake_probes: cube_size must be a multiple of 8 in 8..4096"};
@@ -293,8 +336,7 @@ struct PostFxFrame {
     probe_grid.reset(new OctahedralProbeGrid(graph, grid_size, probe_size));
     probe_renderer->render_probe_grid(graph, *scene_renderer, glm::vec3{mn[0], mn[1], mn[2]}, glm::vec3{mx[0], mx[1], mx[2]}, *probe_grid);
     graph.submit();
-    task_names.clear();
-    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
+    record_submitted(false);
   }
 
   void set_shadow_lights(const float* mvps, uint32_t count, uint32_t size) {
@@ -322,52 +364,31 @@ struct PostFxFrame {
     shadows_rendered = false;
   }
 
+  bool has(Needs needs) const {
+    const bool tlas = scene_as && scene_as->tlas;
+    return needs == Needs::Scene ? scene_renderer != nullptr : needs == Needs::Tlas ? tlas : needs == Needs::TlasAndScene ? tlas && scene_renderer
+           : needs == Needs::Probes ? probe_grid != nullptr : true;
+  }
+  void check_stage_rules(uint32_t mask) {
+    for (const StageRule& rule : STAGE_RULES) {
+      if (!(mask & rule.stage)) continue;
+      const auto refuse = [&](const char* how, const char* tail, const char* end) {
+        throw std::runtime_error{std::string{"vkrh_run: "} + rule.name + how + tail + end};
+      };
+      if (cfg.tiled && rule.tiled) refuse(" on a tiled frame (", rule.tiled, ")");
+      if (mask & rule.rivals) refuse(" together with ", rule.rivals_tail, "");
+      if (!has(rule.needs)) refuse(" without ", rule.needs_tail, "");
+      // the two rules that are no table entries, at their stage's place in the order
+      if (rule.stage == VKRH_STAGE_BACKBUFFER) (void)backbuffer_source_id();  // a source that does not exist (yet) throws
+      if (rule.stage == VKRH_STAGE_SHADOW_MASK && !(mask & VKRH_STAGE_SHADOW) && !shadow_maps_current)
+        refuse(" without ", "rendered shadow maps (VKRH_STAGE_SHADOW for the lights in use)", "");
+    }
+  }
+
   void run(uint32_t mask) {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
-    if ((mask & VKRH_STAGE_CLEAR_PREV_DEPTH) && cfg.tiled)  // refused before anything is recorded
-      throw std::runtime_error{"vkrh_run: VKRH_STAGE_CLEAR_PREV_DEPTH on a tiled frame (transfers take whole images)"};
-    if ((mask & VKRH_STAGE_SSAO) && cfg.tiled)  // refused before anything is recorded
-      throw std::runtime_error{"vkrh_run: VKRH_STAGE_SSAO on a tiled frame (a sample's reach is unbounded near the eye: SSAO runs on one GPU)"};
-    if ((mask & VKRH_STAGE_TILE_REGRESSION) && cfg.tiled)  // refused before anything is recorded
-      throw std::runtime_error{"vkrh_run: VKRH_STAGE_TILE_REGRESSION on a tiled frame (halved strip bounds are no multiples of 8: tiles would straddle owners)"};
-    if ((mask & VKRH_STAGE_BACKBUFFER) && cfg.tiled)  // refused before anything is recorded
-      throw std::runtime_error{"vkrh_run: VKRH_STAGE_BACKBUFFER on a tiled frame (the uv of a pixel spans the whole source: the backbuffer is drawn on one GPU)"};
-    if (mask & VKRH_STAGE_BACKBUFFER) (void)backbuffer_source_id();  // a source that does not exist (yet) is refused before anything is recorded
-    if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT on a tiled frame (the rays reach anywhere: ray-traced shadows run on one GPU)"};
-      if (mask & VKRH_STAGE_SHADOW_MASK)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT together with VKRH_STAGE_SHADOW_MASK (both write the image shadow_mask)"};
-      if (!scene_as || !scene_as->tlas)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
-    }
-    if (mask & VKRH_STAGE_REFLECTIONS_RT) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT on a tiled frame (the rays reach anywhere: ray-traced reflections run on one GPU)"};
-      if (mask & (VKRH_STAGE_SSR | VKRH_STAGE_SSR_CLASSIFIED | VKRH_STAGE_SSR_RESOLVE | VKRH_STAGE_SSR_TRACE | VKRH_STAGE_SSR_TRACE_HEAD | VKRH_STAGE_SSR_TRACE_RESUME))
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT together with an SSR stage (VKRH_STAGE_SSR, _SSR_CLASSIFIED, _SSR_RESOLVE, _SSR_TRACE*: all write the images reflections / blurred)"};
-      if (!scene_as || !scene_as->tlas || !scene_renderer)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_REFLECTIONS_RT without a loaded scene (vkrh_load_scene builds its acceleration structure and attribute table)"};
-    }
-    if (mask & VKRH_STAGE_SHADOW_MASK) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK on a tiled frame (the shadow maps are rendered on one GPU)"};
-      if (!(mask & VKRH_STAGE_SHADOW) && !shadow_maps_current)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW_MASK without rendered shadow maps (VKRH_STAGE_SHADOW for the lights in use)"};
-    }
-    if (mask & VKRH_STAGE_SHADOW) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW on a tiled frame (the shadow maps are rendered on one GPU)"};
-      if (!scene_renderer) throw std::runtime_error{"vkrh_run: VKRH_STAGE_SHADOW without a loaded scene (vkrh_load_scene)"};
-    }
-    if (mask & VKRH_STAGE_GTAO_RT) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT on a tiled frame (ray-traced AO runs on one GPU)"};
-      if (mask & VKRH_STAGE_GTAO)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT together with VKRH_STAGE_GTAO (both write GTAO's raw, filtered and accumulated images)"};
-      if (!scene_as || !scene_as->tlas)
-        throw std::runtime_error{"vkrh_run: VKRH_STAGE_GTAO_RT without a loaded scene (vkrh_load_scene builds its acceleration structure)"};
-    }
+    check_stage_rules(mask);  // refused before anything is recorded
     const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
-    if (mask & VKRH_STAGE_PROBE_TRACE) {  // refused before anything is recorded
-      if (cfg.tiled) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE on a tiled frame (probes are traced on one GPU)"};
-      if (!probe_grid) throw std::runtime_error{"vkrh_run: VKRH_STAGE_PROBE_TRACE without baked probes (vkrh_bake_probes)"};
-    }
     if (mask & VKRH_STAGE_CLEAR_PREV_DEPTH) clear_depth(graph, gbuffer.prev_depth);  // main.cpp:306
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
     if (mask & VKRH_STAGE_BRDF_LUT) { ssr.preintegrate_brdf(graph); brdf_lut_ran = true; }
@@ -506,10 +527,7 @@ struct PostFxFrame {
     }
     graph.submit();
     if ((mask & (VKRH_STAGE_GBUFFER | VKRH_STAGE_RASTER)) && gbuffer.pipelined) copy_depth_to_next_set();
-    task_names.clear();
-    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
-    task_lanes.clear();
-    for (uint32_t l : graph.last_submitted_lanes()) { task_lanes += std::to_string(l); task_lanes += ' '; }
+    record_submitted(true);
   }
 
   // pipelined: the G-buffer's depth (mip 0 of the depth image) also into the second set — the G-buffer of the benchmark is one
@@ -542,30 +560,24 @@ struct PostFxFrame {
 
   std::map<std::string, rendergraph::ImageResourceId> user_images;  // vkrh_create_image
 
-  static VkFormat vk_format(uint32_t format) {
-    switch (format) {
-      case VKR_FMT_D24_UNORM_S8: return VK_FORMAT_D24_UNORM_S8_UINT; case VKR_FMT_RG16_UNORM: return VK_FORMAT_R16G16_UNORM;
-      case VKR_FMT_RG16_SFLOAT: return VK_FORMAT_R16G16_SFLOAT; case VKR_FMT_RGBA8_SRGB: return VK_FORMAT_R8G8B8A8_SRGB;
-      case VKR_FMT_RGBA8_UNORM: return VK_FORMAT_R8G8B8A8_UNORM; case VKR_FMT_RGBA16_UNORM: return VK_FORMAT_R16G16B16A16_UNORM;
-      case VKR_FMT_RGBA16_SFLOAT: return VK_FORMAT_R16G16B16A16_SFLOAT; case VKR_FMT_R16_SFLOAT: return VK_FORMAT_R16_SFLOAT;
-      case VKR_FMT_R32_SFLOAT: return VK_FORMAT_R32_SFLOAT; case VKR_FMT_R8_UNORM: return VK_FORMAT_R8_UNORM;
-      case VKR_FMT_RGBA32_SFLOAT: return VK_FORMAT_R32G32B32A32_SFLOAT; case VKR_FMT_R16_UNORM: return VK_FORMAT_R16_UNORM;
-      default: throw std::runtime_error{"vkrh_create_image: unknown format " + std::to_string(format)};
-    }
+  static VkFormat vk_format(uint32_t format) {  // the inverse of gpu::to_vkr_format
+    for (VkFormat f : {VK_FORMAT_D24_UNORM_S8_UINT, VK_FORMAT_R16G16_UNORM, VK_FORMAT_R16G16_SFLOAT, VK_FORMAT_R8G8B8A8_SRGB, VK_FORMAT_R8G8B8A8_UNORM,
+                       VK_FORMAT_R16G16B16A16_UNORM, VK_FORMAT_R16G16B16A16_SFLOAT, VK_FORMAT_R16_SFLOAT, VK_FORMAT_R32_SFLOAT, VK_FORMAT_R8_UNORM,
+                       VK_FORMAT_R32G32B32A32_SFLOAT, VK_FORMAT_R16_UNORM})
+      if (gpu::to_vkr_format(f) == format) return f;
+    throw std::runtime_error{"vkrh_create_image: unknown format " + std::to_string(format)};
   }
   void create_user_image(const char* name, uint32_t format, uint32_t w, uint32_t h, uint32_t mips, uint32_t layers) {
     if (!name || !*name) throw std::runtime_error{"vkrh_create_image: NULL name"};
-    if (cfg.tiled) throw std::runtime_error{"vkrh_create_image: on a tiled frame (transfers take whole images)"};
-    bool taken = user_images.count(name) != 0;
-    if (!taken) { try { lookup(name); taken = true; } catch (const std::exception& e) { taken = std::string{e.what()}.find("unknown image") == std::string::npos; } }
-    if (taken) throw std::runtime_error{std::string{"vkrh_create_image: the name '"} + name + "' is taken"};
+    refuse_tiled("vkrh_create_image", "transfers take whole images");
+    if (user_images.count(name) || named_image(name)) throw std::runtime_error{std::string{"vkrh_create_image: the name '"} + name + "' is taken"};
     const VkFormat fmt = vk_format(format);
     if (!w || !h || !mips || mips > VKR_MAX_MIPS || !layers) throw std::runtime_error{"vkrh_create_image: bad extent, mip or layer count"};
     const VkImageAspectFlags aspect = format == VKR_FMT_D24_UNORM_S8 ? VK_IMAGE_ASPECT_DEPTH_BIT | VK_IMAGE_ASPECT_STENCIL_BIT : VK_IMAGE_ASPECT_COLOR_BIT;
     user_images[name] = graph.create_frame_image(gpu::ImageInfo{fmt, aspect, w, h, 1, mips, layers});
   }
   void transfer(uint32_t op, const char* image, const char* dst, const float* value) {
-    if (cfg.tiled) throw std::runtime_error{"vkrh_transfer: on a tiled frame (transfers take whole images)"};
+    refuse_tiled("vkrh_transfer", "transfers take whole images");
     if (!image) throw std::runtime_error{"vkrh_transfer: NULL image name"};
     const rendergraph::ImageResourceId id = lookup(image);
     switch (op) {
@@ -588,50 +600,57 @@ struct PostFxFrame {
       default: throw std::runtime_error{"vkrh_transfer: unknown operation " + std::to_string(op)};
     }
     graph.submit();
-    task_names.clear();
-    for (const auto& n : graph.last_submitted_tasks()) { task_names += n; task_names += '\n'; }
+    record_submitted(false);
   }
 
+  // The names vkrh_image and its kin know besides the user's own: what each stands for and, for an image that is created on
+  // demand, when it exists ("vkrh_image: '<name>' <absent>" until then).  A new image is one line here.
+  struct NamedImage {
+    const char* name;
+    rendergraph::ImageResourceId (*image)(PostFxFrame&);
+    bool (*exists)(const PostFxFrame&) = nullptr;  // nullptr: always
+    const char* absent = nullptr;
+  };
+  static const NamedImage* named_image(const std::string& name) {
+    using F = PostFxFrame;
+    static constexpr const char* BAKED = "only exists after vkrh_bake_probes";
+    static const NamedImage table[] = {
+        {"depth", [](F& f) { return f.gbuffer.depth; }}, {"prev_depth", [](F& f) { return f.gbuffer.prev_depth; }}, {"normal", [](F& f) { return f.gbuffer.normal; }},
+        {"albedo", [](F& f) { return f.gbuffer.albedo; }}, {"material", [](F& f) { return f.gbuffer.material; }}, {"velocity", [](F& f) { return f.gbuffer.velocity_vectors; }},
+        {"dn", [](F& f) { return f.gbuffer.downsampled_normals; }}, {"dv", [](F& f) { return f.gbuffer.downsampled_velocity_vectors; }}, {"raw", [](F& f) { return f.gtao.raw; }},
+        {"filtered", [](F& f) { return f.gtao.filtered; }}, {"acc_ao", [](F& f) { return f.gtao.accumulated_ao; }}, {"acc_hist", [](F& f) { return f.gtao.accumulated_history; }},
+        {"rays", [](F& f) { return f.ssr.get_rays(); }}, {"reflections", [](F& f) { return f.ssr.get_ouput(); }}, {"blurred", [](F& f) { return f.ssr.get_blurred(); }},
+        {"blurred_hist", [](F& f) { return f.ssr.get_blurred_history(); }}, {"pdf", [](F& f) { return f.ssr.get_preintegrated_pdf(); }}, {"taa_hist", [](F& f) { return f.taa_pass.get_history(); }},
+        {"taa_target", [](F& f) { return f.taa_pass.get_output(); }}, {"frame_hiz", [](F& f) { return f.gbuffer.frame_hiz; }}, {"frame_normals", [](F& f) { return f.gbuffer.frame_normals; }},
+        {"frame_albedo", [](F& f) { return f.gbuffer.frame_albedo; }}, {"color_out", [](F& f) { return f.color_out_tex; }}, {"brdf", [](F& f) { return f.ssr.get_preintegrated_brdf(); }},
+        {"ao_prev_frame", [](F& f) { return f.gtao.prev_frame; }}, {"ao_output", [](F& f) { return f.gtao.output; }}, {"deinterleaved_depth", [](F& f) { return f.gtao.deinterleaved_depth; }},
+        {"st_raw", [](F& f) { return f.screen_trace.raw; }}, {"st_filtered", [](F& f) { return f.screen_trace.filtered; }}, {"st_accumulated", [](F& f) { return f.screen_trace.accumulated; }},
+        {"pend_mask", [](F& f) { return f.gbuffer.pend_mask; }, [](const F& f) { return f.gbuffer.normals_by_request; }, "only exists with hit normals by request"},
+        {"probe_trace", [](F& f) { return f.probe_trace_out; }, [](const F& f) { return f.has_probe_trace_out; }, "only exists after VKRH_STAGE_PROBE_TRACE"},
+        {"probe_color", [](F& f) { return f.probe_grid->color_array; }, [](const F& f) { return f.probe_grid != nullptr; }, BAKED},
+        {"probe_depth", [](F& f) { return f.probe_grid->depth_array; }, [](const F& f) { return f.probe_grid != nullptr; }, BAKED},
+        {"cubemap_color", [](F& f) { return f.probe_renderer->get_cubemap_color(); }, [](const F& f) { return f.probe_grid != nullptr; }, BAKED},
+        {"cubemap_distance", [](F& f) { return f.probe_renderer->get_cubemap_distance(); }, [](const F& f) { return f.probe_grid != nullptr; }, BAKED},
+        {"shadows", [](F& f) { return f.shadows; }, [](const F& f) { return f.has_shadows; }, "only exists after VKRH_STAGE_SHADOW"},
+        {"readback", [](F& f) { return f.readback_image; }, [](const F& f) { return f.has_readback_image; },
+         "only exists after a final-frame capture (vkrh_capture kind 3)"},
+        {"ssao", [](F& f) { return f.ssao_tex; }, [](const F& f) { return f.ssao_pass != nullptr; }, "only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"},
+        {"tile_planes", [](F& f) { return f.ssr.get_tile_planes(); }, [](const F& f) { return f.has_tile_planes; }, "only exists after VKRH_STAGE_TILE_REGRESSION"},
+        {"backbuffer", [](F& f) { return f.graph.get_backbuffer(); }, [](const F& f) { return f.backbuffer_drawn; }, "only exists after VKRH_STAGE_BACKBUFFER"},
+        {"shadow_mask", [](F& f) { return f.shadow_mask_tex; }, [](const F& f) { return f.shadow_mask_pass != nullptr; },
+         "only exists after VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT"},
+    };
+    for (const NamedImage& e : table)
+      if (name == e.name) return &e;
+    return nullptr;
+  }
   rendergraph::ImageResourceId lookup(const std::string& name) {
-    {
-      auto user = user_images.find(name);
-      if (user != user_images.end()) return user->second;
-    }
-    static const std::map<std::string, int> ids = {
-        {"depth", 0}, {"prev_depth", 1}, {"normal", 2}, {"albedo", 3}, {"material", 4}, {"velocity", 5}, {"dn", 6}, {"dv", 7},
-        {"raw", 8}, {"filtered", 9}, {"acc_ao", 10}, {"acc_hist", 11}, {"rays", 12}, {"reflections", 13}, {"blurred", 14},
-        {"blurred_hist", 15}, {"pdf", 16}, {"taa_hist", 17}, {"taa_target", 18}, {"frame_hiz", 19}, {"frame_normals", 20},
-        {"frame_albedo", 21}, {"color_out", 22}, {"brdf", 23}, {"ao_prev_frame", 24}, {"ao_output", 25}, {"deinterleaved_depth", 26},
-        {"st_raw", 27}, {"st_filtered", 28}, {"st_accumulated", 29}, {"pend_mask", 30}, {"probe_trace", 31}, {"probe_color", 32},
-        {"probe_depth", 33}, {"cubemap_color", 34}, {"cubemap_distance", 35}, {"shadows", 36}, {"readback", 37}, {"ssao", 38},
-        {"tile_planes", 39}, {"backbuffer", 40}, {"shadow_mask", 41}};
-    auto it = ids.find(name);
-    if (it == ids.end()) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
-    switch (it->second) {
-      case 0: return gbuffer.depth; case 1: return gbuffer.prev_depth; case 2: return gbuffer.normal; case 3: return gbuffer.albedo;
-      case 4: return gbuffer.material; case 5: return gbuffer.velocity_vectors; case 6: return gbuffer.downsampled_normals;
-      case 7: return gbuffer.downsampled_velocity_vectors; case 8: return gtao.raw; case 9: return gtao.filtered;
-      case 10: return gtao.accumulated_ao; case 11: return gtao.accumulated_history; case 12: return ssr.get_rays();
-      case 13: return ssr.get_ouput(); case 14: return ssr.get_blurred(); case 15: return ssr.get_blurred_history();
-      case 16: return ssr.get_preintegrated_pdf(); case 17: return taa_pass.get_history(); case 18: return taa_pass.get_output();
-      case 19: return gbuffer.frame_hiz; case 20: return gbuffer.frame_normals; case 21: return gbuffer.frame_albedo;
-      case 22: return color_out_tex; case 23: return ssr.get_preintegrated_brdf(); case 24: return gtao.prev_frame;
-      case 25: return gtao.output; case 26: return gtao.deinterleaved_depth; case 27: return screen_trace.raw;
-      case 28: return screen_trace.filtered;
-      case 31: if (!has_probe_trace_out) throw std::runtime_error{"vkrh_image: 'probe_trace' only exists after VKRH_STAGE_PROBE_TRACE"}; return probe_trace_out;
-      case 32: case 33: case 34: case 35:
-        if (!probe_grid) throw std::runtime_error{"vkrh_image: '" + name + "' only exists after vkrh_bake_probes"};
-        return it->second == 32 ? probe_grid->color_array : it->second == 33 ? probe_grid->depth_array
-               : it->second == 34 ? probe_renderer->get_cubemap_color() : probe_renderer->get_cubemap_distance();
-      case 36: if (!has_shadows) throw std::runtime_error{"vkrh_image: 'shadows' only exists after VKRH_STAGE_SHADOW"}; return shadows;
-      case 37: if (!has_readback_image) throw std::runtime_error{"vkrh_image: 'readback' only exists after a final-frame capture (vkrh_capture kind 3)"}; return readback_image;
-      case 38: if (!ssao_pass) throw std::runtime_error{"vkrh_image: 'ssao' only exists after VKRH_STAGE_SSAO or vkrh_set_ssao_samples"}; return ssao_tex;
-      case 39: if (!has_tile_planes) throw std::runtime_error{"vkrh_image: 'tile_planes' only exists after VKRH_STAGE_TILE_REGRESSION"}; return ssr.get_tile_planes();
-      case 40: if (!backbuffer_drawn) throw std::runtime_error{"vkrh_image: 'backbuffer' only exists after VKRH_STAGE_BACKBUFFER"}; return graph.get_backbuffer();
-      case 41: if (!shadow_mask_pass) throw std::runtime_error{"vkrh_image: 'shadow_mask' only exists after VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT"}; return shadow_mask_tex;
-      case 30: if (!gbuffer.normals_by_request) throw std::runtime_error{"vkrh_image: 'pend_mask' only exists with hit normals by request"}; return gbuffer.pend_mask;
-      default: return screen_trace.accumulated;
-    }
+    const auto user = user_images.find(name);
+    if (user != user_images.end()) return user->second;
+    const NamedImage* e = named_image(name);
+    if (!e) throw std::runtime_error{"vkrh_image: unknown image '" + name + "'"};
+    if (e->exists && !e->exists(*this)) throw std::runtime_error{"vkrh_image: '" + name + "' " + e->absent};
+    return e->image(*this);
   }
 };
 
@@ -1334,6 +1353,31 @@ PostFxFrame& frame_ref(void* frame) {
   return *(PostFxFrame*)frame;
 }
 
+// ---- what the selftests share: they write lines into `out` and hand them to the caller's buffer ----
+void expect(std::string& out, const char* name, const std::function<void()>& f) {  // "case: no error" or "case: <what()>"
+  try { f(); out += std::string{name} + ": no error\n"; }
+  catch (const std::exception& e) { out += std::string{name} + ": " + e.what() + "\n"; }
+}
+// one line per task recorded since the last submit: "name: R<image>.<mip> ... W<image>.<mip> ...", the declared reads and writes
+void dump_pending_tasks(const rendergraph::RenderGraph& graph, std::string& out) {
+  for (const auto& t : graph.pending_tasks()) {
+    out += t.name + ":";
+    for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
+    out += "\n";
+  }
+}
+// a struct of 32-bit words as floats (%.9g) and the end of the line
+template <typename T> void append_words(std::string& out, const T& value) {
+  float words[sizeof(T) / 4];
+  std::memcpy(words, &value, sizeof(T));
+  for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
+  out += "\n";
+}
+int copy_out(char* buf, uint32_t buf_size, const std::string& out) {
+  if (buf && buf_size) std::snprintf(buf, buf_size, "%s", out.c_str());
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1408,7 +1452,7 @@ int vkrh_scene_texture_image(void* frame, uint32_t index, vkr_img* out) {
   return guarded([&] {
     auto* f = &frame_ref(frame);
     if (!out) throw std::runtime_error{"vkrh_scene_texture_image: NULL argument"};
-    if (f->cfg.tiled) throw std::runtime_error{"vkrh_scene_texture_image: on a tiled frame (scene textures live on one GPU)"};
+    f->refuse_tiled("vkrh_scene_texture_image", "scene textures live on one GPU");
     if (!f->loaded_scene) throw std::runtime_error{"vkrh_scene_texture_image: without a loaded scene (vkrh_load_scene)"};
     if (index >= f->loaded_scene->images.size()) throw std::runtime_error{"vkrh_scene_texture_image: texture " + std::to_string(index) + " of " + std::to_string(f->loaded_scene->images.size())};
     const auto& img = f->loaded_scene->images[index];
@@ -1429,12 +1473,8 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
     std::memcpy(out, f->shadow_lights.data(), 64 * f->shadow_lights.size());
   });
 }
-int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply) {
-  return guarded([&] { frame_ref(frame).set_shadow_mask(bias, radius, apply); });
-}
-int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) {
-  return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); });
-}
+int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply) { return guarded([&] { frame_ref(frame).set_shadow_mask(bias, radius, apply); }); }
+int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) { return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); }); }
 int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
   return guarded([&] { frame_ref(frame).set_backbuffer(source_image, flags, width, height); });
 }
@@ -1447,9 +1487,7 @@ int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_off
 int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side) {
   return guarded([&] { frame_ref(frame).set_shadow_area_lights(radii, count, sample_count, pattern_side); });
 }
-int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) {
-  return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); });
-}
+int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) { return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); }); }
 
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {
@@ -1604,35 +1642,22 @@ const char* vkrh_collect_task_times(void* frame) {
 }
 int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
   std::string out;
-  auto expect = [&](const char* name, std::function<void()> f) {
-    try { f(); out += std::string{name} + ": no error\n"; }
-    catch (const std::exception& e) { out += std::string{name} + ": " + e.what() + "\n"; }
+  expect(out, "unknown_program", [] { gpu::create_compute_pipeline("no_such_program"); });
+  expect(out, "known_program", [] { gpu::create_compute_pipeline("gtao_compute_main"); });
+  const auto downsample = [](uint32_t depth_mips, uint32_t normals_width) {  // DownsamplePass::run on a 16 x 16 G-buffer
+    rendergraph::RenderGraph g;
+    const auto u = VK_IMAGE_USAGE_SAMPLED_BIT;
+    auto d = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 16, 16, 1, depth_mips, 1}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto n = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto v = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto on = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, normals_width, 8}, VK_IMAGE_TILING_OPTIMAL, u);
+    auto ov = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, u);
+    DownsamplePass pass;
+    pass.run(g, n, v, d, on, ov);
   };
-  expect("unknown_program", [] { gpu::create_compute_pipeline("no_such_program"); });
-  expect("known_program", [] { gpu::create_compute_pipeline("gtao_compute_main"); });
-  expect("single_mip_depth", [] {
-    rendergraph::RenderGraph g;
-    const auto u = VK_IMAGE_USAGE_SAMPLED_BIT;
-    auto d = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto n = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto v = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto on = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto ov = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, u);
-    DownsamplePass pass;
-    pass.run(g, n, v, d, on, ov);
-  });
-  expect("mismatched_outputs", [] {
-    rendergraph::RenderGraph g;
-    const auto u = VK_IMAGE_USAGE_SAMPLED_BIT;
-    auto d = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 16, 16, 1, 5, 1}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto n = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto v = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 16, 16}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto on = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 4, 8}, VK_IMAGE_TILING_OPTIMAL, u);
-    auto ov = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, u);
-    DownsamplePass pass;
-    pass.run(g, n, v, d, on, ov);
-  });
-  expect("incompatible_usage", [] {
+  expect(out, "single_mip_depth", [&] { downsample(1, 8); });
+  expect(out, "mismatched_outputs", [&] { downsample(5, 4); });
+  expect(out, "incompatible_usage", [] {
     rendergraph::RenderGraph g;
     auto img = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT);
     struct D { rendergraph::ImageViewId a, b; };
@@ -1640,14 +1665,14 @@ int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
       [&](D& d, rendergraph::RenderGraphBuilder& b) { d.a = b.sample_image(img, VK_SHADER_STAGE_COMPUTE_BIT); d.b = b.use_storage_image(img, VK_SHADER_STAGE_COMPUTE_BIT, 0, 0); },
       [](D&, rendergraph::RenderResources&, gpu::CmdContext&) {});
   });
-  expect("read_then_write_in_separate_tasks", [] {
+  expect(out, "read_then_write_in_separate_tasks", [] {
     rendergraph::RenderGraph g;
     auto img = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT);
     struct D { rendergraph::ImageViewId a; };
     g.add_task<D>("r", [&](D& d, rendergraph::RenderGraphBuilder& b) { d.a = b.sample_image(img, VK_SHADER_STAGE_COMPUTE_BIT); }, [](D&, rendergraph::RenderResources&, gpu::CmdContext&) {});
     g.add_task<D>("w", [&](D& d, rendergraph::RenderGraphBuilder& b) { d.a = b.use_storage_image(img, VK_SHADER_STAGE_COMPUTE_BIT, 0, 0); }, [](D&, rendergraph::RenderResources&, gpu::CmdContext&) {});
   });
-  expect("remap_keeps_ids_valid", [&] {
+  expect(out, "remap_keeps_ids_valid", [&] {
     rendergraph::RenderGraph g;
     auto a = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 8, 8}, VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT);
     auto b = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16_SFLOAT, VK_IMAGE_ASPECT_COLOR_BIT, 16, 8}, VK_IMAGE_TILING_OPTIMAL, VK_IMAGE_USAGE_STORAGE_BIT);
@@ -1657,7 +1682,7 @@ int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
     if (g.get_image(a)->device_ptr() != pb || g.get_image(b)->device_ptr() != pa || g.get_descriptor(a).width != 16)
       throw std::runtime_error{"remap did not swap the table entries"};
   });
-  expect("tasks_run_in_submission_order", [&] {
+  expect(out, "tasks_run_in_submission_order", [&] {
     rendergraph::RenderGraph g;
     std::string order;
     struct D {};
@@ -1667,14 +1692,26 @@ int vkrh_selftest_errors(char* buf, uint32_t buf_size) {
     g.submit();
     if (order != "abc") throw std::runtime_error{"tasks reordered: " + order};
   });
-  expect("ray_query_gtao", [] { rendergraph::RenderGraph g; GTAO gtao{g, 64, 64, true}; });
-  expect("ubo_ring_overflow", [] {
+  expect(out, "ray_query_gtao", [] { rendergraph::RenderGraph g; GTAO gtao{g, 64, 64, true}; });
+  expect(out, "ubo_ring_overflow", [] {
     gpu::UniformBufferPool pool;
     struct Big { char b[6000]; };
     pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>(); pool.allocate_ubo<Big>();
   });
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return copy_out(buf, buf_size, out);
+}
+
+int vkrh_selftest_programs(char* buf, uint32_t buf_size) {
+  std::string out;
+  gpu::register_hot_path_programs();
+  for (const std::string& name : gpu::program_names())
+    expect(out, name.c_str(), [&] {
+      gpu::CmdContext cmd;
+      cmd.bind_pipeline(gpu::create_compute_pipeline(name.c_str()));
+      cmd.bind_descriptors_compute(0, {cmd.allocate_set()});
+      cmd.dispatch(1, 1, 1);
+    });
+  return copy_out(buf, buf_size, out);
 }
 
 int vkrh_create_image(void* frame, const char* name, uint32_t format, uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t array_layers) {
@@ -1699,15 +1736,9 @@ int vkrh_selftest_transfers(char* buf, uint32_t buf_size) {
     red.float32[0] = 1.f;
     clear_color(g, color, red);
     blit_image(g, src, dst);
-    for (const auto& t : g.pending_tasks()) {
-      out += t.name + ":";
-      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
-      out += "\n";
-    }
+    dump_pending_tasks(g, out);
   });
-  if (rc != 0) return rc;
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return rc != 0 ? rc : copy_out(buf, buf_size, out);
 }
 
 int vkrh_selftest_ssao(char* buf, uint32_t buf_size) {
@@ -1721,25 +1752,16 @@ int vkrh_selftest_ssao(char* buf, uint32_t buf_size) {
     for (uint32_t k = 0; k < 16; k++) pass.sphere_samples[k] = glm::vec3{float(3 * k), float(3 * k + 1), float(3 * k + 2)};
     const SSAOInParams params{glm::mat4{1.f}, 1.0f, 1.5f, 0.05f, 80.f};
     pass.draw(g, depth, target, params);
-    for (const auto& t : g.pending_tasks()) {
-      out += t.name + ":";
-      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
-      out += "\n";
-    }
+    dump_pending_tasks(g, out);
     for (const bool std140 : {false, true}) {
       pass.std140_samples = std140;
       const std::vector<uint8_t> block = pass.uniform_block(params);
       const vkr_ssao_params p = gpu::ssao_params_from_block(block.data(), block.size());
       out += "packing " + std::to_string(block.size()) + ":";
-      float words[sizeof(p) / 4];
-      std::memcpy(words, &p, sizeof(p));
-      for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
-      out += "\n";
+      append_words(out, p);
     }
   });
-  if (rc != 0) return rc;
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return rc != 0 ? rc : copy_out(buf, buf_size, out);
 }
 
 int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size) {
@@ -1757,21 +1779,12 @@ int vkrh_selftest_tile_regression(char* buf, uint32_t buf_size) {
     out += "images: depth " + std::to_string(depth) + " tile_planes " + std::to_string(planes) + "\n";
     const auto ext = g.get_descriptor(pass.get_tile_planes());
     out += "tile_planes: " + std::to_string(ext.width) + "x" + std::to_string(ext.height) + " format " + std::to_string(int(ext.format)) + "\n";
-    for (const auto& t : g.pending_tasks()) {
-      out += t.name + ":";
-      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
-      out += "\n";
-    }
+    dump_pending_tasks(g, out);
     const vkr_tile_regression_push pc = AdvancedSSR::tile_regression_push(params);
-    float words[sizeof(pc) / 4];
-    std::memcpy(words, &pc, sizeof(pc));
     out += "push " + std::to_string(sizeof(pc)) + ":";
-    for (float w : words) { char num[32]; std::snprintf(num, sizeof num, " %.9g", w); out += num; }
-    out += "\n";
+    append_words(out, pc);
   });
-  if (rc != 0) return rc;
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return rc != 0 ? rc : copy_out(buf, buf_size, out);
 }
 
 int vkrh_selftest_texdraw(char* buf, uint32_t buf_size) {
@@ -1787,58 +1800,42 @@ int vkrh_selftest_texdraw(char* buf, uint32_t buf_size) {
     out += "images: source " + std::to_string(source.get_index()) + " backbuffer " + std::to_string(backbuffer.get_index()) + "\n";
     const auto ext = g.get_descriptor(backbuffer);
     out += "backbuffer: " + std::to_string(ext.width) + "x" + std::to_string(ext.height) + " format " + std::to_string(int(ext.format)) + "\n";
-    for (const auto& t : g.pending_tasks()) {
-      out += t.name + ":";
-      for (const auto& a : t.accesses) out += std::string{a.write ? " W" : " R"} + std::to_string(a.key >> 8) + "." + std::to_string(a.key & 0xFF);
-      out += "\n";
-    }
+    dump_pending_tasks(g, out);
     out += std::string{"program: texdraw "} + (gpu::has_program("texdraw") ? "1" : "0") + "\n";
     const vkr_texdraw_push pc = texdraw_push(DrawTex::ShowR);
     out += "push " + std::to_string(sizeof(pc)) + ": " + std::to_string(pc.flags) + "\n";
   });
-  if (rc != 0) return rc;
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return rc != 0 ? rc : copy_out(buf, buf_size, out);
 }
 
 int vkrh_selftest_ray_query(char* buf, uint32_t buf_size) {
   std::string out;
-  auto expect = [&](const char* name, std::function<void()> f) {
-    try { f(); out += std::string{name} + ": no error\n"; }
-    catch (const std::exception& e) { out += std::string{name} + ": " + e.what() + "\n"; }
-  };
   const GTAORTParams params{glm::mat4{1.f}, 1.0f, 1.0f, 0.05f, 80.f};
   auto images = [](rendergraph::RenderGraph& g, rendergraph::ImageResourceId& depth, rendergraph::ImageResourceId& normal) {
     const auto u = VK_IMAGE_USAGE_SAMPLED_BIT;
     depth = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_D24_UNORM_S8_UINT, VK_IMAGE_ASPECT_DEPTH_BIT, 64, 64, 1, 7, 1}, VK_IMAGE_TILING_OPTIMAL, u);
     normal = g.create_image(VK_IMAGE_TYPE_2D, gpu::ImageInfo{VK_FORMAT_R16G16_UNORM, VK_IMAGE_ASPECT_COLOR_BIT, 64, 64}, VK_IMAGE_TILING_OPTIMAL, u);
   };
-  expect("default_graph", [] { rendergraph::RenderGraph g; GTAO gtao{g, 64, 64, true}; });
-  expect("ray_query_graph", [] { rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}}; GTAO gtao{g, 64, 64, true}; });
-  expect("device_config", [] {
+  expect(out, "default_graph", [] { rendergraph::RenderGraph g; GTAO gtao{g, 64, 64, true}; });
+  expect(out, "ray_query_graph", [] { rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}}; GTAO gtao{g, 64, 64, true}; });
+  expect(out, "device_config", [] {
     rendergraph::RenderGraph a, b{nullptr, gpu::DeviceConfig{true}};
     if (a.get_device_config().use_ray_query || !b.get_device_config().use_ray_query) throw std::runtime_error{"device config not kept per graph"};
   });
-  expect("null_tlas", [&] {
+  const auto rt_pass = [&](bool ray_query, bool with_tlas) {  // add_main_rt_pass of a GTAO built with / without ray query
     rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}};
-    GTAO gtao{g, 64, 64, true};
+    GTAO gtao{g, 64, 64, ray_query};
     rendergraph::ImageResourceId depth, normal;
     images(g, depth, normal);
-    gtao.add_main_rt_pass(g, params, nullptr, depth, normal);
-  });
-  expect("rt_pass_without_ray_query", [&] {
-    rendergraph::RenderGraph g{nullptr, gpu::DeviceConfig{true}};
-    GTAO gtao{g, 64, 64, false};
-    rendergraph::ImageResourceId depth, normal;
-    images(g, depth, normal);
-    gtao.add_main_rt_pass(g, params, (VkAccelerationStructureKHR)&gtao, depth, normal);
-  });
-  expect("null_accel_binding", [] {
+    gtao.add_main_rt_pass(g, params, with_tlas ? (VkAccelerationStructureKHR)&gtao : nullptr, depth, normal);
+  };
+  expect(out, "null_tlas", [&] { rt_pass(true, false); });
+  expect(out, "rt_pass_without_ray_query", [&] { rt_pass(false, true); });
+  expect(out, "null_accel_binding", [] {
     gpu::CmdContext cmd;
     gpu::write_set(cmd.allocate_set(), gpu::AccelerationStructBinding{3, nullptr});
   });
-  if (buf && buf_size) { std::snprintf(buf, buf_size, "%s", out.c_str()); }
-  return 0;
+  return copy_out(buf, buf_size, out);
 }
 
 // ---- tiled frame ----------------------------------------------------------------------------------------------------

@@ -267,6 +267,10 @@ const char* vkrh_collect_task_times(void* frame);
 /* Exercises the rendergraph / pass error paths the reference signals with exceptions (no kernel is
  * launched; images come from the installed allocator).  Writes "case: message" lines into buf. */
 int vkrh_selftest_errors(char* buf, uint32_t buf_size);
+/* Every registered program launched on an empty descriptor set, with no attachments and no push constants (no kernel is
+ * launched: each program refuses first).  Writes one line "program: message" per program, sorted by name; a program that
+ * does not refuse is reported as "program: no error". */
+int vkrh_selftest_programs(char* buf, uint32_t buf_size);
 /* The transfer helpers of util_passes.hpp on images of the frame's graph, for launchers written against the rendergraph API.
  * vkrh_create_image adds an image of the caller's own (format: a vkr_format; never a window of the frame) that vkrh_image /
  * vkrh_image_layer then find under `name`; a name of the frame's own images or one already taken is refused.  vkrh_transfer records

@@ -289,6 +289,113 @@ template <typename T> const T* push(const LaunchState& st, const char* prog) {
   if (st.push_size < sizeof(T)) throw std::runtime_error{std::string{prog} + ": push constants missing"};
   return (const T*)st.push;
 }
+Buffer* ssbo(const LaunchState& st, uint32_t slot, const char* prog) {
+  const SetSlot& s = st.set ? st.set->slots[slot] : SetSlot{};
+  if (!st.set || s.kind != SetSlot::Ssbo || !s.buffer) throw std::runtime_error{std::string{prog} + ": storage buffer " + std::to_string(slot) + " is not bound"};
+  return s.buffer.get();
+}
+// the Halton(2,3) table of a program, completed and on the device (halton_table)
+const float* halton(const LaunchState& st, uint32_t slot, const char* prog) {
+  const SetSlot& h = st.set->slots[slot];
+  if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{std::string{prog} + ": Halton buffer (binding " + std::to_string(slot) + ") is not bound"};
+  return halton_table(h.buffer.get(), st.stream);
+}
+const vkr_accel* accel(const LaunchState& st, uint32_t slot, const char* prog) {
+  const SetSlot& as = st.set->slots[slot];
+  if (as.kind != SetSlot::AccelStruct || !as.tlas)
+    throw std::runtime_error{std::string{prog} + ": acceleration structure (binding " + std::to_string(slot) + ") is not bound"};
+  return (const vkr_accel*)as.tlas;
+}
+// attachment `i` of a graphics program (colour..., depth last) as a one-mip image; `store`: only the rows the frame asked for
+// (a tiled frame shades its strip and one row either side, Image::set_store_rows)
+vkr_img attachment(const LaunchState& st, size_t i, bool store = false) {
+  const ImageViewObject& a = st.attachments[i];
+  return store ? a.image->describe_store(a.range.base_mip, 1) : a.image->describe(a.range.base_mip, 1);
+}
+// the full-screen programs draw into exactly one colour attachment
+void expect_one_attachment(const LaunchState& st, const char* prog) {
+  if (st.attachments.size() != 1) throw std::runtime_error{std::string{prog} + ": expects one colour attachment"};
+}
+// the view behind a texture / storage binding, for the programs that look at the image's layers themselves
+const ImageViewObject& bound_view(const LaunchState& st, uint32_t slot, SetSlot::Kind kind, const char* prog) {
+  if (!st.set || st.set->slots[slot].kind != kind || !st.set->slots[slot].view.image)
+    throw std::runtime_error{std::string{prog} + ": binding " + std::to_string(slot) + " is not bound as expected"};
+  return st.set->slots[slot].view;
+}
+// a view of one layer of an array image (or of a plain image) as the C-ABI descriptor of its mips
+vkr_img layer_view(const ImageViewObject& v) {
+  return v.image->get_array_layers() > 1 ? v.image->describe_layer(v.range.base_layer, v.range.base_mip, v.range.mips_count)
+                                         : v.image->describe(v.range.base_mip, v.range.mips_count);
+}
+std::vector<vkr_img> layers_of(const LaunchState& st, uint32_t slot, SetSlot::Kind kind, const char* prog) {
+  const Image& image = *bound_view(st, slot, kind, prog).image;
+  std::vector<vkr_img> layers;
+  for (uint32_t l = 0; l < image.get_array_layers(); l++) layers.push_back(image.describe_layer(l));
+  return layers;
+}
+// What the three windowed traces bind at the same slots, after the depth at 0 (the head: its window's pyramid levels at 0 and the
+// whole-frame pyramid at 10).  Looked up in slot order, so the first unbound slot is the one reported.
+struct WindowedTraceImages {
+  vkr_img normal, material, rays, occ, pdf, mask, data;
+  WindowedTraceImages(const LaunchState& st, const char* prog)
+      : normal{tex(st, 1, SetSlot::Texture, prog)}, material{tex(st, 2, SetSlot::Texture, prog)}, rays{tex(st, 5, SetSlot::StorageTexture, prog)},
+        occ{tex(st, 6, SetSlot::StorageTexture, prog)}, pdf{tex(st, 7, SetSlot::Texture, prog)}, mask{tex(st, 8, SetSlot::StorageTexture, prog)},
+        data{tex(st, 9, SetSlot::StorageTexture, prog)} {}
+};
+// What the three raster programs hand their kernels: the bound geometry, the host-visible transforms at binding 1, the textures
+// of `textures_from` and one vkr_raster_draw per recorded draw_indexed, from the first `push_bytes` bytes of its PushData
+// {transform, albedo, mr, flags}; an index the push constants do not carry is 0xFFFFFFFF, no texture.  A program makes the two
+// checks where it always made them (its own checks of the attachments lie between them), then builds the scene.
+struct RasterScene {
+  std::vector<vkr_img> textures;
+  std::vector<vkr_raster_draw> draws;
+  vkr_raster_scene scene{};
+  uint32_t triangles = 0;
+  static void expect_geometry(const LaunchState& st, const char* prog) {
+    if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{std::string{prog} + ": vertex / index buffer not bound"};
+  }
+  static Buffer* host_transforms(const LaunchState& st, const char* prog) {
+    Buffer* transforms = ssbo(st, 1, prog);
+    if (!transforms->host_data()) throw std::runtime_error{std::string{prog} + ": the transform buffer must be host-visible on this path"};
+    return transforms;
+  }
+  // `flag_opaque_albedo`: VKR_RASTER_DRAW_OPAQUE_ALBEDO where the discard of the fragment shader cannot fire
+  RasterScene(const LaunchState& st, const char* prog, Buffer* transforms, size_t push_bytes, const DescriptorSetObject* textures_from, bool flag_opaque_albedo) {
+    if (textures_from)
+      for (const auto& v : textures_from->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
+    for (const auto& d : st.indexed_draws) {
+      if (d.push.size() < push_bytes) throw std::runtime_error{std::string{prog} + ": push constants missing"};
+      vkr_raster_draw r{};
+      std::memcpy(&r, d.push.data(), push_bytes);
+      if (push_bytes < 8) r.albedo_index = 0xFFFFFFFFu;
+      if (push_bytes < 12) r.mr_index = 0xFFFFFFFFu;
+      r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
+      if (flag_opaque_albedo && textures_from && r.albedo_index < textures_from->image_array.size() && textures_from->image_array[r.albedo_index].image->alpha_never_zero)
+        r.reserved |= VKR_RASTER_DRAW_OPAQUE_ALBEDO;
+      triangles += d.index_count / 3u;
+      draws.push_back(r);
+    }
+    scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
+    scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
+    scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
+    scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
+    scene.transforms = (const vkr_raster_transform*)transforms->host_data();
+    scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
+    scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
+    scene.textures = textures.empty() ? nullptr : textures.data(); scene.texture_count = (uint32_t)textures.size();
+  }
+  RasterScene(const RasterScene&) = delete;  // `scene` points into the vectors
+};
+// grows a device allocation of the command context: the old one may still be in use on the stream
+void* grow_only(void*& memory, uint64_t& have, uint64_t bytes, void* stream) {
+  if (bytes > have) {
+    if (memory) { (void)hipStreamSynchronize((hipStream_t)stream); device_free(memory); }
+    memory = nullptr; have = 0;  // (should the allocation throw)
+    memory = device_alloc(bytes);
+    have = bytes;
+  }
+  return memory;
+}
 }  // namespace
 
 vkr_ssao_params ssao_params_from_block(const void* block, uint64_t bytes) {
@@ -299,6 +406,11 @@ vkr_ssao_params ssao_params_from_block(const void* block, uint64_t bytes) {
 
 void create_program(const std::string& name, ProgramFn fn) { programs()[name] = std::move(fn); }
 bool has_program(const std::string& name) { return programs().count(name) != 0; }
+std::vector<std::string> program_names() {
+  std::vector<std::string> names;
+  for (const auto& p : programs()) names.push_back(p.first);
+  return names;
+}
 
 void register_hot_path_programs() {
   static std::once_flag once;
@@ -314,8 +426,7 @@ void register_hot_path_programs() {
         throw std::runtime_error{"downsample_gbuffer: depth attachment must be the next mip of the sampled depth"};
       vkr_img depth = ds.view.image->describe(ds.view.range.base_mip, 2);
       vkr_img n = tex(st, 1, T, P), v = tex(st, 2, T, P);
-      vkr_img on = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
-      vkr_img ov = st.attachments[1].image->describe(st.attachments[1].range.base_mip, 1);
+      vkr_img on = attachment(st, 0), ov = attachment(st, 1);
       return vkr_downsample_gbuffer(&depth, &n, &v, &on, &ov, st.stream);
     });
     // advanced_ssr/depth_mips.frag: set {0 depth mip i-1}; attachments {depth mip i, i+1, ...}.
@@ -344,15 +455,14 @@ void register_hot_path_programs() {
     // gtao/rt_main.frag: set {0 GTAORTParams, 1 depth, 2 normal, 3 acceleration structure, 4 RandomVectors}; colour attachment raw
     create_program("gtao_rt_main", [=](LaunchState& st) {
       const char* P = "gtao_rt_main";
-      if (st.attachments.size() != 1) throw std::runtime_error{"gtao_rt_main: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img depth = tex(st, 1, T, P), normal = tex(st, 2, T, P);
-      const SetSlot& as = st.set->slots[3];
-      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"gtao_rt_main: acceleration structure (binding 3) is not bound"};
+      const vkr_accel* scene = accel(st, 3, P);
       const SetSlot& dirs = st.set->slots[4];
       if (dirs.kind != SetSlot::Ubo || !dirs.buffer || dirs.buffer->get_size() < 64 * 16)
         throw std::runtime_error{"gtao_rt_main: random directions (binding 4, 64 x vec4) are not bound"};
-      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
-      return vkr_gtao_rt_main(ubo<vkr_gtao_rt_params>(st, 0, P), &depth, &normal, (const vkr_accel*)as.tlas,
+      vkr_img out = attachment(st, 0);
+      return vkr_gtao_rt_main(ubo<vkr_gtao_rt_params>(st, 0, P), &depth, &normal, scene,
                               (const float*)dirs.buffer->device_ptr(st.stream), &out, push<vkr_gtao_rt_push>(st, P), st.stream);
     });
     create_program("pdf_preintegrate", [=](LaunchState& st) {
@@ -363,8 +473,7 @@ void register_hot_path_programs() {
       const char* P = "sssr_trace";
       vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P);
       vkr_img rays = tex(st, 5, S, P), occ = tex(st, 6, S, P), pdf = tex(st, 7, T, P);
-      const SetSlot& h = st.set->slots[4];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"sssr_trace: Halton buffer (binding 4) is not bound"};
+      const float* table = halton(st, 4, P);
       // Two launches where they pay: the rays still marching after step 48 (two of the four compacted rounds: a tenth of them) are
       // parked in the context's workspace and finished by the resume launch, 256 rays of many tiles per block.  Same images bit
       // for bit.  Measured on one MI355X (tools/trace_split_probe.py): 3840x2160 0.259 against 0.272 ms (park after one round
@@ -373,43 +482,39 @@ void register_hot_path_programs() {
       // 270 MB at 15360x8640) must stay in the caches between the two launches for the resume launch to be cheap.
       const uint64_t n_rays = uint64_t(rays.width) * rays.height;
       if ((vkr_get_switches() & VKR_SWITCH_TRACE_ONE_LAUNCH) || n_rays < (1ull << 20) || n_rays > (6ull << 20))
-        return vkr_sssr_trace(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream),
-                              &rays, &occ, &pdf, push<vkr_trace_push>(st, P), st.stream);
+        return vkr_sssr_trace(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), table, &rays, &occ, &pdf, push<vkr_trace_push>(st, P), st.stream);
       const uint64_t bytes = vkr_sssr_trace_workspace_bytes(rays.width, rays.height);
-      return vkr_sssr_trace_split(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream),
-                                  &rays, &occ, &pdf, push<vkr_trace_push>(st, P), st.require_workspace(bytes), bytes, 2u, st.stream);
+      return vkr_sssr_trace_split(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), table, &rays, &occ, &pdf, push<vkr_trace_push>(st, P),
+                                  st.require_workspace(bytes), bytes, 2u, st.stream);
     });
     create_program("sssr_trace_windowed", [=](LaunchState& st) {  // multi-GPU variant (include/vkr_postfx.h), bindings 0..9
       const char* P = "sssr_trace_windowed";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P);
-      vkr_img rays = tex(st, 5, S, P), occ = tex(st, 6, S, P), pdf = tex(st, 7, T, P), mask = tex(st, 8, S, P), data = tex(st, 9, S, P);
-      const SetSlot& h = st.set->slots[4];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"sssr_trace_windowed: Halton buffer (binding 4) is not bound"};
-      return vkr_sssr_trace_windowed(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream),
-                                     &rays, &occ, &pdf, &mask, &data, push<vkr_trace_window_push>(st, P), st.stream);
+      vkr_img depth = tex(st, 0, T, P);
+      WindowedTraceImages w{st, P};
+      const float* table = halton(st, 4, P);
+      return vkr_sssr_trace_windowed(&depth, &w.normal, &w.material, ubo<vkr_trace_params>(st, 3, P), table, &w.rays, &w.occ, &w.pdf, &w.mask, &w.data,
+                                     push<vkr_trace_window_push>(st, P), st.stream);
     });
     // the windowed trace in two tasks (include/vkr_postfx.h): bindings of sssr_trace_windowed, the head with the window's own
     // pyramid levels at 0 and the whole-frame pyramid (extents only) at 10; both use the context's workspace
     create_program("sssr_trace_windowed_head", [=](LaunchState& st) {
       const char* P = "sssr_trace_windowed_head";
-      vkr_img local = tex(st, 0, T, P), frame = tex(st, 10, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P);
-      vkr_img rays = tex(st, 5, S, P), occ = tex(st, 6, S, P), pdf = tex(st, 7, T, P), mask = tex(st, 8, S, P), data = tex(st, 9, S, P);
-      const SetSlot& h = st.set->slots[4];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"sssr_trace_windowed_head: Halton buffer (binding 4) is not bound"};
-      const uint64_t bytes = vkr_sssr_trace_workspace_bytes(rays.width, rays.height);
-      return vkr_sssr_trace_windowed_head(&local, &frame, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream),
-                                          &rays, &occ, &pdf, &mask, &data, push<vkr_trace_window_push>(st, P), st.require_workspace(bytes), bytes, 2u, st.stream);
+      vkr_img local = tex(st, 0, T, P), frame = tex(st, 10, T, P);
+      WindowedTraceImages w{st, P};
+      const float* table = halton(st, 4, P);
+      const uint64_t bytes = vkr_sssr_trace_workspace_bytes(w.rays.width, w.rays.height);
+      return vkr_sssr_trace_windowed_head(&local, &frame, &w.normal, &w.material, ubo<vkr_trace_params>(st, 3, P), table, &w.rays, &w.occ, &w.pdf, &w.mask,
+                                          &w.data, push<vkr_trace_window_push>(st, P), st.require_workspace(bytes), bytes, 2u, st.stream);
     });
     create_program("sssr_trace_windowed_resume", [=](LaunchState& st) {
       const char* P = "sssr_trace_windowed_resume";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P);
-      vkr_img rays = tex(st, 5, S, P), occ = tex(st, 6, S, P), pdf = tex(st, 7, T, P), mask = tex(st, 8, S, P), data = tex(st, 9, S, P);
-      const SetSlot& h = st.set->slots[4];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"sssr_trace_windowed_resume: Halton buffer (binding 4) is not bound"};
-      const uint64_t bytes = vkr_sssr_trace_workspace_bytes(rays.width, rays.height);
+      vkr_img depth = tex(st, 0, T, P);
+      WindowedTraceImages w{st, P};
+      const float* table = halton(st, 4, P);
+      const uint64_t bytes = vkr_sssr_trace_workspace_bytes(w.rays.width, w.rays.height);
       if (st.workspace_bytes < bytes) throw std::runtime_error{"sssr_trace_windowed_resume: no head launch has filled the workspace"};
-      return vkr_sssr_trace_windowed_resume(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream),
-                                            &rays, &occ, &pdf, &mask, &data, push<vkr_trace_window_push>(st, P), st.workspace, bytes, st.stream);
+      return vkr_sssr_trace_windowed_resume(&depth, &w.normal, &w.material, ubo<vkr_trace_params>(st, 3, P), table, &w.rays, &w.occ, &w.pdf, &w.mask,
+                                            &w.data, push<vkr_trace_window_push>(st, P), st.workspace, bytes, st.stream);
     });
     create_program("sssr_filter", [=](LaunchState& st) {
       const char* P = "sssr_filter";
@@ -452,44 +557,37 @@ void register_hot_path_programs() {
     // ssr/shader.frag: set {0 normal, 1 depth (nearest/border sampler), 2 frame, 3 SSRParams, 4 material}; attachment {out}
     create_program("ssr", [=](LaunchState& st) {
       const char* P = "ssr";
-      if (st.attachments.size() != 1) throw std::runtime_error{"ssr: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img normal = tex(st, 0, T, P), depth = tex(st, 1, T, P, true), frame = tex(st, 2, T, P), material = tex(st, 4, T, P);
-      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      vkr_img out = attachment(st, 0);
       return vkr_ssr(&normal, &depth, &frame, ubo<vkr_ssr_params>(st, 3, P), &material, &out, st.stream);
     });
     create_program("brdf_preintegrate", [=](LaunchState& st) {
-      const SetSlot& h = st.set->slots[0];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"brdf_preintegrate: Halton buffer (binding 0) is not bound"};
+      const float* table = halton(st, 0, "brdf_preintegrate");
       vkr_img out = tex(st, 1, S, "brdf_preintegrate");
-      return vkr_brdf_preintegrate(halton_table(h.buffer.get(), st.stream), &out, st.stream);
+      return vkr_brdf_preintegrate(table, &out, st.stream);
     });
     // defered_shading/shader.frag: set {0 albedo, 1 normal, 2 material, 3 depth, 4 Constants, 5 shadow (unused), 6 occlusion, 7 brdf, 8 reflections}
     create_program("defered_shading", [=](LaunchState& st) {
       const char* P = "defered_shading";
-      if (st.attachments.size() != 1) throw std::runtime_error{"defered_shading: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img albedo = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P), depth = tex(st, 3, T, P);
       vkr_img occlusion = tex(st, 6, T, P), brdf = tex(st, 7, T, P), refl = tex(st, 8, T, P);
-      // (the rows the frame asked for: a tiled frame shades its strip and one row either side, Image::set_store_rows)
-      vkr_img out = st.attachments[0].image->describe_store(st.attachments[0].range.base_mip, 1);
+      vkr_img out = attachment(st, 0, true);  // the rows the frame asked for
       return vkr_defered_shading(&albedo, &normal, &material, &depth, ubo<vkr_shading_params>(st, 4, P), &occlusion, &brdf, &refl, &out,
                                  push<vkr_shading_push>(st, P), st.stream);
     });
     // the same set plus {9 shadow mask}: DeferedShadingPass::draw_shadowed
     create_program("defered_shading_shadowed", [=](LaunchState& st) {
       const char* P = "defered_shading_shadowed";
-      if (st.attachments.size() != 1) throw std::runtime_error{"defered_shading_shadowed: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img albedo = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P), depth = tex(st, 3, T, P);
       vkr_img occlusion = tex(st, 6, T, P), brdf = tex(st, 7, T, P), refl = tex(st, 8, T, P), mask = tex(st, 9, T, P);
-      vkr_img out = st.attachments[0].image->describe_store(st.attachments[0].range.base_mip, 1);
+      vkr_img out = attachment(st, 0, true);
       return vkr_defered_shading_shadowed(&albedo, &normal, &material, &depth, ubo<vkr_shading_params>(st, 4, P), &occlusion, &brdf, &refl, &mask,
                                           &out, push<vkr_shading_push>(st, P), st.stream);
     });
     // ---- tile-classified trace ----
-    auto ssbo =[](const LaunchState& st, uint32_t slot, const char* prog) -> Buffer* {
-      const SetSlot& s = st.set ? st.set->slots[slot] : SetSlot{};
-      if (!st.set || s.kind != SetSlot::Ssbo || !s.buffer) throw std::runtime_error{std::string{prog} + ": storage buffer " + std::to_string(slot) + " is not bound"};
-      return s.buffer.get();
-    };
     create_program("sssr_classification", [=](LaunchState& st) {
       const char* P = "sssr_classification";
       vkr_img material = tex(st, 0, T, P);
@@ -501,10 +599,9 @@ void register_hot_path_programs() {
       const char* P = "sssr_trace_indirect";
       if (!st.indirect) throw std::runtime_error{"sssr_trace_indirect: must be launched with dispatch_indirect"};
       vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), material = tex(st, 2, T, P), rays = tex(st, 5, S, P);
-      const SetSlot& h = st.set->slots[4];
-      if (h.kind != SetSlot::Ubo || !h.buffer) throw std::runtime_error{"sssr_trace_indirect: Halton buffer (binding 4) is not bound"};
+      const float* table = halton(st, 4, P);
       Buffer* tiles = ssbo(st, 6, P);
-      return vkr_sssr_trace_indirect(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), halton_table(h.buffer.get(), st.stream), &rays,
+      return vkr_sssr_trace_indirect(&depth, &normal, &material, ubo<vkr_trace_params>(st, 3, P), table, &rays,
                                      (const int32_t*)tiles->device_ptr(st.stream), (const uint32_t*)st.indirect->device_ptr(st.stream),
                                      (uint32_t)(tiles->get_size() / sizeof(int32_t)), push<vkr_trace_indirect_push>(st, P), st.stream);
     });
@@ -516,34 +613,12 @@ void register_hot_path_programs() {
       const char* P = "gbuf_opaque_taa";
       if (st.attachments.size() != 5) throw std::runtime_error{"gbuf_opaque_taa: expects 4 colour attachments + depth"};
       if (!st.cleared_color || !st.cleared_depth) throw std::runtime_error{"gbuf_opaque_taa: attachments must be cleared (colour 0, depth 1)"};
-      if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{"gbuf_opaque_taa: vertex / index buffer not bound"};
-      Buffer* transforms = ssbo(st, 1, P);
-      if (!transforms->host_data()) throw std::runtime_error{"gbuf_opaque_taa: the transform buffer must be host-visible on this path"};
-      auto att = [&](size_t i) { return st.attachments[i].image->describe(st.attachments[i].range.base_mip, 1); };
-      vkr_img albedo = att(0), normal = att(1), material = att(2), velocity = att(3), depth = att(4);
-      std::vector<vkr_img> textures;
-      if (st.set1)
-        for (const auto& v : st.set1->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
-      std::vector<vkr_raster_draw> draws;
-      for (const auto& d : st.indexed_draws) {
-        if (d.push.size() < 16) throw std::runtime_error{"gbuf_opaque_taa: push constants missing"};
-        vkr_raster_draw r{};
-        std::memcpy(&r, d.push.data(), 16);
-        r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
-        if (st.set1 && r.albedo_index < st.set1->image_array.size() && st.set1->image_array[r.albedo_index].image->alpha_never_zero)
-          r.reserved |= VKR_RASTER_DRAW_OPAQUE_ALBEDO;  // the discard of opaque_taa.frag:32-34 cannot fire
-        draws.push_back(r);
-      }
-      vkr_raster_scene scene{};
-      scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
-      scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
-      scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
-      scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
-      scene.transforms = (const vkr_raster_transform*)transforms->host_data();
-      scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
-      scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
-      scene.textures = textures.data(); scene.texture_count = (uint32_t)textures.size();
-      return vkr_raster_gbuffer(&scene, ubo<vkr_gbuf_const>(st, 0, P), &albedo, &normal, &material, &velocity, &depth,
+      RasterScene::expect_geometry(st, P);
+      Buffer* transforms = RasterScene::host_transforms(st, P);
+      vkr_img albedo = attachment(st, 0), normal = attachment(st, 1), material = attachment(st, 2), velocity = attachment(st, 3), depth = attachment(st, 4);
+      // PushData {transform, albedo, mr, flags}; flagged: the draws for which the discard of opaque_taa.frag:32-34 cannot fire
+      const RasterScene raster{st, P, transforms, 16, st.set1, true};
+      return vkr_raster_gbuffer(&raster.scene, ubo<vkr_gbuf_const>(st, 0, P), &albedo, &normal, &material, &velocity, &depth,
                                 st.scratch, st.scratch_bytes, st.stream);
     });
     // ---- shadow map (scene_renderer.cpp:222-274): shadows/default.{vert,frag} ----
@@ -554,48 +629,19 @@ void register_hot_path_programs() {
       const char* P = "default_shadow";
       if (st.attachments.size() != 1) throw std::runtime_error{"default_shadow: expects one depth attachment"};
       if (!st.cleared_depth) throw std::runtime_error{"default_shadow: the depth attachment must be cleared (depth 1)"};
-      if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{"default_shadow: vertex / index buffer not bound"};
-      Buffer* transforms = ssbo(st, 1, P);
-      if (!transforms->host_data()) throw std::runtime_error{"default_shadow: the transform buffer must be host-visible on this path"};
+      RasterScene::expect_geometry(st, P);
+      Buffer* transforms = RasterScene::host_transforms(st, P);
       const ImageViewObject& depth = st.attachments[0];
       if (depth.range.base_mip != 0) throw std::runtime_error{"default_shadow: the depth attachment must be mip 0 of a layer"};
       if (st.fb_width != depth.image->get_info().width || st.fb_height != depth.image->get_info().height)
         throw std::runtime_error{"default_shadow: the framebuffer must cover the (square) depth attachment"};
       const vkr_img layer = depth.image->get_array_layers() > 1 ? depth.image->describe_layer(depth.range.base_layer, 0, 1) : depth.image->describe(0, 1);
-      std::vector<vkr_raster_draw> draws;
-      uint32_t triangles = 0;
-      for (const auto& d : st.indexed_draws) {
-        if (d.push.size() < 4) throw std::runtime_error{"default_shadow: push constants missing"};
-        vkr_raster_draw r{};
-        std::memcpy(&r.transform_index, d.push.data(), 4);
-        r.albedo_index = r.mr_index = 0xFFFFFFFFu;
-        r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
-        triangles += d.index_count / 3u;
-        draws.push_back(r);
-      }
-      vkr_raster_scene scene{};
-      scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
-      scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
-      scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
-      scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
-      scene.transforms = (const vkr_raster_transform*)transforms->host_data();
-      scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
-      scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
+      const RasterScene raster{st, P, transforms, 4, nullptr, false};  // the push constant is transform_index: no textures
       static_assert(sizeof(vkr_mat4) == 64, "ShadowConst of shadows/default.vert");
-      if (st.scratch_bytes < vkr_default_shadow_scratch_bytes(layer.width, 1, triangles)) throw std::runtime_error{"default_shadow: no scratch (CmdContext::require_scratch)"};
-      return vkr_default_shadow(&scene, ubo<vkr_mat4>(st, 0, P), &layer, 1, st.scratch, st.scratch_bytes, st.stream);
+      if (st.scratch_bytes < vkr_default_shadow_scratch_bytes(layer.width, 1, raster.triangles)) throw std::runtime_error{"default_shadow: no scratch (CmdContext::require_scratch)"};
+      return vkr_default_shadow(&raster.scene, ubo<vkr_mat4>(st, 0, P), &layer, 1, st.scratch, st.scratch_bytes, st.stream);
     });
     // ---- octahedral probes (probe_renderer.cpp): cubemap_probe, cube2oct, probe_downsample, trace_probe ----
-    // a view of one layer of an array image (or of a plain image) as the C-ABI descriptor of its mips
-    auto layer_view = [](const ImageViewObject& v) {
-      return v.image->get_array_layers() > 1 ? v.image->describe_layer(v.range.base_layer, v.range.base_mip, v.range.mips_count)
-                                             : v.image->describe(v.range.base_mip, v.range.mips_count);
-    };
-    auto bound_view = [](const LaunchState& st, uint32_t slot, SetSlot::Kind kind, const char* prog) -> const ImageViewObject& {
-      if (!st.set || st.set->slots[slot].kind != kind || !st.set->slots[slot].view.image)
-        throw std::runtime_error{std::string{prog} + ": binding " + std::to_string(slot) + " is not bound as expected"};
-      return st.set->slots[slot].view;
-    };
     // cubemap_probe/shader.{vert,frag}: set 0 {0 ShaderUbo {projection, camera}, 1 transforms, 2 material textures[], 3 sampler};
     // vertex + index buffers; one draw_indexed per primitive with PushData {transform, albedo}; attachments {cube colour layer,
     // cube distance layer, depth}, cleared to (100, 0, 0, 0) and 1.  One render pass per face, faces 0..5 in order.
@@ -605,7 +651,7 @@ void register_hot_path_programs() {
       if (st.attachments.size() != 3) throw std::runtime_error{"cubemap_probe: expects colour, distance and depth attachments"};
       if (!st.cleared_color || !st.cleared_depth || st.clear_color[0] != 100.f)
         throw std::runtime_error{"cubemap_probe: attachments must be cleared (colour (100, 0, 0, 0), depth 1)"};
-      if (!st.vertex_buffer || !st.index_buffer) throw std::runtime_error{"cubemap_probe: vertex / index buffer not bound"};
+      RasterScene::expect_geometry(st, P);
       const ImageViewObject &color = st.attachments[0], &distance = st.attachments[1];
       const uint32_t side = color.range.base_layer;
       if (color.image->get_array_layers() != 6 || distance.image->get_array_layers() != 6 || distance.range.base_layer != side || side >= 6)
@@ -621,33 +667,11 @@ void register_hot_path_programs() {
       st.cube.faces = side + 1;
       if (side != 5) return 0;
       st.cube.faces = 0;
-      Buffer* transforms = ssbo(st, 1, P);
-      if (!transforms->host_data()) throw std::runtime_error{"cubemap_probe: the transform buffer must be host-visible on this path"};
-      std::vector<vkr_img> textures;
-      for (const auto& v : st.set->image_array) textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
-      std::vector<vkr_raster_draw> draws;
-      for (const auto& d : st.indexed_draws) {
-        if (d.push.size() < 8) throw std::runtime_error{"cubemap_probe: push constants missing"};
-        vkr_raster_draw r{};
-        std::memcpy(&r, d.push.data(), 8);  // PushData {transform_index, albedo_index}
-        r.mr_index = 0xFFFFFFFFu;
-        r.index_offset = d.first_index; r.index_count = d.index_count; r.vertex_offset = (uint32_t)d.vertex_offset;
-        if (r.albedo_index < st.set->image_array.size() && st.set->image_array[r.albedo_index].image->alpha_never_zero)
-          r.reserved |= VKR_RASTER_DRAW_OPAQUE_ALBEDO;  // the discard of shader.frag cannot fire
-        draws.push_back(r);
-      }
-      vkr_raster_scene scene{};
-      scene.vertices = (const vkr_raster_vertex*)st.vertex_buffer->device_ptr(st.stream);
-      scene.vertex_count = (uint32_t)(st.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
-      scene.indices = (const uint32_t*)st.index_buffer->device_ptr(st.stream);
-      scene.index_count = (uint32_t)(st.index_buffer->get_size() / sizeof(uint32_t));
-      scene.transforms = (const vkr_raster_transform*)transforms->host_data();
-      scene.transform_count = (uint32_t)(transforms->get_size() / sizeof(vkr_raster_transform));
-      scene.draws = draws.data(); scene.draw_count = (uint32_t)draws.size();
-      scene.textures = textures.data(); scene.texture_count = (uint32_t)textures.size();
+      // PushData {transform_index, albedo_index}; flagged: the draws for which the discard of shader.frag cannot fire
+      const RasterScene raster{st, P, RasterScene::host_transforms(st, P), 8, st.set, true};
       vkr_img cc[6], cd[6];
       for (uint32_t f = 0; f < 6; f++) { cc[f] = color.image->describe_layer(f); cd[f] = distance.image->describe_layer(f); }
-      return vkr_cubemap_probe(&scene, pos, cc, cd, st.scratch, st.scratch_bytes, st.stream);
+      return vkr_cubemap_probe(&raster.scene, pos, cc, cd, st.scratch, st.scratch_bytes, st.stream);
     });
     // cube2oct/shader.comp: set {0 cube colour (cube view), 1 cube distance (cube view), 2 oct colour (storage, one layer), 3 oct
     // depth (storage, mip 0 of one layer)}
@@ -663,7 +687,7 @@ void register_hot_path_programs() {
     // probe_downsample/shader.frag: set {0 depth mip i - 1 of one layer}; colour attachment: mip i of the same layer
     create_program("probe_downsample", [=](LaunchState& st) {
       const char* P = "probe_downsample";
-      if (st.attachments.size() != 1) throw std::runtime_error{"probe_downsample: expects one colour attachment"};
+      expect_one_attachment(st, P);
       const ImageViewObject &src = bound_view(st, 0, T, P), &dst = st.attachments[0];
       if (src.image != dst.image || dst.range.base_mip != src.range.base_mip + 1 || dst.range.base_layer != src.range.base_layer)
         throw std::runtime_error{"probe_downsample: the attachment must be the next mip of the sampled layer"};
@@ -688,7 +712,7 @@ void register_hot_path_programs() {
     // it, whatever size the host struct has (ssao_params_from_block).
     create_program("ssao", [=](LaunchState& st) {
       const char* P = "ssao";
-      if (st.attachments.size() != 1) throw std::runtime_error{"ssao: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img depth = tex(st, 0, T, P);
       const SetSlot& b = st.set->slots[1];
       const void* data = b.host_data ? b.host_data : (b.buffer ? b.buffer->host_data() : nullptr);
@@ -696,7 +720,7 @@ void register_hot_path_programs() {
       if (b.kind != SetSlot::Ubo || !data || size < 80) throw std::runtime_error{"ssao: uniform block 1 is not bound"};
       static_assert(sizeof(vkr_ssao_params) == 336 && offsetof(vkr_ssao_params, samples) == 80, "SSAOParams of ssao/shader.frag (std140)");
       const vkr_ssao_params params = ssao_params_from_block(data, size);
-      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      vkr_img out = attachment(st, 0);
       return vkr_ssao(&depth, &params, &out, st.stream);
     });
     // ---- shadow mask (ShadowMaskPass; no reference program) ----
@@ -714,42 +738,26 @@ void register_hot_path_programs() {
       for (uint32_t l = 0; l < params->layer_count; l++) layers[l] = maps.image->describe_layer(l, 0, 1);
       return vkr_shadow_mask(&depth, layers, params, &out, st.stream);
     });
-    // ---- ray-traced shadow mask (ShadowMaskPass::run_rt; no reference program) ----
-    // set {0 depth (mip 0), 1 normal, 2 acceleration structure, 3 vkr_shadow_rt_params, 4 the mask (storage)}: the C-ABI's order
-    create_program("shadow_mask_rt", [=](LaunchState& st) {
-      const char* P = "shadow_mask_rt";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
-      const SetSlot& as = st.set->slots[2];
-      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"shadow_mask_rt: acceleration structure (binding 2) is not bound"};
-      static_assert(sizeof(vkr_shadow_rt_params) == 160, "vkr_shadow_rt_params: a matrix, four floats, four lights and four words");
-      return vkr_shadow_mask_rt(&depth, &normal, (const vkr_accel*)as.tlas, ubo<vkr_shadow_rt_params>(st, 3, P), &out, st.stream);
-    });
-    // ---- ray-traced reflections (AdvancedSSR::run_reflections_rt_pass; no reference program) ----
-    // set {0 depth (mip 0 of the view), 1 normal, 2 rays (bound only in fill mode), 3 acceleration structure, 4 the attribute table,
-    // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace.
-    // "reflections_rt_cutout": the same set and 8 vkr_ray_cutout
-    struct HitTable {  // what a program that looks at hits binds besides its images: the structure, its attribute table, the textures
+    // ---- what a program that looks at hits binds besides its images: the structure, its attribute table, the textures ----
+    struct HitTable {
       const vkr_accel* accel;
       const vkr_hit_attrib* attribs;
       uint32_t attrib_count;
       std::vector<vkr_img> textures;
       uint32_t opaque_mask;  // bit i: no texel of textures[i] has alpha 0 (Image::alpha_never_zero, what VKR_RASTER_DRAW_OPAQUE_ALBEDO comes from)
     };
-    auto hit_table = [](LaunchState& st, uint32_t accel_slot, uint32_t attrib_slot, const std::string& P) {
+    auto hit_table = [](LaunchState& st, uint32_t accel_slot, uint32_t attrib_slot, const char* P) {
       HitTable h {};
-      const SetSlot& as = st.set->slots[accel_slot];
-      if (as.kind != SetSlot::AccelStruct || !as.tlas)
-        throw std::runtime_error{P + ": acceleration structure (binding " + std::to_string(accel_slot) + ") is not bound"};
+      h.accel = accel(st, accel_slot, P);
       const SetSlot& at = st.set->slots[attrib_slot];
-      if (at.kind != SetSlot::Ubo || !at.buffer) throw std::runtime_error{P + ": attribute table (binding " + std::to_string(attrib_slot) + ") is not bound"};
+      if (at.kind != SetSlot::Ubo || !at.buffer) throw std::runtime_error{std::string{P} + ": attribute table (binding " + std::to_string(attrib_slot) + ") is not bound"};
       for (const auto& v : st.set->image_array) {
         if (v.image->alpha_never_zero && h.textures.size() < 32) h.opaque_mask |= 1u << h.textures.size();
         h.textures.push_back(v.image->describe(v.range.base_mip, v.range.mips_count));
       }
-      h.accel = (const vkr_accel*)as.tlas;
       // the table of an empty scene still holds one (unused) record: a buffer has no size 0
       uint32_t triangles = 0;
-      if (vkr_accel_info(h.accel, nullptr, &triangles) != 0) throw std::runtime_error{P + ": " + vkr_last_error()};
+      if (vkr_accel_info(h.accel, nullptr, &triangles) != 0) throw std::runtime_error{std::string{P} + ": " + vkr_last_error()};
       const uint64_t records = at.buffer->get_size() / sizeof(vkr_hit_attrib);
       h.attribs = (const vkr_hit_attrib*)at.buffer->device_ptr(st.stream);
       h.attrib_count = records >= triangles ? triangles : (uint32_t)records;
@@ -762,6 +770,53 @@ void register_hot_path_programs() {
       c.opaque_texture_mask |= h.opaque_mask;
       return c;
     };
+    // the area lights of a _soft program: the block (its samples pointer is not read) and the sample table behind it
+    auto soft_block = [=](LaunchState& st, uint32_t slot, uint32_t table_slot, const char* P) {
+      static_assert(sizeof(vkr_shadow_rt_soft) == 40, "vkr_shadow_rt_soft: four radii, two words, a pointer and two words");
+      vkr_shadow_rt_soft soft = *ubo<vkr_shadow_rt_soft>(st, slot, P);
+      const SetSlot& table = st.set->slots[table_slot];
+      if (table.kind != SetSlot::Ubo || !table.buffer) throw std::runtime_error{std::string{P} + ": sample table (binding " + std::to_string(table_slot) + ") is not bound"};
+      if (table.buffer->get_size() < sizeof(float) * 2 * (uint64_t)soft.sample_count * soft.pattern_side * soft.pattern_side)
+        throw std::runtime_error{std::string{P} + ": the sample table is smaller than sample_count x pattern_side^2 pairs"};
+      soft.samples = (const float*)table.buffer->device_ptr(st.stream);
+      return soft;
+    };
+    // ---- ray-traced shadow mask (ShadowMaskPass::run_rt; no reference program), in four programs: {cutouts, soft} ----
+    // "shadow_mask_rt": set {0 depth (mip 0), 1 normal, 2 acceleration structure, 3 vkr_shadow_rt_params, 4 the mask (storage)}: the
+    // C-ABI's order;
+    // "shadow_mask_rt_cutout" (the rays see alpha cutouts): the same and {5 the attribute table, 6 vkr_ray_cutout, 7 the scene's
+    // textures[]};
+    // "shadow_mask_rt_soft" (area lights, after update_rt_soft): the set of "shadow_mask_rt", 5 vkr_shadow_rt_soft, 6 the sample table;
+    // "shadow_mask_rt_soft_cutout": the set of "shadow_mask_rt_cutout", 8 vkr_shadow_rt_soft, 9 the sample table
+    for (const bool cutouts : {false, true})
+      for (const bool soft : {false, true}) {
+        const char* P = cutouts ? (soft ? "shadow_mask_rt_soft_cutout" : "shadow_mask_rt_cutout") : (soft ? "shadow_mask_rt_soft" : "shadow_mask_rt");
+        create_program(P, [=](LaunchState& st) {
+          vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
+          static_assert(sizeof(vkr_shadow_rt_params) == 160, "vkr_shadow_rt_params: a matrix, four floats, four lights and four words");
+          if (!cutouts) {
+            const vkr_accel* scene = accel(st, 2, P);
+            if (!soft) return vkr_shadow_mask_rt(&depth, &normal, scene, ubo<vkr_shadow_rt_params>(st, 3, P), &out, st.stream);
+            const vkr_shadow_rt_soft lights = soft_block(st, 5, 6, P);
+            return vkr_shadow_mask_rt_soft(&depth, &normal, scene, ubo<vkr_shadow_rt_params>(st, 3, P), &lights, &out, st.stream);
+          }
+          const HitTable h = hit_table(st, 2, 5, P);
+          const vkr_ray_cutout c = cutout_block(st, 6, h, P);
+          const vkr_shadow_rt_soft lights = soft ? soft_block(st, 8, 9, P) : vkr_shadow_rt_soft{};
+          const uint32_t count = (uint32_t)h.textures.size();
+          const uint64_t bytes = vkr_accel_cutout_scratch_bytes(count);
+          const vkr_img* textures = h.textures.empty() ? nullptr : h.textures.data();
+          if (!soft)
+            return vkr_shadow_mask_rt_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, textures, count, ubo<vkr_shadow_rt_params>(st, 3, P), &c, &out,
+                                             st.require_workspace(bytes), bytes, st.stream);
+          return vkr_shadow_mask_rt_soft_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, textures, count, ubo<vkr_shadow_rt_params>(st, 3, P), &c,
+                                                &lights, &out, st.require_workspace(bytes), bytes, st.stream);
+        });
+      }
+    // ---- ray-traced reflections (AdvancedSSR::run_reflections_rt_pass; no reference program) ----
+    // set {0 depth (mip 0 of the view), 1 normal, 2 rays (bound only in fill mode), 3 acceleration structure, 4 the attribute table,
+    // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace.
+    // "reflections_rt_cutout": the same set and 8 vkr_ray_cutout
     for (const bool cutouts : {false, true})
       create_program(cutouts ? "reflections_rt_cutout" : "reflections_rt", [=](LaunchState& st) {
         const char* P = cutouts ? "reflections_rt_cutout" : "reflections_rt";
@@ -782,69 +837,24 @@ void register_hot_path_programs() {
         return vkr_reflections_rt_cutout(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, textures, count, params, &c, &out,
                                          st.require_workspace(bytes), bytes, st.stream);
       });
-    // ---- the ray-traced shadow mask that sees alpha cutouts (ShadowMaskPass::run_rt with cutouts; no reference program) ----
-    // set {0 depth (mip 0), 1 normal, 2 acceleration structure, 3 vkr_shadow_rt_params, 4 the mask (storage), 5 the attribute table,
-    // 6 vkr_ray_cutout, 7 the scene's textures[]}
-    create_program("shadow_mask_rt_cutout", [=](LaunchState& st) {
-      const char* P = "shadow_mask_rt_cutout";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
-      const HitTable h = hit_table(st, 2, 5, P);
-      const vkr_ray_cutout c = cutout_block(st, 6, h, P);
-      const uint32_t count = (uint32_t)h.textures.size();
-      const uint64_t bytes = vkr_accel_cutout_scratch_bytes(count);
-      return vkr_shadow_mask_rt_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, h.textures.empty() ? nullptr : h.textures.data(), count,
-                                       ubo<vkr_shadow_rt_params>(st, 3, P), &c, &out, st.require_workspace(bytes), bytes, st.stream);
-    });
-    // ---- the traced shadow mask with area lights (ShadowMaskPass::run_rt after update_rt_soft; no reference program) ----
-    // "shadow_mask_rt_soft": the set of "shadow_mask_rt", 5 vkr_shadow_rt_soft (its samples pointer is not read), 6 the sample table;
-    // "shadow_mask_rt_soft_cutout": the set of "shadow_mask_rt_cutout", 8 vkr_shadow_rt_soft, 9 the sample table
-    auto soft_block = [=](LaunchState& st, uint32_t slot, uint32_t table_slot, const char* P) {
-      static_assert(sizeof(vkr_shadow_rt_soft) == 40, "vkr_shadow_rt_soft: four radii, two words, a pointer and two words");
-      vkr_shadow_rt_soft soft = *ubo<vkr_shadow_rt_soft>(st, slot, P);
-      const SetSlot& table = st.set->slots[table_slot];
-      if (table.kind != SetSlot::Ubo || !table.buffer) throw std::runtime_error{std::string{P} + ": sample table (binding " + std::to_string(table_slot) + ") is not bound"};
-      if (table.buffer->get_size() < sizeof(float) * 2 * (uint64_t)soft.sample_count * soft.pattern_side * soft.pattern_side)
-        throw std::runtime_error{std::string{P} + ": the sample table is smaller than sample_count x pattern_side^2 pairs"};
-      soft.samples = (const float*)table.buffer->device_ptr(st.stream);
-      return soft;
-    };
-    create_program("shadow_mask_rt_soft", [=](LaunchState& st) {
-      const char* P = "shadow_mask_rt_soft";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
-      const SetSlot& as = st.set->slots[2];
-      if (as.kind != SetSlot::AccelStruct || !as.tlas) throw std::runtime_error{"shadow_mask_rt_soft: acceleration structure (binding 2) is not bound"};
-      const vkr_shadow_rt_soft soft = soft_block(st, 5, 6, P);
-      return vkr_shadow_mask_rt_soft(&depth, &normal, (const vkr_accel*)as.tlas, ubo<vkr_shadow_rt_params>(st, 3, P), &soft, &out, st.stream);
-    });
-    create_program("shadow_mask_rt_soft_cutout", [=](LaunchState& st) {
-      const char* P = "shadow_mask_rt_soft_cutout";
-      vkr_img depth = tex(st, 0, T, P), normal = tex(st, 1, T, P), out = tex(st, 4, S, P);
-      const HitTable h = hit_table(st, 2, 5, P);
-      const vkr_ray_cutout c = cutout_block(st, 6, h, P);
-      const vkr_shadow_rt_soft soft = soft_block(st, 8, 9, P);
-      const uint32_t count = (uint32_t)h.textures.size();
-      const uint64_t bytes = vkr_accel_cutout_scratch_bytes(count);
-      return vkr_shadow_mask_rt_soft_cutout(&depth, &normal, h.accel, h.attribs, h.attrib_count, h.textures.empty() ? nullptr : h.textures.data(), count,
-                                            ubo<vkr_shadow_rt_params>(st, 3, P), &c, &soft, &out, st.require_workspace(bytes), bytes, st.stream);
-    });
     // ---- backbuffer (backbuffer_subpass2.cpp) ----
     // texdraw/shader.frag: set {0 target_tex}; push constants flags; colour attachment the backbuffer.  The clear to 0 the
     // reference records first is covered by the triangle and not executed.
     create_program("texdraw", [=](LaunchState& st) {
       const char* P = "texdraw";
-      if (st.attachments.size() != 1) throw std::runtime_error{"texdraw: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img target_tex = tex(st, 0, T, P);
       static_assert(sizeof(vkr_texdraw_push) == 4, "Constants of texdraw/shader.frag");
-      vkr_img backbuffer = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      vkr_img backbuffer = attachment(st, 0);
       return vkr_texdraw(&target_tex, &backbuffer, push<vkr_texdraw_push>(st, P), st.stream);
     });
     // ---- dormant GTAO variants ----
     // gtao/main.frag: set {0 depth, 1 GTAOParams, 2 normal}; colour attachment raw
     create_program("gtao_main", [=](LaunchState& st) {
       const char* P = "gtao_main";
-      if (st.attachments.size() != 1) throw std::runtime_error{"gtao_main: expects one colour attachment"};
+      expect_one_attachment(st, P);
       vkr_img depth = tex(st, 0, T, P), normal = tex(st, 2, T, P);
-      vkr_img out = st.attachments[0].image->describe(st.attachments[0].range.base_mip, 1);
+      vkr_img out = attachment(st, 0);
       return vkr_gtao_main_graphics(&depth, ubo<vkr_gtao_params>(st, 1, P), &normal, &out, push<vkr_gtao_gfx_push>(st, P), st.stream);
     });
     create_program("gtao_reproject", [=](LaunchState& st) {
@@ -852,14 +862,6 @@ void register_hot_path_programs() {
       vkr_img depth = tex(st, 1, T, P), pdepth = tex(st, 2, T, P), ao = tex(st, 3, T, P), pao = tex(st, 4, T, P), out = tex(st, 5, S, P);
       return vkr_gtao_reproject(ubo<vkr_gtao_reprojection>(st, 0, P), &depth, &pdepth, &ao, &pao, &out, st.stream);
     });
-    auto layers_of = [](const LaunchState& st, uint32_t slot, SetSlot::Kind kind, const char* prog) {
-      const SetSlot& s = st.set ? st.set->slots[slot] : SetSlot{};
-      if (!st.set || s.kind != kind || !s.view.image)
-        throw std::runtime_error{std::string{prog} + ": binding " + std::to_string(slot) + " is not bound as expected"};
-      std::vector<vkr_img> layers;
-      for (uint32_t l = 0; l < s.view.image->get_array_layers(); l++) layers.push_back(s.view.image->describe_layer(l));
-      return layers;
-    };
     create_program("deinterleave_depth", [=](LaunchState& st) {
       const char* P = "deinterleave_depth";
       vkr_img depth = tex(st, 0, T, P);
@@ -892,13 +894,12 @@ void register_hot_path_programs() {
     // synthetic G-buffer "raster" program: attachments {albedo, normal, material, velocity, depth} or {depth}
     create_program("synthetic_gbuffer", [=](LaunchState& st) {
       const vkr_synth_params* p = ubo<vkr_synth_params>(st, 0, "synthetic_gbuffer");
-      auto att = [&](size_t i) { return st.attachments[i].image->describe(st.attachments[i].range.base_mip, 1); };
       if (st.attachments.size() == 1) {
-        vkr_img d = att(0);
+        vkr_img d = attachment(st, 0);
         return vkr_synth_gbuffer(&d, nullptr, nullptr, nullptr, nullptr, p, st.stream);
       }
       if (st.attachments.size() != 5) throw std::runtime_error{"synthetic_gbuffer: expects 4 colour attachments + depth"};
-      vkr_img a = att(0), n = att(1), m = att(2), v = att(3), d = att(4);
+      vkr_img a = attachment(st, 0), n = attachment(st, 1), m = attachment(st, 2), v = attachment(st, 3), d = attachment(st, 4);
       return vkr_synth_gbuffer(&d, &n, &a, &m, &v, p, st.stream);
     });
   });
@@ -939,22 +940,8 @@ void CmdContext::bind_sets(uint32_t first_set, const std::initializer_list<VkDes
   (first_set == 0 ? state.set : state.set1) = (const DescriptorSetObject*)*s.begin();
 }
 CmdContext::~CmdContext() { device_free(state.scratch); device_free(state.workspace); }
-void* LaunchState::require_workspace(uint64_t bytes) {
-  if (bytes > workspace_bytes) {
-    if (workspace) { (void)hipStreamSynchronize((hipStream_t)stream); device_free(workspace); }
-    workspace = device_alloc(bytes);
-    workspace_bytes = bytes;
-  }
-  return workspace;
-}
-void* CmdContext::require_scratch(uint64_t bytes) {
-  if (bytes > state.scratch_bytes) {
-    if (state.scratch) { (void)hipStreamSynchronize((hipStream_t)stream); device_free(state.scratch); }
-    state.scratch = device_alloc(bytes);
-    state.scratch_bytes = bytes;
-  }
-  return state.scratch;
-}
+void* LaunchState::require_workspace(uint64_t bytes) { return grow_only(workspace, workspace_bytes, bytes, stream); }
+void* CmdContext::require_scratch(uint64_t bytes) { return grow_only(state.scratch, state.scratch_bytes, bytes, stream); }
 void CmdContext::clear_color_attachments(float r, float g, float b, float a) {
   // the programs clear their own attachments: to 0, or (cubemap_probe, probe_renderer.cpp:121) to (100, 0, 0, 0)
   const bool zero = r == 0.f && g == 0.f && b == 0.f && a == 0.f, probe = r == 100.f && g == 0.f && b == 0.f && a == 0.f;

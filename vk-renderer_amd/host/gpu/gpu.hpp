@@ -270,6 +270,7 @@ using ProgramFn = std::function<int(LaunchState&)>;
 void create_program(const std::string& name, ProgramFn fn);
 void register_hot_path_programs();
 bool has_program(const std::string& name);
+std::vector<std::string> program_names();  // every registered program, sorted
 // What program "ssao" hands to vkr_ssao for a bound uniform block of `bytes` bytes: the first min(bytes, 336) bytes over a
 // zero-initialised vkr_ssao_params.  The reference's host struct is 272 bytes (vec3 samples at a 12-byte stride) under a
 // shader that reads 336 (std140, 16-byte stride): bytes the host never wrote read as 0 (DESIGN_NUMERICS.md, SSAO).
