@@ -766,6 +766,34 @@ int vkr_shadow_mask_rt_soft_cutout(const vkr_img* depth, const vkr_img* normal, 
  * Nothing is written for a NULL out, S outside 1..64 or P not 1, 2 or 4.                                                       */
 void vkr_shadow_disk_samples(uint32_t sample_count, uint32_t pattern_side, float* out);
 
+/* ---- the edge-aware filter of the shadow mask (DESIGN_NUMERICS.md, "Shadow mask, filter") ------------------------------------------
+ * No reference program.  The reconstruction filter of a mask whose neighbouring pixels carry different sample patterns
+ * (vkr_shadow_mask_rt_soft with pattern_side P; the box taps of vkr_shadow_mask): per pixel the tent-weighted mean of the mask over
+ * the taps that lie on the pixel's own surface.  With reach == P every one of the P * P patterns enters a fully accepted pixel
+ * with the same weight: (R - |d|) over |d| < R gives every residue class mod R the total weight R.                             */
+typedef struct vkr_shadow_filter_params {   /* 96 bytes */
+  vkr_mat4 inverse_camera;                  /* view -> world, as in vkr_shadow_rt_params */
+  float    fovy, aspect, znear, zfar;
+  uint32_t reach;                           /* R, 1..4: taps at |dx|, |dy| < R; 1 copies the mask */
+  float    normal_min_dot;                  /* a tap is accepted only if dot(n_g, n_t) >= this */
+  float    plane_tolerance;                 /* ... and |dot(n_g, W_t - W_g)| <= plane_tolerance * |view_g.z| */
+  uint32_t reserved;                        /* 0 */
+} vkr_shadow_filter_params;
+/* depth: D24_UNORM_S8 (mip 0 of the view); normal: RG16_UNORM; mask, out_mask: RGBA8_UNORM; whole frames of one extent.  Per pixel g:
+ * d_g = the exact decode of depth texel g; d_g >= 1 (sky) stores mask[g].  Otherwise view_g, W_g = world and n_g are those of
+ * vkr_shadow_mask_rt for pixel g (uv = (g + 0.5) / extent, reconstruct_view_vec, inverse_camera * (view, 1), decode_normal of the
+ * texel by index).  Tap t = g + (dx, dy), |dx|, |dy| < R, has the integer weight w = (R - |dx|)(R - |dy|).  The centre tap is always
+ * accepted; another tap is accepted when it lies inside the image, d_t < 1, dot(n_g, n_t) >= normal_min_dot and
+ * |dot(n_g, W_t - W_g)| <= plane_tolerance * |view_g.z| (W_t - W_g three subtractions, each dot product x, then y, then z with the
+ * multiply-adds contract 2 fuses, the bound one multiplication; a compare with a NaN is false: the tap is rejected).  In unsigned
+ * integers, A = the sum of w and V_c = the sum of w * mask[t].c over the accepted taps (one accept set for the four channels):
+ * out[g].c = (2 V_c + A) / (2 A), the weighted mean rounded half up.  Every texel of out_mask is written, nothing outside it.
+ * Refused before any launch: a NULL argument, a descriptor without memory, other formats, different extents, an extent above
+ * 65535, a windowed descriptor anywhere (the taps cross strip borders: a single-GPU pass), reach outside 1..4, normal_min_dot or
+ * plane_tolerance NaN, reserved != 0, mask and out_mask whose memory overlaps (the taps read neighbours: never in place).      */
+int vkr_shadow_mask_filter(const vkr_img* depth, const vkr_img* normal, const vkr_img* mask, const vkr_shadow_filter_params* params,
+                           const vkr_img* out_mask, void* stream);
+
 /* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
  * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one

@@ -1,0 +1,414 @@
+"""vkr_shadow_mask_filter on the GPU: the filtered mask byte for byte against the numpy restatement
+(tests/shadow_mask_filter_reference.py) at 8 x 8 (one wave), 17 x 9 and 33 x 17 (partial tiles, taps across wave and block borders),
+1 x 1, 1 x 9, 9 x 1 and 64 x 36, with reach 1, 2, 3 and 4 everywhere, on the procedural scene through the oracle's rasteriser, on the
+G-buffer content classes sky_all, checker_px and normal_noise, on a checker of sky in 8 x 8 tiles and on the all-accepted plane; with
+masks of random bytes, of all 255, of the residue classes (the interior must be one value) and with the real output of
+vkr_shadow_mask_rt_soft at (S, P) = (1, 4); the early-out at 33 x 17 and 64 x 36 (a mask of one value but for one texel at distance
+R - 1 and R from a wave's tile); the thresholds that reject or accept everything and a NaN camera; out_mask pre-filled and fully
+overwritten with the guard rows around it untouched; and the frame: vkrh_set_shadow_mask_filter against the entry called by hand
+after either mask stage, applied by the shading, switched off again, refused on a tiled frame."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from vk_renderer_amd import abi, host
+from vk_renderer_amd import scene as scn
+from vk_renderer_amd.camera import LIGHT_POS, FrameSetup
+from vk_renderer_amd.chain import PostFxChain
+from vk_renderer_amd.images import ImageBuf
+
+import gbuffer_content as content
+import shadow_light as sl
+import shadow_mask_filter_cases as cases
+import shadow_mask_filter_reference as ref
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+FILL = 0xA5
+GUARD = 3  # rows of FILL above and below out_mask
+SKY = 0xFFFFFF
+SIZES = [(8, 8), (17, 9), (33, 17), (1, 1), (1, 9), (9, 1), (64, 36)]
+REACHES = [1, 2, 3, 4]
+THRESHOLDS = (cases.NORMAL_MIN_DOT, cases.PLANE_TOLERANCE)
+POINT_A = tuple(LIGHT_POS) + (1.0,)
+POINT_B = (3.0, 4.0, 2.0, 1.0)
+SUN_A = (1.5, 4.5, -1.5, 0.0)
+
+
+def _stream():
+    import torch
+
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _sync():
+    import torch
+
+    torch.cuda.synchronize()
+
+
+def _arith():
+    return ref.Arith(int(abi.product().vkr_numeric_contract()))
+
+
+@functools.lru_cache(maxsize=None)
+def _scene():
+    sc = scn.procedural_scene(detail=8)
+    return sc, abi.scene_triangles(sc)
+
+
+@functools.lru_cache(maxsize=None)
+def _raster(size):
+    """the procedural scene through the oracle's rasteriser at the next even extent, cut to size (as tests/test_shadow_mask_rt_soft_gpu.py)"""
+    w, h = size
+    ew, eh = w + (w & 1), h + (h & 1)
+    setup = FrameSetup(ew, eh)
+    chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
+    chain.raster(_scene()[0])
+    return chain.depth.raw(0)[:h, :w, 0].astype(np.uint32), chain.normal.raw(0)[:h, :w].copy(), setup
+
+
+class _Gbuffer:
+    """what a content class of tests/gbuffer_content.py touches of a chain: host images of the two inputs of the pass"""
+
+    def __init__(self, size):
+        w, h = size
+        words, codes, self.setup = _raster(size)
+        self.depth = self.prev_depth = ImageBuf(abi.FMT_D24_UNORM_S8, w, h)
+        self.normal = ImageBuf(abi.FMT_RG16_UNORM, w, h)
+        self.depth.set_raw(words.reshape(h, w, 1))
+        self.normal.set_raw(codes)
+
+
+def _checker_tile8(c, rng):
+    x, y = content._grid(c.depth)
+    content._set_depth(c.depth, SKY, (((x // 8) + (y // 8)) & 1) == 1)
+
+
+def _plane(c, rng):
+    words, codes = cases.plane_gbuffer((c.depth.width, c.depth.height), c.setup)
+    c.depth.set_raw(words.reshape(c.depth.height, c.depth.width, 1))
+    c.normal.set_raw(codes)
+
+
+CLASSES = {"raster": lambda c, rng: None, "sky_all": content.sky_all, "checker_px": content.checker_px, "normal_noise": content.normal_noise,
+           "checker_tile8": _checker_tile8, "plane": _plane}
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(name, size):
+    """-> (depth words [h, w], normal codes [h, w, 2], setup, the two images' bytes)"""
+    g = _Gbuffer(size)
+    CLASSES[name](g, np.random.default_rng([0xF117E5, sorted(CLASSES).index(name), size[0], size[1]]))
+    return g.depth.raw(0)[..., 0].copy(), g.normal.raw(0).copy(), g.setup, g.depth.to_host().copy(), g.normal.to_host().copy()
+
+
+def _random_mask(size, seed):
+    return np.random.default_rng([0x3A5C, seed, size[0], size[1]]).integers(0, 256, size=(size[1], size[0], 4), dtype=np.uint8)
+
+
+def _device_image(fmt, size, host_bytes):
+    im = ImageBuf(fmt, size[0], size[1], device="cuda")
+    im.upload(host_bytes)
+    return im
+
+
+def _mask_image(size, mask):
+    h = ImageBuf(abi.FMT_RGBA8_UNORM, size[0], size[1])
+    h.set_raw(mask)
+    return _device_image(abi.FMT_RGBA8_UNORM, size, h.to_host())
+
+
+def _launch(name, size, mask, reach, thresholds=THRESHOLDS, inverse_camera=None):
+    """-> the RGBA8 codes [h, w, 4] of out_mask; out_mask lies between guard rows, everything pre-filled with FILL: every texel
+    must have been written, and nothing else"""
+    w, h = size
+    _, _, setup, depth_bytes, normal_bytes = _inputs(name, size)
+    depth = _device_image(abi.FMT_D24_UNORM_S8, size, depth_bytes)
+    normal = _device_image(abi.FMT_RG16_UNORM, size, normal_bytes)
+    src = _mask_image(size, mask)
+    tall = ImageBuf(abi.FMT_RGBA8_UNORM, w, h + 2 * GUARD, device="cuda", fill=FILL)
+    out = tall.desc()
+    out.base = tall.ptr + GUARD * tall.pitch[0]
+    out.height = out.full_height = h
+    params = abi.shadow_filter_params(setup.inv_view if inverse_camera is None else inverse_camera, *setup.fazz, reach, *thresholds)
+    abi.shadow_mask_filter(depth.desc(), normal.desc(), src.desc(), params, out, _stream())
+    _sync()
+    host_bytes = tall.to_host()
+    pitch = tall.pitch[0]
+    rows = host_bytes[: pitch * (h + 2 * GUARD)].reshape(h + 2 * GUARD, pitch)
+    assert (rows[:GUARD] == FILL).all() and (rows[GUARD + h:] == FILL).all(), "a guard row was written"
+    assert (rows[:, 4 * w:] == FILL).all() and (host_bytes[pitch * (h + 2 * GUARD):] == FILL).all(), "bytes outside the rows were written"
+    assert np.array_equal(src.raw(0), mask), "the input mask was written"
+    return np.ascontiguousarray(rows[GUARD:GUARD + h, : 4 * w]).reshape(h, w, 4)
+
+
+def _expected(name, size, mask, reach, thresholds=THRESHOLDS, inverse_camera=None):
+    words, codes, setup, _, _ = _inputs(name, size)
+    return ref.shadow_mask_filter(_arith(), words, codes, mask, setup.inv_view if inverse_camera is None else inverse_camera, *setup.fazz, reach, *thresholds)
+
+
+def _differing(name, got, want):
+    bad = (got != want).any(axis=-1)
+    assert not bad.any(), (f"{name}: {int(bad.sum())} of {bad.size} texels differ, first at {tuple(np.argwhere(bad)[0])}: "
+                           f"{got[bad][:4].tolist()} != {want[bad][:4].tolist()}")
+
+
+# ---- byte for byte against the restatement ------------------------------------------------------------------------------------------
+CASES = [(name, size) for name in sorted(CLASSES) for size in SIZES]
+
+
+@pytest.mark.parametrize("name,size", CASES, ids=[f"{n}-{s[0]}x{s[1]}" for n, s in CASES])
+def test_parity(name, size):
+    words = _inputs(name, size)[0]
+    ones = np.full((size[1], size[0], 4), 255, np.uint8)
+    for reach in REACHES:
+        mask = _random_mask(size, reach)
+        got = _launch(name, size, mask, reach)
+        want = _expected(name, size, mask, reach)
+        print(f"[shadow mask filter] {name} {size[0]}x{size[1]} reach {reach}: {int(((words & SKY) != SKY).sum())} geometry pixels, "
+              f"{int((want != mask).any(axis=-1).sum())} texels changed by the rule, differing texels {int((got != want).any(axis=-1).sum())}")
+        _differing(f"{name} {size} reach {reach}, random bytes", got, want)
+        sky = (words & SKY) == SKY
+        assert np.array_equal(got[sky], mask[sky]), "a sky texel did not pass through"
+        if reach == 1 or name == "sky_all":
+            assert np.array_equal(got, mask)
+        _differing(f"{name} {size} reach {reach}, all 255", _launch(name, size, ones, reach), ones)
+    if name == "raster" and size == (64, 36):  # not vacuous
+        assert (want != mask).any()
+
+
+@pytest.mark.parametrize("size", SIZES, ids=[f"{s[0]}x{s[1]}" for s in SIZES])
+def test_residue_classes_filter_to_one_value(size):
+    for reach in (2, 3, 4):
+        mask = cases.residue_mask(size, reach)
+        got = _launch("plane", size, mask, reach)
+        _differing(f"residue classes {size} reach {reach}", got, _expected("plane", size, mask, reach))
+        inner = cases.interior(size, reach)
+        if inner.any():
+            assert (got[inner] == cases.residue_mean(reach)).all(), f"reach {reach}: the interior is not the one mean of the classes"
+    assert cases.interior((64, 36), 4).any()
+
+
+@functools.lru_cache(maxsize=None)
+def _soft_mask():
+    """what vkr_shadow_mask_rt_soft writes at (S, P) = (1, 4) for two lights of radius 0.5 on the rasterised scene at 64 x 36"""
+    size = (64, 36)
+    _, _, setup, depth_bytes, normal_bytes = _inputs("raster", size)
+    depth = _device_image(abi.FMT_D24_UNORM_S8, size, depth_bytes)
+    normal = _device_image(abi.FMT_RG16_UNORM, size, normal_bytes)
+    out = ImageBuf(abi.FMT_RGBA8_UNORM, *size, device="cuda", fill=FILL)
+    accel = abi.Accel(_scene()[1])
+    try:
+        params = abi.shadow_rt_params(setup.inv_view, [POINT_A, POINT_B], *setup.fazz)
+        soft = abi.shadow_rt_soft((0.5, 0.5), 1, 4, device="cuda")
+        abi.shadow_mask_rt_soft(depth.desc(), normal.desc(), accel, params, soft, out.desc(), _stream())
+        _sync()
+    finally:
+        accel.close()
+    return out.raw(0).copy()
+
+
+@pytest.mark.parametrize("reach", REACHES)
+def test_the_soft_mask_of_one_ray_and_sixteen_patterns(reach):
+    size = (64, 36)
+    mask = _soft_mask()
+    assert set(np.unique(mask[..., :2]).tolist()) == {0, 255} and (mask[..., 2:] == 255).all()  # S = 1: dither, nothing between
+    got = _launch("raster", size, mask, reach)
+    _differing(f"soft mask, reach {reach}", got, _expected("raster", size, mask, reach))
+    between = (got[..., :2] > 0) & (got[..., :2] < 255)
+    print(f"[shadow mask filter] soft mask S 1 P 4, reach {reach}: {int(between.sum())} channel values strictly between 0 and 255")
+    assert between.any() == (reach > 1), "the filter makes no penumbra of the dither" if reach > 1 else "reach 1 changed the mask"
+
+
+# ---- the early-out ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("reach", REACHES)
+@pytest.mark.parametrize("size", [(33, 17), (64, 36)], ids=["33x17", "64x36"])
+def test_one_texel_reaches_exactly_its_window(size, reach):
+    """a mask of one value but for one texel that differs in alpha only: at distance R - 1 from a wave's tile it changes that tile's
+    output, at distance R it does not — a window test of the early-out that is too small or too large fails one of the two"""
+    base = np.array(cases.BASE, np.uint8)
+    seen = {True: 0, False: 0}
+    for name, at, (tx, ty), changes in cases.single_texel_cases(size, reach):
+        mask = cases.single_texel_mask(size, at)
+        got = _launch("plane", size, mask, reach)
+        _differing(f"{size} reach {reach} {name}", got, _expected("plane", size, mask, reach))
+        assert (got[ty:ty + 8, tx:tx + 8] != base).any() == changes, name
+        seen[changes] += 1
+    assert seen[True] >= 3 and seen[False] >= 3, seen
+
+
+# ---- the thresholds ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [(17, 9), (64, 36)], ids=["17x9", "64x36"])
+@pytest.mark.parametrize("name", ["raster", "normal_noise", "checker_px"])
+def test_thresholds(name, size):
+    words, _, setup, _, _ = _inputs(name, size)
+    sky = (words & SKY) == SKY
+    for reach in (2, 4):
+        mask = _random_mask(size, 10 + reach)
+        # every tap but the centre rejected: the identity
+        _differing(f"normal_min_dot 2, {name} {size} reach {reach}", _launch(name, size, mask, reach, (2.0, 0.01)), mask)
+        # every tap that is not sky accepted
+        wide = (-2.0, float("inf"))
+        got = _launch(name, size, mask, reach, wide)
+        _differing(f"every tap accepted, {name} {size} reach {reach}", got, _expected(name, size, mask, reach, wide))
+        assert np.array_equal(got[sky], mask[sky])
+        # a NaN in the camera: every plane test is false, the centre stays: the identity
+        nan_camera = np.array(setup.inv_view, F32).copy()
+        nan_camera[0, 0] = np.nan
+        got = _launch(name, size, mask, reach, THRESHOLDS, nan_camera)
+        _differing(f"NaN camera against the restatement, {name} {size} reach {reach}", got, _expected(name, size, mask, reach, THRESHOLDS, nan_camera))
+        _differing(f"NaN camera, {name} {size} reach {reach}", got, mask)
+
+
+# ---- the frame ----------------------------------------------------------------------------------------------------------------------------
+W, H = 256, 144
+FRAME_LIGHTS = [POINT_A, SUN_A, POINT_B]
+FRAME_RADII = [0.5, 0.25, 0.0]
+
+
+def _by_hand(frame, setup, reach, thresholds=THRESHOLDS):
+    """the entry on the frame's own depth, normal and "shadow_mask" """
+    out = ImageBuf(abi.FMT_RGBA8_UNORM, W, H, device="cuda", fill=FILL)
+    params = abi.shadow_filter_params(setup.inv_view, *setup.fazz, reach, *thresholds)
+    abi.shadow_mask_filter(frame.image("depth", 0, 1), frame.image("normal"), frame.image("shadow_mask"), params, out.desc(), _stream())
+    _sync()
+    return out.raw(0)
+
+
+def test_frame_after_the_traced_mask():
+    sc = scn.procedural_scene(detail=12)
+    setup = FrameSetup(W, H)
+    frame = host.HostFrame(setup, device="cuda")
+    try:
+        frame.load_scene(sc)
+        frame.set_shadow_rays(FRAME_LIGHTS)
+        frame.set_shadow_area_lights(FRAME_RADII, 1, 4)
+        frame.run(host.STAGE_RASTER | host.STAGE_SHADOW_MASK_RT)
+        _sync()
+        assert frame.last_tasks() == ["GbufferPass", "ShadowMaskRTSoft"], frame.last_tasks()
+        with pytest.raises(RuntimeError, match="'shadow_mask_filtered' only exists after"):
+            frame.image("shadow_mask_filtered")
+        unfiltered = frame.download("shadow_mask").raw(0)
+        for reach, thresholds in ((4, THRESHOLDS), (2, (0.5, 0.1))):
+            frame.set_shadow_mask_filter(reach, *thresholds)
+            frame.run(host.STAGE_RASTER | host.STAGE_SHADOW_MASK_RT)
+            _sync()
+            assert frame.last_tasks() == ["GbufferPass", "ShadowMaskRTSoft", "ShadowMaskFilter"], frame.last_tasks()
+            d = frame.image("shadow_mask_filtered")
+            assert (d.format, d.width, d.height) == (abi.FMT_RGBA8_UNORM, W, H)
+            _differing("the unfiltered mask stays what it was", frame.download("shadow_mask").raw(0), unfiltered)
+            staged = frame.download("shadow_mask_filtered").raw(0)
+            _differing(f"reach {reach}, against the entry called by hand", staged, _by_hand(frame, setup, reach, thresholds))
+            between = (staged[..., 0] > 0) & (staged[..., 0] < 255)
+            assert between.sum() > ((unfiltered[..., 0] > 0) & (unfiltered[..., 0] < 255)).sum(), "the filter makes no penumbra of the dither"
+            assert np.array_equal(staged[..., 3], unfiltered[..., 3]) and (staged[..., 3] == 255).all()
+        with pytest.raises(RuntimeError, match="vkrh_set_shadow_mask_filter: reach 5"):
+            frame.set_shadow_mask_filter(5)
+    finally:
+        frame.close()
+
+
+def test_frame_after_the_looked_up_mask():
+    sc = scn.procedural_scene(detail=12)
+    setup = FrameSetup(W, H)
+    frame = host.HostFrame(setup, device="cuda")
+    try:
+        frame.load_scene(sc)
+        frame.set_shadow_lights([sl.mvp("A"), sl.mvp("B")], 360)
+        frame.set_shadow_mask(bias=4096, radius=1)
+        frame.set_shadow_mask_filter(3)
+        frame.run(host.STAGE_RASTER | host.STAGE_SHADOW | host.STAGE_SHADOW_MASK)
+        _sync()
+        assert frame.last_tasks() == ["GbufferPass", "ShadowPass", "ShadowPass", "ShadowMask", "ShadowMaskFilter"], frame.last_tasks()
+        staged = frame.download("shadow_mask_filtered").raw(0)
+        _differing("after VKRH_STAGE_SHADOW_MASK, against the entry called by hand", staged, _by_hand(frame, setup, 3))
+        assert (staged != frame.download("shadow_mask").raw(0)).any()
+    finally:
+        frame.close()
+
+
+def _shading_blocks(setup):
+    consts = abi.ShadingParams()
+    consts.inverse_camera = abi.Mat4.from_np(setup.inv_view)
+    consts.camera = abi.Mat4.from_np(setup.view)
+    consts.shadow_mvp = abi.Mat4.from_np(np.eye(4))
+    consts.fovy, consts.aspect, consts.znear, consts.zfar = [float(v) for v in setup.fazz]
+    return consts, abi.ShadingPush((C.c_float * 2)(0.0, 1.0), 0)
+
+
+def test_frame_shades_with_the_filtered_mask():
+    """vkrh_set_shadow_mask(apply = 1) with the filter on: color_out equals vkr_defered_shading_shadowed called by hand on the frame's
+    images with "shadow_mask_filtered" as its mask"""
+    sc = scn.procedural_scene(detail=12)
+    setup = FrameSetup(W, H)
+    frame = host.HostFrame(setup, device="cuda")
+    try:
+        frame.load_scene(sc)
+        frame.run(host.STAGE_LUT | host.STAGE_BRDF_LUT | host.STAGE_PREV_DEPTH)
+        stages = host.STAGE_RASTER | host.STAGE_SHADOW_MASK_RT | host.STAGE_CHAIN | host.STAGE_SHADING
+        consts, push = _shading_blocks(setup)
+
+        def by_hand(mask_name):
+            images = [frame.image(n) for n in ("albedo", "normal", "material", "depth")]
+            tail = [frame.image(n) for n in ("acc_ao", "brdf", "blurred")]
+            out = ImageBuf(abi.FMT_RGBA8_SRGB, W, H, device="cuda", fill=FILL)
+            abi.defered_shading_shadowed(*images, consts, *tail, frame.image(mask_name), out.desc(), push, _stream())
+            _sync()
+            return out.raw(0)
+
+        frame.set_shadow_mask(apply=1)
+        frame.set_shadow_area_lights([0.5], 1, 4)
+        frame.set_shadow_mask_filter(4)
+        frame.run(stages)
+        _sync()
+        tasks = frame.last_tasks()
+        assert tasks.index("ShadowMaskRTSoft") + 1 == tasks.index("ShadowMaskFilter") < tasks.index("DeferedShading"), tasks
+        got = frame.download("color_out").raw(0)
+        filtered, raw = by_hand("shadow_mask_filtered"), by_hand("shadow_mask")
+        assert np.array_equal(got, filtered), f"{int((got != filtered).any(axis=-1).sum())} texels differ from the shading of the filtered mask by hand"
+        print(f"[shadow mask filter] frame: {int((filtered != raw).any(axis=-1).sum())} texels of color_out differ between the filtered and the raw mask")
+        assert (filtered != raw).any()
+    finally:
+        frame.close()
+
+
+def test_frame_switched_off_again_is_a_frame_that_never_called_it():
+    sc = scn.procedural_scene(detail=12)
+    setup = FrameSetup(W, H)
+    stages = host.STAGE_RASTER | host.STAGE_SHADOW_MASK_RT | host.STAGE_SHADING
+    results = []
+    for use in (True, False):
+        frame = host.HostFrame(setup, device="cuda")
+        try:
+            frame.load_scene(sc)
+            frame.run(host.STAGE_LUT | host.STAGE_BRDF_LUT | host.STAGE_PREV_DEPTH)
+            frame.set_shadow_mask(apply=1)
+            frame.set_shadow_area_lights([0.5], 1, 4)
+            if use:
+                frame.set_shadow_mask_filter(4)
+            frame.run(stages)
+            _sync()
+            assert ("ShadowMaskFilter" in frame.last_tasks()) == use
+            if use:
+                frame.set_shadow_mask_filter(0)
+            frame.run(stages)
+            _sync()
+            assert frame.last_tasks() == ["GbufferPass", "ShadowMaskRTSoft", "DeferedShading"], frame.last_tasks()
+            results.append({n: frame.download(n).raw(0).copy() for n in ("shadow_mask", "color_out", "depth", "normal", "albedo")})
+        finally:
+            frame.close()
+    for n in results[0]:
+        assert np.array_equal(results[0][n], results[1][n]), f"{n} differs from the frame that never called vkrh_set_shadow_mask_filter"
+
+
+def test_frame_setter_is_refused_on_a_tiled_frame():
+    tiled = host.HostFrame(FrameSetup(W, H), device="cuda", tiled=True)
+    try:
+        with pytest.raises(RuntimeError, match="vkrh_set_shadow_mask_filter: on a tiled frame"):
+            tiled.set_shadow_mask_filter(4)
+    finally:
+        tiled.close()

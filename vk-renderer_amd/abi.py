@@ -271,6 +271,16 @@ class ShadowRtSoft(C.Structure):  # vkr_shadow_rt_soft, 40 bytes
                 ("reserved", C.c_uint32 * 2)]
 
 
+# ---- the edge-aware filter of the shadow mask ----
+# the defaults of the accept test, the host frame's too (host/frame.cpp); DESIGN.md 7.13 says what they rest on
+SHADOW_FILTER_NORMAL_MIN_DOT, SHADOW_FILTER_PLANE_TOLERANCE = 0.9, 0.01
+
+
+class ShadowFilterParams(C.Structure):  # vkr_shadow_filter_params, 96 bytes
+    _fields_ = [("inverse_camera", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float), ("zfar", C.c_float),
+                ("reach", C.c_uint32), ("normal_min_dot", C.c_float), ("plane_tolerance", C.c_float), ("reserved", C.c_uint32)]
+
+
 # ---- the closest-hit ray query and program reflections_rt ----
 ACCEL_MISS = 0xFFFFFFFF  # vkr_accel_hit.index of a ray that hits nothing
 
@@ -456,6 +466,9 @@ def product():
             getattr(lib, "vkr_" + name).restype = C.c_int
         lib.vkr_shadow_disk_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
         lib.vkr_shadow_disk_samples.restype = None
+        # the edge-aware filter of the shadow mask (checked against the numpy restatement tests/shadow_mask_filter_reference.py)
+        lib.vkr_shadow_mask_filter.argtypes = [_IMG, _IMG, _IMG, P(ShadowFilterParams), _IMG, C.c_void_p]
+        lib.vkr_shadow_mask_filter.restype = C.c_int
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
         lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
@@ -832,6 +845,28 @@ def shadow_mask_rt_soft_cutout(depth, normal, accel, attribs, attrib_count, text
     handle = accel.handle if accel is not None else None
     check(lib.vkr_shadow_mask_rt_soft_cutout(ref(depth), ref(normal), handle, attribs, int(attrib_count), textures, int(texture_count), ref(params),
                                              ref(cutout), ref(soft), ref(out_mask), scratch, int(scratch_bytes), stream), lib)
+
+
+def shadow_filter_params(inverse_camera, fovy, aspect, znear, zfar, reach, normal_min_dot=SHADOW_FILTER_NORMAL_MIN_DOT,
+                         plane_tolerance=SHADOW_FILTER_PLANE_TOLERANCE):
+    """ShadowFilterParams from the camera's view -> world matrix (4x4, maths convention), the camera's four floats, the reach R
+    (taps at |dx|, |dy| < R; the pattern_side of the soft mask it reconstructs) and the two thresholds of the accept test.
+    Everything is passed on as given (the entry refuses what it does not take)."""
+    p = ShadowFilterParams()
+    p.inverse_camera = Mat4.from_np(inverse_camera)
+    p.fovy, p.aspect, p.znear, p.zfar = float(fovy), float(aspect), float(znear), float(zfar)
+    p.reach, p.normal_min_dot, p.plane_tolerance, p.reserved = int(reach), float(normal_min_dot), float(plane_tolerance), 0
+    return p
+
+
+def shadow_mask_filter(depth, normal, mask, params, out_mask, stream=None):
+    """vkr_shadow_mask_filter: out_mask (RGBA8_UNORM VkrImg) := per pixel the tent-weighted mean, rounded half up, of `mask`
+    (RGBA8_UNORM VkrImg, other memory than out_mask) over the taps within params.reach that lie on the pixel's surface as `depth`
+    (D24_UNORM_S8 VkrImg, mip 0 of the view) and `normal` (RG16_UNORM VkrImg) tell it, all of one extent, under `params`
+    (ShadowFilterParams, e.g. shadow_filter_params(...)).  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    check(lib.vkr_shadow_mask_filter(ref(depth), ref(normal), ref(mask), ref(params), ref(out_mask), stream), lib)
 
 
 def reflections_rt_cutout(depth, normal, rays, accel, attribs, attrib_count, textures, texture_count, params, cutout, out_reflections, scratch,

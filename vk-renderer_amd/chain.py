@@ -507,6 +507,22 @@ class PostFxChain:
         abi.shadow_mask_rt_cutout(self.depth.desc(0, 1), self.normal.desc(), accel, attribs.data_ptr(), attribs.numel() * attribs.element_size() // 32,
                                   scene.textures, scene.texture_count, p, setting, self.shadow_mask_out.desc(), scratch, nbytes, self.stream)
 
+    def shadow_mask_filter(self, reach, normal_min_dot=abi.SHADOW_FILTER_NORMAL_MIN_DOT, plane_tolerance=abi.SHADOW_FILTER_PLANE_TOLERANCE):
+        """vkr_shadow_mask_filter on this chain's depth, normal and shadow_mask_out (of shadow_mask or shadow_mask_rt) ->
+        shadow_mask_filtered_out (RGBA8_UNORM): the tent-weighted mean over the taps within `reach` that lie on the pixel's
+        surface; reach is the pattern_side of the soft mask it reconstructs.
+        Product backend only: the expectation is the numpy restatement tests/shadow_mask_filter_reference.py, not a checker library."""
+        if self.backend != "product":
+            raise RuntimeError("PostFxChain.shadow_mask_filter: only the product backend has the entry vkr_shadow_mask_filter")
+        if self.tiled:
+            raise RuntimeError("PostFxChain.shadow_mask_filter: not on a window of the frame (the taps cross strip borders: a single-GPU pass)")
+        if not hasattr(self, "shadow_mask_out"):
+            raise RuntimeError("PostFxChain.shadow_mask_filter: no shadow_mask_out (run shadow_mask or shadow_mask_rt first)")
+        if not hasattr(self, "shadow_mask_filtered_out"):
+            self.shadow_mask_filtered_out = ImageBuf(abi.FMT_RGBA8_UNORM, self.depth.width, self.depth.height, device=self.device)
+        p = abi.shadow_filter_params(self.setup.inv_view, *self.setup.fazz, reach, normal_min_dot=normal_min_dot, plane_tolerance=plane_tolerance)
+        abi.shadow_mask_filter(self.depth.desc(0, 1), self.normal.desc(), self.shadow_mask_out.desc(), p, self.shadow_mask_filtered_out.desc(), self.stream)
+
     def _cutout_scratch(self, texture_count):
         """-> (bytes, device pointer) of the texture table of a ray-traced pass (one size for the opaque and the cutout entries)"""
         import torch

@@ -158,6 +158,8 @@ def lib():
                            ("vkrh_set_shadow_rays", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float]),
                            # area lights in the ray-traced shadow mask (same rule)
                            ("vkrh_set_shadow_area_lights", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]),
+                           # the edge-aware filter of the shadow mask (same rule)
+                           ("vkrh_set_shadow_mask_filter", [C.c_void_p, C.c_uint32, C.c_float, C.c_float]),
                            # the ray-traced reflections (same rule)
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
@@ -397,6 +399,13 @@ class HostFrame:
         stage.  Not on a tiled frame."""
         flat = (C.c_float * max(4, len(radii)))(*[float(r) for r in radii])
         self._check(lib().vkrh_set_shadow_area_lights(self.h, flat, len(radii), int(sample_count), int(pattern_side)))
+
+    def set_shadow_mask_filter(self, reach, normal_min_dot=abi.SHADOW_FILTER_NORMAL_MIN_DOT, plane_tolerance=abi.SHADOW_FILTER_PLANE_TOLERANCE):
+        """vkrh_set_shadow_mask_filter: reach 1..4: STAGE_SHADOW_MASK and STAGE_SHADOW_MASK_RT record vkr_shadow_mask_filter (task
+        ShadowMaskFilter) right after the mask, from image "shadow_mask" into image "shadow_mask_filtered", which the shadowed
+        shading then reads; reach is the pattern_side of the area lights it reconstructs.  reach 0 (the default): off.  Not on a
+        tiled frame."""
+        self._check(lib().vkrh_set_shadow_mask_filter(self.h, int(reach), float(normal_min_dot), float(plane_tolerance)))
 
     def set_reflection_rays(self, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, max_distance=None,
                             texture_lod=0):

@@ -191,6 +191,29 @@ struct PostFxFrame {
     shadow_mask_bias = bias; shadow_mask_radius = radius; shadow_mask_apply = apply != 0;
   }
 
+  // The edge-aware filter of the mask (vkrh_set_shadow_mask_filter), right after either mask stage into a second image, created
+  // on the first run with the filter on.  Default: reach 0, off.
+  uint32_t shadow_filter_reach = 0;
+  float shadow_filter_normal_min_dot = 0.9f, shadow_filter_plane_tolerance = 0.01f;
+  bool has_shadow_mask_filtered = false;
+  rendergraph::ImageResourceId shadow_mask_filtered_tex;
+  void set_shadow_mask_filter(uint32_t reach, float normal_min_dot, float plane_tolerance) {
+    refuse_tiled("vkrh_set_shadow_mask_filter", "the taps cross strip borders: the filter runs on one GPU");
+    if (reach > 4) throw std::runtime_error{"vkrh_set_shadow_mask_filter: reach " + std::to_string(reach) + ", needs 0 (off) or 1..4"};
+    if (std::isnan(normal_min_dot) || std::isnan(plane_tolerance)) throw std::runtime_error{"vkrh_set_shadow_mask_filter: a threshold is NaN"};
+    shadow_filter_reach = reach; shadow_filter_normal_min_dot = normal_min_dot; shadow_filter_plane_tolerance = plane_tolerance;
+  }
+  // after the mask stage of this run has been recorded
+  void record_shadow_mask_filter(ShadowMaskPass& pass) {
+    if (shadow_filter_reach == 0) return;
+    if (!has_shadow_mask_filtered) {
+      shadow_mask_filtered_tex = create_shadow_mask_texture(graph, cfg.width, cfg.height);
+      has_shadow_mask_filtered = true;
+    }
+    pass.update_filter(shadow_filter_reach, shadow_filter_normal_min_dot, shadow_filter_plane_tolerance);
+    pass.run_filter(graph, gbuffer.depth, gbuffer.normal, shadow_mask_tex, shadow_mask_filtered_tex);
+  }
+
   // VKRH_STAGE_SHADOW_MASK_RT: the lights and offsets of the rays (vkrh_set_shadow_rays).  Default: one point light at the shading
   // pass's LIGHT_POS; normal_offset and tmin as measured on the plane-only scene.
   std::vector<float> shadow_rays{-1.85867f, 5.81832f, -0.247114f, 1.0f};
@@ -413,6 +436,7 @@ struct PostFxFrame {
       ShadowMaskPass& pass = ensure_shadow_mask();
       pass.update_params(view, shadow_lights.data(), (uint32_t)shadow_lights.size(), fazz.x, fazz.y, fazz.z, fazz.w, shadow_mask_radius, shadow_mask_bias);
       pass.run(graph, gbuffer.depth, shadows, (uint32_t)shadow_lights.size(), shadow_mask_tex);
+      record_shadow_mask_filter(pass);
     }
     if (mask & VKRH_STAGE_SHADOW_MASK_RT) {  // reads depth mip 0 and the normal of this run's G-buffer; the slot of the looked-up mask
       ShadowMaskPass& pass = ensure_shadow_mask();
@@ -425,6 +449,7 @@ struct PostFxFrame {
                     ray_cutouts, shadow_mask_tex);
       else
         pass.run_rt(graph, gbuffer.depth, gbuffer.normal, scene_as->tlas, shadow_mask_tex);
+      record_shadow_mask_filter(pass);
     }
     if (mask & VKRH_STAGE_SSAO) {  // reads depth mip 0 only: before the downsample writes the other mips
       SSAOPass& pass = ensure_ssao();
@@ -514,7 +539,7 @@ struct PostFxFrame {
       shading_pass.update_params(view, lit ? shadow_lights[0] : glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
       if (shadow_mask_apply && (mask & (VKRH_STAGE_SHADOW_MASK | VKRH_STAGE_SHADOW_MASK_RT)))  // vkrh_set_shadow_mask(apply) and the mask of this run
         shading_pass.draw_shadowed(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(),
-                                   shadow_mask_tex, color_out_tex);
+                                   shadow_filter_reach ? shadow_mask_filtered_tex : shadow_mask_tex, color_out_tex);  // the filtered mask when the filter is on
       else
         shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
     }
@@ -639,6 +664,8 @@ struct PostFxFrame {
         {"backbuffer", [](F& f) { return f.graph.get_backbuffer(); }, [](const F& f) { return f.backbuffer_drawn; }, "only exists after VKRH_STAGE_BACKBUFFER"},
         {"shadow_mask", [](F& f) { return f.shadow_mask_tex; }, [](const F& f) { return f.shadow_mask_pass != nullptr; },
          "only exists after VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT"},
+        {"shadow_mask_filtered", [](F& f) { return f.shadow_mask_filtered_tex; }, [](const F& f) { return f.has_shadow_mask_filtered; },
+         "only exists after a mask stage with vkrh_set_shadow_mask_filter on"},
     };
     for (const NamedImage& e : table)
       if (name == e.name) return &e;
@@ -1474,6 +1501,9 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
   });
 }
 int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply) { return guarded([&] { frame_ref(frame).set_shadow_mask(bias, radius, apply); }); }
+int vkrh_set_shadow_mask_filter(void* frame, uint32_t reach, float normal_min_dot, float plane_tolerance) {
+  return guarded([&] { frame_ref(frame).set_shadow_mask_filter(reach, normal_min_dot, plane_tolerance); });
+}
 int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) { return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); }); }
 int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
   return guarded([&] { frame_ref(frame).set_backbuffer(source_image, flags, width, height); });

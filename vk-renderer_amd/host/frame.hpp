@@ -182,6 +182,14 @@ int vkrh_set_shadow_rays(void* frame, const float* lights, uint32_t count, float
  * NaN or infinite.  Default: every radius 0, under which the stage records what it always recorded.  A vkrh_set_shadow_rays with
  * another number of lights sets every radius back to 0.  No new stage bit.  Not on a tiled frame. */
 int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side);
+/* The edge-aware filter of the shadow mask (vkr_shadow_mask_filter): with reach 1..4 a VKRH_STAGE_SHADOW_MASK or
+ * VKRH_STAGE_SHADOW_MASK_RT records, right after the mask, the task ShadowMaskFilter from image "shadow_mask" (which stays the
+ * unfiltered mask) into image "shadow_mask_filtered" (RGBA8_UNORM at the frame's extent; exists only after such a run), and the
+ * shadowed shading of vkrh_set_shadow_mask(apply) reads the filtered image.  reach is the side of the tent, the pattern_side of the
+ * area lights it reconstructs; a tap counts when dot(n, n_tap) >= normal_min_dot and its distance from the pixel's tangent plane
+ * is at most plane_tolerance times the pixel's view depth.  An error: reach above 4, a NaN threshold.  Default: reach 0, off, under
+ * which every stage records what it always recorded.  No new stage bit.  Not on a tiled frame. */
+int vkrh_set_shadow_mask_filter(void* frame, uint32_t reach, float normal_min_dot, float plane_tolerance);
 /* The rays of VKRH_STAGE_REFLECTIONS_RT: fill_misses != 0 traces only the pixels whose screen-space ray is invalid, after the
  * screen-space trace and filter; the ray's origin is the surface point moved by normal_offset along the normal, the ray runs
  * t in [tmin, max_distance] along the unit mirror direction (tmin or max_distance NaN is an error), a hit samples mip level

@@ -923,6 +923,7 @@ void ShadowMaskPass::update_params(const glm::mat4 &camera, const glm::mat4 *mvp
   for (uint32_t l = 0; l < count; l++) copy_mat(params.mvps[l], mvps[l]);
   params.fovy = fovy; params.aspect = aspect; params.znear = znear; params.zfar = zfar;
   params.layer_count = count; params.radius = radius; params.bias = bias;
+  camera_is_rt = false;
 }
 
 // task "ShadowMask": set {0 depth (mip 0), 1 the shadow array (every layer), 2 the block, 3 the mask (storage)}, one 16 x 16 group
@@ -950,6 +951,7 @@ void ShadowMaskPass::update_rt_params(const glm::mat4 &camera, const float *ligh
   for (uint32_t l = 0; l < count; l++)
     for (int k = 0; k < 4; k++) rt_params.lights[l][k] = lights[4*l + k];
   rt_params.light_count = count; rt_params.normal_offset = normal_offset; rt_params.tmin = tmin;
+  camera_is_rt = true;
 }
 
 void ShadowMaskPass::update_rt_soft(const float radius[4], uint32_t sample_count, uint32_t pattern_side) {
@@ -1109,6 +1111,31 @@ void blit_image(RenderGraph &graph, ImageResourceId src, ImageResourceId dst) {
     const vkr_img s = resources.get_image(src)->describe(0, 1), d = resources.get_image(dst)->describe(0, 1);
     transfer_status(vkr_blit_image(&s, &d, VKR_FILTER_LINEAR, stream), "CopyImage");  // the reference blits with VK_FILTER_LINEAR
   });
+}
+
+// ==== ShadowMaskPass, the filter (shadow_mask.hpp): here because the task is a direct C-ABI call like the transfers above ==========
+void ShadowMaskPass::update_filter(uint32_t reach, float normal_min_dot, float plane_tolerance) {
+  if (reach < 1 || reach > 4) throw std::runtime_error {"ShadowMaskPass::update_filter: reach " + std::to_string(reach) + ", needs 1..4"};
+  if (std::isnan(normal_min_dot) || std::isnan(plane_tolerance)) throw std::runtime_error {"ShadowMaskPass::update_filter: a threshold is NaN"};
+  filter.reach = reach; filter.normal_min_dot = normal_min_dot; filter.plane_tolerance = plane_tolerance;
+}
+
+void ShadowMaskPass::run_filter(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, ImageResourceId mask, ImageResourceId out) {
+  if (filter.reach == 0) throw std::runtime_error {"ShadowMaskPass::run_filter: update_filter first"};
+  vkr_shadow_filter_params block = filter;
+  if (camera_is_rt) {
+    block.inverse_camera = rt_params.inverse_camera;
+    block.fovy = rt_params.fovy; block.aspect = rt_params.aspect; block.znear = rt_params.znear; block.zfar = rt_params.zfar;
+  } else {
+    block.inverse_camera = params.inverse_camera;
+    block.fovy = params.fovy; block.aspect = params.aspect; block.znear = params.znear; block.zfar = params.zfar;
+  }
+  add_transfer_task(graph, "ShadowMaskFilter", {{depth, 0, 1, 1}, {normal, 0, 1, 1}, {mask, 0, 1, 1}}, {{out, 0, 1, 1}},
+    [=](rendergraph::RenderResources &resources, void *stream) {
+      const vkr_img d = resources.get_image(depth)->describe(0, 1), n = resources.get_image(normal)->describe(0, 1);
+      const vkr_img m = resources.get_image(mask)->describe(0, 1), o = resources.get_image(out)->describe(0, 1);
+      transfer_status(vkr_shadow_mask_filter(&d, &n, &m, &block, &o, stream), "ShadowMaskFilter");
+    });
 }
 
 // ==== scene (scene/scene.cpp, scene/images.cpp) and SceneRenderer (scene_renderer.cpp:46-220) ===========================

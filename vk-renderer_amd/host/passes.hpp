@@ -746,6 +746,15 @@ struct ShadowMaskPass {
   void run_rt(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
     const AdvancedSSR::RtScene &scene, const RtCutouts &cutouts, rendergraph::ImageResourceId out);
 
+  // The edge-aware filter of the mask (vkr_shadow_mask_filter): reach 1..4 (taps at |dx|, |dy| < reach; the
+  // pattern_side of the soft mask it reconstructs), the two thresholds of the accept test.  The camera is the one of the last
+  // update_params / update_rt_params: the filter follows a mask pass.
+  void update_filter(uint32_t reach, float normal_min_dot, float plane_tolerance);
+  // task "ShadowMaskFilter": depth (mip 0), the full-resolution normal and the mask -> out, another image of the mask's format and
+  // extent.  No program of the table: the task calls the C-ABI entry, as the transfers of util_passes.hpp do.
+  void run_filter(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
+    rendergraph::ImageResourceId mask, rendergraph::ImageResourceId out);
+
 private:
   gpu::ComputePipeline pipeline;
   gpu::ComputePipeline rt_pipeline;  // "shadow_mask_rt", bound by the first run_rt()
@@ -758,6 +767,8 @@ private:
   vkr_shadow_rt_soft rt_soft {};  // samples stays NULL here: the program takes the pointer from rt_soft_table
   gpu::BufferPtr rt_soft_table;  // sample_count x pattern_side^2 x (u, v)
   bool rt_soft_on() const { return rt_soft.radius[0] > 0.f || rt_soft.radius[1] > 0.f || rt_soft.radius[2] > 0.f || rt_soft.radius[3] > 0.f; }
+  vkr_shadow_filter_params filter {};  // the camera is filled in by run_filter
+  bool camera_is_rt {false};  // which of params / rt_params was updated last
 };
 
 
