@@ -208,7 +208,8 @@ def probe_downsample(mip0_codes, mips):
 
 # ---- trace_probe ----------------------------------------------------------------------------------------------------------
 class ProbeArrays:
-    """the probe colour array (RGBA8 codes [L, S, S, 4]) and depth array (R16_UNORM codes per mip, [L, h_m, w_m])"""
+    """the probe colour array (RGBA8 codes [L, S, S, 4]) and depth array (R16_UNORM codes per mip, [L, h_m, w_m]).
+    past_last_mip counts the lanes of fetch() that asked for a mip the array does not have (they read 0)."""
 
     def __init__(self, color_codes, depth_mips):
         self.color = np.asarray(color_codes, np.uint8)
@@ -225,10 +226,12 @@ class ProbeArrays:
         self.flat = np.concatenate(flat + [np.zeros(1, F32)])  # the last entry: the 0 of a fetch out of range
         self.zero = acc
         self.mip0 = unorm16_to_float(depth_mips[0])
+        self.past_last_mip = 0
 
     def fetch(self, px, py, layer, mip):
         x, y = f2i_index(px), f2i_index(py)
         m = np.minimum(mip, self.mips + 31)
+        self.past_last_mip += int((mip >= self.mips).sum())
         w, h = self.w[m], self.h[m]
         ok = (mip < self.mips) & (x >= 0) & (y >= 0) & (x < w) & (y < h)
         idx = np.where(ok, self.off[m] + (layer * h + np.where(ok, y, 0)) * w + np.where(ok, x, 0), self.zero)

@@ -61,7 +61,8 @@ def quirk_packed(samples16x3):
 def ssao(ar, depth_bits, proj, fovy, aspect, znear, zfar, samples16x4, out_w, out_h, stats=None):
     """-> (R8 codes [out_h, out_w] uint8, counts [out_h, out_w]).  depth_bits: raw D24S8 words [h, w] of the view's base mip;
     proj: 4x4 in maths convention; samples16x4: the block's slots ([16, 3] works too), .w unused.  stats: a dict that receives
-    `offscreen_taps` (sample_uv outside [0, 1]^2, NaN included) and `taps`."""
+    `offscreen_taps` (sample_uv outside [0, 1]^2, NaN included), `nonfinite_sample_uv` (taps with an infinite or NaN sample_uv
+    component: a sample on or next to the eye plane) and `taps`."""
     M = np.asarray(proj, F32)
     S = np.asarray(samples16x4, F32)
     depth = d24_to_float(np.asarray(depth_bits).astype(np.uint32))
@@ -78,7 +79,7 @@ def ssao(ar, depth_bits, proj, fovy, aspect, znear, zfar, samples16x4, out_w, ou
         yd = ar.cfma(F32(2.0), uvy, F32(-1.0))
         cam = [-xd * ((z * F32(aspect)) * tg), -yd * (z * tg), z]
         counts = np.zeros((out_h, out_w), np.int64)
-        offscreen = 0
+        offscreen = nonfinite = 0
         one = np.ones_like(z)
         for i in range(SAMPLES):
             pos = [ar.cfma(F32(0.05), np.broadcast_to(S[i, c], z.shape), cam[c]) for c in range(3)]  # madd(camera_pos, 0.05, sample)
@@ -88,9 +89,11 @@ def ssao(ar, depth_bits, proj, fovy, aspect, znear, zfar, samples16x4, out_w, ou
             sample = sample_depth(ar, depth, su, sv)
             counts += nz < (sample + F32(0.0000001)).astype(F32)
             offscreen += int((~((su >= 0) & (su <= 1) & (sv >= 0) & (sv <= 1))).sum())
+            nonfinite += int((~(np.isfinite(su) & np.isfinite(sv))).sum())
         codes = encode_unorm8(counts.astype(F32) / F32(SAMPLES))
     if stats is not None:
         stats["offscreen_taps"] = offscreen
+        stats["nonfinite_sample_uv"] = nonfinite
         stats["taps"] = SAMPLES * out_w * out_h
     return codes, counts
 
