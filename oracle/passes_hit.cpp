@@ -4,8 +4,9 @@
 //
 // passes_hit.cpp — hit colours / hit normals by request / reply (include/vkr_postfx.h): which footprint rows of
 // texture(albedo, hit uv) (filter.comp:112-134) and texture(normal, hit uv) (trace.comp:103-109) a rank lacks, the owner's
-// answer, and where the answer goes.  Sequential, so request order is deterministic (the product's order is not: compare
-// as sets per owner).
+// answer, and where the answer goes.  Sequential: the requests of an owner come out in row-major order of the rays.  The
+// product's order is fixed too, but another one — block, tile, wave, request of the ray, lane (csrc/hit_exchange.hip) — so
+// against this twin requests are compared as sets per owner; tests/hit_exchange_reference.py restates the product's order.
 #include <vector>
 
 #include "shader_common.hpp"
@@ -62,6 +63,7 @@ extern "C" int vkr_ref_hit_reply(const vkr_img* albedo, const vkr_img* normals, 
   uint32_t* out = (uint32_t*)replies;
   for (uint32_t i = 0; i < count; i++) {
     const uint32_t r = requests[i];
+    if (r == VKR_HIT_NO_REQUEST) { std::memset(out + 4 * i, 0, 16); continue; }  // an unused slot of a fixed-capacity segment
     const bool nrm = (r & VKR_HIT_NORMAL) != 0u, both = (r & VKR_HIT_BOTH_ROWS) != 0u;
     if (nrm && !normals) { (*error_counter)++; std::memset(out + 4 * i, 0, 16); continue; }
     Image T(nrm ? *normals : *albedo);
@@ -78,6 +80,7 @@ extern "C" int vkr_ref_hit_scatter(const vkr_img* frame_albedo, const vkr_img* f
   const uint32_t* in = (const uint32_t*)replies;
   for (uint32_t i = 0; i < count; i++) {
     const uint32_t r = requests[i];
+    if (r == VKR_HIT_NO_REQUEST) continue;
     Image T((r & VKR_HIT_NORMAL) ? *frame_normals : *frame_albedo);
     const int row = (int)(r & 0x3FFFu), x = (int)((r >> 14) & 0x3FFFu);
     T.store_u32(x, row, 0, in[4 * i + 0]); T.store_u32(x + 1, row, 0, in[4 * i + 1]);

@@ -2,7 +2,8 @@
 vkr_hit_requests (both passes), vkr_hit_reply, vkr_hit_scatter, vkr_sssr_validate (csrc/hit_exchange.hip, csrc/ssr.hip vs
 oracle/passes_hit.cpp, oracle/passes_ssr.cpp).  One frame cut into two strips; the lower strip's window is traced with only
 its own rows of the downsampled normals in memory, asks the upper strip for what it lacks, and must end with the rays the
-plain trace stores.  Requests are an unordered set per owner on the GPU (block-aggregated atomics): compared sorted."""
+plain trace stores.  The GPU's slot order (block, tile, wave, request, lane) is not the twin's row-major one: requests are
+compared sorted here, and in order against tests/hit_exchange_reference.py by tests/test_hit_exchange_cases_gpu.py."""
 import numpy as np
 import pytest
 
@@ -10,6 +11,7 @@ from vk_renderer_amd import abi
 from vk_renderer_amd.camera import FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 
+from hit_round import gather
 from parity import mismatches
 
 pytestmark = pytest.mark.gpu
@@ -31,22 +33,8 @@ def _chains(backend, device):
     for c in [plain] + ranks:
         c.synth(); c.build_prev_hiz(); c.init_histories(); c.preintegrate_pdf(); c.downsample()
     plain.ssr_trace(frame_random=0)
-    for c in ranks:  # the gathered pyramid: whole-frame image mips 1..L-1
-        for m in range(c.frame_hiz.mips):
-            src = plain.depth
-            h = max(1, (H // 2) >> m)
-            a = src.to_host()[src.offset[m + 1]: src.offset[m + 1] + src.pitch[m + 1] * h]
-            dst = c.frame_hiz
-            assert src.pitch[m + 1] == dst.pitch[m]
-            host = dst.to_host().copy()
-            host[dst.offset[m]: dst.offset[m] + dst.pitch[m] * h] = a
-            dst.upload(host)
-        c.hiz_tail(4)
-        for src, dst in ((c.albedo, c.frame_albedo), (c.dn, c.frame_normals)):  # own rows only
-            host = np.full(dst.nbytes, 0xA5, dtype=np.uint8)  # poison: a texel nobody delivers shows
-            o = src.origin[1] * dst.pitch[0]
-            host[o: o + src.height * src.pitch[0]] = src.to_host()[: src.height * src.pitch[0]]
-            dst.upload(host)
+    for c in ranks:  # the gathered pyramid (whole-frame image mips 1..L-1) and the own rows of the whole-frame albedo / normals
+        gather(plain, c)
     return plain, ranks
 
 

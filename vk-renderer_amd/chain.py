@@ -378,7 +378,7 @@ class PostFxChain:
 
     def hit_reply(self, requests, count, normals=True):
         """16 bytes per request from this window's albedo / downsampled normals -> (uint32 buffer [4 * count], errors)"""
-        replies, errors = self._u32_buffer(4 * count), self._u32_buffer(1)
+        replies, errors = self._u32_buffer(4 * count), self._u32_buffer(3)  # (the counter and the two diagnostic words behind it)
         dn = self.dn.desc()
         self.call("hit_reply", C.byref(self.albedo.desc()), C.byref(dn) if normals else None, self._buf_ptr(requests), count,
                   self._buf_ptr(replies), self._buf_ptr(errors))
