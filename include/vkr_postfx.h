@@ -585,7 +585,9 @@ typedef struct vkr_accel_tri {   /* 64 bytes: v0, its edges e1 = v1 - v0, e2 = v
 typedef struct vkr_accel vkr_accel;
 /* Pure host function, no GPU: the hierarchy of tri_count world-space triangles (tri_vertices: tri_count x 3 vertices x xyz,
  * host memory) into caller-provided host arrays: at most max(1, 2 * tri_count - 1) nodes (node_capacity), exactly tri_count
- * triangle records.  *node_count receives the number of nodes written (0 for an empty scene).                                 */
+ * triangle records.  *node_count receives the number of nodes written (0 for an empty scene).  Vertices that are not finite
+ * are accepted (a loader can meet them): the build stays deterministic, a node box takes no NaN bound, and such a triangle is
+ * hit exactly where the frozen test says so, where "NaN is a miss" (DESIGN_NUMERICS.md, "Ray query, scenes and scale").        */
 int vkr_accel_layout(const float* tri_vertices, uint32_t tri_count, vkr_accel_node* nodes, uint32_t node_capacity,
                      vkr_accel_tri* tris, uint32_t* node_count);
 /* layout + upload (synchronous, allocates device memory): the handle the ray-query kernels take                               */

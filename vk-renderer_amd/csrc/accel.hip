@@ -178,9 +178,13 @@ struct Builder {
     BuildTri* mid = std::stable_partition(p, p + n, [&](const BuildTri& t) { return bin_of(t.c[axis], c0, ext) <= bin; });
     return (uint32_t)(mid - p);
   }
+  // the bin is chosen by comparisons before anything is converted: a NaN or infinite centroid, or an infinite centroid extent,
+  // gives a quotient that no int holds (NaN goes to bin 0); for every finite quotient this is the truncation it always was
   static int bin_of(float c, float lo, float ext) {
-    const int b = (int)((double)(c - lo) / (double)ext * ACCEL_BINS);
-    return std::min(std::max(b, 0), ACCEL_BINS - 1);
+    const double x = (double)(c - lo) / (double)ext * ACCEL_BINS;
+    if (!(x >= 0.0)) return 0;
+    if (x >= (double)ACCEL_BINS) return ACCEL_BINS - 1;
+    return (int)x;
   }
 };
 
