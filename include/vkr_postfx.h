@@ -848,7 +848,7 @@ int vkr_trace_probe(const vkr_img* depth, const vkr_img* normal, const vkr_img* 
  * rint(clamp(x, 0, 1) * (2^b - 1)), fp16 round to nearest even, fp32 unchanged (DESIGN_NUMERICS.md, "Image transfers").        */
 typedef struct vkr_clear_value {
   float    color[4];   /* colour formats                                    */
-  float    depth;      /* D24_UNORM_S8: rint(clamp(depth, 0, 1) * 16777215) */
+  float    depth;      /* D24_UNORM_S8: rint(clamp(depth, 0, 1) * 16777215), NaN -> 0 */
   uint32_t stencil;    /* ... | (stencil & 0xFF) << 24                      */
 } vkr_clear_value;
 /* vkCmdClearColorImage / vkCmdClearDepthStencilImage over every mip of the view, one launch.  Only the texels of a row are written

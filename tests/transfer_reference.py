@@ -1,5 +1,6 @@
 """Numpy restatement of the image transfers (csrc/transfer.hip: vkr_clear_image, vkr_blit_image, vkr_gen_mipmaps) — the checker
-of tests/test_transfer.py and tests/test_transfer_gpu.py.
+of tests/test_transfer.py, tests/test_transfer_gpu.py and, on the constructed cases of tests/transfer_cases.py,
+tests/test_transfer_cases.py (which also replaces the helpers below one at a time by wrong rules) and tests/test_transfer_cases_gpu.py.
 
 Test infrastructure, like the oracle: the product package never imports it.  Every fp32 operation is written in the order
 DESIGN_NUMERICS.md ("Image transfers") gives; the fused multiply-adds of numeric contract 2 (the accumulation of the bilinear
@@ -64,12 +65,26 @@ def float_to_srgb8(x):
     return np.where(np.isnan(x), 0, code).astype(np.uint32)
 
 
+def half_to_float(h):
+    """fp16 -> fp32: exact, denormals included"""
+    return np.asarray(h, np.float16).astype(F32)
+
+
+def float_to_half(x):
+    """fp32 -> fp16: round to nearest even, denormals kept, overflow (65520 and above) to infinity"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.asarray(x, F32).astype(np.float16)
+
+
+ABSENT_ALPHA = F32(1.0)  # the alpha a format without an alpha channel decodes to (absent r, g, b: 0)
+
+
 def decode(fmt, raw):
     """texels [h, w, c] of the storage type -> float32 RGBA [h, w, 4], absent channels 0, 0, 0, 1"""
     raw = np.asarray(raw)
     h, w = raw.shape[:2]
     out = np.zeros((h, w, 4), F32)
-    out[..., 3] = 1.0
+    out[..., 3] = ABSENT_ALPHA
     if fmt in (FMT_RG16_UNORM, FMT_RGBA16_UNORM, FMT_R16_UNORM):
         out[..., :raw.shape[2]] = unorm_to_float(raw, 16)
     elif fmt in (FMT_RGBA8_UNORM, FMT_R8_UNORM):
@@ -78,7 +93,7 @@ def decode(fmt, raw):
         out[..., :3] = SRGB_DECODE[raw[..., :3]]
         out[..., 3] = unorm_to_float(raw[..., 3], 8)
     elif fmt in (FMT_RG16_SFLOAT, FMT_RGBA16_SFLOAT, FMT_R16_SFLOAT, FMT_R32_SFLOAT, FMT_RGBA32_SFLOAT):
-        out[..., :raw.shape[2]] = raw.astype(F32)
+        out[..., :raw.shape[2]] = half_to_float(raw) if raw.dtype == np.float16 else raw
     else:
         raise ValueError(fmt)
     return out
@@ -98,19 +113,22 @@ def encode(fmt, rgba):
         out[..., 3] = float_to_unorm(rgba[..., 3], 8)
         return out
     if fmt in (FMT_RG16_SFLOAT, FMT_RGBA16_SFLOAT, FMT_R16_SFLOAT):
-        with np.errstate(over="ignore"):
-            return rgba[..., :c].astype(np.float16)  # round to nearest even
+        return float_to_half(rgba[..., :c])
     if fmt in (FMT_R32_SFLOAT, FMT_RGBA32_SFLOAT):
         return rgba[..., :c].copy()
     raise ValueError(fmt)
 
 
 # ---- clear ----------------------------------------------------------------------------------------------------------------
+def depth_to_d24(depth):
+    """rint(clamp(depth, 0, 1) * 16777215), the product in fp32; NaN -> 0 (fmaxf(NaN, 0) is 0), as for every UNORM store"""
+    return int(float_to_unorm(depth, 24))
+
+
 def clear_texel(fmt, color=(0.0, 0.0, 0.0, 0.0), depth=1.0, stencil=0):
     """the stored texel [c] every texel of every mip holds after vkr_clear_image"""
     if fmt == FMT_D24_UNORM_S8:
-        d = np.minimum(np.maximum(F32(depth), F32(0.0)), F32(1.0))
-        return np.array([int(np.rint(d * F32(16777215.0))) | ((int(stencil) & 0xFF) << 24)], np.uint32)
+        return np.array([depth_to_d24(depth) | ((int(stencil) & 0xFF) << 24)], np.uint32)
     return encode(fmt, np.array(color, F32).reshape(1, 1, 4))[0, 0]
 
 
@@ -118,6 +136,25 @@ def clear_texel(fmt, color=(0.0, 0.0, 0.0, 0.0), depth=1.0, stencil=0):
 def _coords(dst_n, src_n):
     scale = F32(src_n) / F32(dst_n)                       # one IEEE division on the host
     return (np.arange(dst_n).astype(F32) + F32(0.5)) * scale  # u = (i + 0.5) * scale: an add and a multiply, nothing fused
+
+
+def linear_coords(dst_n, src_n):
+    """x = u - 0.5: a subtraction of its own, not fused with the multiply of u"""
+    return _coords(dst_n, src_n) - F32(0.5)
+
+
+floor = np.floor  # step 3 and step 4: floor, not truncation (x is negative in the first texels of a magnifying blit)
+
+
+def mix(ar, a, b, t):
+    """the sampler's mixf; every tap is multiplied, a weight of 0 included (0 * inf is NaN)"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return ar.mixf(a, b, t)
+
+
+def bilinear(ar, t00, t10, t01, t11, wx, wy):
+    """rows first, then columns"""
+    return mix(ar, mix(ar, t00, t10, wx), mix(ar, t01, t11, wx), wy)
 
 
 def blit(src_raw, src_fmt, dst_w, dst_h, dst_fmt, filt, contract=2):
@@ -130,12 +167,12 @@ def blit(src_raw, src_fmt, dst_w, dst_h, dst_fmt, filt, contract=2):
         return src_raw.copy()
     img = decode(src_fmt, src_raw)
     if filt == NEAREST:
-        sx = np.clip(np.floor(u).astype(np.int64), 0, sw - 1)
-        sy = np.clip(np.floor(v).astype(np.int64), 0, sh - 1)
+        sx = np.clip(floor(u).astype(np.int64), 0, sw - 1)
+        sy = np.clip(floor(v).astype(np.int64), 0, sh - 1)
         return encode(dst_fmt, img[sy][:, sx])
     ar = Arith(contract)
-    xf, yf = u - F32(0.5), v - F32(0.5)
-    x0f, y0f = np.floor(xf), np.floor(yf)
+    xf, yf = linear_coords(dst_w, sw), linear_coords(dst_h, sh)
+    x0f, y0f = floor(xf), floor(yf)
     fx, fy = (xf - x0f).astype(F32), (yf - y0f).astype(F32)
     x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
     xa, xb = np.clip(x0, 0, sw - 1), np.clip(x0 + 1, 0, sw - 1)
@@ -143,24 +180,29 @@ def blit(src_raw, src_fmt, dst_w, dst_h, dst_fmt, filt, contract=2):
     t00, t10, t01, t11 = img[ya][:, xa], img[ya][:, xb], img[yb][:, xa], img[yb][:, xb]
     wx = np.broadcast_to(fx[None, :, None], t00.shape)
     wy = np.broadcast_to(fy[:, None, None], t00.shape)
-    top = ar.mixf(t00, t10, wx)   # mixf(a, b, t) = cfma(b, t, a * (1 - t)): the accumulation is the fused step
-    bot = ar.mixf(t01, t11, wx)
-    return encode(dst_fmt, ar.mixf(top, bot, wy))
+    # mixf(a, b, t) = cfma(b, t, a * (1 - t)): the accumulation is the fused step
+    return encode(dst_fmt, bilinear(ar, t00, t10, t01, t11, wx, wy))
 
 
 # ---- the mip chain --------------------------------------------------------------------------------------------------------
-def mip_level(fmt, src_raw):
-    """one level of the project's mip rule from the STORED previous level"""
-    src_raw = np.asarray(src_raw)
-    sh, sw = src_raw.shape[:2]
+def mip_taps(lin):
+    """the four taps a, b, c, d of every destination texel: (2X, 2Y), (x1, 2Y), (2X, y1), (x1, y1), x1 and y1 clamped to the edge"""
+    sh, sw = lin.shape[:2]
     dh, dw = max(1, sh // 2), max(1, sw // 2)
-    lin = decode(fmt, src_raw)
     y0, y1 = np.minimum(2 * np.arange(dh), sh - 1), np.minimum(2 * np.arange(dh) + 1, sh - 1)
     x0, x1 = np.minimum(2 * np.arange(dw), sw - 1), np.minimum(2 * np.arange(dw) + 1, sw - 1)
-    a, b, c, d = lin[y0][:, x0], lin[y0][:, x1], lin[y1][:, x0], lin[y1][:, x1]
+    return lin[y0][:, x0], lin[y0][:, x1], lin[y1][:, x0], lin[y1][:, x1]
+
+
+def avg4(a, b, c, d):
+    """((a + b) + (c + d)) * 0.25 in fp32, denormals kept"""
     with np.errstate(over="ignore", invalid="ignore"):
-        avg = ((a + b) + (c + d)) * F32(0.25)
-    return encode(fmt, avg)
+        return ((a + b) + (c + d)) * F32(0.25)
+
+
+def mip_level(fmt, src_raw):
+    """one level of the project's mip rule from the STORED previous level"""
+    return encode(fmt, avg4(*mip_taps(decode(fmt, np.asarray(src_raw)))))
 
 
 def mip_count(w, h):

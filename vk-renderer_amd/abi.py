@@ -537,7 +537,8 @@ def cubemap_probe(scene, pos, cube_color, cube_distance, scratch, scratch_bytes,
 
 def clear_image(img, color=(0.0, 0.0, 0.0, 0.0), depth=1.0, stencil=0, stream=None):
     """vkr_clear_image: every mip of the view `img` (VkrImg) to one value: `color` for colour formats (stored as the format
-    stores it), rint(depth * 16777215) | stencil << 24 for D24_UNORM_S8.  Raises RuntimeError with the library's message on a refusal."""
+    stores it), rint(clamp(depth, 0, 1) * 16777215) | stencil << 24 for D24_UNORM_S8 (a NaN depth stores 0).  Raises RuntimeError with
+    the library's message on a refusal."""
     lib = product()
     v = ClearValue((C.c_float * 4)(*[float(c) for c in color]), float(depth), int(stencil))
     check(lib.vkr_clear_image(C.byref(img), C.byref(v), stream), lib)

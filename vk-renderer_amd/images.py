@@ -23,8 +23,10 @@ def mip_extent(v, i):
 
 
 class ImageBuf:
-    def __init__(self, fmt, width, height, mips=1, device=None, full=None, origin=(0, 0), fill=0):
-        """width/height: extent of the window held in memory (mip 0); full: frame extent."""
+    def __init__(self, fmt, width, height, mips=1, device=None, full=None, origin=(0, 0), fill=0, row_align=ROW_ALIGN, guard=0):
+        """width/height: extent of the window held in memory (mip 0); full: frame extent.  row_align: what rows and mips are
+        aligned to (the C-ABI only asks for a pitch that is a multiple of the texel size and a base aligned to min(bpp, 4)).
+        guard: bytes allocated before and after the image, filled like it and never described: `guards()` returns them."""
         self.format = fmt
         self.width, self.height, self.mips = int(width), int(height), int(mips)
         self.full = (int(full[0]), int(full[1])) if full else (self.width, self.height)
@@ -33,22 +35,30 @@ class ImageBuf:
         self.pitch, self.offset = [], []
         off = 0
         for i in range(self.mips):
-            p = _align(mip_extent(self.width, i) * self.bpp, ROW_ALIGN)
+            p = _align(mip_extent(self.width, i) * self.bpp, row_align)
             self.pitch.append(p)
             self.offset.append(off)
-            off += _align(p * mip_extent(self.height, i), ROW_ALIGN)
+            off += _align(p * mip_extent(self.height, i), row_align)
         self.nbytes = off
         self.device = device
         if device is None:
-            self.host = np.full(self.nbytes, fill, dtype=np.uint8)
+            self._whole = np.full(guard + self.nbytes + guard, fill, dtype=np.uint8)
+            self.host = self._whole[guard: guard + self.nbytes]
             self.tensor = None
-            self.ptr = self.host.ctypes.data
+            self.ptr = self._whole.ctypes.data + guard
         else:
             import torch
 
-            self.tensor = torch.full((self.nbytes,), fill, dtype=torch.uint8, device=device)
+            self._whole = torch.full((guard + self.nbytes + guard,), fill, dtype=torch.uint8, device=device)
+            self.tensor = self._whole[guard: guard + self.nbytes]
             self.host = None
             self.ptr = self.tensor.data_ptr()
+
+    def guards(self):
+        """the guard bytes before and after the image, as one host array"""
+        whole = self._whole if self.host is not None else self._whole.cpu().numpy()
+        lead = (len(whole) - self.nbytes) // 2
+        return np.concatenate([whole[:lead], whole[lead + self.nbytes:]])
 
     # ---- descriptors ------------------------------------------------------------
     def desc(self, base_mip=0, mip_count=None):
