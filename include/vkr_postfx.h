@@ -629,6 +629,49 @@ typedef struct vkr_accel_hit { float t, u, v; uint32_t index; } vkr_accel_hit;  
 int vkr_accel_closest(const vkr_accel* accel, const float* origins, const float* dirs, float tmin, float tmax, uint32_t n,
                       vkr_accel_hit* out_hits, void* stream);
 
+/* ---- refit: moving geometry under the topology of vkr_accel_create (DESIGN_NUMERICS.md "Ray query: refit") ------
+ * The structure keeps the hierarchy the host builder chose; only the bytes that depend on vertex positions are recomputed, on the
+ * device, from tri_vertices (device, tri_count x 9 floats, in the order of the INPUT of vkr_accel_create; tri_count as created:
+ * triangles are neither added nor removed).  Every record slot keeps its place and its `index`; its v0, e1, e2, lo, hi become what
+ * vkr_accel_layout computes for triangle `index` of tri_vertices (the same operations in the same order, the margin
+ * (max |coordinate| + 1) * 2^-12).  Every node keeps `first` and `count`; a leaf's box becomes the union of its records' boxes, an
+ * interior node's the union of its two children's, both from +-inf with the builder's minimum / maximum, so a NaN bound never
+ * enters a node.  Boxes are recomputed on every call, never grown: what one pose put into them (a NaN, an infinity, a far vertex)
+ * is gone after the next.  Since every answer of the ray query is that of the frozen test over all triangles whatever the
+ * hierarchy, the refitted structure answers bit for bit like one created from tri_vertices; a walk may take longer where the old
+ * topology no longer fits the moved triangles (the escape is to create the structure again).
+ * Ordering: asynchronous on `stream`.  Queries (and passes that take the structure) submitted to the same stream after the call
+ * see the refitted structure, those submitted before it the earlier one; tri_vertices must stay valid and unchanged until the
+ * call's work has run.  Work on other streams that uses the structure is the caller's to order against the refit.
+ * An empty structure is a no-op; a NULL handle, or NULL vertices for a structure with triangles, is VKR_ERR_NULL.               */
+int vkr_accel_refit(vkr_accel* accel, const float* tri_vertices, void* stream);
+/* The same rule as a pure host function, no GPU: applied in place to the arrays of vkr_accel_layout (or of vkr_accel_download)
+ * from tri_vertices (host, tri_count x 9, input order).  A malformed topology — an interior node whose children are not stored
+ * behind it inside the array, a leaf whose record range or a record whose input index leaves the arrays — is refused with
+ * VKR_ERR_EXTENT before anything is written or read outside the arrays.                                                        */
+int vkr_accel_refit_layout(vkr_accel_node* nodes, uint32_t node_count, vkr_accel_tri* tris, uint32_t tri_count, const float* tri_vertices);
+/* For tests and tools: synchronises `stream`, then copies the device arrays into host arrays (vkr_accel_info gives the counts;
+ * a capacity below them is VKR_ERR_EXTENT).                                                                                     */
+int vkr_accel_download(const vkr_accel* accel, vkr_accel_node* nodes, uint32_t node_capacity, vkr_accel_tri* tris, uint32_t tri_capacity,
+                       void* stream);
+/* For tests and tools: how vkr_accel_refit walks the hierarchy.  level_sizes[h]: the number of nodes of height h (a leaf has
+ * height 0, an interior node 1 + the larger height of its children; at most 49 levels), *level_count their number (0 for an empty
+ * structure).  A refit is one launch over the records, one launch per level of more than *tail_nodes nodes (level sizes never
+ * grow with the height, so these are the first ones), and one single-workgroup launch for all remaining levels up to the root.  */
+int vkr_accel_refit_schedule(const vkr_accel* accel, uint32_t* level_sizes, uint32_t level_capacity, uint32_t* level_count, uint32_t* tail_nodes);
+/* The world-space triangles of a raster scene, on the device, as vkr_accel_create / vkr_accel_refit take them: draw by draw,
+ * index_count / 3 triangles per draw, vertex k of triangle j of a draw = vertices[indices[index_offset + 3 j + k] + vertex_offset]
+ * .pos, transformed by m = transforms[transform_index].model as ((m[0][r] x + m[1][r] y) + m[2][r] z) + m[3][r] per row r, every
+ * product and sum rounded on its own (no fused multiply-add under either numeric contract).  out_tri_vertices: device, room for
+ * out_tri_capacity triangles of 9 floats; scratch: device, vkr_scene_triangles_scratch_bytes(draw_count) (the draw table, which
+ * travels as kernel arguments: no host staging, nothing synchronises).  The gates of the rasterisers' scenes apply (NULL arrays,
+ * a draw outside the index or transform arrays); texture indices are not read.  A triangle with an index outside the vertex buffer
+ * gets three NaN vertices, so no ray hits it, and nothing is read outside the buffer.  Only pos, the
+ * indices, model and the four range fields of a draw are read.                                                                  */
+uint64_t vkr_scene_triangles_scratch_bytes(uint32_t draw_count);
+int vkr_scene_triangles(const vkr_raster_scene* scene, float* out_tri_vertices, uint64_t out_tri_capacity, void* scratch, uint64_t scratch_bytes,
+                        void* stream);
+
 /* program "reflections_rt" (no reference program): the `reflections` image of AdvancedSSR (RGBA8_UNORM, half resolution in the
  * frame) traced through the scene's ray-query structure: per pixel the mirror ray of the view direction, its closest hit, and the
  * albedo of the hit triangle there ("radiance = albedo at the hit", as ssr/filter.comp; alpha 0 as the filter stores it).  Where

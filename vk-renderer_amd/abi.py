@@ -441,6 +441,16 @@ def product():
         # and tests/reflections_rt_reference.py)
         lib.vkr_accel_closest.argtypes = lib.vkr_accel_query.argtypes
         lib.vkr_accel_closest.restype = C.c_int
+        # refit (checked against the numpy restatement tests/accel_refit_reference.py) and the scene's triangles on the device
+        lib.vkr_accel_refit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.vkr_accel_refit_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.vkr_accel_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.vkr_accel_refit_schedule.argtypes = [C.c_void_p, P(C.c_uint32), C.c_uint32, P(C.c_uint32), P(C.c_uint32)]
+        lib.vkr_scene_triangles_scratch_bytes.argtypes = [C.c_uint32]
+        lib.vkr_scene_triangles_scratch_bytes.restype = C.c_uint64
+        lib.vkr_scene_triangles.argtypes = [P(RasterScene), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        for name in ("accel_refit", "accel_refit_layout", "accel_download", "accel_refit_schedule", "scene_triangles"):
+            getattr(lib, "vkr_" + name).restype = C.c_int
         lib.vkr_reflections_rt_scratch_bytes.argtypes = [C.c_uint32]
         lib.vkr_reflections_rt_scratch_bytes.restype = C.c_uint64
         lib.vkr_reflections_rt.argtypes = [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ReflectRtParams), _IMG,
@@ -1018,6 +1028,43 @@ def accel_layout(triangles):
     return node_arr, tri_arr
 
 
+def accel_refit_layout(nodes, tris, triangles):
+    """vkr_accel_refit_layout on the host (no GPU): the arrays of accel_layout() (or Accel.download()) refitted to `triangles`
+    ((n, 3, 3) float32 in input order) -> (nodes, tris), new arrays; the arguments are left as they are.  Raises RuntimeError
+    where the library refuses the topology."""
+    import numpy as np
+
+    # any array of the records' bytes: the uint8 rows of accel_layout() or a structured view of them
+    node_arr = np.frombuffer(np.ascontiguousarray(nodes).tobytes(), dtype=np.uint8).reshape(-1, C.sizeof(AccelNode)).copy()
+    tri_arr = np.frombuffer(np.ascontiguousarray(tris).tobytes(), dtype=np.uint8).reshape(-1, C.sizeof(AccelTri)).copy()
+    tri = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    lib = product()
+    check(lib.vkr_accel_refit_layout(node_arr.ctypes.data if len(node_arr) else None, len(node_arr), tri_arr.ctypes.data if len(tri_arr) else None,
+                                     len(tri_arr), tri.ctypes.data if len(tri) else None), lib)
+    return node_arr, tri_arr
+
+
+def scene_triangles_scratch_bytes(draw_count):
+    """vkr_scene_triangles_scratch_bytes: the device scratch of one vkr_scene_triangles call (the draw table)"""
+    return int(product().vkr_scene_triangles_scratch_bytes(int(draw_count)))
+
+
+def scene_world_triangles(raster_scene, triangle_count, device="cuda", stream=None):
+    """vkr_scene_triangles: the world-space triangles of a RasterScene (scene.Scene.to_device()'s descriptor, or one a test made)
+    as a device tensor (triangle_count, 3, 3) float32 — scene_triangles() computed on the device, in its order.  A triangle with an
+    index outside the vertex buffer is three NaN vertices."""
+    import torch
+
+    out = torch.zeros((int(triangle_count), 3, 3), dtype=torch.float32, device=device)
+    nbytes = scene_triangles_scratch_bytes(raster_scene.draw_count)
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    lib = product()
+    check(lib.vkr_scene_triangles(C.byref(raster_scene), out.data_ptr(), int(triangle_count), scratch.data_ptr(), nbytes, stream), lib)
+    # the call is asynchronous; the scratch tensor may be released only once the stream has passed it
+    (torch.cuda.current_stream(out.device) if stream is None else torch.cuda.ExternalStream(stream)).synchronize()
+    return out
+
+
 class Accel:
     """vkr_accel_create / _destroy around world-space triangles ((n, 3, 3) float32, e.g. scene_triangles(sc))."""
 
@@ -1053,6 +1100,35 @@ class Accel:
         float32 bits and the index of the input triangle, 0xFFFFFFFF for a miss (numpy: accel_hit_dtype())"""
         n = int(origins.shape[0])
         check(self.lib.vkr_accel_closest(self.handle, origins.data_ptr(), dirs.data_ptr(), float(tmin), float(tmax), n, out.data_ptr(), stream), self.lib)
+
+    def refit(self, triangles, stream=None):
+        """vkr_accel_refit: triangles: device tensor (n, 3, 3) / (n, 9) float32, contiguous, n = info()[1], in the order of the
+        triangles this structure was created from.  Asynchronous on `stream`: what is queued there afterwards sees the new pose;
+        the tensor must stay alive and unchanged until then."""
+        import torch
+
+        tris = self.info()[1]
+        if tris and not (triangles.is_cuda and triangles.dtype == torch.float32 and triangles.is_contiguous() and triangles.numel() == 9 * tris):
+            raise ValueError(f"refit: a contiguous float32 device tensor of 9 floats for each of the structure's {tris} triangles")
+        check(self.lib.vkr_accel_refit(self.handle, triangles.data_ptr() if triangles is not None and tris else None, stream), self.lib)
+
+    def download(self, stream=None):
+        """vkr_accel_download (synchronises `stream`): -> (nodes, tris) as accel_layout() returns them"""
+        import numpy as np
+
+        n, t = self.info()
+        nodes = np.zeros((n, C.sizeof(AccelNode)), np.uint8)
+        tris = np.zeros((t, C.sizeof(AccelTri)), np.uint8)
+        check(self.lib.vkr_accel_download(self.handle, nodes.ctypes.data if n else None, n, tris.ctypes.data if t else None, t, stream), self.lib)
+        return nodes, tris
+
+    def refit_schedule(self):
+        """vkr_accel_refit_schedule: -> (level_sizes, tail_nodes): the number of nodes of every height and the size up to which a
+        level is left to the single-workgroup tail launch of refit()"""
+        sizes = (C.c_uint32 * 64)()
+        count, tail = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.vkr_accel_refit_schedule(self.handle, sizes, 64, C.byref(count), C.byref(tail)), self.lib)
+        return list(sizes[:count.value]), tail.value
 
     def close(self):
         if self.handle:

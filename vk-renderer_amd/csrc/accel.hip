@@ -5,7 +5,8 @@
 //
 // MI355X has no ray-tracing hardware, so the traversal is software.  The hierarchy is one level over world-space triangles
 // (an any-hit query of a static scene gains nothing from instancing); it is built once per scene on the host (binned SAH,
-// deterministic) and read-only on the device.
+// deterministic) and read-only for every query on the device.  accel_refit.hip moves it to new vertex positions under the same
+// topology; the record rule it shares with the build here is accel_record.hpp.
 //
 // Traversal: a wave of 64 rays walks the hierarchy TOGETHER, with scalar loads of nodes and triangles and the node order on a
 // per-wave stack in LDS (no private array: nothing goes to scratch).  gtao_rt_main runs one wave per pixel, one lane per
@@ -14,6 +15,7 @@
 // that of a brute-force loop over all triangles (tests/test_accel_gpu.py).
 #include "vkr_host.hpp"
 #include "accel_traverse.hpp"
+#include "accel_record.hpp"
 #include "gtao_slice.hpp"
 
 #include <algorithm>
@@ -188,21 +190,6 @@ struct Builder {
   }
 };
 
-// v: 9 floats of one triangle -> its record (everything the device test reads)
-static void make_record(const float* v, uint32_t index, vkr_accel_tri& r) {
-  float s = 0.0f;
-  for (int k = 0; k < 9; k++) s = std::max(s, std::fabs(v[k]));
-  const float margin = (s + 1.0f) * 0x1p-12f;
-  for (int k = 0; k < 3; k++) {
-    r.v0[k] = v[k];
-    r.e1[k] = v[3 + k] - v[k];
-    r.e2[k] = v[6 + k] - v[k];
-    r.lo[k] = std::min(std::min(v[k], v[3 + k]), v[6 + k]) - margin;
-    r.hi[k] = std::max(std::max(v[k], v[3 + k]), v[6 + k]) + margin;
-  }
-  r.index = index;
-}
-
 static int layout(const float* verts, uint32_t tri_count, std::vector<vkr_accel_node>& nodes, std::vector<vkr_accel_tri>& tris) {
   if (!verts && tri_count) { set_error("vkr_accel_layout: NULL triangles"); return VKR_ERR_NULL; }
   if (tri_count > (1u << 30)) { set_error("vkr_accel_layout: %u triangles, at most 2^30", tri_count); return VKR_ERR_EXTENT; }
@@ -260,6 +247,11 @@ extern "C" int vkr_accel_create(const float* tri_vertices, uint32_t tri_count, v
     if (e == hipSuccess) e = hipMalloc((void**)&a->tris, t.size() * sizeof(vkr_accel_tri));
     if (e == hipSuccess) e = hipMemcpy(a->nodes, n.data(), n.size() * sizeof(vkr_accel_node), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(a->tris, t.data(), t.size() * sizeof(vkr_accel_tri), hipMemcpyHostToDevice);
+    // the order in which vkr_accel_refit recomputes the node boxes: no query reads it
+    std::vector<uint32_t> order;
+    refit_schedule(n, &order, &a->level_begin);
+    if (e == hipSuccess) e = hipMalloc((void**)&a->order, order.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(a->order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   }
   if (e != hipSuccess) {
     set_error("vkr_accel_create: upload failed: %s", hipGetErrorString(e));
@@ -274,6 +266,7 @@ extern "C" int vkr_accel_destroy(vkr_accel* accel) {
   if (!accel) return VKR_OK;
   if (accel->nodes) (void)hipFree(accel->nodes);
   if (accel->tris) (void)hipFree(accel->tris);
+  if (accel->order) (void)hipFree(accel->order);
   delete accel;
   return VKR_OK;
 }

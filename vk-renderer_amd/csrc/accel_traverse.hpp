@@ -5,12 +5,17 @@
 #ifndef VKR_ACCEL_TRAVERSE_HPP
 #define VKR_ACCEL_TRAVERSE_HPP
 
+#include <vector>
+
 #include "vkr_host.hpp"
 
 struct vkr_accel {
   vkr_accel_node* nodes;  // device
   vkr_accel_tri* tris;    // device
   uint32_t node_count, tri_count;
+  // the refit schedule (accel_record.hpp: refit_schedule), made by vkr_accel_create and read by vkr_accel_refit alone
+  uint32_t* order = nullptr;          // device, node_count ids sorted by (height, id)
+  std::vector<uint32_t> level_begin;  // host: the nodes of height h are order[level_begin[h] .. level_begin[h + 1])
 };
 
 namespace vkr {

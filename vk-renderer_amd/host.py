@@ -164,6 +164,8 @@ def lib():
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
                            ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32]),
+                           # moving draws: the raster table and a refit of the ray-query structure (same rule)
+                           ("vkrh_set_draw_transforms", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
                            # the first refusal of every program of the table (same rule)
                            ("vkrh_selftest_programs", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):
@@ -315,6 +317,14 @@ class HostFrame:
                 tex[i].levels[m] = a.ctypes.data
         self._check(lib().vkrh_load_scene(self.h, C.c_void_p(verts.ctypes.data), len(verts), C.c_void_p(idx.ctypes.data), len(idx),
                                           draws, len(sc.draws), tex, len(sc.textures)))
+
+    def set_draw_transforms(self, models):
+        """vkrh_set_draw_transforms: one 4 x 4 model matrix (maths convention, as scene.Scene keeps them) per draw of the scene
+        given to load_scene, in its order — for a scene.Scene `sc`: [sc.transforms[d["transform"]][0] for d in sc.draws].  From the
+        next run() the raster, shadow-map and cube stages and every ray-traced stage see that pose (the ray-query structure is
+        refitted on the frame's stream, not rebuilt)."""
+        flat = np.ascontiguousarray(np.stack([np.asarray(m, dtype=np.float32).T for m in models]).reshape(-1), dtype=np.float32) if len(models) else np.zeros(0, np.float32)
+        self._check(lib().vkrh_set_draw_transforms(self.h, flat.ctypes.data_as(C.POINTER(C.c_float)), len(models)))
 
     def scene_texture(self, index):
         """vkrh_scene_texture_image: descriptor (every level) of texture `index` of the loaded scene"""

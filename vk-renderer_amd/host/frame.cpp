@@ -1518,6 +1518,20 @@ int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count,
   return guarded([&] { frame_ref(frame).set_shadow_area_lights(radii, count, sample_count, pattern_side); });
 }
 int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) { return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); }); }
+int vkrh_set_draw_transforms(void* frame, const float* transforms, uint32_t count) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    f->refuse_tiled("vkrh_set_draw_transforms", "the ray-traced stages run on one GPU");
+    if (!f->loaded_scene || !f->scene_renderer || !f->scene_as) throw std::runtime_error{"vkrh_set_draw_transforms: without a loaded scene (vkrh_load_scene)"};
+    auto& nodes = f->loaded_scene->base_nodes;  // one per draw of vkrh_load_scene, in its order (scene::make_scene)
+    if (count != nodes.size())
+      throw std::runtime_error{"vkrh_set_draw_transforms: " + std::to_string(count) + " transforms for the " + std::to_string(nodes.size()) + " draws of vkrh_load_scene"};
+    if (!transforms && count) throw std::runtime_error{"vkrh_set_draw_transforms: NULL argument"};
+    for (uint32_t i = 0; i < count; i++) std::memcpy((void*)&nodes[i].transform, transforms + 16 * size_t(i), 64);
+    f->scene_renderer->update_scene();
+    f->scene_as->refit(*f->loaded_scene, f->graph.get_stream());
+  });
+}
 
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
   return guarded([&] {

@@ -202,6 +202,15 @@ int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_off
  * without an alpha-0 texel are masked opaque from the scene's images.  Default: off, and a frame that never calls this or calls it
  * with enable == 0 records the opaque entries.  VKRH_STAGE_GTAO_RT stays opaque (rt_main.frag is).  Not on a tiled frame.          */
 int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod);
+/* Moves the draws of the loaded scene: transforms is count x 16 floats, one model matrix per draw of vkrh_load_scene in its order
+ * and layout (glm: column-major); count must be that draw count.  Writes the node transforms, then SceneRenderer::update_scene()
+ * (the table the raster, shadow-map and cube stages read) and SceneAccelerationStructure::refit() on the frame's stream
+ * (vkr_scene_triangles + vkr_accel_refit: no host build, no upload, no synchronisation).  From the next vkrh_run the raster,
+ * shadow-map and cube stages and every ray-traced stage see the same pose; images are those of a frame that loaded the scene
+ * already in that pose, byte for byte.  `velocity` stays camera-only; baked probes and rendered shadow maps stay as they are until
+ * they are rendered again.  Off unless called: no stage bit, no task in any frame.  Refused: without a loaded scene, with another
+ * count, on a tiled frame (the ray-traced stages run on one GPU).                                                              */
+int vkrh_set_draw_transforms(void* frame, const float* transforms, uint32_t count);
 /* Pins the 16 samples of VKRH_STAGE_SSAO (xyz: 16 x 3 floats) and their packing in the uniform block: std140 = 0 the reference's
  * (vec3 at a 12-byte stride in 272 bytes: the shader's sample i is floats [4i, 4i + 1, 4i + 2] of the flat array for i <= 11 and
  * zero for i = 12..15), std140 != 0 one 16-byte slot per sample in 336 bytes (SSAOPass::std140_samples).  Not on a tiled frame. */

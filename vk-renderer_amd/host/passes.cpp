@@ -11,6 +11,8 @@
 #include <functional>
 #include <stdexcept>
 
+#include <hip/hip_runtime_api.h>
+
 #include "pass_recorder.hpp"
 #include "probe_renderer.hpp"
 #include "scene/scene_as.hpp"
@@ -1273,6 +1275,62 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
   hit_attributes = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, std::max<uint64_t>(bytes, sizeof(vkr_hit_attrib)), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
   std::memset(hit_attributes->get_mapped_ptr(), 0, hit_attributes->get_size());  // an empty scene: one unused record (a buffer has no size 0)
   if (bytes) std::memcpy(hit_attributes->get_mapped_ptr(), world_attributes.data(), bytes);
+  refit_triangles.reset();  // another structure: the first refit() allocates for it
+  refit_scratch.reset();
+}
+
+void SceneAccelerationStructure::refit(const CompiledScene &source, void *stream) {
+  if (!tlas) throw std::runtime_error {"SceneAccelerationStructure::refit: no structure (build first)"};
+  std::vector<FlatNode> nodes;
+  for (const auto &node : source.base_nodes) flatten_nodes(nodes, node, glm::mat4 {1.f});
+  // the draw list in build_tlas() order, with a model matrix per node
+  std::vector<vkr_raster_transform> transforms(nodes.size());
+  std::vector<vkr_raster_draw> draws;
+  uint64_t triangles = 0;
+  for (size_t i = 0; i < nodes.size(); i++) {
+    if (size_t(nodes[i].mesh) >= source.root_meshes.size()) throw std::runtime_error {"SceneAccelerationStructure::refit: a node names a mesh the scene does not have"};
+    std::memcpy(transforms[i].model.m, &nodes[i].transform, sizeof(transforms[i].model.m));
+    std::memset(transforms[i].normal.m, 0, sizeof(transforms[i].normal.m));  // not read
+    for (const auto &prim : source.root_meshes[nodes[i].mesh].primitives) {
+      vkr_raster_draw d {};
+      d.transform_index = uint32_t(i);
+      d.albedo_index = d.mr_index = 0xFFFFFFFFu;
+      d.index_offset = prim.index_offset; d.index_count = prim.index_count; d.vertex_offset = prim.vertex_offset;
+      draws.push_back(d);
+      triangles += prim.index_count / 3u;
+    }
+  }
+  if (triangles != world_triangles.size() / 9)
+    throw std::runtime_error {"SceneAccelerationStructure::refit: the scene has " + std::to_string(triangles) + " triangles, the structure was built from " +
+                              std::to_string(world_triangles.size() / 9) + " (a refit moves triangles; build() again to add or remove some)"};
+  if (triangles == 0) return;
+  const uint64_t scratch_bytes = vkr_scene_triangles_scratch_bytes(uint32_t(draws.size()));
+  if (!refit_triangles) refit_triangles = gpu::create_buffer(VMA_MEMORY_USAGE_GPU_ONLY, sizeof(float) * 9 * triangles, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+  if (!refit_scratch || refit_scratch->get_size() < scratch_bytes) {
+    // an earlier refit() may still read the old table on the stream
+    if (refit_scratch && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) throw std::runtime_error {"SceneAccelerationStructure::refit: the stream is in error"};
+    refit_scratch = gpu::create_buffer(VMA_MEMORY_USAGE_GPU_ONLY, scratch_bytes, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+  }
+  vkr_raster_scene scene {};
+  scene.vertices = (const vkr_raster_vertex *)source.vertex_buffer->device_ptr(stream);
+  scene.vertex_count = uint32_t(source.vertex_buffer->get_size() / sizeof(vkr_raster_vertex));
+  scene.indices = (const uint32_t *)source.index_buffer->device_ptr(stream);
+  scene.index_count = uint32_t(source.index_buffer->get_size() / sizeof(uint32_t));
+  scene.transforms = transforms.data(); scene.transform_count = uint32_t(transforms.size());
+  scene.draws = draws.data(); scene.draw_count = uint32_t(draws.size());
+  float *moved = (float *)refit_triangles->device_ptr(stream);
+  if (vkr_scene_triangles(&scene, moved, triangles, refit_scratch->device_ptr(stream), scratch_bytes, stream) != 0 ||
+      vkr_accel_refit((vkr_accel *)tlas, moved, stream) != 0)
+    throw std::runtime_error {std::string {"SceneAccelerationStructure::refit: "} + vkr_last_error()};
+}
+
+std::vector<float> SceneAccelerationStructure::download_world_triangles(void *stream) {
+  if (!refit_triangles) return world_triangles;
+  std::vector<float> out(world_triangles.size());
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
+      hipMemcpy(out.data(), refit_triangles->device_ptr(stream), sizeof(float) * out.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error {"SceneAccelerationStructure::download_world_triangles: the copy failed"};
+  return out;
 }
 
 }  // namespace scene

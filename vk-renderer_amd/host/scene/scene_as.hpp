@@ -32,7 +32,19 @@ struct SceneAccelerationStructure {
 
   // object-space triangles of each mesh, in build_blas() order (9 floats per triangle)
   std::vector<std::vector<float>> blas_triangles;
-  // the world-space triangles build_tlas() put into the structure (9 floats per triangle)
+  // Moves the structure to the pose the node transforms of `source` have NOW, without building it again (vkr_accel_refit): the
+  // nodes are flattened as build_tlas() does, vkr_scene_triangles makes the world-space triangles on the device from source's
+  // vertex and index buffers (one draw per primitive, node by node, within a node the mesh's primitives in order: the order of
+  // build_tlas(); the model matrices travel in a table of the structure's own), and `tlas` is refitted to them, all on `stream`
+  // and without a synchronisation.  Only transforms may have changed since build(): another number of triangles is an error (the
+  // escape is build()).  hit_attributes is untouched: uvs and textures do not move.
+  void refit(const CompiledScene &source, void *stream);
+  // the triangles the structure holds on the device after the last refit(), 9 floats per triangle in the order of
+  // world_triangles (synchronises `stream`); before any refit() it is world_triangles
+  std::vector<float> download_world_triangles(void *stream);
+
+  // the world-space triangles build_tlas() put into the structure (9 floats per triangle).  They stay AS BUILT: refit() does not
+  // touch them (the moved ones exist on the device only; download_world_triangles() reads them back)
   std::vector<float> world_triangles;
   VkAccelerationStructureKHR tlas {nullptr};
 
@@ -44,6 +56,9 @@ struct SceneAccelerationStructure {
   std::vector<std::vector<vkr_hit_attrib>> blas_attributes;
   std::vector<vkr_hit_attrib> world_attributes;
   gpu::BufferPtr hit_attributes;
+
+  // refit(): the moved triangles and the draw table of vkr_scene_triangles, on the device, allocated by the first refit()
+  gpu::BufferPtr refit_triangles, refit_scratch;
 };
 
 }  // namespace scene
