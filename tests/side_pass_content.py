@@ -14,10 +14,10 @@ import numpy as np
 
 from vk_renderer_amd import abi
 from vk_renderer_amd import scene as scn
-from vk_renderer_amd.camera import FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 from vk_renderer_amd.images import ImageBuf
 
+import camera_cases as cc
 import gbuffer_content as content
 import gtao_rt_reference as gtao_ref
 import probe_reference as probe_ref
@@ -42,7 +42,7 @@ def _raster(size, depth_mip):
     is the extent of depth mip 1, the G-buffer (and the normal) has twice that"""
     w, h = size
     ew, eh = (w + (w & 1), h + (h & 1)) if depth_mip == 0 else (2 * w, 2 * h)
-    setup = FrameSetup(ew, eh)
+    setup = cc.frame_setup(size, ew, eh)  # the frozen camera, or the case an Extent names
     chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
     chain.raster(scn.procedural_scene(detail=RASTER_DETAIL))
     if depth_mip == 0:
@@ -60,7 +60,7 @@ class Gbuffer:
 
     def __init__(self, size, depth_mip=0):
         w, h = size
-        words, codes, self.setup = _raster(tuple(size), depth_mip)
+        words, codes, self.setup = _raster(size, depth_mip)
         self.depth = self.prev_depth = ImageBuf(abi.FMT_D24_UNORM_S8, w, h)
         self.normal = ImageBuf(abi.FMT_RG16_UNORM, codes.shape[1], codes.shape[0])
         self.depth.set_raw(words.reshape(h, w, 1))

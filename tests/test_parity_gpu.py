@@ -405,14 +405,20 @@ def test_defered_shading(size, oracle_lib):
 def test_host_mirror_frame_with_shading(size, oracle_lib):
     """The C++ host mirror (rendergraph + pass structs, host/frame.cpp) drives the whole frame including the
     deferred-shading composite; every output must match the oracle driven through the flat Python chain."""
+    from vk_renderer_amd.camera import FrameSetup
+
+    host_frame_with_shading(FrameSetup(*size))
+
+
+def host_frame_with_shading(setup, tag="host"):
+    """the body of test_host_mirror_frame_with_shading under any FrameSetup (tests/test_camera_cases_gpu.py runs it under other
+    cameras) -> {image: texels outside tolerance}"""
     import torch
 
     from vk_renderer_amd import host
-    from vk_renderer_amd.camera import FrameSetup
     from parity import mismatches
 
-    W, H = size
-    setup = FrameSetup(W, H)
+    W, H = setup.width, setup.height
     frame = host.HostFrame(setup, device="cuda")
     frame.run(host.STAGE_LUT | host.STAGE_BRDF_LUT | host.STAGE_GBUFFER | host.STAGE_PREV_DEPTH)
     ref = PostFxChain(W, H, backend="oracle", setup=setup)
@@ -431,10 +437,13 @@ def test_host_mirror_frame_with_shading(size, oracle_lib):
     torch.cuda.synchronize()
     assert frame.last_tasks() == ["DownsampleGbuffer", "DownsampleDepth", "SSSR_trace", "SSSR_filter", "SSSR_blur", "GTAO_main",
                                   "GTAO_filter", "GTAO_accumulate", "DeferedShading", "TAA"]
+    counts = {}
     for hname, rimg in (("color_out", ref.color_out), ("taa_hist", ref.taa_hist), ("acc_hist", ref.acc_hist),
                         ("blurred_hist", ref.blurred_hist), ("rays", ref.rays), ("brdf", ref.brdf)):
         got = frame.download(hname)
         bad = int(mismatches(rimg.format, got.decode(0), rimg.decode(0)).sum())
-        print(f"[parity] host {hname:13s} outside-tol {bad}")
+        print(f"[parity] {tag} {hname:13s} outside-tol {bad}")
         assert bad <= 8, f"host frame {hname}: {bad} texels outside tolerance (measured: 0)"
+        counts[hname] = bad
     frame.close()
+    return counts

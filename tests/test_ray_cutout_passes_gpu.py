@@ -17,6 +17,7 @@ from vk_renderer_amd.camera import FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 from vk_renderer_amd.images import ImageBuf
 
+import camera_cases as cc
 import gbuffer_content as content
 import ray_cutout_reference as ref
 
@@ -73,7 +74,7 @@ def _accel():
 def _raster(size):
     w, h = size
     ew, eh = w + (w & 1), h + (h & 1)
-    setup = FrameSetup(ew, eh)
+    setup = cc.frame_setup(size, ew, eh)  # the frozen camera, or the case an Extent names
     chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
     chain.raster(_scene()[0])
     return chain.depth.raw(0)[:h, :w, 0].astype(np.uint32), chain.normal.raw(0)[:h, :w].copy(), setup

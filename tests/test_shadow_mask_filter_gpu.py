@@ -19,6 +19,7 @@ from vk_renderer_amd.camera import LIGHT_POS, FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 from vk_renderer_amd.images import ImageBuf
 
+import camera_cases as cc
 import gbuffer_content as content
 import shadow_light as sl
 import shadow_mask_filter_cases as cases
@@ -65,7 +66,7 @@ def _raster(size):
     """the procedural scene through the oracle's rasteriser at the next even extent, cut to size (as tests/test_shadow_mask_rt_soft_gpu.py)"""
     w, h = size
     ew, eh = w + (w & 1), h + (h & 1)
-    setup = FrameSetup(ew, eh)
+    setup = cc.frame_setup(size, ew, eh)  # the frozen camera, or the case an Extent names
     chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
     chain.raster(_scene()[0])
     return chain.depth.raw(0)[:h, :w, 0].astype(np.uint32), chain.normal.raw(0)[:h, :w].copy(), setup

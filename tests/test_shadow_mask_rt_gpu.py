@@ -17,6 +17,7 @@ from vk_renderer_amd.camera import LIGHT_POS, FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 from vk_renderer_amd.images import ImageBuf
 
+import camera_cases as cc
 import gbuffer_content as content
 import shadow_mask_rt_reference as ref
 
@@ -63,7 +64,7 @@ def _raster(size):
     even extent (the flat chain driver only takes those), cut to size"""
     w, h = size
     ew, eh = w + (w & 1), h + (h & 1)
-    setup = FrameSetup(ew, eh)
+    setup = cc.frame_setup(size, ew, eh)  # the frozen camera, or the case an Extent names
     chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
     chain.raster(_scene()[0])
     return chain.depth.raw(0)[:h, :w, 0].astype(np.uint32), chain.normal.raw(0)[:h, :w].copy(), setup

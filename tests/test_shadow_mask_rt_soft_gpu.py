@@ -22,6 +22,7 @@ from vk_renderer_amd.camera import LIGHT_POS, FrameSetup
 from vk_renderer_amd.chain import PostFxChain
 from vk_renderer_amd.images import ImageBuf
 
+import camera_cases as cc
 import gbuffer_content as content
 import shadow_mask_rt_reference as hard_ref
 import shadow_mask_rt_soft_reference as ref
@@ -81,7 +82,7 @@ def _raster(size, cutout=False):
     """the procedural scene through the oracle's rasteriser at the next even extent, cut to size"""
     w, h = size
     ew, eh = w + (w & 1), h + (h & 1)
-    setup = FrameSetup(ew, eh)
+    setup = cc.frame_setup(size, ew, eh)  # the frozen camera, or the case an Extent names
     chain = PostFxChain(ew, eh, backend="oracle", setup=setup)
     chain.raster(_scene(cutout)[0])
     return chain.depth.raw(0)[:h, :w, 0].astype(np.uint32), chain.normal.raw(0)[:h, :w].copy(), setup

@@ -55,6 +55,18 @@ def camera_view(pos, yaw_deg=90.0, pitch_deg=0.0, world_up=(0.0, -1.0, 0.0)):
     return look_at_rh(pos, pos + f, up)
 
 
+def rolled_view(pos, yaw_deg=90.0, pitch_deg=0.0, roll_deg=0.0):
+    """Rz(roll) * camera_view(pos, yaw, pitch): the camera turned about its own view axis.  roll 0 is camera_view itself, to the
+    bit (the product with the identity would turn its -0.0 entries into +0.0)."""
+    v = camera_view(pos, yaw_deg, pitch_deg)
+    if roll_deg == 0.0:
+        return v
+    c, s = math.cos(math.radians(roll_deg)), math.sin(math.radians(roll_deg))
+    r = np.eye(4, dtype=np.float64)
+    r[0, 0], r[0, 1], r[1, 0], r[1, 1] = c, -s, s, c
+    return r @ v
+
+
 LIGHT_POS = (-1.85867, 5.81832, -0.247114)  # main.cpp:295; LIGHT_POS of defered_shading/shader.frag
 
 
@@ -107,7 +119,10 @@ class FrameSetup:
     angle_offset = 60/360, weight_ratio 1, max_roughness 1, render_flags 7, accumulate 1."""
 
     def __init__(self, width, height, frame_random=0, use_mis=1, eye=(0.0, 1.0, -1.0), yaw=90.0,
-                 prev_delta=(0.02, 0.0, 0.01), prev_yaw_delta=0.2, material="flat"):
+                 prev_delta=(0.02, 0.0, 0.01), prev_yaw_delta=0.2, material="flat", *, fovy=FOVY, znear=ZNEAR, zfar=ZFAR,
+                 pitch=0.0, roll=0.0, aspect=None, prev_pitch_delta=0.0, prev_roll_delta=0.0):
+        """fovy in radians; yaw, pitch, roll and their previous-frame deltas in degrees.  view = Rz(roll) * camera_view(eye, yaw,
+        pitch): the roll turns the picture about the view axis.  aspect None: width / height."""
         self.width, self.height = width, height
         # "flat": one roughness per object (the frozen scene of SURVEY 8(d)); "textured": per-texel roughness
         # (VKR_SYNTH_TEXTURED_ROUGHNESS, include/vkr_postfx.h)
@@ -115,15 +130,16 @@ class FrameSetup:
             raise ValueError(f"material {material!r}: 'flat' or 'textured'")
         self.material = material
         self.synth_flags = abi.SYNTH_TEXTURED_ROUGHNESS if material == "textured" else 0
-        self.aspect = float(width) / float(height)
+        self.aspect = float(width) / float(height) if aspect is None else float(aspect)
         # glm computes in float32; here every *input* matrix is rounded to float32 first and every
         # derived matrix is evaluated in float64 from those and rounded once (host/glm_compat.hpp does
-        # the same), so the Python and the C++ host layers hand bit-identical uniforms to the kernels.
+        # the same), so the Python and the C++ host layers hand bit-identical uniforms to the kernels (the inverses up to the
+        # entries that are zero in exact arithmetic, where LU and cofactors leave different residues: tests/test_camera_cases.py).
         f32 = lambda m: np.asarray(m, dtype=np.float32).astype(np.float64)
-        self.proj = f32(perspective_rh_zo(FOVY, self.aspect, ZNEAR, ZFAR))
-        self.view = f32(camera_view(eye, yaw))
+        self.proj = f32(perspective_rh_zo(fovy, self.aspect, znear, zfar))
+        self.view = f32(rolled_view(eye, yaw, pitch, roll))
         peye = tuple(e + d for e, d in zip(eye, prev_delta))
-        self.prev_view = f32(camera_view(peye, yaw + prev_yaw_delta))
+        self.prev_view = f32(rolled_view(peye, yaw + prev_yaw_delta, pitch + prev_pitch_delta, roll + prev_roll_delta))
         self.mvp = f32(self.proj @ self.view)
         self.prev_mvp = f32(self.proj @ self.prev_view)
         self.inv_view = f32(np.linalg.inv(self.view))
@@ -132,7 +148,7 @@ class FrameSetup:
         self.prev_normal_mat = self.prev_inv_view.T
         self.frame_random = frame_random
         self.use_mis = use_mis
-        self.fazz = (np.float32(FOVY), np.float32(self.aspect), np.float32(ZNEAR), np.float32(ZFAR))
+        self.fazz = (np.float32(fovy), np.float32(self.aspect), np.float32(znear), np.float32(zfar))
 
     def _fazz4(self):
         return (C.c_float * 4)(*[float(v) for v in self.fazz])

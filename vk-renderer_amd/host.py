@@ -166,6 +166,8 @@ def lib():
                            ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32]),
                            # moving draws: the raster table and a refit of the ray-query structure (same rule)
                            ("vkrh_set_draw_transforms", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
+                           # the matrices derived from the camera (same rule)
+                           ("vkrh_camera_matrices", [C.c_void_p, C.POINTER(C.c_float)]),
                            # the first refusal of every program of the table (same rule)
                            ("vkrh_selftest_programs", [C.c_char_p, C.c_uint32])):
             if hasattr(l, name):

@@ -1542,6 +1542,17 @@ int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out) {
     std::memcpy(out, &p, sizeof(*out));
   });
 }
+int vkrh_camera_matrices(void* frame, float* out48) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    if (!f || !out48) throw std::runtime_error{"NULL argument"};
+    if (!f->has_camera) throw std::runtime_error{"vkrh_camera_matrices: camera not set"};
+    // nothing is evaluated here that the frame does not hand on: the two products are set_camera's, stored in the block every
+    // pass reads; the inverse is the one gtao_rt_params() gives the ray-traced stages
+    const glm::mat4 held[3] = {f->draw_params.mvp, f->draw_params.prev_mvp, f->gtao_rt_params().camera_to_world};
+    std::memcpy(out48, held, sizeof(held));
+  });
+}
 int vkrh_gtao_directions(float* out, uint32_t count) {
   return guarded([&] {
     if (!out && count) throw std::runtime_error{"NULL argument"};

@@ -239,6 +239,9 @@ int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, u
 int vkrh_selftest_texdraw(char* buf, uint32_t buf_size);
 /* GTAORTParams the frame hands to VKRH_STAGE_GTAO_RT for the current camera: camera_to_world = inverse(view) (main.cpp:369-371) */
 int vkrh_gtao_rt_params(void* frame, vkr_gtao_rt_params* out);
+/* The camera matrices the frame holds after vkrh_set_camera, 3 x 16 floats in glm layout: projection * view and projection *
+ * prev_view as stored in the block its passes read, and the inverse(view) of vkrh_gtao_rt_params.  No GPU is touched. */
+int vkrh_camera_matrices(void* frame, float* out48);
 /* the first `count` random directions of GTAO's ray-query pass (gtao.cpp:415-443), 4 floats each; no GPU is touched */
 int vkrh_gtao_directions(float* out, uint32_t count);
 /* the ray-query cases of the host mirror's error paths (no kernel is launched; writes "case: message" lines into buf) */
