@@ -1021,7 +1021,7 @@ int vkr_hit_scatter(const vkr_img* frame_albedo, const vkr_img* frame_normals, c
                     uint32_t count, void* stream);
 
 /* Measurement switches — the library's only process-wide state.  The environment (VKR_BLUR_NO_SKIP, VKR_FILTER_NO_SKIP,
- * VKR_TAA_GENERIC, VKR_SHADING_GENERIC, VKR_BLUR_GENERIC, VKR_BLUR_LANE_LOOPS, VKR_TRACE_ONE_LAUNCH, VKR_MIPS_PER_LEVEL, VKR_MIPS_FUSED) is read once, at the first launch that asks; afterwards only vkr_set_switches
+ * VKR_TAA_GENERIC, VKR_SHADING_GENERIC, VKR_BLUR_GENERIC, VKR_BLUR_LANE_LOOPS, VKR_TRACE_ONE_LAUNCH, VKR_MIPS_PER_LEVEL, VKR_MIPS_FUSED, VKR_BLUR_NO_FLAT, VKR_BLUR_COUNT_PATHS) is read once, at the first launch that asks; afterwards only vkr_set_switches
  * changes them.  NO_SKIP: evaluate every tap of the blur / filter even in tiles without a reflection / hit (a
  * content-independent time; the stored texels are the same wherever every weight is finite).  GENERIC: the TAA /
  * shading instantiations that do not assume equal window layouts.                                                  */
@@ -1035,8 +1035,14 @@ int vkr_hit_scatter(const vkr_img* frame_albedo, const vkr_img* frame_normals, c
                                           * head + resume (vkr_sssr_trace_split); the library's entries do what their names say either way */
 #define VKR_SWITCH_MIPS_PER_LEVEL 128u /* vkr_gen_mipmaps: one launch per level ... */
 #define VKR_SWITCH_MIPS_FUSED     256u /* ... or the fused tiles, whatever the default is (per level wins if both are set); same bytes */
+#define VKR_SWITCH_BLUR_NO_FLAT   512u /* blur tiles whose staged normals are one RG16 code on the per-tap normal weight, like every other tile (BLUR_GENERIC implies it) */
+#define VKR_SWITCH_BLUR_COUNT_PATHS 1024u /* every blur block adds itself to the counters vkr_debug_blur_paths reads (one atomic per block; off: none) */
 uint32_t vkr_get_switches(void);
 void vkr_set_switches(uint32_t mask);
+/* Blocks of the blur launches since the last reset that ran with VKR_SWITCH_BLUR_COUNT_PATHS: out[0] empty tiles (skipped), [1] lit
+ * tiles whose staged normals are one code ("flat"), [2] the other lit tiles, [3] blocks with at least one wave on a
+ * constant-normal-weight tap loop.  Waits for the device; reset != 0 zeroes the counters afterwards.                        */
+int vkr_debug_blur_paths(uint32_t out[4], int reset);
 
 /* float4 streaming-read microbenchmark: the measured-roofline denominator of
  * SURVEY.md 8(d).  Reads `bytes` from `src`, writes one float per block to `sink`.      */

@@ -413,6 +413,8 @@ def product():
         lib.vkr_get_switches.restype = C.c_uint32
         lib.vkr_set_switches.argtypes = [C.c_uint32]
         lib.vkr_set_switches.restype = None
+        lib.vkr_debug_blur_paths.argtypes = [P(C.c_uint32), C.c_int]
+        lib.vkr_debug_blur_paths.restype = C.c_int
         lib.vkr_comm_available.restype = C.c_int
         lib.vkr_copy_rects.restype = C.c_int
         lib.vkr_sssr_trace_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
@@ -905,6 +907,16 @@ COMM_ID_BYTES = 128
 # measurement switches (include/vkr_postfx.h VKR_SWITCH_*): vkr_get_switches / vkr_set_switches
 SWITCH_BLUR_NO_SKIP, SWITCH_FILTER_NO_SKIP, SWITCH_TAA_GENERIC, SWITCH_SHADING_GENERIC, SWITCH_BLUR_GENERIC, SWITCH_TRACE_ONE_LAUNCH, SWITCH_BLUR_LANE_LOOPS = 1, 2, 4, 8, 16, 32, 64
 SWITCH_MIPS_PER_LEVEL, SWITCH_MIPS_FUSED = 128, 256  # vkr_gen_mipmaps: force one launch per level / the fused tiles (same bytes)
+SWITCH_BLUR_NO_FLAT, SWITCH_BLUR_COUNT_PATHS = 512, 1024  # the blur without its constant-normal-weight loops / counting blocks per path
+
+
+def debug_blur_paths(reset=True):
+    """vkr_debug_blur_paths: (empty, lit flat, lit not flat, blocks with a wave on a flat loop) counted by the blur launches that
+    ran with SWITCH_BLUR_COUNT_PATHS since the last reset."""
+    lib = product()
+    out = (C.c_uint32 * 4)()
+    check(lib.vkr_debug_blur_paths(out, 1 if reset else 0), lib)
+    return tuple(int(v) for v in out)
 
 
 class Comm:

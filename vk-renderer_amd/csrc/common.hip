@@ -31,6 +31,8 @@ uint32_t switches() {
     if (getenv("VKR_BLUR_LANE_LOOPS")) v |= VKR_SWITCH_BLUR_LANE_LOOPS;
     if (getenv("VKR_MIPS_PER_LEVEL")) v |= VKR_SWITCH_MIPS_PER_LEVEL;
     if (getenv("VKR_MIPS_FUSED")) v |= VKR_SWITCH_MIPS_FUSED;
+    if (getenv("VKR_BLUR_NO_FLAT")) v |= VKR_SWITCH_BLUR_NO_FLAT;
+    if (getenv("VKR_BLUR_COUNT_PATHS")) v |= VKR_SWITCH_BLUR_COUNT_PATHS;
     uint32_t expected = 0x80000000u;
     if (!g_switches.compare_exchange_strong(expected, v)) v = expected;
   }

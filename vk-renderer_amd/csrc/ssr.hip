@@ -606,6 +606,8 @@ struct BlurArgs {
   uint32_t skip_empty_tiles;  // 1: a tile whose staged reflections are all black skips its taps (the sums are exactly 0)
   uint32_t uniform_sigma_path;  // 1: waves whose pixels share one sigma take blur_uniform_sigma
   uint32_t rows_path;           // 1: every other wave takes blur_rows (0: the per-lane loops, VKR_SWITCH_BLUR_LANE_LOOPS)
+  uint32_t flat_path;           // 1: tiles whose staged normals are one RG16 code take the constant-normal-weight tap loops (0: VKR_SWITCH_BLUR_NO_FLAT)
+  uint32_t count_paths;         // 1: every block adds itself to g_blur_paths (VKR_SWITCH_BLUR_COUNT_PATHS)
 };
 
 // Tile geometry of the blur: a block resolves BLUR_BX x BLUR_BY pixels and stages the pixels within
@@ -658,6 +660,13 @@ __device__ unsigned long long g_blur_stamps[65536 * 8];
 #define VKR_STAMP(slot) do {} while (0)
 #define VKR_STAMP_VALUE(slot, v) do {} while (0)
 #endif
+
+// VKR_SWITCH_BLUR_COUNT_PATHS: blocks per kind — [0] empty tiles, [1] lit tiles whose normals are one code, [2] the other lit tiles,
+// [3] blocks with at least one wave on a constant-normal-weight loop — each on a 128-byte line of its own (counters that share a
+// line serialise).  vkr_debug_blur_paths reads them.
+#define BLUR_PATH_STRIDE 32
+__device__ uint32_t g_blur_paths[4 * BLUR_PATH_STRIDE];
+VKR_DEV void blur_count_path(int kind) { __hip_atomic_fetch_add(&g_blur_paths[kind * BLUR_PATH_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // A staged pixel is ONE 16-byte record, so a tap is one ds_read_b128: {normal.x, normal.y, normal.z, depth} as floats, with the low
 // mantissa byte of the three normal components replaced by the R, G, B codes of the reflection texel.  v_cvt_f32_ubyte0 reads a
@@ -719,12 +728,24 @@ template <bool SWAP> VKR_DEV v2f pk_mul_rows(v2f a, v2f p) {
   return r;
 }
 
-template <int R> VKR_DEV void blur_uniform_sigma(const uint4* s_px, const BlurCentre* c, f4& accA, f4& accB) {
+//
+// FLAT (every staged normal of the tile is one RG16 code, blur_tile): the normal weight of a pixel is the one number nw0 =
+// clamp(dot(centre normal, decode(code))) at all of its taps, so it is multiplied into the row factors once per thread — T[k] =
+// {nw0_A E(k), nw0_B E(k)}, the same R + 1 register pairs, per thread instead of per wave — and a tap pair drops the four
+// packed instructions of the normal weight: kdz, the two |kdz| FMAs (which read the halves T[|s|].x, T[|s - 1|].y directly: no
+// packed multiply, hence no operand selectors), the three byte converts, the four accumulator ops.  The unpaired end rows skip
+// the half whose factor is 0.
+template <int R, bool FLAT> VKR_DEV void blur_uniform_sigma(const uint4* s_px, const BlurCentre* c, v2f nw0, f4& accA, f4& accB) {
   const float nie = c[0].neg_inv_e_log2, g = c[0].g;  // the same in every lane and for both pixels
   v2f P[R + 1];
 #pragma unroll
   for (int k = 0; k <= R; k++)
     P[k] = (v2f){__builtin_amdgcn_exp2f((float)(k * k) * nie), k < R ? __builtin_amdgcn_exp2f((float)((k + 1) * (k + 1)) * nie) : 0.0f};
+  v2f T[R + 1];
+  if (FLAT) {
+#pragma unroll
+    for (int k = 0; k <= R; k++) T[k] = nw0 * splat2(__builtin_amdgcn_exp2f((float)(k * k) * nie));
+  }
   const v2f cnx = {c[0].normal.x, c[1].normal.x}, cny = {c[0].normal.y, c[1].normal.y}, cnz = {c[0].normal.z, c[1].normal.z};
   const v2f kb = {c[0].k_bilateral, c[1].k_bilateral};
   const v2f kcd = kb * (v2f){c[0].depth, c[1].depth};
@@ -743,19 +764,31 @@ template <int R> VKR_DEV void blur_uniform_sigma(const uint4* s_px, const BlurCe
       const uint4 p = ahead[(s + R) % BLUR_AHEAD];
       if (s + R + BLUR_AHEAD <= 2 * R + 1) ahead[(s + R) % BLUR_AHEAD] = lds_load4(col + (s + R + BLUR_AHEAD) * BLUR_TW);
       const v2f nzw = {__uint_as_float(p.z), __uint_as_float(p.w)};
-      const v2f nxy = __builtin_elementwise_fma(cny, splat2(__uint_as_float(p.y)), cnx * splat2(__uint_as_float(p.x)));
-      v2f nw, kdz;
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] clamp" : "=v"(nw) : "v"(cnz), "v"(nzw), "v"(nxy));
+      v2f kdz, tw;
       asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]"
           : "=v"(kdz) : "v"(kb), "v"(nzw), "v"(kcd));
-      const v2f tw = s >= 1 ? pk_mul_rows<true>(nw, P[s >= 1 ? s - 1 : 0]) : pk_mul_rows<false>(nw, P[s >= 1 ? 0 : -s]);
+      if (FLAT) {
+        const int ja = s < 0 ? -s : s, jb = s < 1 ? 1 - s : s - 1;  // row s of A is row s - 1 of B
+        tw = (v2f){ja <= R ? T[ja <= R ? ja : 0].x : 0.0f, jb <= R ? T[jb <= R ? jb : 0].y : 0.0f};
+      } else {
+        const v2f nxy = __builtin_elementwise_fma(cny, splat2(__uint_as_float(p.y)), cnx * splat2(__uint_as_float(p.x)));
+        v2f nw;
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] clamp" : "=v"(nw) : "v"(cnz), "v"(nzw), "v"(nxy));
+        tw = s >= 1 ? pk_mul_rows<true>(nw, P[s >= 1 ? s - 1 : 0]) : pk_mul_rows<false>(nw, P[s >= 1 ? 0 : -s]);
+      }
       v2f w;
       w.x = __builtin_fminf(__builtin_fmaxf(__builtin_fmaf(-__builtin_fabsf(kdz.x), tw.x, tw.x), 0.0f), 1.0f);
       w.y = __builtin_fminf(__builtin_fmaxf(__builtin_fmaf(-__builtin_fabsf(kdz.y), tw.y, tw.y), 0.0f), 1.0f);
+      // The end rows' outer half is beyond the radius: its factor is the literal 0 above and the clamp already makes the weight 0
+      // (also for a NaN kdz).  Writing the 0 lets the compiler drop that half's FMA, which it may not fold itself (0 * NaN).
+      if (FLAT && s == -R) w.y = 0.0f;     // row -R - 1 of B
+      if (FLAT && s == R + 1) w.x = 0.0f;  // row R + 1 of A
       col_r = __builtin_elementwise_fma(w, splat2((float)(p.x & 0xFFu)), col_r);
       col_g = __builtin_elementwise_fma(w, splat2((float)(p.y & 0xFFu)), col_g);
       col_b = __builtin_elementwise_fma(w, splat2((float)(p.z & 0xFFu)), col_b);
       col_w += w;
+      // without the normal weight's chain the scheduler would pull every read of the column to its top and spill the table
+      if (FLAT) __builtin_amdgcn_sched_barrier(0);
     }
     const v2f e2 = splat2(ei);
     acc_r = __builtin_elementwise_fma(e2, col_r, acc_r);
@@ -778,7 +811,10 @@ template <int R> VKR_DEV void blur_uniform_sigma(const uint4* s_px, const BlurCe
 // diverges.  Replaces the per-lane loops of rounds 1-3 (11 VALU instructions per pixel-tap on divergent trip counts, pairs of
 // different radius resolved one pixel at a time) where a wave does not share one sigma: 7 per pixel-tap.  Per pixel the taps and
 // weights are the shader's; the sums are formed row by row.
-template <int R> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, bool has_b, f4& accA, f4& accB) {
+//
+// FLAT (see blur_uniform_sigma): the pixel's one normal weight nw0 is folded into its column factors, C[k] = {nw0_A E_A(k),
+// nw0_B E_B(k)}, and a tap reads its pair as it is.
+template <int R, bool FLAT> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, bool has_b, v2f nw0, f4& accA, f4& accB) {
   const int rA = c[0].r, rB = has_b ? c[1].r : -1;
   const v2f nie = {c[0].neg_inv_e_log2, c[1].neg_inv_e_log2};
   v2f C[R + 1];
@@ -786,6 +822,7 @@ template <int R> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, 
   for (int k = 0; k <= R; k++) {
     const v2f e = exp2_2((float)(k * k) * nie);
     C[k] = (v2f){k <= rA ? e.x : 0.0f, k <= rB ? e.y : 0.0f};
+    if (FLAT) C[k] = nw0 * C[k];
   }
   const v2f cnx = {c[0].normal.x, c[1].normal.x}, cny = {c[0].normal.y, c[1].normal.y}, cnz = {c[0].normal.z, c[1].normal.z};
   const v2f kb = {c[0].k_bilateral, c[1].k_bilateral};
@@ -807,12 +844,17 @@ template <int R> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, 
       const uint4 p = ahead[(i + R) % BLUR_AHEAD];
       if (i + R + BLUR_AHEAD <= 2 * R) ahead[(i + R) % BLUR_AHEAD] = lds_load4(row + (i + R + BLUR_AHEAD));
       const v2f nzw = {__uint_as_float(p.z), __uint_as_float(p.w)};
-      const v2f nxy = __builtin_elementwise_fma(cny, splat2(__uint_as_float(p.y)), cnx * splat2(__uint_as_float(p.x)));
-      v2f nw, kdz;
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] clamp" : "=v"(nw) : "v"(cnz), "v"(nzw), "v"(nxy));
+      v2f kdz, tw;
       asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]"
           : "=v"(kdz) : "v"(kb), "v"(nzw), "v"(kcd));
-      const v2f tw = nw * C[i < 0 ? -i : i];
+      if (FLAT) {
+        tw = C[i < 0 ? -i : i];
+      } else {
+        const v2f nxy = __builtin_elementwise_fma(cny, splat2(__uint_as_float(p.y)), cnx * splat2(__uint_as_float(p.x)));
+        v2f nw;
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] clamp" : "=v"(nw) : "v"(cnz), "v"(nzw), "v"(nxy));
+        tw = nw * C[i < 0 ? -i : i];
+      }
       v2f w;
       w.x = __builtin_fminf(__builtin_fmaxf(__builtin_fmaf(-__builtin_fabsf(kdz.x), tw.x, tw.x), 0.0f), 1.0f);
       w.y = __builtin_fminf(__builtin_fmaxf(__builtin_fmaf(-__builtin_fabsf(kdz.y), tw.y, tw.y), 0.0f), 1.0f);
@@ -820,6 +862,7 @@ template <int R> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, 
       row_g = __builtin_elementwise_fma(w, splat2((float)(p.y & 0xFFu)), row_g);
       row_b = __builtin_elementwise_fma(w, splat2((float)(p.z & 0xFFu)), row_b);
       row_w += w;
+      if (FLAT) __builtin_amdgcn_sched_barrier(0);  // as in blur_uniform_sigma
     }
     acc_r = __builtin_elementwise_fma(f, row_r, acc_r);
     acc_g = __builtin_elementwise_fma(f, row_g, acc_g);
@@ -831,9 +874,45 @@ template <int R> VKR_DEV void blur_rows(const uint4* s_px, const BlurCentre* c, 
   accB = mk4(acc_r.y * gB, acc_g.y * gB, acc_b.y * gB, acc_w.y * gB);
 }
 
+// the instantiation for a wave-uniform radius; false: none for it, the caller goes on to the next path
+template <bool FLAT> VKR_DEV bool blur_uniform_sigma_of(int r, const uint4* s_px, const BlurCentre* c, v2f nw0, f4& accA, f4& accB) {
+  switch (r) {
+    case 1: blur_uniform_sigma<1, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 2: blur_uniform_sigma<2, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 3: blur_uniform_sigma<3, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 4: blur_uniform_sigma<4, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 5: blur_uniform_sigma<5, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 6: blur_uniform_sigma<6, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 7: blur_uniform_sigma<7, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 8: blur_uniform_sigma<8, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 9: blur_uniform_sigma<9, FLAT>(s_px, c, nw0, accA, accB); return true;
+    case 10: blur_uniform_sigma<10, FLAT>(s_px, c, nw0, accA, accB); return true;
+    // (radius 11 — roughness near 1 — is left to blur_rows<11>: measured faster than blur_uniform_sigma<11>, whose 12 factor pairs
+    // no longer fit beside the unrolled rows: 0.724 against 0.768 ms per frame with the empty-tile skips off, where the sky's tiles count)
+    default: return false;
+  }
+}
+template <bool FLAT> VKR_DEV bool blur_rows_of(int rmax, const uint4* s_px, const BlurCentre* c, bool has_b, v2f nw0, f4& accA, f4& accB) {
+  switch (rmax) {
+    case 0: case 1: blur_rows<1, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 2: blur_rows<2, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 3: blur_rows<3, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 4: blur_rows<4, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 5: blur_rows<5, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 6: blur_rows<6, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 7: blur_rows<7, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 8: blur_rows<8, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 9: blur_rows<9, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 10: blur_rows<10, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    case 11: blur_rows<11, FLAT>(s_px, c, has_b, nw0, accA, accB); return true;
+    default: return false;
+  }
+}
+
 // one BLUR_BX x BLUR_BY tile of the output; s_px: the staged tile, one 16-byte record per pixel (blur_pack); s_lut: the sRGB
-// decode table (storage; staged inside, visible after the first barrier)
-VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lut, const int tid) {
+// decode table (storage; staged inside, visible after the first barrier); s_flat: one {normal code, agreed} pair per wave;
+// s_flat_loops: the block's "a wave ran a flat loop" flag of VKR_SWITCH_BLUR_COUNT_PATHS
+VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lut, uint2* s_flat, uint32_t* s_flat_loops, const int tid) {
   const int bx0 = a.out.ox + blk.x * BLUR_BX - BLUR_R;  // frame coordinates of the tile origin
   const int by0 = a.out.oy + blk.y * BLUR_BY - BLUR_R;
   const f2 tex_size = mk2((float)a.out.fw, (float)a.out.fh);
@@ -890,13 +969,25 @@ VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lu
       const uint32_t d = load_u32_clamped(a.depth1, px, py);
       stage_depth[k] = in_depth ? d : 0u;  // D24 word 0 decodes to 0.0f
     }
+    // Is every raw RG16 word under the tile and its apron one and the same (a planar surface without a normal map)?  Codes are
+    // compared, not decoded values: the bilinear mix of four equal codes may differ in the last bit from pixel to pixel.
+    const bool look = a.flat_path != 0 || a.count_paths != 0;  // (GENERIC / NO_FLAT runs do not pay for the compare)
+    const uint32_t code = stage_normal[0].t00;
+    bool one_code = look;
 #pragma unroll
     for (int k = 0; k < STAGE_ITERS; k++) {
       const int t = min(tid + k * BLUR_THREADS, BLUR_TW * BLUR_TH - 1);
       const f3 n = decode_normal_fast(taps_resolve<FmtRG16U>(stage_normal[k]));  // only enters the normal weight
       lds_store4(&s_px[t], blur_pack(n, FmtD24::decode(stage_depth[k]), stage_refl[k]));
+      if (look) one_code = one_code && stage_normal[k].t00 == code && stage_normal[k].t10 == code && stage_normal[k].t01 == code && stage_normal[k].t11 == code;
     }
+    // each wave agrees on its first lane's word and leaves {word, agreed} in LDS; the words of the waves are compared behind
+    // the barrier that ends staging
+    const uint32_t wave_code = (uint32_t)__builtin_amdgcn_readfirstlane((int)code);
+    const bool wave_flat = __ballot(one_code && code == wave_code) == __ballot(true);
+    if (look && (tid & 63) == 0) s_flat[tid >> 6] = make_uint2(wave_code, wave_flat ? 1u : 0u);
   }
+  if (a.count_paths != 0 && tid == 0) *s_flat_loops = 0u;
 
   // (3): prev_uv needs the velocity, which has arrived by now
   f2 velocity[2], prev_uv[2];
@@ -916,6 +1007,20 @@ VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lu
   }
   __syncthreads();
   VKR_STAMP(1);  // tile staged, per-pixel loads issued
+  bool flat_tile = false;
+  uint32_t flat_code = 0u;
+  if (!empty_tile && (a.flat_path != 0 || a.count_paths != 0)) {
+    flat_code = s_flat[0].x;
+    uint32_t agreed = 1u;
+#pragma unroll
+    for (int k = 0; k < BLUR_THREADS / 64; k++) {
+      const uint2 wv = s_flat[k];
+      agreed &= wv.y & (wv.x == flat_code ? 1u : 0u);
+    }
+    flat_tile = __builtin_amdgcn_readfirstlane((int)agreed) != 0;
+  }
+  if (a.count_paths != 0 && tid == 0) blur_count_path(empty_tile ? 0 : flat_tile ? 1 : 2);
+  const bool flat = flat_tile && a.flat_path != 0;
   if (!live) return;
 
   // per-pixel set-up (blur.comp:34-55) and the temporal test (blur.comp:79-105) for A and B
@@ -959,28 +1064,26 @@ VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lu
   VKR_STAMP(2);  // per-pixel set-up done
   VKR_STAMP_VALUE(5, empty_tile ? 0 : c[0].r);
   f4 accA = mk4(0, 0, 0, 0), accB = mk4(0, 0, 0, 0);
+  // flat tile: the one staged normal n0 — the existing decode of a footprint of four equal words — and each pixel's normal
+  // weight against it, with the operations and order of the per-tap form
+  v2f nw0 = {0.0f, 0.0f};
+  if (flat) {
+    BilinearTaps one;
+    one.t00 = one.t10 = one.t01 = one.t11 = flat_code;
+    one.fx = one.fy = 0.0f;
+    const f3 n0 = decode_normal_fast(taps_resolve<FmtRG16U>(one));
+    const v2f cnx = {c[0].normal.x, c[1].normal.x}, cny = {c[0].normal.y, c[1].normal.y}, cnz = {c[0].normal.z, c[1].normal.z};
+    const v2f nxy = __builtin_elementwise_fma(cny, splat2(n0.y), cnx * splat2(n0.x));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nw0) : "v"(cnz), "v"(splat2(n0.z)), "v"(nxy));
+  }
   bool uniform_sigma = false;
   if (!empty_tile && a.uniform_sigma_path != 0) {
     const uint32_t key = __float_as_uint(c[0].neg_inv_e_log2);
     const uint32_t key0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
     const bool same = has_b && key == key0 && __float_as_uint(c[1].neg_inv_e_log2) == key0;
     if (__ballot(same) == ~0ull) {  // a full wave, every pixel with the same sigma (hence the same radius and normalisation)
-      uniform_sigma = true;
-      switch (__builtin_amdgcn_readfirstlane(c[0].r)) {
-        case 1: blur_uniform_sigma<1>(s_px, c, accA, accB); break;
-        case 2: blur_uniform_sigma<2>(s_px, c, accA, accB); break;
-        case 3: blur_uniform_sigma<3>(s_px, c, accA, accB); break;
-        case 4: blur_uniform_sigma<4>(s_px, c, accA, accB); break;
-        case 5: blur_uniform_sigma<5>(s_px, c, accA, accB); break;
-        case 6: blur_uniform_sigma<6>(s_px, c, accA, accB); break;
-        case 7: blur_uniform_sigma<7>(s_px, c, accA, accB); break;
-        case 8: blur_uniform_sigma<8>(s_px, c, accA, accB); break;
-        case 9: blur_uniform_sigma<9>(s_px, c, accA, accB); break;
-        case 10: blur_uniform_sigma<10>(s_px, c, accA, accB); break;
-        // (radius 11 — roughness near 1 — is left to blur_rows<11>: measured faster than blur_uniform_sigma<11>, whose 12 factor pairs
-        // no longer fit beside the unrolled rows: 0.724 against 0.768 ms per frame with the empty-tile skips off, where the sky's tiles count)
-        default: uniform_sigma = false; break;
-      }
+      const int r = __builtin_amdgcn_readfirstlane(c[0].r);
+      uniform_sigma = flat ? blur_uniform_sigma_of<true>(r, s_px, c, nw0, accA, accB) : blur_uniform_sigma_of<false>(r, s_px, c, nw0, accA, accB);
     }
   }
   bool by_rows = false;
@@ -989,22 +1092,11 @@ VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lu
     int rmax = max(c[0].r, has_b ? c[1].r : 0);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) rmax = max(rmax, __shfl_xor(rmax, off));
-    by_rows = true;
-    switch (__builtin_amdgcn_readfirstlane(rmax)) {
-      case 0: case 1: blur_rows<1>(s_px, c, has_b, accA, accB); break;
-      case 2: blur_rows<2>(s_px, c, has_b, accA, accB); break;
-      case 3: blur_rows<3>(s_px, c, has_b, accA, accB); break;
-      case 4: blur_rows<4>(s_px, c, has_b, accA, accB); break;
-      case 5: blur_rows<5>(s_px, c, has_b, accA, accB); break;
-      case 6: blur_rows<6>(s_px, c, has_b, accA, accB); break;
-      case 7: blur_rows<7>(s_px, c, has_b, accA, accB); break;
-      case 8: blur_rows<8>(s_px, c, has_b, accA, accB); break;
-      case 9: blur_rows<9>(s_px, c, has_b, accA, accB); break;
-      case 10: blur_rows<10>(s_px, c, has_b, accA, accB); break;
-      case 11: blur_rows<11>(s_px, c, has_b, accA, accB); break;
-      default: by_rows = false; break;
-    }
+    rmax = __builtin_amdgcn_readfirstlane(rmax);
+    by_rows = flat ? blur_rows_of<true>(rmax, s_px, c, has_b, nw0, accA, accB) : blur_rows_of<false>(rmax, s_px, c, has_b, nw0, accA, accB);
   }
+  // the first wave of the block that ran a flat loop counts the block
+  if (a.count_paths != 0 && flat && (uniform_sigma || by_rows) && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u && atomicOr(s_flat_loops, 1u) == 0u) blur_count_path(3);
   if (empty_tile || uniform_sigma || by_rows) {
     // empty: nothing to add up, both sums stay 0 and the epilogue turns them into colour 0 (then the history mix)
   } else if (!has_b || c[0].r != c[1].r) {
@@ -1084,6 +1176,8 @@ VKR_DEV void blur_tile(const BlurArgs& a, const i2 blk, uint4* s_px, float* s_lu
 __global__ __launch_bounds__(BLUR_THREADS, BLUR_WAVES) void k_sssr_blur(BlurArgs a) {
   __shared__ uint4 s_px[BLUR_TH * BLUR_TW];
   __shared__ float s_lut[VKR_SRGB_LUT_SIZE];
+  __shared__ uint2 s_flat[BLUR_THREADS / 64];
+  __shared__ uint32_t s_flat_loops;
   const int tid = threadIdx.y * BLUR_BX + threadIdx.x;
   VKR_STAMP(0);
 #ifdef VKR_BLUR_STAMPS
@@ -1094,7 +1188,7 @@ __global__ __launch_bounds__(BLUR_THREADS, BLUR_WAVES) void k_sssr_blur(BlurArgs
     VKR_STAMP_VALUE(6, ((unsigned long long)xcc << 32) | hw);
   }
 #endif
-  blur_tile(a, xcd_block<4, 64 / BLUR_BY>(), s_px, s_lut, tid);  // chunks of 128 x 64 output pixels; stages s_lut
+  blur_tile(a, xcd_block<4, 64 / BLUR_BY>(), s_px, s_lut, s_flat, &s_flat_loops, tid);  // chunks of 128 x 64 output pixels; stages s_lut
   VKR_STAMP(4);
 }
 
@@ -1346,6 +1440,8 @@ static int make_blur_args(BlurArgs& a, const vkr_img* depth, const vkr_img* norm
   a.skip_empty_tiles = (switches() & VKR_SWITCH_BLUR_NO_SKIP) ? 0u : 1u;  // measurement switch: identical output for finite weights
   a.uniform_sigma_path = (switches() & VKR_SWITCH_BLUR_GENERIC) ? 0u : 1u;
   a.rows_path = (switches() & VKR_SWITCH_BLUR_LANE_LOOPS) ? 0u : 1u;
+  a.flat_path = (switches() & (VKR_SWITCH_BLUR_NO_FLAT | VKR_SWITCH_BLUR_GENERIC)) ? 0u : 1u;  // GENERIC: a frame whose content helps nowhere
+  a.count_paths = (switches() & VKR_SWITCH_BLUR_COUNT_PATHS) ? 1u : 0u;
   if (a.max_roughness > 1.0f || a.max_roughness < 0.0f) {  // sigma <= 4 bounds the staged radius (blur.comp:45)
     set_error("sssr_blur: max_roughness must be in [0,1] (reference slider range, advanced_ssr.cpp:558)");
     return VKR_ERR_EXTENT;
@@ -1358,6 +1454,20 @@ extern "C" int vkr_debug_blur_stamps(void* dst, uint64_t bytes) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_blur_stamps), bytes < sizeof(g_blur_stamps) ? bytes : sizeof(g_blur_stamps));
 }
 #endif
+
+extern "C" int vkr_debug_blur_paths(uint32_t out[4], int reset) {
+  if (!out) { set_error("debug_blur_paths: NULL argument"); return VKR_ERR_NULL; }
+  uint32_t host[4 * BLUR_PATH_STRIDE];
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_blur_paths), sizeof(host));
+  for (int k = 0; k < 4; k++) out[k] = e == hipSuccess ? host[k * BLUR_PATH_STRIDE] : 0u;
+  if (e == hipSuccess && reset) {
+    memset(host, 0, sizeof(host));
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_blur_paths), host, sizeof(host));
+  }
+  if (e != hipSuccess) { set_error("debug_blur_paths: %s", hipGetErrorString(e)); return (int)e; }
+  return VKR_OK;
+}
 
 extern "C" int vkr_sssr_blur(const vkr_img* depth, const vkr_img* normal, const vkr_img* reflections,
                              const vkr_img* material, const vkr_img* history, const vkr_img* velocity,
