@@ -779,6 +779,54 @@ int vkr_reflections_rt_cutout(const vkr_img* depth, const vkr_img* normal, const
                               const vkr_reflect_rt_params* params, const vkr_ray_cutout* cutout, const vkr_img* out_reflections,
                               void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- lit ray-traced reflections (DESIGN_NUMERICS.md, "Reflections, ray traced, lit") ----------------------------------------------
+ * vkr_reflections_rt whose hit is lit and shadowed before it is stored: up to four point or directional lights (the convention of
+ * vkr_shadow_rt_params), one shadow ray per light from the hit, a constant ambient term, and the albedo of the hit times the sum.
+ * Everything up to and including the closest hit is vkr_reflections_rt's, bit for bit (vkr_reflections_rt_cutout's in the _cutout
+ * entry).  For a hit (t, u, v, index) of ray (origin, dir), every operation rounded on its own, cfma the multiply-add contract 2
+ * fuses:  P = cfma(t, dir, origin);  w = (1 - u) - v, Ni = (w n0 + u n1) + v n2 with n0..n2 = normals[index].n, Ns = normalize(Ni);
+ * N = -Ns when dot(Ns, dir) > 0, else Ns (two-sided; a NaN normal stays NaN and is lit by ambient alone);  Po = P + shadow_offset N;
+ * acc = ambient.rgb;  per light l < light_count in index order: dvec = lights[l].xyz - Po (w == 1) or lights[l].xyz (w == 0);
+ * unless dot(N, dvec) > 0 the light adds nothing and casts no ray; it adds nothing when the frozen any-hit of (Po, dvec,
+ * shadow_tmin, 1) reports a hit (vkr_accel_occluded's answer; vkr_accel_occluded_cutout's in the _cutout entry); otherwise
+ * ld2 = dot(dvec, dvec), L = normalize(dvec), ndl = dot(N, L) or 0 unless ndl > 0, k = ndl for a directional light and
+ * ndl * min'(1 / ld2, 1) for a point light (min'(q, 1) = q < 1 ? q : 1), acc.c = cfma(k, colour[l].c, acc.c).  The texel is
+ * rint(255 clamp(albedo.c * acc.c)) per channel, alpha 0, albedo as vkr_reflections_rt computes it.  With light_count 0 and
+ * ambient (1, 1, 1) the image is vkr_reflections_rt's.                                                                            */
+typedef struct vkr_hit_normal { float n[3][4]; } vkr_hit_normal;   /* 48 bytes, one per INPUT triangle, in input order (device memory,
+                                                                      16-byte aligned): the world-space normals of the three
+                                                                      vertices, not normalised; n[k][3] is not read */
+typedef struct vkr_reflect_lights {     /* 176 bytes */
+  float    lights[4][4];                /* as vkr_shadow_rt_params.lights */
+  float    colour[4][4];                /* rgb of light l; .w must be 0 */
+  float    ambient[4];                  /* rgb; .w must be 0 */
+  uint32_t light_count;                 /* 0..4 */
+  float    shadow_offset;               /* the shadow ray starts at P + shadow_offset * N */
+  float    shadow_tmin;                 /* its segment is Po + t * dvec, t in [shadow_tmin, 1] */
+  uint32_t reserved[5];                 /* 0 */
+} vkr_reflect_lights;
+/* The arguments, scratch (vkr_reflections_rt_scratch_bytes) and gates of vkr_reflections_rt / vkr_reflections_rt_cutout, then,
+ * still before any launch: lights NULL; normals NULL with triangles present; normals not 16-byte aligned; normal_count != the
+ * structure's triangle count; light_count > 4; a light in use whose w is neither 0 nor 1; a non-zero .w of colour / ambient or a
+ * non-zero reserved; shadow_offset or shadow_tmin NaN; a NaN in ambient or in the colour of a light in use.                     */
+int vkr_reflections_rt_lit(const vkr_img* depth, const vkr_img* normal, const vkr_img* rays, const vkr_accel* accel,
+                           const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_hit_normal* normals, uint32_t normal_count,
+                           const vkr_img* textures, uint32_t texture_count, const vkr_reflect_rt_params* params,
+                           const vkr_reflect_lights* lights, const vkr_img* out_reflections, void* scratch, uint64_t scratch_bytes,
+                           void* stream);
+int vkr_reflections_rt_lit_cutout(const vkr_img* depth, const vkr_img* normal, const vkr_img* rays, const vkr_accel* accel,
+                                  const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_hit_normal* normals, uint32_t normal_count,
+                                  const vkr_img* textures, uint32_t texture_count, const vkr_reflect_rt_params* params,
+                                  const vkr_reflect_lights* lights, const vkr_ray_cutout* cutout, const vkr_img* out_reflections,
+                                  void* scratch, uint64_t scratch_bytes, void* stream);
+/* The twin of vkr_scene_triangles for vertex normals: one vkr_hit_normal per triangle, in its order, with its scratch
+ * (vkr_scene_triangles_scratch_bytes) and its gates.  n[k] = transforms[t].normal * (norm, 0) of vertex k, computed as
+ * (m[0][r] x + m[1][r] y) + m[2][r] z per row r: no translation, no fused multiply-add under either numeric contract, not
+ * normalised (the pass normalises after interpolation); n[k][3] = 0.  A triangle with an index outside the vertex buffer gets NaN
+ * normals, and nothing is read outside the buffer.  out: device, 16-byte aligned, room for out_capacity records.               */
+int vkr_scene_triangle_normals(const vkr_raster_scene* scene, vkr_hit_normal* out, uint64_t out_capacity, void* scratch, uint64_t scratch_bytes,
+                               void* stream);
+
 /* ---- area lights in the traced shadow mask (DESIGN_NUMERICS.md, "Shadow mask, ray traced, area lights") ---------------------------
  * A light with a radius is a disk that faces the surface point; the channel is the share of S points of the disk that the surface
  * point sees, in 255ths.  Everything but the per-light step is vkr_shadow_mask_rt's.  Light l with radius[l] == 0 is traced as

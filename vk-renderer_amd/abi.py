@@ -307,6 +307,20 @@ class RayCutout(C.Structure):  # vkr_ray_cutout, 8 bytes
     _fields_ = [("alpha_lod", C.c_uint32), ("opaque_texture_mask", C.c_uint32)]
 
 
+# ---- lit ray-traced reflections ----
+class HitNormal(C.Structure):  # vkr_hit_normal, 48 bytes, one per input triangle; numpy twin: hit_normal_dtype()
+    _fields_ = [("n", (C.c_float * 4) * 3)]
+
+
+class ReflectLights(C.Structure):  # vkr_reflect_lights, 176 bytes
+    _fields_ = [("lights", (C.c_float * 4) * 4), ("colour", (C.c_float * 4) * 4), ("ambient", C.c_float * 4), ("light_count", C.c_uint32),
+                ("shadow_offset", C.c_float), ("shadow_tmin", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+# the offsets of the shadow ray cast from a reflection's hit: the host frame's defaults (host/frame.cpp), those of the shadow mask's rays
+REFLECT_SHADOW_OFFSET, REFLECT_SHADOW_TMIN = 1e-3, 0.0
+
+
 TEXDRAW_SHOW_ALL, TEXDRAW_SHOW_R, TEXDRAW_SHOW_G, TEXDRAW_SHOW_B, TEXDRAW_SHOW_A = 0, 1, 2, 4, 8  # VKR_TEXDRAW_*: DrawTex
 
 
@@ -358,13 +372,21 @@ ENTRY_ARGS = {
     "hit_requests_bounded": [P(HitSources), P(C.c_uint32), C.c_uint32, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_void_p, C.c_void_p],
     "hit_reply": [_IMG, _IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
     "hit_scatter": [_IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32],
+    # lit ray-traced reflections: vkr_reflections_rt's arguments with (normals, normal_count) behind the attributes and the lights
+    # behind params; trailing (scratch pointer, scratch bytes); and the scene's vertex normals made on the device
+    "reflections_rt_lit": [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(ReflectRtParams),
+                           P(ReflectLights), _IMG, C.c_void_p, C.c_uint64],
+    "reflections_rt_lit_cutout": [_IMG, _IMG, _IMG, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                  P(ReflectRtParams), P(ReflectLights), P(RayCutout), _IMG, C.c_void_p, C.c_uint64],
+    "scene_triangle_normals": [P(RasterScene), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64],
 }
 
 
 # entries without a twin in a checker library: a different SCHEDULE of another entry (same images bit for bit), or a variant
-# of pass 2 of the hit requests that the checker library does not restate (held to tests/hit_exchange_reference.py instead)
+# of pass 2 of the hit requests that the checker library does not restate (held to tests/hit_exchange_reference.py instead), or
+# a ray-query entry without a reference program, held to the numpy restatement tests/reflections_rt_lit_reference.py
 SCHEDULE_VARIANTS = {"sssr_trace_split": "sssr_trace", "sssr_trace_windowed_head": "sssr_trace_windowed", "sssr_trace_windowed_resume": "sssr_trace_windowed",
-                     "hit_requests_bounded": "hit_requests"}
+                     "hit_requests_bounded": "hit_requests", "reflections_rt_lit": None, "reflections_rt_lit_cutout": None, "scene_triangle_normals": None}
 
 
 class RectCopy(C.Structure):  # vkr_rect_copy
@@ -893,6 +915,56 @@ def reflections_rt_cutout(depth, normal, rays, accel, attribs, attrib_count, tex
                                         ref(params), ref(cutout), ref(out_reflections), scratch, int(scratch_bytes), stream), lib)
 
 
+def hit_normal_dtype():
+    """the numpy dtype of vkr_hit_normal (48 bytes): the world-space normals of a triangle's three vertices, .w unused"""
+    import numpy as np
+
+    return np.dtype([("n", np.float32, (3, 4))])
+
+
+def reflect_lights(lights=(), colours=(), ambient=(1.0, 1.0, 1.0), shadow_offset=REFLECT_SHADOW_OFFSET, shadow_tmin=REFLECT_SHADOW_TMIN):
+    """ReflectLights from 0..4 lights of (x, y, z, w) (the convention of shadow_rt_params), one rgb colour per light, the ambient rgb
+    and the two offsets of the shadow ray cast from a hit.  Everything is passed on as given (the entry refuses what it does not
+    take).  Without lights and with the default ambient the lit pass stores what reflections_rt stores."""
+    if len(lights) > 4 or len(colours) != len(lights):
+        raise RuntimeError(f"reflect_lights: {len(lights)} lights and {len(colours)} colours, at most 4 and as many of one as of the other")
+    p = ReflectLights()
+    for l, (v, c) in enumerate(zip(lights, colours)):
+        for k in range(4):
+            p.lights[l][k] = float(v[k])
+        for k in range(3):
+            p.colour[l][k] = float(c[k])
+    for k in range(3):
+        p.ambient[k] = float(ambient[k])
+    p.light_count, p.shadow_offset, p.shadow_tmin = len(lights), float(shadow_offset), float(shadow_tmin)
+    return p
+
+
+def reflections_rt_lit(depth, normal, rays, accel, attribs, attrib_count, normals, normal_count, textures, texture_count, params, lights,
+                       out_reflections, scratch, scratch_bytes, stream=None):
+    """vkr_reflections_rt_lit: reflections_rt whose hit is lit by `lights` (a ReflectLights, e.g. reflect_lights(...)) and shadowed
+    by one ray per light from the hit; normals: device pointer (16-byte aligned) to normal_count vkr_hit_normal records
+    (scene_triangle_normals order); everything else as reflections_rt.  Raises RuntimeError with the library's message on a
+    refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_reflections_rt_lit(ref(depth), ref(normal), ref(rays), handle, attribs, int(attrib_count), normals, int(normal_count), textures,
+                                     int(texture_count), ref(params), ref(lights), ref(out_reflections), scratch, int(scratch_bytes), stream), lib)
+
+
+def reflections_rt_lit_cutout(depth, normal, rays, accel, attribs, attrib_count, normals, normal_count, textures, texture_count, params, lights,
+                              cutout, out_reflections, scratch, scratch_bytes, stream=None):
+    """vkr_reflections_rt_lit_cutout: reflections_rt_lit whose mirror rays and shadow rays pass through the holes of alpha-tested
+    triangles (cutout: a RayCutout).  Raises RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    handle = accel.handle if accel is not None else None
+    check(lib.vkr_reflections_rt_lit_cutout(ref(depth), ref(normal), ref(rays), handle, attribs, int(attrib_count), normals, int(normal_count),
+                                            textures, int(texture_count), ref(params), ref(lights), ref(cutout), ref(out_reflections), scratch,
+                                            int(scratch_bytes), stream), lib)
+
+
 def defered_shading_shadowed(albedo, normal, material, depth, consts, occlusion, brdf, reflections, shadow_mask, out, push, stream=None):
     """vkr_defered_shading_shadowed: vkr_defered_shading (same VkrImg bindings, ShadingParams and ShadingPush) with channel .x of
     `shadow_mask` (RGBA8_UNORM VkrImg at out's extent) on the direct term.  Raises RuntimeError with the library's message on a
@@ -1023,6 +1095,27 @@ def scene_triangle_attributes(sc):
     return np.concatenate(out) if out else np.zeros(0, hit_attrib_dtype())
 
 
+def scene_triangle_normals(sc):
+    """One vkr_hit_normal per triangle of scene_triangles(sc), in its order, as a numpy array of hit_normal_dtype(): the normals of
+    the triangle's three vertices under the draw's normal matrix, (m[r][0] x + m[r][1] y) + m[r][2] z per row in fp32 (no
+    translation, nothing fused), not normalised; .w is 0."""
+    import numpy as np
+
+    out = []
+    for d in sc.draws:
+        m = np.asarray(sc.transforms[d["transform"]][1], dtype=np.float32)
+        n = d["index_count"] // 3 * 3
+        idx = sc.indices[d["index_offset"]:d["index_offset"] + n].astype(np.int64) + d["vertex_offset"]
+        p = sc.vertices[idx, 3:6].astype(np.float32)
+        rec = np.zeros(n // 3, hit_normal_dtype())
+        w = np.zeros((n, 4), np.float32)
+        for r in range(3):
+            w[:, r] = (m[r, 0] * p[:, 0] + m[r, 1] * p[:, 1]) + m[r, 2] * p[:, 2]
+        rec["n"] = w.reshape(-1, 3, 4)
+        out.append(rec)
+    return np.concatenate(out) if out else np.zeros(0, hit_normal_dtype())
+
+
 def accel_layout(triangles):
     """vkr_accel_layout on the host (no GPU): -> (nodes, tris) as numpy structured copies of the records"""
     import numpy as np
@@ -1072,6 +1165,22 @@ def scene_world_triangles(raster_scene, triangle_count, device="cuda", stream=No
     scratch = torch.zeros(nbytes, dtype=torch.uint8, device=device)
     lib = product()
     check(lib.vkr_scene_triangles(C.byref(raster_scene), out.data_ptr(), int(triangle_count), scratch.data_ptr(), nbytes, stream), lib)
+    # the call is asynchronous; the scratch tensor may be released only once the stream has passed it
+    (torch.cuda.current_stream(out.device) if stream is None else torch.cuda.ExternalStream(stream)).synchronize()
+    return out
+
+
+def scene_world_normals(raster_scene, triangle_count, device="cuda", stream=None):
+    """vkr_scene_triangle_normals: the vertex normals of a RasterScene's triangles as a device tensor (triangle_count, 3, 4) float32
+    — scene_triangle_normals() computed on the device, in its order.  A triangle with an index outside the vertex buffer is three
+    NaN normals."""
+    import torch
+
+    out = torch.zeros((int(triangle_count), 3, 4), dtype=torch.float32, device=device)
+    nbytes = scene_triangles_scratch_bytes(raster_scene.draw_count)
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    lib = product()
+    check(lib.vkr_scene_triangle_normals(C.byref(raster_scene), out.data_ptr(), int(triangle_count), scratch.data_ptr(), nbytes, stream), lib)
     # the call is asynchronous; the scratch tensor may be released only once the stream has passed it
     (torch.cuda.current_stream(out.device) if stream is None else torch.cuda.ExternalStream(stream)).synchronize()
     return out

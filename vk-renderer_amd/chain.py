@@ -533,13 +533,15 @@ class PostFxChain:
         return nbytes, self._reflect_rt_scratch.data_ptr()
 
     def reflections_rt(self, accel, attribs, scene, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN,
-                       max_distance=None, texture_lod=0, cutouts=None):
+                       max_distance=None, texture_lod=0, cutouts=None, lights=None, normals=None):
         """vkr_reflections_rt on this chain's half-resolution set (depth mip 1, dn, rays) -> reflections (RGBA8_UNORM): the albedo at
         the closest hit of the mirror ray through `accel` (abi.Accel); `attribs`: device tensor of abi.scene_triangle_attributes
         records; `scene`: the abi.RasterScene of Scene.upload(device) whose textures the records index.  fill_misses: only texels
         whose screen-space ray (rays.w) is invalid are written, in place on what the filter left.  cutouts: None, or an abi.RayCutout
-        for vkr_reflections_rt_cutout (the mirror ray passes through holes).  Product backend only: the
-        expectation is the numpy restatement tests/reflections_rt_reference.py, not a checker library."""
+        for vkr_reflections_rt_cutout (the mirror ray passes through holes).  lights: None, or an abi.ReflectLights for
+        vkr_reflections_rt_lit / _lit_cutout (the hit is lit and shadowed), with `normals` a device tensor of
+        abi.scene_triangle_normals records.  Product backend only: the expectation is the numpy restatement
+        tests/reflections_rt_reference.py (lit: tests/reflections_rt_lit_reference.py), not a checker library."""
         if self.backend != "product":
             raise RuntimeError("PostFxChain.reflections_rt: only the product backend has the program reflections_rt")
         if self.tiled:
@@ -551,6 +553,18 @@ class PostFxChain:
             self._reflect_rt_scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         p = abi.reflect_rt_params(self.setup.inv_view, *self.setup.fazz, fill_misses=fill_misses, normal_offset=normal_offset, tmin=tmin,
                                   max_distance=max_distance, texture_lod=texture_lod)
+        if lights is not None:
+            if normals is None:
+                raise RuntimeError("PostFxChain.reflections_rt: lights= needs normals= (a device tensor of abi.scene_triangle_normals records)")
+            head = (self.depth.desc(1, 1), self.dn.desc(), self.rays.desc() if fill_misses else None, accel, attribs.data_ptr(),
+                    attribs.numel() * attribs.element_size() // 32, normals.data_ptr(), normals.numel() * normals.element_size() // 48, scene.textures,
+                    scene.texture_count, p, lights)
+            tail = (self.reflections.desc(), self._reflect_rt_scratch.data_ptr(), nbytes, self.stream)
+            if cutouts is not None:
+                abi.reflections_rt_lit_cutout(*head, cutouts, *tail)
+            else:
+                abi.reflections_rt_lit(*head, *tail)
+            return
         if cutouts is not None:
             abi.reflections_rt_cutout(self.depth.desc(1, 1), self.dn.desc(), self.rays.desc() if fill_misses else None, accel, attribs.data_ptr(),
                                       attribs.numel() * attribs.element_size() // 32, scene.textures, scene.texture_count, p, cutouts,

@@ -17,6 +17,7 @@
 // Level sizes never grow with the height, so the levels of the tail are the last ones.
 #include "raster_common.hpp"
 #include "accel_record.hpp"
+#include "scene_triangles.hpp"
 
 #include <vector>
 
@@ -82,32 +83,14 @@ __global__ __launch_bounds__(ACCEL_REFIT_TAIL_NODES) void k_accel_refit_tail(vkr
   }
 }
 
-// ---- vkr_scene_triangles -------------------------------------------------------------------------------------------------------
-struct TriDraw {      // 64 bytes
-  float m[4][3];      // m[c][r] of the model matrix: the three rows that make a position
-  uint32_t index_offset, vertex_offset, tri_base, tri_count;
-};
-struct SceneTriArgs {
-  const vkr_raster_vertex* vertices;
-  const uint32_t* indices;
-  const TriDraw* draws;
-  float* out;
-  uint32_t vertex_count, draw_count, total;
-};
-
+// ---- vkr_scene_triangles (the draw table, the corners and the gates: scene_triangles.hpp) --------------------------------------------
 __global__ __launch_bounds__(256) void k_scene_triangles(SceneTriArgs a) {
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   if (g >= a.total) return;
-  const TriDraw d = a.draws[draw_of(a.draws, a.draw_count, g)];
-  const uint32_t j = g - d.tri_base;
+  TriDraw d;
   uint64_t vi[3];
-  bool inside = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    vi[k] = (uint64_t)a.indices[d.index_offset + 3u * j + (uint32_t)k] + d.vertex_offset;  // check_scene: the index range is inside
-    inside = inside && vi[k] < a.vertex_count;
-  }
-  float* dst = a.out + 9ull * g;
+  const bool inside = scene_triangle_corners(a, g, &d, vi);
+  float* dst = (float*)a.out + 9ull * g;
   if (!inside) {  // a triangle the rasterisers do not draw and no ray hits; nothing is read outside the vertex buffer
 #pragma unroll
     for (int k = 0; k < 9; k++) dst[k] = __uint_as_float(0x7FC00000u);
@@ -208,41 +191,15 @@ extern "C" int vkr_accel_download(const vkr_accel* accel, vkr_accel_node* nodes,
   return VKR_OK;
 }
 
-extern "C" uint64_t vkr_scene_triangles_scratch_bytes(uint32_t draw_count) { return align_up(sizeof(TriDraw) * (uint64_t)(draw_count ? draw_count : 1u), 256); }
+extern "C" uint64_t vkr_scene_triangles_scratch_bytes(uint32_t draw_count) { return scene_triangles_scratch(draw_count); }
 
 extern "C" int vkr_scene_triangles(const vkr_raster_scene* scene, float* out_tri_vertices, uint64_t out_tri_capacity, void* scratch, uint64_t scratch_bytes,
                                    void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!scene) { set_error("scene_triangles: NULL scene"); return VKR_ERR_NULL; }
-  uint64_t total = 0;
-  VKR_TRY(check_scene("scene_triangles", scene, false, &total));
-  if (total == 0) return VKR_OK;
-  if (total > (1u << 30)) { set_error("scene_triangles: %llu triangles, at most 2^30", (unsigned long long)total); return VKR_ERR_EXTENT; }
-  if (!out_tri_vertices || !scratch) { set_error("scene_triangles: NULL output or scratch"); return VKR_ERR_NULL; }
-  if (total > out_tri_capacity) {
-    set_error("scene_triangles: %llu triangles do not fit into %llu", (unsigned long long)total, (unsigned long long)out_tri_capacity);
-    return VKR_ERR_EXTENT;
-  }
-  const uint64_t need = vkr_scene_triangles_scratch_bytes(scene->draw_count);
-  if (scratch_bytes < need) { set_error("scene_triangles: scratch too small (%llu bytes, %llu needed)", (unsigned long long)scratch_bytes, (unsigned long long)need); return VKR_ERR_EXTENT; }
-  std::vector<TriDraw> draws(scene->draw_count);
-  uint32_t tri_base = 0;
-  for (uint32_t i = 0; i < scene->draw_count; i++) {
-    const vkr_raster_draw& s = scene->draws[i];
-    const vkr_mat4& model = scene->transforms[s.transform_index].model;
-    TriDraw& d = draws[i];
-    for (int c = 0; c < 4; c++)
-      for (int r = 0; r < 3; r++) d.m[c][r] = model.m[c * 4 + r];
-    d.index_offset = s.index_offset; d.vertex_offset = s.vertex_offset;
-    d.tri_base = tri_base; d.tri_count = s.index_count / 3u;
-    tri_base += d.tri_count;
-  }
   SceneTriArgs a;
-  a.vertices = scene->vertices; a.indices = scene->indices;
-  a.draws = (const TriDraw*)scratch;
-  a.out = out_tri_vertices;
-  a.vertex_count = scene->vertex_count; a.draw_count = scene->draw_count; a.total = tri_base;
-  store_table<32>(draws, a.draws, stream);
-  hipLaunchKernelGGL(k_scene_triangles, dim3((tri_base + 255) / 256), dim3(256), 0, stream, a);
+  bool launch = false;
+  VKR_TRY(scene_triangles_args("scene_triangles", scene, out_tri_vertices, out_tri_capacity, scratch, scratch_bytes, false, stream, &a, &launch));
+  if (!launch) return VKR_OK;
+  hipLaunchKernelGGL(k_scene_triangles, dim3((a.total + 255) / 256), dim3(256), 0, stream, a);
   return launch_status("scene_triangles");
 }

@@ -1,6 +1,7 @@
 // reflections_rt.hpp — program "reflections_rt" but for the walk: the kernel argument, the shading of a hit, the pass over the
 // pixels of a block with the closest hit of a lane's ray handed in, the scratch layout, and every gate of the entry up to the
-// launch.  reflections_rt.hip instantiates it with the opaque walk, accel_cutout.hip with the walk that sees alpha cutouts.
+// launch.  reflections_rt.hip instantiates it with the opaque walk, accel_cutout.hip with the walk that sees alpha cutouts, and
+// reflections_rt_lit.hip with either walk and a shading of its own (reflections_rt_lit.hpp: the hit lit and shadowed).
 #ifndef VKR_REFLECTIONS_RT_HPP
 #define VKR_REFLECTIONS_RT_HPP
 
@@ -21,8 +22,8 @@ struct ReflectRtArgs : RtSurfaceArgs {
   float normal_offset, tmin, max_distance;
 };
 
-// the RGBA8_UNORM word of a hit: the albedo of triangle h.index at (h.u, h.v), alpha 0
-VKR_DEV uint32_t shade_hit(const ReflectRtArgs& a, const vkr_accel_hit& h, const float* lut) {
+// the albedo of triangle h.index at (h.u, h.v)
+VKR_DEV f3 hit_albedo(const ReflectRtArgs& a, const vkr_accel_hit& h, const float* lut) {
   const vkr_hit_attrib at = a.attribs[h.index];
   const f2 uv = hit_uv(at, h.u, h.v);
   f3 c = mk3(0.5f, 0.5f, 0.5f);
@@ -31,12 +32,24 @@ VKR_DEV uint32_t shade_hit(const ReflectRtArgs& a, const vkr_accel_hit& h, const
     const uint32_t level = min(a.texture_lod, (uint32_t)(p.count - 1));
     c = xyz(sample_level_repeat(p.mip[level], uv, lut));
   }
-  return float_to_unorm8(c.x) | (float_to_unorm8(c.y) << 8) | (float_to_unorm8(c.z) << 16);
+  return c;
 }
+// the RGBA8_UNORM word of a colour, alpha 0
+VKR_DEV uint32_t reflection_word(f3 c) { return float_to_unorm8(c.x) | (float_to_unorm8(c.y) << 8) | (float_to_unorm8(c.z) << 16); }
+// the RGBA8_UNORM word of a hit: its albedo, alpha 0
+VKR_DEV uint32_t shade_hit(const ReflectRtArgs& a, const vkr_accel_hit& h, const float* lut) { return reflection_word(hit_albedo(a, h, lut)); }
 
-// the pass; `walk(origin, dir, cast, stack, &hit)` is the closest hit of a lane's ray, called by the whole wave
-template <class Walk>
-VKR_DEV void reflections_rt_pixels(const ReflectRtArgs& a, uint32_t (*stacks)[ACCEL_STACK], float* s_lut, const Walk& walk) {
+// what the pass stores for a lane's ray: the albedo at its hit, 0 without one
+struct ShadeAlbedo {
+  const ReflectRtArgs& a;
+  const float* lut;
+  VKR_DEV uint32_t operator()(f3, f3, bool hit, const vkr_accel_hit& h, uint32_t*) const { return hit ? shade_hit(a, h, lut) : 0u; }
+};
+
+// the pass; `walk(origin, dir, cast, stack, &hit)` is the closest hit of a lane's ray and `shade(origin, dir, hit, h, stack)` the
+// word stored for it (hit: the lane cast a ray and h is its hit), both called by the whole wave
+template <class Walk, class Shade>
+VKR_DEV void reflections_rt_pixels(const ReflectRtArgs& a, uint32_t (*stacks)[ACCEL_STACK], float* s_lut, const Walk& walk, const Shade& shade) {
   srgb_lut_stage(s_lut, threadIdx.x, 256);
   __syncthreads();
   const RtPixel p = rt_pixel(a);
@@ -52,21 +65,28 @@ VKR_DEV void reflections_rt_pixels(const ReflectRtArgs& a, uint32_t (*stacks)[AC
     if (__ballot(cast) != 0ull) {  // the whole wave: lanes without a ray follow the walk
       vkr_accel_hit h;
       walk(s.origin, dir, cast, stacks[p.wave], &h);
-      if (cast && h.index != 0xFFFFFFFFu) result = shade_hit(a, h, s_lut);
+      result = shade(s.origin, dir, cast && h.index != 0xFFFFFFFFu, h, stacks[p.wave]);
     }
   }
   if (p.inside && !keep) *texel_ptr<uint32_t>(a.out, p.lx, p.ly) = result;
+}
+template <class Walk>
+VKR_DEV void reflections_rt_pixels(const ReflectRtArgs& a, uint32_t (*stacks)[ACCEL_STACK], float* s_lut, const Walk& walk) {
+  reflections_rt_pixels(a, stacks, s_lut, walk, ShadeAlbedo{a, s_lut});
 }
 
 // the scratch: the texture table, one layout for every entry that binds the scene's textures to a ray query
 using ReflectRtLayout = CutoutLayout;
 
-// both entries: every gate of the pass, its kernel argument and the upload of the texture table (recorded on the stream: the
-// last step before the entry's launch), under `program`'s prefix; has_cutout: the entry takes a vkr_ray_cutout
+// every entry: every gate of the pass, its kernel argument and the upload of the texture table (recorded on the stream: the
+// last step before the entry's launch), under `program`'s prefix; has_cutout: the entry takes a vkr_ray_cutout; more(): the
+// gates an entry adds behind these, asked before anything is recorded
+struct NoMoreGates { int operator()() const { return VKR_OK; } };
+template <class More = NoMoreGates>
 inline int reflections_rt_args(const char* program, const vkr_img* depth, const vkr_img* normal, const vkr_img* rays, const vkr_accel* accel,
                                const vkr_hit_attrib* attribs, uint32_t attrib_count, const vkr_img* textures, uint32_t texture_count,
                                const vkr_reflect_rt_params* params, bool has_cutout, const vkr_ray_cutout* cutout, const vkr_img* out_reflections, void* scratch,
-                               uint64_t scratch_bytes, hipStream_t stream, ReflectRtArgs* args) {
+                               uint64_t scratch_bytes, hipStream_t stream, ReflectRtArgs* args, const More& more = More()) {
   static_assert(sizeof(vkr_reflect_rt_params) == 112, "vkr_reflect_rt_params: a matrix, eight floats / words, the flags and three words");
   static_assert(sizeof(vkr_hit_attrib) == 32, "vkr_hit_attrib: three uv pairs and two words");
   const std::string prefix = std::string(program) + ": ", dotted = std::string(program) + ".rays";
@@ -105,6 +125,7 @@ inline int reflections_rt_args(const char* program, const vkr_img* depth, const 
     set_error("%s: scratch too small (%llu bytes, %llu needed)", program, (unsigned long long)scratch_bytes, (unsigned long long)lay.total);
     return VKR_ERR_EXTENT;
   }
+  VKR_TRY(more());
   a.attribs = attribs;
   a.textures = (const Pyramid*)((uint8_t*)scratch + lay.textures);
   a.texture_count = texture_count; a.texture_lod = params->texture_lod; a.fill_misses = fill ? 1u : 0u;

@@ -164,6 +164,10 @@ def lib():
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
                            ("vkrh_set_ray_cutouts", [C.c_void_p, C.c_uint32, C.c_uint32]),
+                           # lit hits in the ray-traced reflections, and the scene's normal table as the device holds it (same rule)
+                           ("vkrh_set_reflection_lights", [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                           C.c_float, C.c_float]),
+                           ("vkrh_scene_hit_normals", [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
                            # moving draws: the raster table and a refit of the ray-query structure (same rule)
                            ("vkrh_set_draw_transforms", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
                            # the matrices derived from the camera (same rule)
@@ -427,6 +431,32 @@ class HostFrame:
         (max_distance None: the camera's zfar), a hit samples level texture_lod of its albedo texture."""
         self._check(lib().vkrh_set_reflection_rays(self.h, 1 if fill_misses else 0, float(normal_offset), float(tmin),
                                                    0.0 if max_distance is None else float(max_distance), int(texture_lod)))
+
+    def set_reflection_lights(self, lights=None, colours=None, ambient=None, shadow_offset=abi.REFLECT_SHADOW_OFFSET,
+                              shadow_tmin=abi.REFLECT_SHADOW_TMIN):
+        """vkrh_set_reflection_lights: from now on STAGE_REFLECTIONS_RT lights and shadows the hit of the mirror ray (task
+        "ReflectionsRTLit"): lights 0..4 of (x, y, z, w) in the convention of set_shadow_rays, colours one rgb per light, ambient an
+        rgb.  With no argument at all: the default light, the direct diffuse term of defered_shading.  Composes with
+        set_reflection_rays, set_ray_cutouts and set_draw_transforms.  Not on a tiled frame."""
+        if lights is None and colours is None and ambient is None:
+            self._check(lib().vkrh_set_reflection_lights(self.h, 1, None, None, None, float(shadow_offset), float(shadow_tmin)))
+            return
+        lights, colours = list(lights or []), list(colours or [])
+        if len(colours) != len(lights) or ambient is None:
+            raise RuntimeError(f"set_reflection_lights: {len(lights)} lights, {len(colours)} colours and ambient {ambient}: one colour per light and an ambient")
+        fl = (C.c_float * max(1, 4 * len(lights)))(*[float(v[k]) for v in lights for k in range(4)])
+        fc = (C.c_float * max(1, 3 * len(lights)))(*[float(v[k]) for v in colours for k in range(3)])
+        fa = (C.c_float * 3)(*[float(ambient[k]) for k in range(3)])
+        self._check(lib().vkrh_set_reflection_lights(self.h, len(lights), fl, fc, fa, float(shadow_offset), float(shadow_tmin)))
+
+    def hit_normals(self):
+        """vkrh_scene_hit_normals: the loaded scene's normal table as the device holds it now, a numpy array of abi.hit_normal_dtype()"""
+        n = C.c_uint32(0)
+        self._check(lib().vkrh_scene_hit_normals(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, abi.hit_normal_dtype())
+        if n.value:
+            self._check(lib().vkrh_scene_hit_normals(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def set_ray_cutouts(self, enable=True, alpha_lod=0):
         """vkrh_set_ray_cutouts: whether the rays of STAGE_SHADOW_MASK_RT and STAGE_REFLECTIONS_RT pass through triangles whose albedo

@@ -262,6 +262,41 @@ struct PostFxFrame {
     reflection_rays.max_distance = max_distance > 0.f ? max_distance : 0.f; reflection_rays.texture_lod = texture_lod;
   }
 
+  // VKRH_STAGE_REFLECTIONS_RT: whether the hit of the mirror ray is lit and shadowed (vkrh_set_reflection_lights).  Default: off, the
+  // unlit albedo.  The default light is the direct diffuse term of defered_shading: its hard-coded light position, colour 10 / pi
+  // (with min(1 / ld2, 1) that kernel's rad / pi) and its ambient 0.6.
+  AdvancedSSR::RtLights reflection_lights {};
+  void set_reflection_lights(uint32_t count, const float* lights, const float* colours, const float* ambient, float shadow_offset, float shadow_tmin) {
+    refuse_tiled("vkrh_set_reflection_lights", "VKRH_STAGE_REFLECTIONS_RT runs on one GPU");
+    if (count > 4) throw std::runtime_error{"vkrh_set_reflection_lights: " + std::to_string(count) + " lights, at most 4"};
+    if (std::isnan(shadow_offset)) throw std::runtime_error{"vkrh_set_reflection_lights: shadow_offset is NaN"};
+    if (std::isnan(shadow_tmin)) throw std::runtime_error{"vkrh_set_reflection_lights: shadow_tmin is NaN"};
+    vkr_reflect_lights b {};
+    if (count == 1 && !lights && !colours && !ambient) {
+      const float pos[4] = {-1.85867f, 5.81832f, -0.247114f, 1.0f};
+      for (int k = 0; k < 4; k++) b.lights[0][k] = pos[k];
+      for (int k = 0; k < 3; k++) { b.colour[0][k] = 10.0f / 3.1415926535897932384626433832795f; b.ambient[k] = 0.6f; }
+    } else {
+      if ((count && (!lights || !colours)) || !ambient) throw std::runtime_error{"vkrh_set_reflection_lights: NULL argument (only count 1 with no array at all selects the default light)"};
+      for (uint32_t l = 0; l < count; l++) {
+        const float w = lights[4 * l + 3];
+        if (!(w == 0.0f || w == 1.0f))
+          throw std::runtime_error{"vkrh_set_reflection_lights: light " + std::to_string(l) + " has w = " + std::to_string(w) + ", expected 1 (a point light) or 0 (a directional light)"};
+        for (int k = 0; k < 4; k++) b.lights[l][k] = lights[4 * l + k];
+        for (int k = 0; k < 3; k++) {
+          if (std::isnan(colours[3 * l + k])) throw std::runtime_error{"vkrh_set_reflection_lights: colour " + std::to_string(l) + " is NaN"};
+          b.colour[l][k] = colours[3 * l + k];
+        }
+      }
+      for (int k = 0; k < 3; k++) {
+        if (std::isnan(ambient[k])) throw std::runtime_error{"vkrh_set_reflection_lights: ambient is NaN"};
+        b.ambient[k] = ambient[k];
+      }
+    }
+    b.light_count = count; b.shadow_offset = shadow_offset; b.shadow_tmin = shadow_tmin;
+    reflection_lights.enable = true; reflection_lights.block = b;
+  }
+
   // VKRH_STAGE_SHADOW_MASK_RT and VKRH_STAGE_REFLECTIONS_RT: whether their rays see alpha cutouts (vkrh_set_ray_cutouts).  Default:
   // off, the opaque query.  VKRH_STAGE_GTAO_RT stays opaque, as the reference's rt_main.frag is.
   RtCutouts ray_cutouts {};
@@ -445,7 +480,7 @@ struct PostFxFrame {
       std::copy(shadow_area_radii.begin(), shadow_area_radii.end(), radii);
       pass.update_rt_soft(radii, shadow_area_samples, shadow_area_pattern);
       if (ray_cutouts.enable && scene_renderer)
-        pass.run_rt(graph, gbuffer.depth, gbuffer.normal, AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()},
+        pass.run_rt(graph, gbuffer.depth, gbuffer.normal, AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images(), nullptr},
                     ray_cutouts, shadow_mask_tex);
       else
         pass.run_rt(graph, gbuffer.depth, gbuffer.normal, scene_as->tlas, shadow_mask_tex);
@@ -489,7 +524,8 @@ struct PostFxFrame {
       const bool classified = ssr.get_settings().use_tile_classification;  // fill mode traces with the plain trace; the setting is the SSR stages'
       ssr.get_settings().use_tile_classification = false;
       ssr.run_rt(graph, assr_params, draw_params, gbuffer, gtao.raw,
-                 AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images()}, rt, ray_cutouts);
+                 AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images(), scene_as->hit_normals}, rt, ray_cutouts,
+                 reflection_lights);
       ssr.get_settings().use_tile_classification = classified;
     }
     if (mask & VKRH_STAGE_GTAO_MAIN_ONLY)
@@ -1516,6 +1552,22 @@ int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_off
 }
 int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count, uint32_t sample_count, uint32_t pattern_side) {
   return guarded([&] { frame_ref(frame).set_shadow_area_lights(radii, count, sample_count, pattern_side); });
+}
+int vkrh_set_reflection_lights(void* frame, uint32_t count, const float* lights, const float* colours, const float* ambient, float shadow_offset,
+                               float shadow_tmin) {
+  return guarded([&] { frame_ref(frame).set_reflection_lights(count, lights, colours, ambient, shadow_offset, shadow_tmin); });
+}
+int vkrh_scene_hit_normals(void* frame, vkr_hit_normal* out, uint32_t capacity, uint32_t* count) {
+  return guarded([&] {
+    auto* f = &frame_ref(frame);
+    if (!count) throw std::runtime_error{"vkrh_scene_hit_normals: NULL argument"};
+    if (!f->scene_as) throw std::runtime_error{"vkrh_scene_hit_normals: without a loaded scene (vkrh_load_scene)"};
+    const std::vector<vkr_hit_normal> table = f->scene_as->download_hit_normals(f->graph.get_stream());
+    *count = (uint32_t)table.size();
+    if (!out) return;  // the size alone
+    if (table.size() > capacity) throw std::runtime_error{"vkrh_scene_hit_normals: " + std::to_string(table.size()) + " records do not fit into " + std::to_string(capacity)};
+    if (!table.empty()) std::memcpy(out, table.data(), sizeof(vkr_hit_normal) * table.size());
+  });
 }
 int vkrh_set_ray_cutouts(void* frame, uint32_t enable, uint32_t alpha_lod) { return guarded([&] { frame_ref(frame).set_ray_cutouts(enable, alpha_lod); }); }
 int vkrh_set_draw_transforms(void* frame, const float* transforms, uint32_t count) {

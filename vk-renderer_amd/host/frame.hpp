@@ -196,6 +196,21 @@ int vkrh_set_shadow_mask_filter(void* frame, uint32_t reach, float normal_min_do
  * texture_lod of its albedo texture (clamped to the chain).  Defaults: fill_misses 0, normal_offset 1e-3 and tmin 0 (those of
  * vkrh_set_shadow_rays), max_distance = the camera's zfar (also what max_distance <= 0 selects), texture_lod 0.  Not on a tiled frame. */
 int vkrh_set_reflection_rays(void* frame, uint32_t fill_misses, float normal_offset, float tmin, float max_distance, uint32_t texture_lod);
+/* Lit hits in VKRH_STAGE_REFLECTIONS_RT: after this call the stage records vkr_reflections_rt_lit (with
+ * vkrh_set_ray_cutouts: vkr_reflections_rt_lit_cutout) under the task name "ReflectionsRTLit" where "ReflectionsRT" stood: the hit of
+ * the mirror ray is lit by `count` (0..4) lights — lights: count x 4 floats in the convention of vkrh_set_shadow_rays, colours: count x 3
+ * floats — shadowed by one ray per light from the hit (its origin moved by shadow_offset along the hit's normal, t in [shadow_tmin, 1])
+ * and stored as albedo x (ambient (3 floats) + the sum).  count 1 with lights, colours and ambient all NULL selects the default light:
+ * the direct diffuse term of defered_shading (its light position, colour 10 / pi, ambient 0.6).  The normal table comes from the
+ * loaded scene and follows vkrh_set_draw_transforms.  Off until called: no stage bit, and a frame that never calls it records the
+ * tasks and bytes it always did.  Composes with vkrh_set_reflection_rays (both modes) and vkrh_set_ray_cutouts.  An error: more than 4
+ * lights, a NULL array otherwise, a light whose w is neither 0 nor 1, a NaN anywhere.  Not on a tiled frame.                        */
+int vkrh_set_reflection_lights(void* frame, uint32_t count, const float* lights, const float* colours, const float* ambient, float shadow_offset,
+                               float shadow_tmin);
+/* For tests and tools: the normal table of the loaded scene as it is on the device now (one vkr_hit_normal per triangle of the
+ * ray-query structure, in its order; after vkrh_set_draw_transforms the moved one).  *count: the number of records; out may be NULL to
+ * ask for it alone.  Synchronises the frame's stream.                                                                               */
+int vkrh_scene_hit_normals(void* frame, vkr_hit_normal* out, uint32_t capacity, uint32_t* count);
 /* Alpha cutouts in the rays of VKRH_STAGE_SHADOW_MASK_RT and VKRH_STAGE_REFLECTIONS_RT: with enable != 0 the two
  * stages record vkr_shadow_mask_rt_cutout / vkr_reflections_rt_cutout, whose rays pass through a triangle where the alpha of its albedo
  * texture at the hit (level alpha_lod, clamped to the chain) is exactly 0, as the rasteriser discards such a fragment; textures

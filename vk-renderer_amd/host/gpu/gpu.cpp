@@ -816,7 +816,10 @@ void register_hot_path_programs() {
     // ---- ray-traced reflections (AdvancedSSR::run_reflections_rt_pass; no reference program) ----
     // set {0 depth (mip 0 of the view), 1 normal, 2 rays (bound only in fill mode), 3 acceleration structure, 4 the attribute table,
     // 5 vkr_reflect_rt_params, 6 reflections (storage), 7 the scene's textures[]}; the texture table goes into the context's workspace.
-    // "reflections_rt_cutout": the same set and 8 vkr_ray_cutout
+    // "reflections_rt_cutout": the same set and 8 vkr_ray_cutout.
+    // Lit hits: a set that also binds 9 the normal table (one vkr_hit_normal per record of the attribute table) and
+    // 10 vkr_reflect_lights makes either program record vkr_reflections_rt_lit / vkr_reflections_rt_lit_cutout: "reflections_rt_lit"
+    // and "reflections_rt_lit_cutout" are the same two programs on the larger set, not further rows of the table
     for (const bool cutouts : {false, true})
       create_program(cutouts ? "reflections_rt_cutout" : "reflections_rt", [=](LaunchState& st) {
         const char* P = cutouts ? "reflections_rt_cutout" : "reflections_rt";
@@ -830,6 +833,21 @@ void register_hot_path_programs() {
         const uint32_t count = (uint32_t)h.textures.size();
         const uint64_t bytes = vkr_reflections_rt_scratch_bytes(count);
         const vkr_img* textures = h.textures.empty() ? nullptr : h.textures.data();
+        if (st.set->slots[10].kind == SetSlot::Ubo) {  // lit
+          const char* L = cutouts ? "reflections_rt_lit_cutout" : "reflections_rt_lit";
+          const SetSlot& nt = st.set->slots[9];
+          if (nt.kind != SetSlot::Ubo || !nt.buffer) throw std::runtime_error{std::string{L} + ": normal table (binding 9) is not bound"};
+          if (nt.buffer->get_size() < sizeof(vkr_hit_normal) * (uint64_t)h.attrib_count) throw std::runtime_error{std::string{L} + ": the normal table is smaller than the attribute table"};
+          const vkr_hit_normal* normals = (const vkr_hit_normal*)nt.buffer->device_ptr(st.stream);
+          static_assert(sizeof(vkr_reflect_lights) == 176, "vkr_reflect_lights: nine float4 and eight words");
+          const vkr_reflect_lights* lights = ubo<vkr_reflect_lights>(st, 10, L);
+          if (!cutouts)
+            return vkr_reflections_rt_lit(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, normals, h.attrib_count, textures, count,
+                                          params, lights, &out, st.require_workspace(bytes), bytes, st.stream);
+          const vkr_ray_cutout c = cutout_block(st, 8, h, L);
+          return vkr_reflections_rt_lit_cutout(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, normals, h.attrib_count, textures,
+                                               count, params, lights, &c, &out, st.require_workspace(bytes), bytes, st.stream);
+        }
         if (!cutouts)
           return vkr_reflections_rt(&depth, &normal, fill ? &rays : nullptr, h.accel, h.attribs, h.attrib_count, textures, count, params, &out,
                                     st.require_workspace(bytes), bytes, st.stream);

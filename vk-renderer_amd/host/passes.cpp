@@ -776,9 +776,10 @@ vkr_reflect_rt_params AdvancedSSR::reflect_rt_params(const AdvancedSSRParams &pa
 // task "ReflectionsRT": set {0 depth (mip 1 of the image: mip 0 of the view), 1 the half-resolution normals, 2 rays (only with
 // fill_misses), 3 the acceleration structure, 4 its attribute table, 5 the block, 6 reflections (storage), 7 the scene's textures[]},
 // one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels of reflections.  Written out instead of rec::compute because of
-// the array of images, which is no graph resource (as in ProbeRenderer's cube pass)
+// the array of images, which is no graph resource (as in ProbeRenderer's cube pass).  Task "ReflectionsRTLit" (lights.enable): the
+// same set, 9 the normal table and 10 the lights: on that set the two programs record the lit entries (gpu/gpu.cpp)
 void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
-  const RtSettings &rt, const RtCutouts &cutouts)
+  const RtSettings &rt, const RtCutouts &cutouts, const RtLights &lights)
 {
   if (!scene.tlas)
     throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: null acceleration structure (tlas): build scene::SceneAccelerationStructure first"};
@@ -786,6 +787,8 @@ void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRP
     throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: no attribute table: build scene::SceneAccelerationStructure first"};
   if (gbuff.tiled)
     throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: on a window of the frame (the rays reach anywhere: a single-GPU pass)"};
+  if (lights.enable && !scene.hit_normals)
+    throw std::runtime_error {"AdvancedSSR::run_reflections_rt_pass: no normal table: build scene::SceneAccelerationStructure first"};
   if (!reflections_rt_pass.has_program()) reflections_rt_pass = gpu::create_compute_pipeline("reflections_rt");
   std::vector<rec::Binding> bindings {rec::sampled_mips(0, gbuff.depth, sampler, DEPTH, 1, 1), rec::sampled(1, gbuff.downsampled_normals, sampler)};
   if (rt.fill_misses) bindings.push_back(rec::sampled(2, rays, sampler));
@@ -795,11 +798,12 @@ void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRP
     if (!reflections_rt_cutout_pass.has_program()) reflections_rt_cutout_pass = gpu::create_compute_pipeline("reflections_rt_cutout");
     bindings.push_back(rec::uniform(8, vkr_ray_cutout {cutouts.alpha_lod, 0u}));
   }
+  if (lights.enable) bindings.insert(bindings.end(), {rec::uniform_buffer(9, scene.hit_normals), rec::uniform(10, lights.block)});
   struct Data { std::vector<rec::Bound> bound; };
   const auto pipeline = cutouts.enable ? reflections_rt_cutout_pass : reflections_rt_pass;
   const auto textures = scene.textures;
   const auto sized_by = reflections;
-  graph.add_task<Data>("ReflectionsRT",
+  graph.add_task<Data>(lights.enable ? "ReflectionsRTLit" : "ReflectionsRT",
     [&](Data &d, rendergraph::RenderGraphBuilder &builder) { d.bound = rec::declare(bindings, builder, VK_SHADER_STAGE_COMPUTE_BIT); },
     [=](Data &d, rendergraph::RenderResources &resources, gpu::CmdContext &cmd) {
       VkDescriptorSet set = rec::write(d.bound, resources, cmd);
@@ -812,13 +816,13 @@ void AdvancedSSR::run_reflections_rt_pass(RenderGraph &graph, const AdvancedSSRP
 }
 
 void AdvancedSSR::run_rt(RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
-  ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts)
+  ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts, const RtLights &lights)
 {
   if (rt.fill_misses) {
     run_trace(graph, params, gbuff, ssr_occlusion);
     run_filter_pass(graph, params, gbuff);
   }
-  run_reflections_rt_pass(graph, params, gbuff, scene, rt, cutouts);
+  run_reflections_rt_pass(graph, params, gbuff, scene, rt, cutouts, lights);
   run_blur_pass(graph, params, taa_params, gbuff);
 }
 
@@ -1201,6 +1205,7 @@ SceneAccelerationStructure::~SceneAccelerationStructure() {
 void SceneAccelerationStructure::build(gpu::TransferCmdPool &transfer_pool, const CompiledScene &source) {  // scene_as.cpp:19-24
   blas_triangles.clear();
   blas_attributes.clear();
+  blas_normals.clear();
   for (const auto &mesh : source.root_meshes) build_blas(transfer_pool, mesh, source);
   build_tlas(transfer_pool, source);
 }
@@ -1210,7 +1215,7 @@ void SceneAccelerationStructure::build_blas(gpu::TransferCmdPool &, const BaseMe
   const auto *indices = (const uint32_t *)source.index_buffer->host_data();
   const uint64_t vertex_count = vertices ? source.vertex_buffer->get_size() / sizeof(Vertex) : 0;
   const uint64_t index_count = indices ? source.index_buffer->get_size() / sizeof(uint32_t) : 0;
-  std::vector<float> tris;
+  std::vector<float> tris, normals;
   std::vector<vkr_hit_attrib> attribs;
   for (const auto &prim : mesh.primitives) {  // scene_as.cpp:60-70: primitiveCount = index_count / 3, firstVertex = vertex_offset
     if (uint64_t(prim.index_offset) + prim.index_count > index_count)
@@ -1223,6 +1228,7 @@ void SceneAccelerationStructure::build_blas(gpu::TransferCmdPool &, const BaseMe
         const uint64_t v = uint64_t(prim.vertex_offset) + indices[prim.index_offset + j + k];
         if (v >= vertex_count) throw std::runtime_error {"SceneAccelerationStructure: an index names a vertex outside the vertex buffer"};
         tris.insert(tris.end(), {vertices[v].pos.x, vertices[v].pos.y, vertices[v].pos.z});
+        normals.insert(normals.end(), {vertices[v].norm.x, vertices[v].norm.y, vertices[v].norm.z});
         a.uv[k][0] = vertices[v].uv.x; a.uv[k][1] = vertices[v].uv.y;
       }
       attribs.push_back(a);
@@ -1230,6 +1236,7 @@ void SceneAccelerationStructure::build_blas(gpu::TransferCmdPool &, const BaseMe
   }
   blas_triangles.push_back(std::move(tris));
   blas_attributes.push_back(std::move(attribs));
+  blas_normals.push_back(std::move(normals));
 }
 
 namespace {
@@ -1246,6 +1253,7 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
   for (const auto &node : source.base_nodes) flatten_nodes(nodes, node, glm::mat4 {1.f});
   world_triangles.clear();
   world_attributes.clear();
+  world_normals.clear();
   for (const auto &n : nodes) {
     if (size_t(n.mesh) >= blas_triangles.size()) throw std::runtime_error {"SceneAccelerationStructure: a node names a mesh without a structure (build_blas first)"};
     const glm::mat4 &m = n.transform;  // m[column][row]
@@ -1258,6 +1266,22 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
         const float p0 = m[0][row] * x, p1 = m[1][row] * y, p2 = m[2][row] * z;
         const float s01 = p0 + p1, s012 = s01 + p2;
         world_triangles.push_back(s012 + m[3][row]);
+      }
+    }
+    if (size_t(n.mesh) < blas_normals.size()) {  // the normal matrix of SceneRenderer::update_scene, no translation
+      const glm::mat4 nm = glm::transpose(glm::inverse(m));
+      const auto &nrm = blas_normals[n.mesh];
+      for (size_t i = 0; i + 9 <= nrm.size(); i += 9) {
+        vkr_hit_normal r {};
+        for (int k = 0; k < 3; k++) {
+          const float x = nrm[i + 3 * k], y = nrm[i + 3 * k + 1], z = nrm[i + 3 * k + 2];
+          for (int row = 0; row < 3; row++) {
+            const float p0 = nm[0][row] * x, p1 = nm[1][row] * y, p2 = nm[2][row] * z;
+            const float s01 = p0 + p1;
+            r.n[k][row] = s01 + p2;
+          }
+        }
+        world_normals.push_back(r);
       }
     }
   }
@@ -1275,6 +1299,14 @@ void SceneAccelerationStructure::build_tlas(gpu::TransferCmdPool &, const Compil
   hit_attributes = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, std::max<uint64_t>(bytes, sizeof(vkr_hit_attrib)), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
   std::memset(hit_attributes->get_mapped_ptr(), 0, hit_attributes->get_size());  // an empty scene: one unused record (a buffer has no size 0)
   if (bytes) std::memcpy(hit_attributes->get_mapped_ptr(), world_attributes.data(), bytes);
+  // the normal table of the lit consumers, with it
+  hit_normals.reset();
+  if (world_normals.size() != world_triangles.size() / 9)
+    throw std::runtime_error {"SceneAccelerationStructure: the normal table does not match the triangles (build_blas before build_tlas)"};
+  const uint64_t normal_bytes = sizeof(vkr_hit_normal) * world_normals.size();
+  hit_normals = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, std::max<uint64_t>(normal_bytes, sizeof(vkr_hit_normal)), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+  std::memset(hit_normals->get_mapped_ptr(), 0, hit_normals->get_size());
+  if (normal_bytes) std::memcpy(hit_normals->get_mapped_ptr(), world_normals.data(), normal_bytes);
   refit_triangles.reset();  // another structure: the first refit() allocates for it
   refit_scratch.reset();
 }
@@ -1290,7 +1322,8 @@ void SceneAccelerationStructure::refit(const CompiledScene &source, void *stream
   for (size_t i = 0; i < nodes.size(); i++) {
     if (size_t(nodes[i].mesh) >= source.root_meshes.size()) throw std::runtime_error {"SceneAccelerationStructure::refit: a node names a mesh the scene does not have"};
     std::memcpy(transforms[i].model.m, &nodes[i].transform, sizeof(transforms[i].model.m));
-    std::memset(transforms[i].normal.m, 0, sizeof(transforms[i].normal.m));  // not read
+    const glm::mat4 normal = glm::transpose(glm::inverse(nodes[i].transform));  // as build_tlas(): read by vkr_scene_triangle_normals
+    std::memcpy(transforms[i].normal.m, &normal, sizeof(transforms[i].normal.m));
     for (const auto &prim : source.root_meshes[nodes[i].mesh].primitives) {
       vkr_raster_draw d {};
       d.transform_index = uint32_t(i);
@@ -1322,6 +1355,20 @@ void SceneAccelerationStructure::refit(const CompiledScene &source, void *stream
   if (vkr_scene_triangles(&scene, moved, triangles, refit_scratch->device_ptr(stream), scratch_bytes, stream) != 0 ||
       vkr_accel_refit((vkr_accel *)tlas, moved, stream) != 0)
     throw std::runtime_error {std::string {"SceneAccelerationStructure::refit: "} + vkr_last_error()};
+  // the normals move with the draws; the two launches read the draw table one after the other on the stream, each after its own
+  // upload of it
+  if (hit_normals &&
+      vkr_scene_triangle_normals(&scene, (vkr_hit_normal *)hit_normals->device_ptr(stream), triangles, refit_scratch->device_ptr(stream), scratch_bytes, stream) != 0)
+    throw std::runtime_error {std::string {"SceneAccelerationStructure::refit: "} + vkr_last_error()};
+}
+
+std::vector<vkr_hit_normal> SceneAccelerationStructure::download_hit_normals(void *stream) {
+  std::vector<vkr_hit_normal> out(world_triangles.size() / 9);
+  if (out.empty() || !hit_normals) return out;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
+      hipMemcpy(out.data(), hit_normals->device_ptr(stream), sizeof(vkr_hit_normal) * out.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error {"SceneAccelerationStructure::download_hit_normals: the copy failed"};
+  return out;
 }
 
 std::vector<float> SceneAccelerationStructure::download_world_triangles(void *stream) {

@@ -416,6 +416,14 @@ struct RtCutouts {
   uint32_t alpha_lod {0};
 };
 
+// Lit hits of AdvancedSSR::run_rt (its two programs on a set that also binds the normal table and the lights): with
+// `enable` the hit of the mirror ray is lit by block.lights, shadowed by one ray per light and stored as albedo x (ambient + the sum);
+// the task is then "ReflectionsRTLit".  AdvancedSSR::RtLights names it.
+struct RtLights {
+  bool enable {false};
+  vkr_reflect_lights block {};
+};
+
 struct AdvancedSSR {
   void render_ui();  // advanced_ssr.cpp:556-567; headless: the ImGui names are inert (imgui_pass.hpp), use get_settings()
 
@@ -486,7 +494,9 @@ struct AdvancedSSR {
     VkAccelerationStructureKHR tlas {nullptr};  // scene::SceneAccelerationStructure::tlas
     gpu::BufferPtr hit_attributes;              // ... ::hit_attributes: one vkr_hit_attrib per triangle of the structure
     std::vector<std::pair<VkImageView, VkSampler>> textures;  // SceneRenderer::get_images(): what albedo_index indexes
+    gpu::BufferPtr hit_normals;                 // ... ::hit_normals: one vkr_hit_normal per triangle; only a lit pass binds it
   };
+  using RtLights = ::RtLights;
   struct RtSettings {
     bool fill_misses {false};
     float normal_offset {1e-3f}, tmin {0.f};  // the offsets of ShadowMaskPass::run_rt
@@ -498,11 +508,12 @@ struct AdvancedSSR {
   // fill_misses: SSSR_trace -> SSSR_filter -> ReflectionsRT (in place on `reflections`, reading `rays`) -> SSSR_blur; everything the
   // trace writes for GTAO is as in run().
   void run_rt(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const DrawTAAParams &taa_params, const Gbuffer &gbuff,
-    rendergraph::ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts = {});
+    rendergraph::ImageResourceId ssr_occlusion, const RtScene &scene, const RtSettings &rt, const RtCutouts &cutouts = {},
+    const RtLights &lights = {});
   // task "ReflectionsRT": depth mip 1, the half-resolution normals, (fill_misses: rays,) the structure, its attributes, the scene's
-  // textures and the block -> reflections
+  // textures and the block -> reflections; with lights.enable task "ReflectionsRTLit": the same, the normal table and the lights
   void run_reflections_rt_pass(rendergraph::RenderGraph &graph, const AdvancedSSRParams &params, const Gbuffer &gbuff, const RtScene &scene,
-    const RtSettings &rt, const RtCutouts &cutouts = {});
+    const RtSettings &rt, const RtCutouts &cutouts = {}, const RtLights &lights = {});
   static vkr_reflect_rt_params reflect_rt_params(const AdvancedSSRParams &params, const RtSettings &rt);
 
 private:

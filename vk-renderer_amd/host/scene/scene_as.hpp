@@ -37,7 +37,9 @@ struct SceneAccelerationStructure {
   // vertex and index buffers (one draw per primitive, node by node, within a node the mesh's primitives in order: the order of
   // build_tlas(); the model matrices travel in a table of the structure's own), and `tlas` is refitted to them, all on `stream`
   // and without a synchronisation.  Only transforms may have changed since build(): another number of triangles is an error (the
-  // escape is build()).  hit_attributes is untouched: uvs and textures do not move.
+  // escape is build()).  hit_attributes is untouched: uvs and textures do not move.  hit_normals moves with the draws:
+  // vkr_scene_triangle_normals recomputes it in place from the same draw list, with transpose(inverse(transform)) of every node as
+  // its normal matrix, on `stream` like the triangles.
   void refit(const CompiledScene &source, void *stream);
   // the triangles the structure holds on the device after the last refit(), 9 floats per triangle in the order of
   // world_triangles (synchronises `stream`); before any refit() it is world_triangles
@@ -56,6 +58,17 @@ struct SceneAccelerationStructure {
   std::vector<std::vector<vkr_hit_attrib>> blas_attributes;
   std::vector<vkr_hit_attrib> world_attributes;
   gpu::BufferPtr hit_attributes;
+
+  // What a lit hit needs besides (program "reflections_rt_lit"): one vkr_hit_normal per triangle, in the order of world_triangles —
+  // the world-space normals of its three vertices, transpose(inverse(node transform)) * norm per row as (m0 x + m1 y) + m2 z in
+  // fp32, not normalised (vkr_scene_triangle_normals' rule, which refit() applies on the device; vk-renderer_amd/abi.py
+  // scene_triangle_normals() restates it in numpy).  blas_normals: per mesh, object space, 9 floats per triangle; hit_normals: the
+  // table on the device, made by build_tlas() (one unused record for a scene without triangles).
+  std::vector<std::vector<float>> blas_normals;
+  std::vector<vkr_hit_normal> world_normals;
+  gpu::BufferPtr hit_normals;
+  // the table as it is on the device now (synchronises `stream`)
+  std::vector<vkr_hit_normal> download_hit_normals(void *stream);
 
   // refit(): the moved triangles and the draw table of vkr_scene_triangles, on the device, allocated by the first refit()
   gpu::BufferPtr refit_triangles, refit_scratch;
