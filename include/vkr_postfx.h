@@ -887,6 +887,45 @@ typedef struct vkr_shadow_filter_params {   /* 96 bytes */
 int vkr_shadow_mask_filter(const vkr_img* depth, const vkr_img* normal, const vkr_img* mask, const vkr_shadow_filter_params* params,
                            const vkr_img* out_mask, void* stream);
 
+/* ---- the temporal accumulation of the shadow mask (DESIGN_NUMERICS.md, "Shadow mask, temporal accumulation") ----------------------
+ * No reference program.  The running mean of the mask over the frames in which a pixel saw the same world point: what makes the
+ * sample patterns of consecutive frames (vkr_shadow_disk_samples_frame) one larger pattern.  It runs after the mask and before
+ * vkr_shadow_mask_filter.                                                                                                        */
+typedef struct vkr_shadow_accum_params {   /* 160 bytes */
+  vkr_mat4 inverse_camera;                 /* view -> world, this frame (as vkr_shadow_rt_params) */
+  vkr_mat4 prev_inverse_camera;            /* view -> world, the frame that wrote prev_depth and the history */
+  float    fovy, aspect, znear, zfar;      /* one lens for both frames, as vkr_gtao_accumulate assumes */
+  uint32_t max_count;                      /* 1..255: the history weighs at most max_count - 1 frames; 1 copies the mask */
+  float    plane_tolerance;                /* as vkr_shadow_filter_params.plane_tolerance */
+  uint32_t reset;                          /* 0 or 1: 1 = no pixel has a history (camera cut, moved light) */
+  uint32_t reserved;                       /* 0 */
+} vkr_shadow_accum_params;
+/* depth, prev_depth: D24_UNORM_S8 (mip 0 of the view); normal: RG16_UNORM; velocity: RG16_SFLOAT (prev_uv - uv); mask, out_mask:
+ * RGBA8_UNORM; history, out_history: RGBA16_UNORM (the running mean per light in 65535ths: a mask code m is 257 m); history_count,
+ * out_count: R8_UNORM (the raw byte is the number n of frames in the mean, 0 = none); whole frames of one extent w x h.  Per pixel g:
+ * m = mask[g]; d_g, uv_g, view_g, W_g, n_g as vkr_shadow_mask_filter has them; vel = the exact decode of velocity texel g;
+ * p = uv_g + vel, f = (p.x * (float)w, p.y * (float)h), every operation rounded on its own; q = floor(f), inside when
+ * 0 <= f.x < w and 0 <= f.y < h on the floats (a compare with a NaN is false).  The history of g is valid when reset == 0,
+ * d_g < 1, q is inside, n = history_count[q] >= 1, d_q = prev_depth[q] < 1 and
+ * |dot(n_g, W'_q - W_g)| <= plane_tolerance * |view_g.z| with W'_q = prev_inverse_camera * (reconstruct_view_vec(uv_q, d_q), 1),
+ * subtraction, dot and bound as in the filter's plane test (a NaN: invalid).  In unsigned integers per channel c: without a valid
+ * history n' = 1 and H'_c = 257 m_c; with one n' = min(n, max_count - 1) + 1 and H'_c = (H_c (n' - 1) + 257 m_c + (n' >> 1)) / n',
+ * H = history[q].  out_history[g] = H', out_count[g] = n', out_mask[g].c = (255 H'_c + 32767) / 65535.  Every texel of the three
+ * outputs is written, nothing outside them.
+ * Refused before any launch: a NULL argument, a descriptor without memory, other formats, different extents, an extent above
+ * 65535, a windowed descriptor anywhere (the reprojection reaches across strips: a single-GPU pass), max_count outside 1..255,
+ * reset > 1, reserved != 0, plane_tolerance NaN, an output whose memory overlaps another image's — but mask and out_mask may be
+ * one image (same memory, same pitch): a pixel reads and writes only its own texel of them.                                      */
+int vkr_shadow_mask_accumulate(const vkr_img* depth, const vkr_img* normal, const vkr_img* velocity, const vkr_img* prev_depth,
+                               const vkr_img* mask, const vkr_img* history, const vkr_img* history_count,
+                               const vkr_shadow_accum_params* params,
+                               const vkr_img* out_history, const vkr_img* out_count, const vkr_img* out_mask, void* stream);
+/* Host only: vkr_shadow_disk_samples for frame `frame` of a cycle of T = frame_count frames: the same layout and rho,
+ * phi = k * 2.399963229728653 + 2 pi * (((7 p) mod P^2) * T + (frame mod T)) / (P^2 * T): the T tables together are P^2 * T evenly
+ * spaced rotations, and T == 1 gives the floats of vkr_shadow_disk_samples bit for bit.  Nothing is written for a NULL out,
+ * S outside 1..64, P not 1, 2 or 4, or T outside 1..64.                                                                         */
+void vkr_shadow_disk_samples_frame(uint32_t sample_count, uint32_t pattern_side, uint32_t frame, uint32_t frame_count, float* out);
+
 /* ---- octahedral probes (probe_renderer.{hpp,cpp}: programs cubemap_probe, cube2oct, probe_downsample, trace_probe) ------------------------
  * Array images follow vkr_deinterleave_depth: one descriptor per layer.  The layers of one array must share format, extent,
  * mip count and pitches, and lie at regular distances: for every mip m, layer l starts at layer 0's mip m plus l times one
@@ -1111,6 +1150,9 @@ int vkr_selftest_sqrt(uint32_t* device_counters2, void* stream);
  * float_to_srgb8_fast: an arithmetic estimate of the code corrected by one threshold compare) differs from the binary search
  * of the blit and the mips (float_to_srgb8_lds).                                                                   */
 int vkr_selftest_srgb_encode(uint32_t* device_counter, void* stream);
+/* Test hook: counts (into one device uint32, zeroed by the caller) the pairs (numerator < 2^24, n' in 1..255) — all of them — for
+ * which the division of vkr_shadow_mask_accumulate (an fp32 reciprocal estimate corrected by its remainder) differs from '/'.  */
+int vkr_selftest_accum_division(uint32_t* device_counter, void* stream);
 
 #ifdef __cplusplus
 }

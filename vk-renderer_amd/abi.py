@@ -281,6 +281,17 @@ class ShadowFilterParams(C.Structure):  # vkr_shadow_filter_params, 96 bytes
                 ("reach", C.c_uint32), ("normal_min_dot", C.c_float), ("plane_tolerance", C.c_float), ("reserved", C.c_uint32)]
 
 
+# ---- the temporal accumulation of the shadow mask ----
+# the defaults of the frame and the chain (DESIGN.md 7.16 says what they rest on): the history weighs at most max_count - 1 frames,
+# the sample patterns cycle over pattern_frames tables
+SHADOW_ACCUM_MAX_COUNT, SHADOW_ACCUM_PATTERN_FRAMES = 8, 8
+
+
+class ShadowAccumParams(C.Structure):  # vkr_shadow_accum_params, 160 bytes
+    _fields_ = [("inverse_camera", Mat4), ("prev_inverse_camera", Mat4), ("fovy", C.c_float), ("aspect", C.c_float), ("znear", C.c_float),
+                ("zfar", C.c_float), ("max_count", C.c_uint32), ("plane_tolerance", C.c_float), ("reset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # ---- the closest-hit ray query and program reflections_rt ----
 ACCEL_MISS = 0xFFFFFFFF  # vkr_accel_hit.index of a ray that hits nothing
 
@@ -503,6 +514,13 @@ def product():
         # the edge-aware filter of the shadow mask (checked against the numpy restatement tests/shadow_mask_filter_reference.py)
         lib.vkr_shadow_mask_filter.argtypes = [_IMG, _IMG, _IMG, P(ShadowFilterParams), _IMG, C.c_void_p]
         lib.vkr_shadow_mask_filter.restype = C.c_int
+        # the temporal accumulation of the shadow mask (checked against tests/shadow_mask_accumulate_reference.py)
+        lib.vkr_shadow_mask_accumulate.argtypes = [_IMG] * 7 + [P(ShadowAccumParams)] + [_IMG] * 3 + [C.c_void_p]
+        lib.vkr_shadow_mask_accumulate.restype = C.c_int
+        lib.vkr_shadow_disk_samples_frame.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.vkr_shadow_disk_samples_frame.restype = None
+        lib.vkr_selftest_accum_division.argtypes = [C.c_void_p, C.c_void_p]
+        lib.vkr_selftest_accum_division.restype = C.c_int
         # octahedral probes (checked against the numpy restatement of tests/test_probe_gpu.py); array images: per-layer descriptors
         lib.vkr_cube2oct.argtypes = [_IMG, _IMG, _IMG, _IMG, C.c_void_p]
         lib.vkr_probe_downsample.argtypes = [_IMG, C.c_void_p]
@@ -902,6 +920,42 @@ def shadow_mask_filter(depth, normal, mask, params, out_mask, stream=None):
     lib = product()
     ref = lambda d: C.byref(d) if d is not None else None
     check(lib.vkr_shadow_mask_filter(ref(depth), ref(normal), ref(mask), ref(params), ref(out_mask), stream), lib)
+
+
+def shadow_accum_params(inverse_camera, prev_inverse_camera, fovy, aspect, znear, zfar, max_count=SHADOW_ACCUM_MAX_COUNT,
+                        plane_tolerance=SHADOW_FILTER_PLANE_TOLERANCE, reset=False):
+    """ShadowAccumParams from the view -> world matrices of this frame and of the frame that wrote prev_depth and the history (4x4,
+    maths convention), the camera's four floats, max_count (the history weighs at most max_count - 1 frames), the tolerance of
+    the plane test and whether no pixel has a history.  Everything is passed on as given (the entry refuses what it does not take)."""
+    p = ShadowAccumParams()
+    p.inverse_camera, p.prev_inverse_camera = Mat4.from_np(inverse_camera), Mat4.from_np(prev_inverse_camera)
+    p.fovy, p.aspect, p.znear, p.zfar = float(fovy), float(aspect), float(znear), float(zfar)
+    p.max_count, p.plane_tolerance, p.reset, p.reserved = int(max_count), float(plane_tolerance), int(reset), 0
+    return p
+
+
+def shadow_mask_accumulate(depth, normal, velocity, prev_depth, mask, history, history_count, params, out_history, out_count, out_mask, stream=None):
+    """vkr_shadow_mask_accumulate: out_history (RGBA16_UNORM), out_count (R8_UNORM) and out_mask (RGBA8_UNORM) := per pixel the
+    running mean of `mask` (RGBA8_UNORM) with the `history` / `history_count` of the texel its `velocity` (RG16_SFLOAT) points at,
+    where `prev_depth` through params.prev_inverse_camera lies on the pixel's surface as `depth` (D24_UNORM_S8, mip 0) and `normal`
+    (RG16_UNORM) tell it; all VkrImg of one extent, under `params` (ShadowAccumParams, e.g. shadow_accum_params(...)).  Raises
+    RuntimeError with the library's message on a refusal."""
+    lib = product()
+    ref = lambda d: C.byref(d) if d is not None else None
+    check(lib.vkr_shadow_mask_accumulate(ref(depth), ref(normal), ref(velocity), ref(prev_depth), ref(mask), ref(history), ref(history_count),
+                                         ref(params), ref(out_history), ref(out_count), ref(out_mask), stream), lib)
+
+
+def shadow_disk_samples_frame(sample_count, pattern_side, frame, frames):
+    """vkr_shadow_disk_samples_frame: the table of shadow_disk_samples for frame `frame` of a cycle of `frames`:
+    float32 [pattern_side^2, sample_count, 2]; frames == 1 is shadow_disk_samples bit for bit"""
+    import numpy as np
+
+    if not (1 <= int(sample_count) <= 64 and int(pattern_side) in (1, 2, 4) and 1 <= int(frames) <= 64):
+        raise RuntimeError(f"shadow_disk_samples_frame: sample_count {sample_count} (1..64), pattern_side {pattern_side} (1, 2 or 4), frames {frames} (1..64)")
+    out = np.zeros((int(pattern_side) ** 2, int(sample_count), 2), np.float32)
+    product().vkr_shadow_disk_samples_frame(int(sample_count), int(pattern_side), int(frame), int(frames), out.ctypes.data)
+    return out
 
 
 def reflections_rt_cutout(depth, normal, rays, accel, attribs, attrib_count, textures, texture_count, params, cutout, out_reflections, scratch,

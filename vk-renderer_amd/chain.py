@@ -523,6 +523,41 @@ class PostFxChain:
         p = abi.shadow_filter_params(self.setup.inv_view, *self.setup.fazz, reach, normal_min_dot=normal_min_dot, plane_tolerance=plane_tolerance)
         abi.shadow_mask_filter(self.depth.desc(0, 1), self.normal.desc(), self.shadow_mask_out.desc(), p, self.shadow_mask_filtered_out.desc(), self.stream)
 
+    def shadow_mask_accumulate(self, prev_depth, prev_inv_view, max_count=abi.SHADOW_ACCUM_MAX_COUNT,
+                               plane_tolerance=abi.SHADOW_FILTER_PLANE_TOLERANCE, velocity=None):
+        """vkr_shadow_mask_accumulate on this chain's depth, normal, velocity and shadow_mask_out (of shadow_mask or shadow_mask_rt)
+        with `prev_depth` (a D24_UNORM_S8 ImageBuf: the depth of the frame before) and `prev_inv_view` (that frame's view -> world
+        matrix) -> shadow_mask_accumulated_out (RGBA8_UNORM).  The chain keeps the ping-pong pair of histories
+        (shadow_history, RGBA16_UNORM) and counts (shadow_history_count, R8_UNORM), swapped after every call: they hold what the
+        call just wrote.  The first call and the first after reset() run with reset = 1.  velocity: another RG16_SFLOAT ImageBuf
+        than the chain's.
+        Product backend only: the expectation is the numpy restatement tests/shadow_mask_accumulate_reference.py."""
+        if self.backend != "product":
+            raise RuntimeError("PostFxChain.shadow_mask_accumulate: only the product backend has the entry vkr_shadow_mask_accumulate")
+        if self.tiled:
+            raise RuntimeError("PostFxChain.shadow_mask_accumulate: not on a window of the frame (the reprojection reaches across strips: a single-GPU pass)")
+        if not hasattr(self, "shadow_mask_out"):
+            raise RuntimeError("PostFxChain.shadow_mask_accumulate: no shadow_mask_out (run shadow_mask or shadow_mask_rt first)")
+        w, h = self.depth.width, self.depth.height
+        if not hasattr(self, "shadow_history"):
+            self.shadow_history, self._shadow_history_next = (ImageBuf(abi.FMT_RGBA16_UNORM, w, h, device=self.device) for _ in range(2))
+            self.shadow_history_count, self._shadow_history_count_next = (ImageBuf(abi.FMT_R8_UNORM, w, h, device=self.device) for _ in range(2))
+            self.shadow_mask_accumulated_out = ImageBuf(abi.FMT_RGBA8_UNORM, w, h, device=self.device)
+            self._shadow_history_reset = True
+        p = abi.shadow_accum_params(self.setup.inv_view, prev_inv_view, *self.setup.fazz, max_count=max_count, plane_tolerance=plane_tolerance,
+                                    reset=self._shadow_history_reset)
+        abi.shadow_mask_accumulate(self.depth.desc(0, 1), self.normal.desc(), (self.velocity if velocity is None else velocity).desc(), prev_depth.desc(0, 1),
+                                   self.shadow_mask_out.desc(), self.shadow_history.desc(), self.shadow_history_count.desc(), p,
+                                   self._shadow_history_next.desc(), self._shadow_history_count_next.desc(), self.shadow_mask_accumulated_out.desc(),
+                                   self.stream)
+        self.shadow_history, self._shadow_history_next = self._shadow_history_next, self.shadow_history
+        self.shadow_history_count, self._shadow_history_count_next = self._shadow_history_count_next, self.shadow_history_count
+        self._shadow_history_reset = False
+
+    def reset(self):
+        """no pixel has a shadow history: the next shadow_mask_accumulate runs with reset = 1 (a camera cut, a moved light)"""
+        self._shadow_history_reset = True
+
     def _cutout_scratch(self, texture_count):
         """-> (bytes, device pointer) of the texture table of a ray-traced pass (one size for the opaque and the cutout entries)"""
         import torch

@@ -160,6 +160,8 @@ def lib():
                            ("vkrh_set_shadow_area_lights", [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]),
                            # the edge-aware filter of the shadow mask (same rule)
                            ("vkrh_set_shadow_mask_filter", [C.c_void_p, C.c_uint32, C.c_float, C.c_float]),
+                           # the temporal accumulation of the shadow mask (same rule)
+                           ("vkrh_set_shadow_mask_accumulate", [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32]),
                            # the ray-traced reflections (same rule)
                            ("vkrh_set_reflection_rays", [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
                            # alpha cutouts in the rays of the two ray-traced stages (same rule)
@@ -422,6 +424,15 @@ class HostFrame:
         shading then reads; reach is the pattern_side of the area lights it reconstructs.  reach 0 (the default): off.  Not on a
         tiled frame."""
         self._check(lib().vkrh_set_shadow_mask_filter(self.h, int(reach), float(normal_min_dot), float(plane_tolerance)))
+
+    def set_shadow_mask_accumulate(self, max_count=abi.SHADOW_ACCUM_MAX_COUNT, plane_tolerance=abi.SHADOW_FILTER_PLANE_TOLERANCE,
+                                   pattern_frames=abi.SHADOW_ACCUM_PATTERN_FRAMES):
+        """vkrh_set_shadow_mask_accumulate: max_count 1..255: STAGE_SHADOW_MASK and STAGE_SHADOW_MASK_RT record
+        vkr_shadow_mask_accumulate (task ShadowMaskAccumulate) right after the mask and before the filter, from image "shadow_mask"
+        and the histories "shadow_history" / "shadow_history_count" into "shadow_history_out" / "shadow_history_count_out" and
+        "shadow_mask_accumulated"; end_frame swaps the history pairs; a traced soft mask cycles over pattern_frames sample
+        tables.  max_count 0: off (the frame's default).  Not on a tiled frame."""
+        self._check(lib().vkrh_set_shadow_mask_accumulate(self.h, int(max_count), float(plane_tolerance), int(pattern_frames)))
 
     def set_reflection_rays(self, fill_misses=False, normal_offset=abi.SHADOW_RT_NORMAL_OFFSET, tmin=abi.SHADOW_RT_TMIN, max_distance=None,
                             texture_lod=0):

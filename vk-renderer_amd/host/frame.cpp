@@ -205,13 +205,62 @@ struct PostFxFrame {
   }
   // after the mask stage of this run has been recorded
   void record_shadow_mask_filter(ShadowMaskPass& pass) {
+    const rendergraph::ImageResourceId source = record_shadow_mask_accumulate(pass);  // before the filter, which then reads its image
     if (shadow_filter_reach == 0) return;
     if (!has_shadow_mask_filtered) {
       shadow_mask_filtered_tex = create_shadow_mask_texture(graph, cfg.width, cfg.height);
       has_shadow_mask_filtered = true;
     }
     pass.update_filter(shadow_filter_reach, shadow_filter_normal_min_dot, shadow_filter_plane_tolerance);
-    pass.run_filter(graph, gbuffer.depth, gbuffer.normal, shadow_mask_tex, shadow_mask_filtered_tex);
+    pass.run_filter(graph, gbuffer.depth, gbuffer.normal, source, shadow_mask_filtered_tex);
+  }
+
+  // The temporal accumulation of the mask (vkrh_set_shadow_mask_accumulate), right after either mask stage and before the filter.
+  // Default: max_count 0, off.  The five images are created on the first run with it on.
+  uint32_t shadow_accum_max_count = 0, shadow_accum_pattern_frames = 1;
+  float shadow_accum_plane_tolerance = 0.01f;
+  bool has_shadow_history = false;
+  ShadowHistoryTextures shadow_history;
+  // The histories hold last frame's visibilities of this frame's lights and geometry, and prev_depth is last frame's depth, only
+  // when all of this holds; otherwise the pass runs with reset = 1:
+  bool shadow_accum_invalid = true;   // a call since the last accumulated run changed what a visibility means (or there was no such run)
+  bool shadow_accum_chained = false;  // the last vkrh_end_frame swapped the depths and followed an accumulated run directly
+  bool shadow_accum_pending = false;  // an accumulated run that no vkrh_end_frame has followed yet
+  uint32_t shadow_accum_frame = 0;    // the runs that recorded the pass: the index into the cycle of sample tables
+  void set_shadow_mask_accumulate(uint32_t max_count, float plane_tolerance, uint32_t pattern_frames) {
+    refuse_tiled("vkrh_set_shadow_mask_accumulate", "the reprojection reaches across strips: the accumulation runs on one GPU");
+    if (max_count > 255) throw std::runtime_error{"vkrh_set_shadow_mask_accumulate: max_count " + std::to_string(max_count) + ", needs 0 (off) or 1..255"};
+    if (pattern_frames < 1 || pattern_frames > 64)
+      throw std::runtime_error{"vkrh_set_shadow_mask_accumulate: pattern_frames " + std::to_string(pattern_frames) + ", needs 1..64"};
+    if (std::isnan(plane_tolerance)) throw std::runtime_error{"vkrh_set_shadow_mask_accumulate: plane_tolerance is NaN"};
+    shadow_accum_max_count = max_count; shadow_accum_plane_tolerance = plane_tolerance; shadow_accum_pattern_frames = pattern_frames;
+  }
+  // the sample tables of this run's traced soft mask: before run_rt
+  void select_shadow_sample_tables(ShadowMaskPass& pass) {
+    if (shadow_accum_max_count && shadow_accum_pattern_frames > 1) pass.update_rt_soft_frame(shadow_accum_frame % shadow_accum_pattern_frames, shadow_accum_pattern_frames);
+  }
+  // after the mask stage of this run has been recorded -> the image the next stage of the shadow pipeline reads
+  rendergraph::ImageResourceId record_shadow_mask_accumulate(ShadowMaskPass& pass) {
+    if (shadow_accum_max_count == 0) {
+      shadow_accum_chained = false;  // a mask the histories never saw
+      return shadow_mask_tex;
+    }
+    if (!has_shadow_history) {
+      shadow_history = create_shadow_history_textures(graph, cfg.width, cfg.height);
+      has_shadow_history = true;
+      for (rendergraph::ImageResourceId id : {shadow_history.history, shadow_history.out_history, shadow_history.count, shadow_history.out_count})
+        clear_color(graph, id, VkClearColorValue{{0.f, 0.f, 0.f, 0.f}});
+    }
+    pass.update_accumulate(shadow_accum_max_count, shadow_accum_plane_tolerance, prev_view, shadow_accum_invalid || !shadow_accum_chained);
+    pass.run_accumulate(graph, gbuffer.depth, gbuffer.normal, gbuffer.velocity_vectors, gbuffer.prev_depth, shadow_mask_tex, shadow_history.history,
+                        shadow_history.count, shadow_history.out_history, shadow_history.out_count, shadow_history.accumulated);
+    shadow_accum_invalid = false; shadow_accum_chained = false; shadow_accum_pending = true;
+    shadow_accum_frame++;
+    return shadow_history.accumulated;
+  }
+  // the last image of the shadow pipeline, for the shadowed shading
+  rendergraph::ImageResourceId shadow_mask_final() const {
+    return shadow_filter_reach ? shadow_mask_filtered_tex : shadow_accum_max_count ? shadow_history.accumulated : shadow_mask_tex;
   }
 
   // VKRH_STAGE_SHADOW_MASK_RT: the lights and offsets of the rays (vkrh_set_shadow_rays).  Default: one point light at the shading
@@ -229,6 +278,7 @@ struct PostFxFrame {
     if (4 * count != shadow_rays.size()) shadow_area_radii.assign(count, 0.0f);  // the radii belong to the lights they were set for
     shadow_rays.assign(lights, lights + 4 * count);
     shadow_rays_offset = normal_offset; shadow_rays_tmin = tmin;
+    shadow_accum_invalid = true;
   }
 
   // VKRH_STAGE_SHADOW_MASK_RT: the sizes of its lights (vkrh_set_shadow_area_lights).  Default: every radius 0, the hard pass.
@@ -249,6 +299,7 @@ struct PostFxFrame {
         throw std::runtime_error{"vkrh_set_shadow_area_lights: light " + std::to_string(l) + ": the radius must be finite and >= 0"};
     shadow_area_radii.assign(radii, radii + count);
     shadow_area_samples = sample_count; shadow_area_pattern = pattern_side;
+    shadow_accum_invalid = true;
   }
 
   // VKRH_STAGE_REFLECTIONS_RT: the mode and the rays (vkrh_set_reflection_rays).  Defaults: every pixel traced, the offsets of the
@@ -303,6 +354,7 @@ struct PostFxFrame {
   void set_ray_cutouts(uint32_t enable, uint32_t alpha_lod) {
     refuse_tiled("vkrh_set_ray_cutouts", "the ray-traced stages run on one GPU");
     ray_cutouts.enable = enable != 0; ray_cutouts.alpha_lod = alpha_lod;
+    shadow_accum_invalid = true;
   }
 
   // VKRH_STAGE_TILE_REGRESSION: AdvancedSSR allocates tile_planes when the pass is first recorded
@@ -405,6 +457,7 @@ struct PostFxFrame {
     for (uint32_t i = 0; i < count; i++) std::memcpy((void*)&shadow_lights[i], mvps + 16 * i, 64);
     shadow_size = size ? size : 1024;
     shadow_maps_current = false;  // VKRH_STAGE_SHADOW_MASK waits for the next VKRH_STAGE_SHADOW
+    shadow_accum_invalid = true;
   }
 
   // the `shadows` image, created on first use (main.cpp:279-287) and again when the size changes
@@ -447,6 +500,7 @@ struct PostFxFrame {
     if (!has_camera && (mask & ~uint32_t(VKRH_STAGE_LUT))) throw std::runtime_error{"vkrh_run: camera not set"};
     check_stage_rules(mask);  // refused before anything is recorded
     const glm::vec4 fazz = draw_params.fovy_aspect_znear_zfar;
+    if (mask & (VKRH_STAGE_CLEAR_PREV_DEPTH | VKRH_STAGE_PREV_DEPTH)) shadow_accum_chained = false;  // prev_depth is no longer last frame's depth
     if (mask & VKRH_STAGE_CLEAR_PREV_DEPTH) clear_depth(graph, gbuffer.prev_depth);  // main.cpp:306
     if (mask & VKRH_STAGE_LUT) ssr.preintegrate_pdf(graph);
     if (mask & VKRH_STAGE_BRDF_LUT) { ssr.preintegrate_brdf(graph); brdf_lut_ran = true; }
@@ -479,6 +533,7 @@ struct PostFxFrame {
       float radii[4] = {0.f, 0.f, 0.f, 0.f};
       std::copy(shadow_area_radii.begin(), shadow_area_radii.end(), radii);
       pass.update_rt_soft(radii, shadow_area_samples, shadow_area_pattern);
+      select_shadow_sample_tables(pass);
       if (ray_cutouts.enable && scene_renderer)
         pass.run_rt(graph, gbuffer.depth, gbuffer.normal, AdvancedSSR::RtScene{scene_as->tlas, scene_as->hit_attributes, scene_renderer->get_images(), nullptr},
                     ray_cutouts, shadow_mask_tex);
@@ -575,7 +630,7 @@ struct PostFxFrame {
       shading_pass.update_params(view, lit ? shadow_lights[0] : glm::mat4{1.f}, fazz.x, fazz.y, fazz.z, fazz.w);
       if (shadow_mask_apply && (mask & (VKRH_STAGE_SHADOW_MASK | VKRH_STAGE_SHADOW_MASK_RT)))  // vkrh_set_shadow_mask(apply) and the mask of this run
         shading_pass.draw_shadowed(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(),
-                                   shadow_filter_reach ? shadow_mask_filtered_tex : shadow_mask_tex, color_out_tex);  // the filtered mask when the filter is on
+                                   shadow_mask_final(), color_out_tex);  // the filtered mask when the filter is on, else the accumulated one
       else
         shading_pass.draw(graph, gbuffer, lit ? shadows : shadow_map, gtao.accumulated_ao, ssr.get_preintegrated_brdf(), ssr.get_blurred(), color_out_tex);
     }
@@ -611,6 +666,12 @@ struct PostFxFrame {
 
   void end_frame(bool swap_depth) {  // main.cpp:416-420
     if (swap_depth) graph.remap(gbuffer.depth, gbuffer.prev_depth);
+    if (shadow_accum_pending) {  // what the accumulation wrote is what it reads next
+      graph.remap(shadow_history.history, shadow_history.out_history);
+      graph.remap(shadow_history.count, shadow_history.out_count);
+    }
+    shadow_accum_chained = shadow_accum_pending && swap_depth;
+    shadow_accum_pending = false;
     graph.remap(gtao.output, gtao.prev_frame);  // main.cpp:417: the reprojection variant's history (gtao.cpp:241-284)
     taa_pass.remap_targets(graph);
     ssr.remap_images(graph);
@@ -675,6 +736,7 @@ struct PostFxFrame {
   static const NamedImage* named_image(const std::string& name) {
     using F = PostFxFrame;
     static constexpr const char* BAKED = "only exists after vkrh_bake_probes";
+    static constexpr const char* SHADOW_HISTORY_ONLY = "only exists after a mask stage with vkrh_set_shadow_mask_accumulate on";
     static const NamedImage table[] = {
         {"depth", [](F& f) { return f.gbuffer.depth; }}, {"prev_depth", [](F& f) { return f.gbuffer.prev_depth; }}, {"normal", [](F& f) { return f.gbuffer.normal; }},
         {"albedo", [](F& f) { return f.gbuffer.albedo; }}, {"material", [](F& f) { return f.gbuffer.material; }}, {"velocity", [](F& f) { return f.gbuffer.velocity_vectors; }},
@@ -702,6 +764,11 @@ struct PostFxFrame {
          "only exists after VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT"},
         {"shadow_mask_filtered", [](F& f) { return f.shadow_mask_filtered_tex; }, [](const F& f) { return f.has_shadow_mask_filtered; },
          "only exists after a mask stage with vkrh_set_shadow_mask_filter on"},
+        {"shadow_mask_accumulated", [](F& f) { return f.shadow_history.accumulated; }, [](const F& f) { return f.has_shadow_history; }, SHADOW_HISTORY_ONLY},
+        {"shadow_history", [](F& f) { return f.shadow_history.history; }, [](const F& f) { return f.has_shadow_history; }, SHADOW_HISTORY_ONLY},
+        {"shadow_history_out", [](F& f) { return f.shadow_history.out_history; }, [](const F& f) { return f.has_shadow_history; }, SHADOW_HISTORY_ONLY},
+        {"shadow_history_count", [](F& f) { return f.shadow_history.count; }, [](const F& f) { return f.has_shadow_history; }, SHADOW_HISTORY_ONLY},
+        {"shadow_history_count_out", [](F& f) { return f.shadow_history.out_count; }, [](const F& f) { return f.has_shadow_history; }, SHADOW_HISTORY_ONLY},
     };
     for (const NamedImage& e : table)
       if (name == e.name) return &e;
@@ -1509,6 +1576,7 @@ int vkrh_load_scene(void* frame, const vkr_raster_vertex* vertices, uint32_t ver
     gpu::TransferCmdPool transfer_pool{f->graph.get_stream()};  // main.cpp:257-258
     f->scene_as.reset(new scene::SceneAccelerationStructure);
     f->scene_as->build(transfer_pool, *f->loaded_scene);
+    f->shadow_accum_invalid = true;
   });
 }
 int vkrh_scene_texture_image(void* frame, uint32_t index, vkr_img* out) {
@@ -1539,6 +1607,9 @@ int vkrh_shadow_lights(void* frame, float* out, uint32_t* count) {
 int vkrh_set_shadow_mask(void* frame, uint32_t bias, uint32_t radius, uint32_t apply) { return guarded([&] { frame_ref(frame).set_shadow_mask(bias, radius, apply); }); }
 int vkrh_set_shadow_mask_filter(void* frame, uint32_t reach, float normal_min_dot, float plane_tolerance) {
   return guarded([&] { frame_ref(frame).set_shadow_mask_filter(reach, normal_min_dot, plane_tolerance); });
+}
+int vkrh_set_shadow_mask_accumulate(void* frame, uint32_t max_count, float plane_tolerance, uint32_t pattern_frames) {
+  return guarded([&] { frame_ref(frame).set_shadow_mask_accumulate(max_count, plane_tolerance, pattern_frames); });
 }
 int vkrh_set_ssao_samples(void* frame, const float* xyz, uint32_t std140) { return guarded([&] { frame_ref(frame).set_ssao_samples(xyz, std140); }); }
 int vkrh_set_backbuffer(void* frame, const char* source_image, uint32_t flags, uint32_t width, uint32_t height) {
@@ -1582,6 +1653,7 @@ int vkrh_set_draw_transforms(void* frame, const float* transforms, uint32_t coun
     for (uint32_t i = 0; i < count; i++) std::memcpy((void*)&nodes[i].transform, transforms + 16 * size_t(i), 64);
     f->scene_renderer->update_scene();
     f->scene_as->refit(*f->loaded_scene, f->graph.get_stream());
+    f->shadow_accum_invalid = true;
   });
 }
 

@@ -190,6 +190,23 @@ int vkrh_set_shadow_area_lights(void* frame, const float* radii, uint32_t count,
  * is at most plane_tolerance times the pixel's view depth.  An error: reach above 4, a NaN threshold.  Default: reach 0, off, under
  * which every stage records what it always recorded.  No new stage bit.  Not on a tiled frame. */
 int vkrh_set_shadow_mask_filter(void* frame, uint32_t reach, float normal_min_dot, float plane_tolerance);
+/* The temporal accumulation of the shadow mask (vkr_shadow_mask_accumulate): with max_count 1..255 a
+ * VKRH_STAGE_SHADOW_MASK or VKRH_STAGE_SHADOW_MASK_RT records, right after the mask and before the filter, the task
+ * ShadowMaskAccumulate: image "shadow_mask" (which stays this frame's mask), the G-buffer's depth, normal and velocity, "prev_depth"
+ * and the histories "shadow_history" (RGBA16_UNORM) / "shadow_history_count" (R8_UNORM) -> "shadow_history_out",
+ * "shadow_history_count_out" and "shadow_mask_accumulated" (RGBA8_UNORM); the five images exist only after such a run, the first
+ * of which also records four Clear_color tasks.  The filter, if on, reads "shadow_mask_accumulated", and the shadowed shading reads
+ * the last image of the chain.  vkrh_end_frame after such a run swaps the two history pairs.  The history weighs at most
+ * max_count - 1 frames; prev_inverse_camera is the inverse of the camera's prev_view.  With pattern_frames T > 1 a traced soft mask
+ * takes the sample table vkr_shadow_disk_samples_frame(S, P, k mod T, T) in the k-th run that records the pass.
+ * The pass runs with reset = 1 (no pixel has a history) in the first such run; after vkrh_set_shadow_rays,
+ * vkrh_set_shadow_area_lights, vkrh_set_shadow_lights, vkrh_set_draw_transforms, vkrh_set_ray_cutouts or vkrh_load_scene; and
+ * whenever "prev_depth" is not the depth of the previous accumulated run: unless the last vkrh_end_frame had swap_depth != 0 and
+ * followed that run with no other vkrh_end_frame between, and no run since has had VKRH_STAGE_PREV_DEPTH,
+ * VKRH_STAGE_CLEAR_PREV_DEPTH or a mask stage without the accumulation.
+ * An error: max_count above 255, pattern_frames outside 1..64, a NaN tolerance.  Default: max_count 0, off, under which every
+ * stage records what it always recorded.  No new stage bit.  Not on a tiled frame. */
+int vkrh_set_shadow_mask_accumulate(void* frame, uint32_t max_count, float plane_tolerance, uint32_t pattern_frames);
 /* The rays of VKRH_STAGE_REFLECTIONS_RT: fill_misses != 0 traces only the pixels whose screen-space ray is invalid, after the
  * screen-space trace and filter; the ray's origin is the surface point moved by normal_offset along the normal, the ray runs
  * t in [tmin, max_distance] along the unit mirror direction (tmin or max_distance NaN is an error), a hit samples mip level

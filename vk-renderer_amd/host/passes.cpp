@@ -915,6 +915,17 @@ ImageResourceId create_shadow_mask_texture(RenderGraph &graph, uint32_t width, u
   return make_image(graph, VK_FORMAT_R8G8B8A8_UNORM, width, height, VK_IMAGE_USAGE_STORAGE_BIT|VK_IMAGE_USAGE_SAMPLED_BIT);
 }
 
+ShadowHistoryTextures create_shadow_history_textures(RenderGraph &graph, uint32_t width, uint32_t height) {
+  const VkImageUsageFlags usage = VK_IMAGE_USAGE_STORAGE_BIT|VK_IMAGE_USAGE_SAMPLED_BIT|VK_IMAGE_USAGE_TRANSFER_DST_BIT;
+  ShadowHistoryTextures t;
+  t.history = make_image(graph, VK_FORMAT_R16G16B16A16_UNORM, width, height, usage);
+  t.out_history = make_image(graph, VK_FORMAT_R16G16B16A16_UNORM, width, height, usage);
+  t.count = make_image(graph, VK_FORMAT_R8_UNORM, width, height, usage);
+  t.out_count = make_image(graph, VK_FORMAT_R8_UNORM, width, height, usage);
+  t.accumulated = create_shadow_mask_texture(graph, width, height);
+  return t;
+}
+
 ShadowMaskPass::ShadowMaskPass() {
   pipeline = gpu::create_compute_pipeline("shadow_mask");
   sampler = default_sampler();
@@ -964,6 +975,7 @@ void ShadowMaskPass::update_rt_soft(const float radius[4], uint32_t sample_count
   if (!radius || sample_count < 1 || sample_count > 64 || (pattern_side != 1 && pattern_side != 2 && pattern_side != 4))
     throw std::runtime_error {"ShadowMaskPass::update_rt_soft: " + std::to_string(sample_count) + " samples in a pattern tile of side " +
                               std::to_string(pattern_side) + ", needs 1..64 and 1, 2 or 4"};
+  rt_soft_frame_table = nullptr;  // update_rt_soft_frame chooses again
   for (int l = 0; l < 4; l++) {
     if (!(radius[l] >= 0.f) || std::isinf(radius[l])) throw std::runtime_error {"ShadowMaskPass::update_rt_soft: light " + std::to_string(l) + ": the radius must be finite and >= 0"};
     rt_soft.radius[l] = radius[l];
@@ -975,6 +987,22 @@ void ShadowMaskPass::update_rt_soft(const float radius[4], uint32_t sample_count
   }
 }
 
+void ShadowMaskPass::update_rt_soft_frame(uint32_t frame, uint32_t frame_count) {
+  if (frame_count < 1 || frame_count > 64) throw std::runtime_error {"ShadowMaskPass::update_rt_soft_frame: " + std::to_string(frame_count) + " frames, needs 1..64"};
+  if (!rt_soft_on() || !rt_soft_table) return;  // the hard pass has no table
+  const uint32_t S = rt_soft.sample_count, P = rt_soft.pattern_side;
+  if (rt_soft_frames.size() != frame_count || rt_soft_frames_key[0] != S || rt_soft_frames_key[1] != P || rt_soft_frames_key[2] != frame_count) {
+    // fresh buffers, never rewritten: a table an earlier submission may still read stays as it is
+    rt_soft_frames.assign(frame_count, nullptr);
+    for (uint32_t t = 0; t < frame_count; t++) {
+      rt_soft_frames[t] = gpu::create_buffer(VMA_MEMORY_USAGE_CPU_TO_GPU, sizeof(float) * 2 * S * P * P, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT);
+      vkr_shadow_disk_samples_frame(S, P, t, frame_count, (float *)rt_soft_frames[t]->get_mapped_ptr());
+    }
+    rt_soft_frames_key[0] = S; rt_soft_frames_key[1] = P; rt_soft_frames_key[2] = frame_count;
+  }
+  rt_soft_frame_table = rt_soft_frames[frame % frame_count];
+}
+
 // task "ShadowMaskRT": set {0 depth (mip 0), 1 normal, 2 the acceleration structure, 3 the block, 4 the mask (storage)} in the
 // C-ABI's order, one 16 x 16 group (four waves of 8 x 8 pixels) per 16 x 16 pixels
 void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, VkAccelerationStructureKHR tlas, ImageResourceId out) {
@@ -984,7 +1012,7 @@ void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageReso
     if (!rt_soft_pipeline.has_program()) rt_soft_pipeline = gpu::create_compute_pipeline("shadow_mask_rt_soft");
     rec::compute(graph, "ShadowMaskRTSoft", rt_soft_pipeline,
       {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, tlas), rec::uniform(3, rt_params),
-       rec::storage(4, out), rec::uniform(5, rt_soft), rec::uniform_buffer(6, rt_soft_table)},
+       rec::storage(4, out), rec::uniform(5, rt_soft), rec::uniform_buffer(6, bound_rt_soft_table())},
       rec::no_push(), rec::Grid {out, 16, 16, rec::Ceil});
     return;
   }
@@ -1011,7 +1039,7 @@ void ShadowMaskPass::run_rt(RenderGraph &graph, ImageResourceId depth, ImageReso
   std::vector<rec::Binding> bindings {rec::sampled_mips(0, depth, sampler, DEPTH, 0, 1), rec::sampled(1, normal, sampler), rec::accel(2, scene.tlas),
     rec::uniform(3, rt_params), rec::storage(4, out), rec::uniform_buffer(5, scene.hit_attributes),
     rec::uniform(6, vkr_ray_cutout {cutouts.alpha_lod, 0u})};
-  if (soft) bindings.insert(bindings.end(), {rec::uniform(8, rt_soft), rec::uniform_buffer(9, rt_soft_table)});
+  if (soft) bindings.insert(bindings.end(), {rec::uniform(8, rt_soft), rec::uniform_buffer(9, bound_rt_soft_table())});
   struct Data { std::vector<rec::Bound> bound; };
   const auto program = pipeline_used;
   const auto textures = scene.textures;
@@ -1141,6 +1169,39 @@ void ShadowMaskPass::run_filter(RenderGraph &graph, ImageResourceId depth, Image
       const vkr_img d = resources.get_image(depth)->describe(0, 1), n = resources.get_image(normal)->describe(0, 1);
       const vkr_img m = resources.get_image(mask)->describe(0, 1), o = resources.get_image(out)->describe(0, 1);
       transfer_status(vkr_shadow_mask_filter(&d, &n, &m, &block, &o, stream), "ShadowMaskFilter");
+    });
+}
+
+// ==== ShadowMaskPass, the temporal accumulation: a direct C-ABI call like the filter ================================================
+void ShadowMaskPass::update_accumulate(uint32_t max_count, float plane_tolerance, const glm::mat4 &prev_view, bool reset) {
+  if (max_count < 1 || max_count > 255) throw std::runtime_error {"ShadowMaskPass::update_accumulate: max_count " + std::to_string(max_count) + ", needs 1..255"};
+  if (std::isnan(plane_tolerance)) throw std::runtime_error {"ShadowMaskPass::update_accumulate: plane_tolerance is NaN"};
+  accum = vkr_shadow_accum_params {};
+  copy_mat(accum.prev_inverse_camera, glm::inverse(prev_view));
+  accum.max_count = max_count; accum.plane_tolerance = plane_tolerance; accum.reset = reset ? 1u : 0u;
+}
+
+void ShadowMaskPass::run_accumulate(RenderGraph &graph, ImageResourceId depth, ImageResourceId normal, ImageResourceId velocity, ImageResourceId prev_depth,
+  ImageResourceId mask, ImageResourceId history, ImageResourceId history_count, ImageResourceId out_history, ImageResourceId out_count,
+  ImageResourceId out_mask)
+{
+  if (accum.max_count == 0) throw std::runtime_error {"ShadowMaskPass::run_accumulate: update_accumulate first"};
+  vkr_shadow_accum_params block = accum;
+  if (camera_is_rt) {
+    block.inverse_camera = rt_params.inverse_camera;
+    block.fovy = rt_params.fovy; block.aspect = rt_params.aspect; block.znear = rt_params.znear; block.zfar = rt_params.zfar;
+  } else {
+    block.inverse_camera = params.inverse_camera;
+    block.fovy = params.fovy; block.aspect = params.aspect; block.znear = params.znear; block.zfar = params.zfar;
+  }
+  add_transfer_task(graph, "ShadowMaskAccumulate",
+    {{depth, 0, 1, 1}, {normal, 0, 1, 1}, {velocity, 0, 1, 1}, {prev_depth, 0, 1, 1}, {mask, 0, 1, 1}, {history, 0, 1, 1}, {history_count, 0, 1, 1}},
+    {{out_history, 0, 1, 1}, {out_count, 0, 1, 1}, {out_mask, 0, 1, 1}},
+    [=](rendergraph::RenderResources &resources, void *stream) {
+      const auto view = [&](ImageResourceId id) { return resources.get_image(id)->describe(0, 1); };
+      const vkr_img d = view(depth), n = view(normal), v = view(velocity), pd = view(prev_depth), m = view(mask), h = view(history),
+                    c = view(history_count), oh = view(out_history), oc = view(out_count), om = view(out_mask);
+      transfer_status(vkr_shadow_mask_accumulate(&d, &n, &v, &pd, &m, &h, &c, &block, &oh, &oc, &om, stream), "ShadowMaskAccumulate");
     });
 }
 

@@ -724,6 +724,11 @@ private:
 
 // RGBA8_UNORM, storage | sampled: channel l = visibility of light l
 rendergraph::ImageResourceId create_shadow_mask_texture(rendergraph::RenderGraph &graph, uint32_t width, uint32_t height);
+// What the temporal accumulation of the mask keeps between frames and writes: the running mean per light (RGBA16_UNORM) and the
+// number of frames in it (R8_UNORM), each twice (read and written; the caller swaps the pairs after the frame), and the
+// accumulated mask (RGBA8_UNORM).  The histories and counts must be cleared to 0 before their first use.
+struct ShadowHistoryTextures { rendergraph::ImageResourceId history, out_history, count, out_count, accumulated; };
+ShadowHistoryTextures create_shadow_history_textures(rendergraph::RenderGraph &graph, uint32_t width, uint32_t height);
 
 struct ShadowMaskPass {
   ShadowMaskPass();
@@ -766,6 +771,22 @@ struct ShadowMaskPass {
   void run_filter(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
     rendergraph::ImageResourceId mask, rendergraph::ImageResourceId out);
 
+  // The temporal accumulation of the mask (vkr_shadow_mask_accumulate): the history weighs at most max_count - 1
+  // (max_count 1..255) frames; prev_view is the view matrix of the frame that wrote prev_depth and the history (the block carries
+  // its inverse); reset: no pixel has a history.  The camera is the one of the last update_params / update_rt_params.
+  void update_accumulate(uint32_t max_count, float plane_tolerance, const glm::mat4 &prev_view, bool reset);
+  // task "ShadowMaskAccumulate": depth and prev_depth (mip 0), the full-resolution normal and velocity, the mask, the history and
+  // its count -> out_history, out_count (the pair the caller swaps with history / history_count after the frame) and out_mask.
+  // No program of the table: the task calls the C-ABI entry.
+  void run_accumulate(rendergraph::RenderGraph &graph, rendergraph::ImageResourceId depth, rendergraph::ImageResourceId normal,
+    rendergraph::ImageResourceId velocity, rendergraph::ImageResourceId prev_depth, rendergraph::ImageResourceId mask,
+    rendergraph::ImageResourceId history, rendergraph::ImageResourceId history_count, rendergraph::ImageResourceId out_history,
+    rendergraph::ImageResourceId out_count, rendergraph::ImageResourceId out_mask);
+  // After update_rt_soft and before run_rt: the soft programs of this run read the table of frame `frame` of a cycle of
+  // frame_count (1..64) frames (vkr_shadow_disk_samples_frame) instead of the one table of update_rt_soft.  The pass owns the
+  // frame_count device tables, remade when sample_count, pattern_side or frame_count change.  The next update_rt_soft ends it.
+  void update_rt_soft_frame(uint32_t frame, uint32_t frame_count);
+
 private:
   gpu::ComputePipeline pipeline;
   gpu::ComputePipeline rt_pipeline;  // "shadow_mask_rt", bound by the first run_rt()
@@ -777,8 +798,13 @@ private:
   gpu::ComputePipeline rt_soft_cutout_pipeline;  // "shadow_mask_rt_soft_cutout", likewise with cutouts
   vkr_shadow_rt_soft rt_soft {};  // samples stays NULL here: the program takes the pointer from rt_soft_table
   gpu::BufferPtr rt_soft_table;  // sample_count x pattern_side^2 x (u, v)
+  std::vector<gpu::BufferPtr> rt_soft_frames;  // update_rt_soft_frame: one table per frame of the cycle, for rt_soft_frames_key
+  uint32_t rt_soft_frames_key[3] {0, 0, 0};  // sample_count, pattern_side, frame_count of rt_soft_frames
+  gpu::BufferPtr rt_soft_frame_table;  // the table of this run's frame, or null: rt_soft_table
+  const gpu::BufferPtr &bound_rt_soft_table() const { return rt_soft_frame_table ? rt_soft_frame_table : rt_soft_table; }
   bool rt_soft_on() const { return rt_soft.radius[0] > 0.f || rt_soft.radius[1] > 0.f || rt_soft.radius[2] > 0.f || rt_soft.radius[3] > 0.f; }
   vkr_shadow_filter_params filter {};  // the camera is filled in by run_filter
+  vkr_shadow_accum_params accum {};  // the camera is filled in by run_accumulate
   bool camera_is_rt {false};  // which of params / rt_params was updated last
 };
 
